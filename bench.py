@@ -5,7 +5,10 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 it
 torch.distributed.run, one rank per GPU (RCCL) - and when it is started WITHOUT a launcher (no WORLD_SIZE in the
 environment) it starts the N ranks itself, as ref:scripts/train_SMB_decoder.sh:123-153 does, and relays rank 0's
 line.  W untimed steps, then exactly K timed steps between barrier + synchronize, MAX over ranks, rank 0 prints
-ONE JSON line.
+ONE JSON line, the last line on stdout and a few KB long: ``ms_per_step`` = the wall time of one timed step.  The full
+record (per-launch kernel table, kernel choice, per-leg tables) is the last line on stderr.  ``--dump-outputs DIR``
+writes what the last timed step computed as .npy files (see ``dump_outputs``).  Nothing else is timed unless asked:
+``--secondary`` adds the other step forms and the evaluation leg, ``--cpu-baseline`` the CPU oracle.
 
 Workload (BASELINE.json configs[1]): shipped Qwen3Multi architecture (8 layers, hidden 256, 6/3 heads,
 6 position-routed experts, V=1041), fp32, per-GPU micro-batch 1024 sequences x 505 tokens
@@ -21,7 +24,8 @@ Extra objects on the JSON line:
                region; `roofline.gemm` = the same object for the largest GEMM family
   cpu_baseline the CPU oracle (a port of the reference algorithm, oracle/) timed on the host cores,
                rank 0, N=1 only, on a bounded sample (micro-batch 32, 1 warm-up + 3 timed
-               steps, same sequence shape)
+               steps, same sequence shape); with --cpu-baseline
+  secondary    with --secondary: {leg: [ms_per_step, value]} of the other step forms (secondary_eval: the decode leg)
 """
 from __future__ import annotations
 
@@ -429,9 +433,14 @@ def parse_args(argv=None):
                     help="engine = Engine.train_step (the fused fast path, headline); module = the nn.Module plug-in surface "
                          "driven the way HF Trainer drives the reference (forward -> loss.backward() -> clip_grad_norm_ -> "
                          "torch AdamW -> zero_grad); module-fused = the same with the module's FusedClipAdamW optimizer")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs (bf16, split6, per-GPU batch 128) the default single-GPU run adds")
+    ap.add_argument("--cpu-baseline", action="store_true", help="also time the CPU oracle's train step (N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(the default; kept for existing command lines)")
+    ap.add_argument("--secondary", action="store_true",
+                    help="also time the secondary legs (bf16, split6, per-GPU batch 128, ...) and the decode leg after the "
+                         "headline (N = 1, default workload only; 2 warm-up + 5 timed steps each)")
+    ap.add_argument("--no-secondary", action="store_true", help="(the default; kept for existing command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-dropout", action="store_true")
     ap.add_argument("--matmul", choices=["f32", "split3", "split6", "split9"], default=None,
                     help="how fp32 matrix products are formed (--dtype f32 only; default split3, the engine's default): "
@@ -459,6 +468,10 @@ def parse_args(argv=None):
         args.matmul = "split3" if args.dtype == "f32" else "f32"
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.cpu_baseline and args.no_cpu_baseline or args.secondary and args.no_secondary:
+        ap.error("--cpu-baseline / --secondary contradict --no-cpu-baseline / --no-secondary")
     if args.batch is not None:
         args.weak = True
     elif args.weak:
@@ -607,6 +620,60 @@ def decode_leg(users: int = 256, beams: int = 20, his: int = 100, catalogue: int
     return out
 
 
+DUMP_SAMPLE = 4 << 20          # positions sampled from each flat buffer by --dump-outputs: 2 x 16 MB of float32
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: str, eng, loss, sample: int = DUMP_SAMPLE, seed: int = DUMP_SEED) -> dict:
+    """--dump-outputs: what the caller of the timed path holds after its last step, as float32 .npy files under `out_dir`:
+    `loss` (the loss the step returned), `params` (the updated flat fp32 parameters) and `grads` (the flat fp32 gradient of
+    the step), the two flat buffers at a fixed, seeded sample of `sample` positions in ascending order (all positions when
+    there are no more than that).  The run's inputs are seeded, so two builds run with the same arguments can be compared
+    file for file.  Returns {name: shape}."""
+    import numpy as np
+    n = eng.flat_p.numel()
+    if n > sample:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:sample].sort().values
+    else:
+        idx = torch.arange(n)
+    idx = idx.to(eng.flat_p.device)
+    arrays = {"loss": torch.as_tensor(loss).detach().float().reshape(-1),
+              "params": eng.flat_p.detach()[idx].float(),
+              "grads": eng.flat_g.detach()[idx].float()}
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        out[name] = list(a.shape)
+    return out
+
+
+# what the result line keeps of a leg's roofline object (the full object is in the record on stderr)
+ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "ms_per_step")
+
+
+def contract_line(result: dict) -> dict:
+    """The ONE JSON line on stdout: headline numbers, configuration, the roofline objects without their provenance
+    strings, the multi-GPU diagnostics and the optional legs as {name: [ms_per_step, value]}; the per-launch kernel
+    tables and the kernel choice stay in the full record."""
+    line = {k: v for k, v in result.items() if k not in ("roofline", "kernels", "kernel_choice", "kernels_measured_in",
+                                                        "secondary", "secondary_eval")}
+    rf = result.get("roofline")
+    if rf is not None:
+        line["roofline"] = {k: rf.get(k) for k in ROOFLINE_KEYS + ("step_algorithmic_tflops", "step_frac_of_matrix_peak")}
+        line["roofline"]["gemm"] = {k: rf["gemm"].get(k) for k in ROOFLINE_KEYS} if rf.get("gemm") else None
+    else:
+        line["roofline"] = None
+    if "secondary" in result:
+        line["secondary"] = {s["name"]: ([s["ms_per_step"], s["value"]] if "error" not in s else "error")
+                             for s in result["secondary"]}
+    if "secondary_eval" in result:
+        line["secondary_eval"] = {s["name"]: ([s["ms_per_batch"], s["value"]] if "error" not in s else "error")
+                                  for s in result["secondary_eval"]}
+    return line
+
+
 def run_leg(args, rank, world, local_rank, force_dist, timer):
     """One measurement: W untimed steps, K timed steps between barrier + synchronize (MAX over ranks).  Returns the result
     dict on rank 0 (None elsewhere).  Frees its engine before returning."""
@@ -736,6 +803,11 @@ def run_leg(args, rank, world, local_rank, force_dist, timer):
     final_loss = float(loss)
     log(f"timed region done: {elapsed / args.steps * 1e3:.1f} ms/step")
     eng.check_inputs()
+    dumped = None
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        # before the diagnostics below, which run further steps / collectives on the same buffers
+        dumped = dump_outputs(args.dump_outputs, eng, loss)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     if world > 1 or force_dist:
         import torch.distributed as dist
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -931,6 +1003,8 @@ def run_leg(args, rank, world, local_rank, force_dist, timer):
                                     else "timed region"),
             "loss": final_loss,
         }
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if allreduce is not None:
             result["allreduce"] = allreduce
         if comm_diag is not None:
@@ -990,17 +1064,20 @@ def main(argv=None):
 
     # Secondary legs (N = 1, default workload only): the other step forms DESIGN.md quotes - bf16 AMP, fp32 Linear
     # products on the bf16 pipe (split6), and both dtypes at the per-GPU batch of the 8-GPU north-star point (128) -
-    # timed by the same run, 2 warm-up + 5 timed steps each, reported under "secondary" on the ONE JSON line.
+    # timed by the same run when --secondary asks for them, 2 warm-up + 5 timed steps each, reported under "secondary".
     default_workload = (world == 1 and not force_dist and args.path == "engine" and args.dtype == "f32" and args.matmul == "split3"
                         and args.batch == 1024 and args.items == 101 and args.variant == "multi" and not args.ragged
                         and not args.no_dropout and args.accum == 1 and not args.augment and not args.deterministic)
-    if default_workload and not args.no_secondary and result is not None:
+    if args.secondary and not default_workload:
+        log("--secondary: the secondary legs go with the default single-GPU workload only; not run")
+    if default_workload and args.secondary and result is not None:
         import copy
         secondary = []
         for leg in SECONDARY_LEGS:
             name, dtype, matmul, batch = leg[:4]
             a = copy.copy(args)
             a.dtype, a.matmul, a.batch, a.steps, a.warmup = dtype, matmul, batch, 5, 2
+            a.dump_outputs = None
             for k_, v_ in (leg[4] if len(leg) > 4 else {}).items():
                 setattr(a, k_, v_)
             try:
@@ -1023,13 +1100,13 @@ def main(argv=None):
         # the evaluation path (BASELINE configs[4]'s shape, one GPU) in the same driver run: under "secondary_eval"
         try:
             timer.reset()                                           # (no per-launch events in the evaluation leg)
-            result["secondary_eval"] = [decode_leg(cpu_users=0 if args.no_cpu_baseline else 1)]
+            result["secondary_eval"] = [decode_leg(cpu_users=1 if args.cpu_baseline else 0)]
         except Exception as e:
             log(f"decode leg failed: {e!r}")
             result["secondary_eval"] = [{"name": "decode_bs256_beams20", "error": repr(e)}]
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             from gamer_amd.config import synthetic_config
             smean = args.session_mean if args.variant == "session" else None
             result["cpu_baseline"] = cpu_baseline(synthetic_config().to_dict(), args.items, session_mean=smean)
@@ -1053,7 +1130,8 @@ def main(argv=None):
         except Exception:
             pass
         sys.stdout.flush()
-        print(json.dumps(result), flush=True)
+        print(json.dumps(result), file=sys.stderr, flush=True)        # the full record: last line on stderr
+        print(json.dumps(contract_line(result)), flush=True)
     if world > 1 or force_dist:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -29,11 +29,9 @@ def test_config_roundtrip_and_validation(tmp_path):
     assert lut.shape == (1041,) and lut[1038] == 0 and lut[1040] == 2 and int((lut >= 0).sum()) == 3
 
 
-def test_reference_config_json_loads_when_present():
-    path = "/root/reference/config/s2s-models/Qwen3Multi"
-    if not os.path.isdir(path):
-        pytest.skip("reference not mounted")
-    cfg = Qwen3MultiConfig.from_pretrained(path)
+def test_reference_config_json_loads():
+    """The reference's shipped config.json (ref:config/s2s-models/Qwen3Multi, stored under tests/golden/)."""
+    cfg = Qwen3MultiConfig.from_pretrained(os.path.join(ROOT, "tests", "golden", "qwen3multi_config"))
     assert cfg.hidden_size == 256 and cfg.cross_attention_decoder == [4, 5, 6, 7] and cfg.vocab_size == 14
 
 
@@ -117,22 +115,14 @@ def test_flat_optimizer_state_of_an_older_parameter_order_is_adopted_by_name():
         new.adopt(flat_old[:-4], cfg, 1)
 
 
-def test_no_decay_rule_matches_hf_trainer_when_reference_present():
-    """oracle.is_no_decay restates HF Trainer.get_decay_parameter_names for this model."""
-    if not os.path.isdir("/root/reference/SeqRec"):
-        pytest.skip("reference not mounted")
-    try:
-        from transformers import Trainer
-    except Exception:
-        pytest.skip("transformers not importable")
-    from oracle import _ref_loader
-    Model, Cfg = _ref_loader.load_reference_classes()
-    cfg = _ref_loader.reference_config(Cfg, 3, 49, synthetic.behavior_maps(8, 3), num_hidden_layers=5,
-                                       sparse_layers_decoder=[0, 1, 2, 3, 4], cross_attention_decoder=[4])
-    model = Model(cfg)
-    decay = set(Trainer.get_decay_parameter_names(None, model))
-    for name, _ in model.named_parameters():
-        assert (name not in decay) == orc.is_no_decay(name), name
+def test_no_decay_rule_matches_hf_trainer(golden):
+    """oracle.is_no_decay restates HF Trainer.get_decay_parameter_names for this model: every parameter of the reference
+    model at a small configuration with the group the Trainer put it in (oracle/make_golden_no_decay.py)."""
+    z, meta = golden("no_decay")
+    names, decay = [str(n) for n in z["names"]], [bool(d) for d in z["decay"]]
+    assert len(names) == 147 and decay.count(False) == 24
+    for name, d in zip(names, decay):
+        assert (not d) == orc.is_no_decay(name), name
 
 
 def test_synthetic_batch_format():

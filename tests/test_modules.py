@@ -49,6 +49,12 @@ def test_oracle_matches_reference_modules(name):
         g = leaves[k].grad
         if "feed_forward.LayerNorm" in k:
             assert g is None and float(ref.abs().max()) == 0.0      # created, never applied (transformer.py:116-118)
+        elif k.endswith("key.bias"):
+            # exactly 0 in exact arithmetic (softmax ignores a constant added to every key score): both this value and the
+            # reference's are rounding noise, which differs between CPUs - held to the HIP test's bound instead
+            qb = leaves[k.replace("key.bias", "query.bias")].grad
+            assert float(g.abs().max()) < 1e-3 * float(qb.abs().max()), k
+            assert float(ref.abs().max()) < 1e-3 * float(qb.abs().max()), k
         else:
             assert _rel(g, ref) < 2e-5, k
 
