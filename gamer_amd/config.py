@@ -170,3 +170,105 @@ def synthetic_config(codebook: int = 256, num_behavior: int = 3, **overrides) ->
         **overrides,
     )
     return cfg
+
+
+_QWEN3_DEFAULTS: Dict[str, Any] = {
+    # the Qwen3-Light backbone of the SMB decoder harness (--backbone Qwen3): HF Qwen3ForCausalLM, no run-time fields
+    "architectures": ["Qwen3ForCausalLM"],
+    "attention_bias": False,
+    "attention_dropout": 0.1,
+    "bos_token_id": 4,
+    "pad_token_id": 4,
+    "eos_token_id": 8,
+    "head_dim": 64,
+    "hidden_act": "silu",
+    "hidden_size": 256,
+    "initializer_range": 0.02,
+    "intermediate_size": 512,
+    "max_position_embeddings": 40960,
+    "max_window_layers": 8,
+    "model_type": "qwen3",
+    "num_attention_heads": 6,
+    "num_hidden_layers": 8,
+    "num_key_value_heads": 3,
+    "rms_norm_eps": 1e-6,
+    "rope_scaling": None,
+    "rope_theta": 1000000,
+    "sliding_window": None,
+    "tie_word_embeddings": True,
+    "torch_dtype": "float32",
+    "use_cache": True,
+    "use_sliding_window": False,
+    "vocab_size": 14,
+}
+
+
+class Qwen3Config:
+    """Configuration of the plain Qwen3 baseline (train_SMB_decoder.py:317-320 builds ``Qwen3WithTemperature`` from it):
+    the keys of HF ``Qwen3Config`` with the Qwen3-Light defaults, and the dict / json surface of ``Qwen3MultiConfig``.
+    None of Qwen3Multi's routing, injection or cross-attention fields exist here."""
+
+    def __init__(self, **kwargs):
+        d = copy.deepcopy(_QWEN3_DEFAULTS)
+        d.update(kwargs)
+        rp = kwargs.get("rope_parameters")
+        if "rope_theta" not in kwargs and isinstance(rp, dict) and "rope_theta" in rp:
+            d["rope_theta"] = rp["rope_theta"]
+        self.__dict__.update(d)
+
+    def __contains__(self, key):
+        return key in self.__dict__
+
+    def to_dict(self) -> Dict[str, Any]:
+        return copy.deepcopy(self.__dict__)
+
+    @classmethod
+    def from_dict(cls, d: Dict[str, Any]) -> "Qwen3Config":
+        return cls(**d)
+
+    @classmethod
+    def from_pretrained(cls, path: str) -> "Qwen3Config":
+        f = os.path.join(path, "config.json") if os.path.isdir(path) else path
+        with open(f) as fh:
+            return cls(**json.load(fh))
+
+    def save_pretrained(self, path: str):
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, "config.json"), "w") as fh:
+            json.dump(self.to_dict(), fh, indent=2, sort_keys=True)
+
+    @classmethod
+    def coerce(cls, config) -> "Qwen3Config":
+        """An instance of this class, a dict, or what the reference hands its model: a transformers ``Qwen3Config`` read
+        from config.json (every field of the schema is read by attribute; ``rope_theta`` also from transformers 5.x's
+        ``rope_parameters``)."""
+        if isinstance(config, cls):
+            return config
+        if isinstance(config, dict):
+            return cls(**config)
+        d = {}
+        for key in _QWEN3_DEFAULTS:
+            if hasattr(config, key):
+                d[key] = copy.deepcopy(getattr(config, key))
+        if "rope_theta" not in d:
+            rp = getattr(config, "rope_parameters", None)
+            if isinstance(rp, dict) and "rope_theta" in rp:
+                d["rope_theta"] = rp["rope_theta"]
+        return cls(**d)
+
+    # the layer sets the shared engine code asks about: no cross attention, no behaviour injection
+    cross_attention_decoder: tuple = ()
+    behavior_injection_decoder: tuple = ()
+
+    def validate(self):
+        if self.head_dim != 64:
+            raise ValueError("the attention kernels are built for head_dim=64")
+        if self.num_attention_heads // self.num_key_value_heads not in (1, 2) or \
+                self.num_attention_heads % self.num_key_value_heads:
+            raise ValueError("GQA group (num_attention_heads / num_key_value_heads) must be 1 or 2")
+        if self.hidden_size % 4 or self.hidden_size > 1024 or self.intermediate_size % 4:
+            raise ValueError("hidden_size must be a multiple of 4 and <= 1024")
+        if not self.tie_word_embeddings:
+            raise ValueError("lm_head is tied to embed_tokens in this model")
+        if self.hidden_act != "silu" or self.attention_bias:
+            raise ValueError("only hidden_act='silu' without attention bias is implemented")

@@ -372,3 +372,59 @@ extern "C" int gamer_check_labels(const int64_t* labels, int64_t n, int V, int i
     GAMER_CHECK_LAUNCH("gamer_check_labels");
     return 0;
 }
+
+// ---- causal + key-padding mask and per-row RoPE positions (the Qwen3 baseline) ----------------------------------------
+// HF Qwen3ForCausalLM's mask is causal plus key padding: allowed(i,j) = j <= i && attention_mask[j] != 0, i.e. the
+// attention kernels' predicate with kl[j] = 0 / INT_MAX and query level 1.  generate() rotates row b's token i by
+// cumsum(attention_mask[b])[i] - 1, 0 at pads (transformers/generation/utils.py, _prepare_position_ids_for_generation),
+// and every generated token by one more: the first one by the number of kept prompt tokens.
+// One workgroup per sequence; an inclusive prefix sum of the kept flags in LDS gives the positions and the empty rows
+// (no kept key at or before the row).
+__global__ void __launch_bounds__(ROUTER_THREADS)
+causal_prep_kernel(const int64_t* __restrict__ attn_mask, int S, int32_t* __restrict__ kl_self,
+                   int32_t* __restrict__ empty_self, int32_t* __restrict__ tile_empty_self,
+                   int32_t* __restrict__ pos_ids, int32_t* __restrict__ next_pos) {
+    extern __shared__ __attribute__((aligned(16))) int32_t cs[];
+    int32_t* a = cs;            // [S] scan ping-pong
+    int32_t* bb = cs + S;       // [S]
+    const int b = blockIdx.x;
+    const int64_t base = (int64_t)b * S;
+    const int n_tiles = (S + 31) / 32;
+    for (int t = threadIdx.x; t < S; t += blockDim.x) {
+        const int keep = attn_mask ? (attn_mask[base + t] != 0 ? 1 : 0) : 1;
+        kl_self[base + t] = keep ? 0 : INT_BIG;
+        a[t] = keep;
+    }
+    __syncthreads();
+    // inclusive prefix sum (Hillis-Steele)
+    for (int off = 1; off < S; off <<= 1) {
+        for (int t = threadIdx.x; t < S; t += blockDim.x) bb[t] = a[t] + (t >= off ? a[t - off] : 0);
+        __syncthreads();
+        int32_t* sw = a; a = bb; bb = sw;
+    }
+    for (int t = threadIdx.x; t < S; t += blockDim.x) {
+        const int c = a[t];
+        empty_self[base + t] = c == 0 ? 1 : 0;
+        if (pos_ids) {
+            const int keep = attn_mask ? (attn_mask[base + t] != 0 ? 1 : 0) : 1;
+            pos_ids[base + t] = keep ? c - 1 : 0;
+        }
+    }
+    for (int qt = threadIdx.x; qt < n_tiles; qt += blockDim.x) {
+        // rows are empty exactly up to the first kept token: the tile has an empty row iff its first row is empty
+        tile_empty_self[(int64_t)b * n_tiles + qt] = a[qt * 32] == 0 ? 1 : 0;
+    }
+    if (next_pos && threadIdx.x == 0) next_pos[b] = a[S - 1];
+}
+
+extern "C" int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t* kl_self, int32_t* empty_self,
+                                 int32_t* tile_empty_self, int32_t* pos_ids, int32_t* next_pos, void* stream) {
+    GAMER_CHECK_ARG(kl_self && empty_self && tile_empty_self, "gamer_causal_prep: null pointer");
+    GAMER_CHECK_ARG(B > 0 && S > 0, "gamer_causal_prep: bad shape B=%d S=%d", B, S);
+    GAMER_CHECK_ARG(S <= 8192, "gamer_causal_prep: S=%d > 8192 unsupported", S);
+    const size_t shmem = (size_t)2 * S * sizeof(int32_t);
+    hipLaunchKernelGGL(causal_prep_kernel, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
+                       attn_mask, S, kl_self, empty_self, tile_empty_self, pos_ids, next_pos);
+    GAMER_CHECK_LAUNCH("gamer_causal_prep");
+    return 0;
+}

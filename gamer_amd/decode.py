@@ -458,17 +458,160 @@ class DecodeSession:
                        cfg.vocab_size, H)
 
 
+class Qwen3DecodeSession(DecodeSession):
+    """K/V cache + single-token step of the plain Qwen3 baseline (``Engine(variant="qwen3")``): self attention only.
+    The prompt pass runs with transformers' generate() positions ``cumsum(attention_mask) - 1`` (gamer_causal_prep builds
+    them on the device) and writes every layer's q|k|v and rotated keys in place; the token generated at step t is
+    rotated by (number of kept prompt tokens) + t - 1, per row - a left-padded prompt by its own offset."""
+
+    def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int):
+        import os
+        cfg, dev = engine.cfg, engine.device
+        self.eng, self.nb, self.tmax = engine, num_beams, max_new_tokens
+        self.reorder_cross_cache = False
+        self.session = False
+        self.B, self.L0 = input_ids.shape
+        B, L0, nb = self.B, self.L0, num_beams
+        self.N = N = B * nb
+        statics = engine.__dict__.setdefault("_decode_static", {})
+        key = (B, L0, nb, max_new_tokens, engine.variant, False, engine.matmul)
+        st = statics.get(key)
+        if st is None:
+            if len(statics) >= 4:
+                statics.pop(next(iter(statics)))
+            st = statics[key] = _DecodeStatic()
+        self.st = st
+        ids0 = input_ids.to(dev, torch.int64)
+        am0 = attention_mask.to(dev, torch.int64)
+        nq, nkv, dh = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        self.NQ, self.NKV = nq * dh, nkv * dh
+        QKV = self.NQ + 2 * self.NKV
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.kp, self.vp = st.kp, st.vp
+        T0 = B * L0
+        if engine.dtype != "f32":
+            raise NotImplementedError("generation (cached decode) is built for dtype='f32' only")
+        want_amax = (engine._amax is not None and engine.matmul == "split3" and os.environ.get("GAMER_DECODE_ATTN_SPLIT", "1") != "0")
+        prompt_amax = {}
+
+        def dest(layer, kind):
+            kk = (layer, kind)
+            if kk not in st.qkvp or st.qkvp[kk].shape[0] != T0:
+                st.qkvp[kk] = torch.empty(T0, QKV, **f32)
+                st.kp[kk] = torch.empty(T0, self.NKV, **f32)
+                st.vp[kk] = st.qkvp[kk][:, self.NQ + self.NKV:]
+            return st.qkvp[kk], st.kp[kk]
+
+        def sink(layer, kind, k, v):
+            if want_amax:
+                sk = engine._amax.peek(k, (1, 0, T0, self.NKV, k.stride(0)))
+                sv = engine._amax.peek(v, (1, 0, T0, self.NKV, v.stride(0)))
+                if sk and sv:
+                    prompt_amax[(layer, kind)] = (sk, sv)
+        engine.forward(ids0, am0, train=False, kv_sink=sink, kv_dest=dest, last_row_logits=True, rope_from_mask=True)
+        self.prefill_logits = engine.last_logits_buf
+
+        def keep(name, value):
+            value = value.contiguous()
+            t = st.small.get(name)
+            if t is None or t.shape != value.shape or t.dtype != value.dtype:
+                st.small[name] = t = value.clone()
+            else:
+                t.copy_(value)
+            return t
+        self.ok_self = keep("ok_self", am0.to(torch.int32))
+        # RoPE position of the token generated at step t: pos_last + t (next_pos = kept prompt tokens, gamer_causal_prep)
+        self.pos_last = keep("pos_last", (engine.ws.mask["next_pos"] - 1).repeat_interleave(nb))
+        if st.gen is None:
+            st.gen = {kk: (torch.zeros(N, max_new_tokens, self.NKV, **f32), torch.zeros(N, max_new_tokens, self.NKV, **f32))
+                      for kk in self.kp}
+            H, I = cfg.hidden_size, cfg.intermediate_size
+            st.buf = dict(x=[torch.empty(N, H, **f32) for _ in range(2)], h=torch.empty(N, H, **f32),
+                          qkv=torch.empty(N, QKV, **f32), q=torch.empty(N, self.NQ, **f32), k=torch.empty(N, self.NKV, **f32),
+                          ao=torch.empty(N, self.NQ, **f32), gu=torch.empty(N, 2 * I, **f32), hm=torch.empty(N, I, **f32),
+                          xn=torch.empty(N, H, **f32), logits=torch.empty(N, engine.ws.ldl, **f32),
+                          gen_tmp=torch.empty(N, max(1, max_new_tokens - 1), self.NKV, **f32))
+            st.small["tok"] = torch.zeros(N, dtype=torch.int64, device=dev)
+            st.small["parent"] = torch.arange(N, dtype=torch.int64, device=dev)
+        self.gen, self.buf = st.gen, st.buf
+        self._pending_reorder = False
+        self.t = 0
+        self.kv_amax = {}
+        if want_amax:
+            if len(prompt_amax) == len(self.kp):
+                self.kv_amax = prompt_amax
+            else:
+                with ops.f32_matmul("split3"), engine._amax:
+                    for kk in self.kp:
+                        kpt, vpt = self.kp[kk], self.vp[kk]
+                        self.kv_amax[kk] = (ops.absmax_slot(kpt, 1, 0, kpt.shape[0], kpt.shape[1], kpt.stride(0)),
+                                            ops.absmax_slot(vpt, 1, 0, vpt.shape[0], vpt.shape[1], vpt.stride(0)))
+        am_ = engine._amax
+        self._sig = None if am_ is None else (len(am_._wkeys), am_.used, 0 if am_.planes is None else am_.planes.data_ptr())
+        if st.graphs and st.sig != self._sig:
+            st.graphs.clear()
+            st.sessions = 0
+        st.sessions += 1
+
+    def _step_body(self, t: int):
+        eng, cfg, b = self.eng, self.eng.cfg, self.buf
+        N, B, nb, L0 = self.N, self.B, self.nb, self.L0
+        H, I = cfg.hidden_size, cfg.intermediate_size
+        nq, nkv, NQ, NKV = cfg.num_attention_heads, cfg.num_key_value_heads, self.NQ, self.NKV
+        QKV = NQ + 2 * NKV
+        eps, scale = float(cfg.rms_norm_eps), float(cfg.head_dim) ** -0.5
+        tokens, parent = self.st.small["tok"], self.st.small["parent"]
+        if t >= 2:
+            # the beams were re-ordered after the last step: the t - 1 generated positions follow them
+            for kg, vg in self.gen.values():
+                tmp = b["gen_tmp"].view(-1)[:N * (t - 1) * NKV].view(N, t - 1, NKV)
+                torch.index_select(kg[:, :t - 1], 0, parent, out=tmp)
+                kg[:, :t - 1] = tmp
+                torch.index_select(vg[:, :t - 1], 0, parent, out=tmp)
+                vg[:, :t - 1] = tmp
+        cos, sin = eng.rope(L0 + self.tmax)
+        pos_ids = (self.pos_last + t).contiguous()       # per beam row; the table is indexed through pos_ids
+        x, x1 = b["x"]
+        ops.embedding_fwd(tokens, eng.params["model.embed_tokens.weight"], x)
+        fuse_qk = ops.qkv_fused_ok(b["h"], N, QKV)
+        for l in range(cfg.num_hidden_layers):
+            W = eng.W[l]
+            Wa = W.self_attn
+            ops.rmsnorm_fwd(x, W.ln1, eps, b["h"])
+            if fuse_qk:
+                ops.gemm(b["h"], H, 1, Wa["qkv"], H, 1, b["qkv"], QKV, N, QKV, H,
+                         qknorm=dict(wq=Wa["qn"], wk=Wa["kn"], eps=eps, cos=cos, sin=sin, q_rot=b["q"], k_rot=b["k"],
+                                     pos_ids=pos_ids, S=1, nq=nq, nkv=nkv))
+            else:
+                ops.linear_fwd(b["h"], H, Wa["qkv"], H, b["qkv"], QKV, N, QKV, H)
+                ops.qknorm_rope_fwd(b["qkv"], 1, nq, nkv, Wa["qn"], Wa["kn"], eps, cos, sin, b["q"], b["k"], pos_ids=pos_ids)
+            kg, vg = self.gen[(l, "self")]
+            ops.kv_append(b["k"], b["qkv"][:, NQ + NKV:], kg, vg, t - 1)
+            ops.attn_decode(b["q"], self.kp[(l, "self")], self.vp[(l, "self")], self.ok_self, kg, vg, t, True, None,
+                            B, nb, L0, nq, nkv, scale, b["ao"], amax=self.kv_amax.get((l, "self")))
+            ops.gemm(b["ao"], NQ, 1, Wa["o"], NQ, 1, x1, H, N, H, NQ, resid=x)
+            ops.rmsnorm_fwd(x1, W.ln2, eps, b["h"])
+            ops.linear_fwd(b["h"], H, W.gu, H, b["gu"], 2 * I, N, 2 * I, H)
+            ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
+            ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, resid=x1)
+        ops.rmsnorm_fwd(x, eng.params["model.norm.weight"], eps, b["xn"])
+        ops.linear_fwd(b["xn"], H, eng.params["model.embed_tokens.weight"], H, b["logits"], b["logits"].stride(0), N,
+                       cfg.vocab_size, H)
+
+
 @torch.no_grad()
 def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, actions: torch.Tensor, trie: ItemTrie,
                 num_beams: int, max_new_tokens: int = 4, use_cache: bool = True, session_ids=None,
                 extended_session_ids=None, reorder_cross_cache: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
-    """input_ids / attention_mask / actions: [B, L0] left-padded prompts ending with the target behaviour token.
+    """input_ids / attention_mask / actions: [B, L0] left-padded prompts ending with the target behaviour token
+    (``actions`` None for the "qwen3" baseline, which has no behaviour levels).
     Returns (sequences [B*num_beams, L0+max_new_tokens] int64, sequences_scores [B*num_beams] fp32), the beams of
     sample b at rows b*num_beams .., best first - the layout of HF's GenerateBeamOutput.
     ``use_cache=False`` re-runs the whole sequence every step (the cross-check of the cache path; it has no slots, so
     it needs ``reorder_cross_cache=True``).  ``reorder_cross_cache``: see ``DecodeSession`` (False = the reference).
     ``session_ids`` / ``extended_session_ids`` [B, L0]: required by a "session" engine (see DecodeSession)."""
-    if not use_cache and not reorder_cross_cache:
+    qwen3 = engine.variant == "qwen3"
+    if not use_cache and not reorder_cross_cache and not qwen3:
         raise ValueError("use_cache=False re-computes every position for its own beam: it can only reproduce "
                          "reorder_cross_cache=True (the shipped reference's un-reordered cross cache needs the cache)")
     dev = engine.device
@@ -478,7 +621,7 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     N = B * nb
     ids0 = input_ids.to(dev, torch.int64)
     am0 = attention_mask.to(dev, torch.int64)
-    act0 = actions.to(dev, torch.int64)
+    act0 = actions.to(dev, torch.int64) if not qwen3 else None
     seqs = ids0[:, None, :].expand(B, nb, L0).contiguous()
     run_scores = torch.zeros(B, nb, device=dev)
     run_scores[:, 1:] = -1e9                       # only beam 0 is live at the first step (HF)
@@ -507,9 +650,13 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
         if repeat:
             sid, ext = sid.repeat_interleave(nb, 0), ext.repeat_interleave(nb, 0)
         return dict(session_ids=sid, extended_session_ids=ext)
-    session = (DecodeSession(engine, ids0, am0, act0, nb, max_new_tokens, session_ids if sess_variant else None,
-                             extended_session_ids if sess_variant else None, reorder_cross_cache=reorder_cross_cache)
-               if use_cache else None)
+    if not use_cache:
+        session = None
+    elif qwen3:
+        session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens)
+    else:
+        session = DecodeSession(engine, ids0, am0, act0, nb, max_new_tokens, session_ids if sess_variant else None,
+                                extended_session_ids if sess_variant else None, reorder_cross_cache=reorder_cross_cache)
     last_tok = None
     for step in range(max_new_tokens):
         cur = L0 + step
@@ -520,6 +667,12 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
             else:
                 logits2d = session.step(last_tok)
                 rows = torch.arange(N, device=dev, dtype=torch.int32)
+        elif qwen3:
+            # the cache-free cross-check: the whole sequence again, positions from the (extended) attention mask
+            flat = ids0 if step == 0 else seqs.reshape(N, cur)
+            am = am0 if step == 0 else torch.cat([am0, am0.new_ones(B, step)], 1).repeat_interleave(nb, 0)
+            engine.forward(flat, am, train=False, rope_from_mask=True)
+            rows = ((torch.arange(N, device=dev, dtype=torch.int32) // (nb if step == 0 else 1)) * cur + (cur - 1))
         elif step == 0:
             # all beams of a sample hold the same prompt: run it once (HF runs num_beams copies)
             engine.forward(ids0, am0, act0, train=False, act_zero_col=L0 - 1, uniform_len=L0, **session_kw(0, False))

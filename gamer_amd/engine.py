@@ -377,6 +377,14 @@ class Engine:
     N_NORM_PARTIAL = 512
     N_SUMSQ_PARTIAL = 1024
 
+    def __new__(cls, *args, **kwargs):
+        # Engine(cfg, variant="qwen3") is the plain Qwen3 baseline's engine (gamer_amd/engine_qwen3.py)
+        variant = kwargs.get("variant", args[3] if len(args) > 3 else "multi")
+        if cls is Engine and variant == "qwen3":
+            from .engine_qwen3 import Qwen3Engine
+            cls = Qwen3Engine
+        return super().__new__(cls)
+
     def __init__(self, cfg: Qwen3MultiConfig, device="cuda", temperature: float = 1.0, variant: str = "multi",
                  dtype: str = "f32", matmul: Optional[str] = None, share_buffers_of: Optional["Engine"] = None,
                  deterministic: Optional[bool] = None):
@@ -428,7 +436,7 @@ class Engine:
         # attention products of the split forms on the bf16 pipe too (csrc/attention_split.hip); False keeps fp32-MFMA attention
         self.split_attention = True
         if variant not in ("multi", "session"):
-            raise ValueError(f"unknown variant {variant!r}")
+            raise ValueError(f"unknown variant {variant!r} (multi, session or qwen3)")
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"unknown dtype {dtype!r} (f32 or bf16; the reference's --fp16 is not built)")
         self.variant = variant

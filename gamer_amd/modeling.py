@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .config import Qwen3MultiConfig
+from .config import Qwen3Config, Qwen3MultiConfig
 from .engine import Engine
 
 
@@ -122,6 +122,7 @@ except Exception:                                             # noqa: BLE001
 
 class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
     VARIANT = "multi"
+    CONFIG_CLASS = Qwen3MultiConfig
 
     def __init__(self, config, device: str = "cuda", dtype: str = "f32", matmul: Optional[str] = None):
         """``config``: the object the reference constructs its model from - a transformers ``Qwen3MoeConfig`` loaded from
@@ -132,12 +133,9 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
         here - bf16 matrix operands and activations, fp32 parameters / gradients (the nn.Parameters stay fp32).
         ``matmul``: the engine's form of the fp32 matrix products (None = its default "split3"; "split6" = exact bf16 pieces; "f32" = fp32 MFMA)."""
         nn.Module.__init__(self)
-        assert hasattr(config, "num_positions") and isinstance(config.num_positions, int), \
-            "Config must have 'num_positions' attribute for Qwen3SessionModel."
-        assert hasattr(config, "model_max_length") and isinstance(config.model_max_length, int), \
-            "Config must have 'model_max_length' attribute for Qwen3SessionModel."
+        self._check_config(config)
         self.config = config
-        self._cfg = Qwen3MultiConfig.coerce(config)
+        self._cfg = self.CONFIG_CLASS.coerce(config)
         self.vocab_size = config.vocab_size
         self.temperature = 1.0
         self.zero_copy_logits = False       # True: the training forward returns a view of the engine's logits buffer
@@ -147,6 +145,13 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
         self._amp_engine: Optional[Engine] = None     # the bf16 step over the SAME masters / gradients, built on first use under autocast
         self._param_keys = list(self.engine.layout.entries.keys())
         self._register_views()
+
+    @staticmethod
+    def _check_config(config):
+        assert hasattr(config, "num_positions") and isinstance(config.num_positions, int), \
+            "Config must have 'num_positions' attribute for Qwen3SessionModel."
+        assert hasattr(config, "model_max_length") and isinstance(config.model_max_length, int), \
+            "Config must have 'model_max_length' attribute for Qwen3SessionModel."
 
     def _engine_for_call(self) -> Engine:
         """The reference's precision switch is the caller's autocast region (HF Trainer, ``TrainingArguments(bf16=True)``:
@@ -260,7 +265,7 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
 
     @classmethod
     def from_pretrained(cls, path: str, device: str = "cuda", dtype: str = "f32", matmul: Optional[str] = None):
-        cfg = Qwen3MultiConfig.from_pretrained(path)
+        cfg = cls.CONFIG_CLASS.from_pretrained(path)
         model = cls(cfg, device=device, dtype=dtype, matmul=matmul)
         st = os.path.join(path, "model.safetensors")
         if os.path.exists(st):
@@ -307,7 +312,7 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         if inputs_embeds is not None or past_key_values is not None or use_cache:
             raise NotImplementedError("gamer_amd implements the training/scoring forward (no KV cache, no inputs_embeds)")
-        if actions is None:
+        if actions is None and self.VARIANT != "qwen3":
             raise ValueError("Qwen3Multi needs `actions` (behaviour level per token) for the cross-attention mask")
         num_items = kwargs.get("num_items_in_batch", None)
         if torch.is_tensor(num_items):
@@ -398,3 +403,42 @@ class Qwen3SessionMultiWithTemperature(Qwen3MultiWithTemperature):
     attention additionally needs a lower behaviour level) and RoPE positions = ``extended_session_ids``.
     ``forward`` needs ``session_ids`` (the reference asserts the same) and validates their order on the host."""
     VARIANT = "session"
+
+
+class Qwen3WithTemperature(Qwen3MultiWithTemperature):
+    """ref:SeqRec/models/generative/Qwen3/model.py - HF ``Qwen3ForCausalLM`` with the temperature loss, the plain baseline of
+    the SMB decoder harness (``--backbone Qwen3``, train_SMB_decoder.py:317-320) - on the HIP engine
+    (``Engine(variant="qwen3")``, gamer_amd/engine_qwen3.py).  The surface of the Multi classes: ``set_hyper``, HF Qwen3's
+    state-dict names, ``from_pretrained`` / ``save_pretrained``, the autograd forward with ``labels`` /
+    ``num_items_in_batch``, bf16 autocast, ``fused_optimizer``, ``enable_dp_overlap`` and ``generate`` (without
+    ``actions``).  The forward accepts the SMB collator's ``actions`` / ``session_ids`` / ``extended_session_ids`` and
+    ignores them, as the reference's ``**kwargs`` does."""
+    VARIANT = "qwen3"
+    CONFIG_CLASS = Qwen3Config
+
+    @staticmethod
+    def _check_config(config):
+        pass
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, attention_mask=None, max_new_tokens: int = 4, num_beams: int = 1,
+                 num_return_sequences=None, prefix_allowed_tokens_fn=None, trie=None, **kwargs):
+        """The call of test_SMB_decoder.py:122-137: left-padded prompts (history + target behaviour token), trie-constrained
+        beam search, all beams returned best first, RoPE positions from the attention mask as transformers' generate()
+        builds them.  ``trie`` / ``prefix_allowed_tokens_fn`` as in ``Qwen3MultiWithTemperature.generate``."""
+        from . import decode
+        if trie is None:
+            trie = getattr(prefix_allowed_tokens_fn, "trie", None)
+        if trie is None and callable(prefix_allowed_tokens_fn):
+            trie = decode.trie_from_callable(prefix_allowed_tokens_fn, input_ids, max_new_tokens,
+                                             device=self.engine.device, pad_token_id=self._cfg.pad_token_id)
+        if trie is None:
+            raise NotImplementedError("generate() needs trie=ItemTrie(...) or prefix_allowed_tokens_fn (constrained beam search "
+                                      "of the SMB evaluation)")
+        if num_return_sequences not in (None, num_beams):
+            raise NotImplementedError("num_return_sequences must equal num_beams (what the evaluation task uses)")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        seqs, scores = decode.beam_search(self.engine, input_ids, attention_mask, None, trie, num_beams, max_new_tokens,
+                                          use_cache=bool(kwargs.get("use_cache", True)))
+        return CausalLMOutput(sequences=seqs, sequences_scores=scores)

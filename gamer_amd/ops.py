@@ -102,6 +102,15 @@ def session_spans(session_ids, extended_session_ids, attn_mask, num_positions, n
          ptr(router["tile_empty_self"]), ptr(router["tile_empty_cross"]), ptr(out["violations"]), stream_ptr())
 
 
+def causal_prep(attn_mask, B, S, kl_self, empty_self, tile_empty_self, pos_ids=None, next_pos=None):
+    """Causal + key-padding mask of the Qwen3 baseline and (optionally) generate()'s per-row RoPE positions
+    (gamer_causal_prep).  attn_mask: int64 [B,S] or None."""
+    if attn_mask is not None:
+        _chk(attn_mask, torch.int64, "attention_mask")
+    call("gamer_causal_prep", ptr(attn_mask), B, S, ptr(kl_self), ptr(empty_self), ptr(tile_empty_self), ptr(pos_ids),
+         ptr(next_pos), stream_ptr())
+
+
 def expert_lists(expert, num_experts, perm, slot, offsets, work):
     B, S = expert.shape
     call("gamer_expert_lists", ptr(expert), B, S, num_experts, ptr(perm), ptr(slot), ptr(offsets), ptr(work),

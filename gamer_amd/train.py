@@ -15,6 +15,9 @@ are synthetic tensors of the same layout.
       --epochs 1 --steps_per_epoch 20 --output_dir /tmp/ckpt
   python -m gamer_amd.train --data_path ./data --dataset ShortVideoAD --tasks smb_explicit_decoder_4 \
       --backbone Qwen3Multi --max_his_len 100 --per_device_batch_size 128 --epochs 2
+
+``--backbone Qwen3`` trains the plain Qwen3 baseline (train_SMB_decoder.py:317-320: the Qwen3-Light config with the
+vocabulary resized; ``Engine(variant="qwen3")``); its checkpoints load into ``gamer_amd.modeling.Qwen3WithTemperature``.
 """
 from __future__ import annotations
 
@@ -26,7 +29,7 @@ import time
 import torch
 
 from . import synthetic
-from .config import synthetic_config
+from .config import Qwen3Config, synthetic_config
 from .dp import GradAllReducer, all_reduce_scalar_
 from .engine import Engine
 from .schedule import cosine_with_warmup, warmup_steps_for
@@ -51,7 +54,7 @@ def parse_args(argv=None):
     ap.add_argument("--dataset", type=str, default="")
     ap.add_argument("--index_file", type=str, default=".index.json")
     ap.add_argument("--tasks", type=str, default="smb_explicit_decoder_4")
-    ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti"])
+    ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti", "Qwen3"])
     ap.add_argument("--patience", type=int, default=10, help="early stopping: evaluations without a better eval_loss")
     ap.add_argument("--save_total_limit", type=int, default=2)
     ap.add_argument("--bf16", action="store_true",
@@ -155,7 +158,7 @@ def main(argv=None):
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl", init_method="env://", device_id=torch.device("cuda", local_rank))
-    variant = "session" if args.backbone == "Qwen3SessionMulti" else "multi"
+    variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3"}.get(args.backbone, "multi")
     accum = args.gradient_accumulation_steps
     real = None
     if args.data_path:
@@ -175,12 +178,17 @@ def main(argv=None):
             raise NotImplementedError(f"tasks={args.tasks}: smb_explicit and smb_explicit_decoder[_N] are built")
         coll = gdata.Collator(ds)
         cfg = gdata.model_config(ds, args.max_his_len)
+        if variant == "qwen3":
+            # the baseline's config: Qwen3-Light with the tokenizer's vocabulary, nothing else set at run time
+            cfg = Qwen3Config(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id)
         per_step = args.per_device_batch_size * accum * world
         args.steps_per_epoch = max(1, len(samples) // per_step)            # drop_last, as the window needs equal shards
         real = dict(samples=samples, coll=coll, valid=ds.valid_samples(args.max_his_len), only_response=only_response)
         if rank == 0:
             print(json.dumps({"dataset": args.dataset, "train_samples": len(samples), "vocab_size": cfg.vocab_size,
                               "steps_per_epoch": args.steps_per_epoch}), flush=True)
+    elif variant == "qwen3":
+        cfg = Qwen3Config(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID)
     else:
         cfg = synthetic_config(n_positions=args.max_his_len + 1)
     eng = Engine(cfg, device=f"cuda:{local_rank}", temperature=args.temperature, variant=variant,
@@ -188,7 +196,9 @@ def main(argv=None):
     eng.init_weights(seed=args.seed)
     # one workspace for the longest batch the collator can produce: shorter batches bind views of it, nothing is
     # allocated inside the loop
-    eng.reserve(args.per_device_batch_size, (args.max_his_len + 1) * cfg.num_positions, train=True)
+    tokens_per_item = getattr(cfg, "num_positions", None) or (real["coll"].data.token_count if real is not None
+                                                                else synthetic.TOKENS_PER_ITEM)
+    eng.reserve(args.per_device_batch_size, (args.max_his_len + 1) * tokens_per_item, train=True)
     eng.base_seed = args.seed * 1000 + rank
     reducer = GradAllReducer(eng.flat_g, eng.layout, cfg.num_hidden_layers) if world > 1 else None
     total_steps = args.epochs * args.steps_per_epoch

@@ -97,6 +97,18 @@ int gamer_session_spans(const int64_t* session_ids, const int64_t* extended_sess
                         int32_t* tile_empty_self, int32_t* tile_empty_cross, int32_t* violations,
                         void* stream);
 
+/* Causal + key-padding mask of the Qwen3 baseline (HF Qwen3ForCausalLM; ref:SeqRec/models/generative/Qwen3/model.py) in the
+ * attention kernels' form, and its per-row RoPE positions.  No router: allowed(i,j) = j <= i && attention_mask[j] != 0.
+ *   attn_mask int64 [B,S] (may be NULL = all ones)
+ *   kl_self int32 [B,S] = 0 for kept keys, INT32_MAX for padded ones (the self query level is the constant 1)
+ *   empty_self int32 [B,S], tile_empty_self int32 [B, ceil(S/32)]: as gamer_router_fwd's (rows before the first kept token)
+ *   pos_ids int32 [B,S] (may be NULL): cumsum(attention_mask)[i] - 1, 0 at padded tokens - the positions transformers'
+ *           generate() gives a left-padded prompt; the q/k-norm + RoPE kernels take them as `pos_ids`
+ *   next_pos int32 [B] (may be NULL): number of kept tokens = the RoPE position of the first generated token
+ * Additive in ABI 9.                                                                                                */
+int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t* kl_self, int32_t* empty_self,
+                      int32_t* tile_empty_self, int32_t* pos_ids, int32_t* next_pos, void* stream);
+
 /* Expert token lists for the position-routed FFN (replaces the boolean-mask gather/scatter loop of
  * MyQwen3SparseMLP.forward, ref:SeqRec/models/generative/Qwen3Moe/FFN.py:63-68, and its 6 host
  * syncs per layer).  Deterministic order: expert-major, then token order.
