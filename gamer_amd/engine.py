@@ -12,6 +12,9 @@ What it computes is Appendix A of SURVEY.md, i.e.
   ref:SeqRec/models/generative/Qwen3Moe/FFN.py:53-72 (position-routed SwiGLU experts),
 and the HF-Trainer update of ref:SeqRec/tasks/train_SMB_decoder.py:396-444.
 
+The plain Qwen3 baseline (engine_qwen3.py) subclasses Engine with its own layout, masks and per-layer loops; what both
+models do alike (layout base, bf16 shadow, workspace, construction, forward / backward blocks) is written once here.
+
 Data layout in HBM (T = B*S tokens, row t = b*S + s, everything fp32):
   residual stream   [T,H] snapshots per sub-block (needed by the RMSNorm backward)
   q|k|v             [T,(nq+2nkv)*64] fused projection output, v consumed in place by attention
@@ -22,8 +25,11 @@ Data layout in HBM (T = B*S tokens, row t = b*S + s, everything fp32):
 """
 from __future__ import annotations
 
+import contextlib
+import functools
 import math
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -38,14 +44,38 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-class ParamLayout:
+class _FlatLayout:
+    """Flat fp32 layout of named parameters: the decayed ones first, the rest (RMSNorm weights: no weight decay under HF
+    Trainer) behind them, so the fused AdamW kernel needs a single boundary (``n_decay``)."""
+
+    def __init__(self, decay: List[Tuple[str, tuple]], nodecay: List[Tuple[str, tuple]]):
+        self.entries: Dict[str, Tuple[int, tuple]] = {}
+        off = 0
+        for i, (name, shp) in enumerate(decay + nodecay):
+            if i == len(decay):
+                self.n_decay = off
+            n = math.prod(shp)
+            assert n % 4 == 0, f"{name}: size {n} is not a multiple of 4"
+            self.entries[name] = (off, shp)
+            off += n
+        self.numel = off
+
+    def views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return {k: flat[o:o + math.prod(s)].view(s) for k, (o, s) in self.entries.items()}
+
+    def span(self, flat: torch.Tensor, first: str, rows: int, cols: int) -> torch.Tensor:
+        """[rows, cols] view that starts at parameter `first` and runs over its successors."""
+        o = self.entries[first][0]
+        return flat[o:o + rows * cols].view(rows, cols)
+
+
+class ParamLayout(_FlatLayout):
     """Flat fp32 layout of all parameters under the reference's state-dict names.
 
-    Decayed parameters first, RMSNorm weights (no weight decay under HF Trainer) last, so the
-    fused AdamW kernel needs a single boundary.  q/k/v projection weights of one attention are
-    adjacent (one fused [768,256] GEMM operand); the experts' gate and up weights of a layer are stored expert by expert as
-    gate_e | up_e (one [2 I, din] operand per expert: the FUSED gate|up projection, input gradient and weight gradient of the
-    grouped GEMMs, constant stride 2 I din), their down weights stacked behind them (stride H I).
+    q/k/v projection weights of one attention are adjacent (one fused [768,256] GEMM operand); the experts' gate and up
+    weights of a layer are stored expert by expert as gate_e | up_e (one [2 I, din] operand per expert: the FUSED gate|up
+    projection, input gradient and weight gradient of the grouped GEMMs, constant stride 2 I din), their down weights
+    stacked behind them (stride H I).
     """
 
     VERSION = 2          # 1 (rounds 1-3): the experts' gate / up / down weights of a layer stacked per kind
@@ -89,23 +119,7 @@ class ParamLayout:
                 nodecay.append((lp + "post_self_attention_layernorm.weight", (H,)))
             nodecay.append((lp + "post_cross_attention_layernorm.weight", (H,)))
         nodecay.append(("model.norm.weight", (H,)))
-        self.entries: Dict[str, Tuple[int, tuple]] = {}
-        off = 0
-        for name, shp in decay:
-            n = math.prod(shp)
-            assert n % 4 == 0, f"{name}: size {n} is not a multiple of 4"
-            self.entries[name] = (off, shp)
-            off += n
-        self.n_decay = off
-        for name, shp in nodecay:
-            n = math.prod(shp)
-            assert n % 4 == 0
-            self.entries[name] = (off, shp)
-            off += n
-        self.numel = off
-
-    def views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return {k: flat[o:o + math.prod(s)].view(s) for k, (o, s) in self.entries.items()}
+        super().__init__(decay, nodecay)
 
     def adopt(self, flat: torch.Tensor, cfg: Qwen3MultiConfig, version) -> torch.Tensor:
         """A flat buffer (optimizer moments of a checkpoint) written under layout `version` (None: a file from before the
@@ -123,11 +137,6 @@ class ParamLayout:
         for k, v in self.views(out).items():
             v.copy_(old[k])
         return out
-
-    def span(self, flat: torch.Tensor, first: str, rows: int, cols: int) -> torch.Tensor:
-        """[rows, cols] view that starts at parameter `first` and runs over its successors."""
-        o = self.entries[first][0]
-        return flat[o:o + rows * cols].view(rows, cols)
 
 
 class _LayerW:
@@ -178,46 +187,32 @@ class Bf16Shadow:
                contraction runs over the padded vocabulary).
     One gamer_cast_params_bf16 launch refreshes both (98 MB read, 98 MB written)."""
 
-    def __init__(self, cfg: Qwen3MultiConfig, layout: ParamLayout, flat_p: torch.Tensor):
+    def __init__(self, cfg, layout: _FlatLayout, flat_p: torch.Tensor):
         dev = flat_p.device
-        H, dh = cfg.hidden_size, cfg.head_dim
-        nq, nkv, I, E = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.intermediate_size, cfg.num_experts
-        QKV = (nq + 2 * nkv) * dh
         self.layout, self.flat_p = layout, flat_p
         self.flat16 = torch.zeros(layout.numel, dtype=torch.bfloat16, device=dev)
         self.ldv = _round_up(cfg.vocab_size, 64)
-        entries = []          # (src offset, rows, cols, ldt, key of the transposed view)
-        toff = 0
         self.t_views: Dict[str, Tuple[int, tuple]] = {}
-
-        def add(first: str, rows: int, cols: int, ldt: Optional[int] = None, tkey: Optional[str] = None):
-            nonlocal toff
-            src = layout.entries[first][0]
-            ldt = ldt or rows
-            entries.append((src, rows, cols, ldt, toff))
+        # the matrices the GEMMs read, in layout order: the tied embedding, the fused q|k|v and gate|up operands (from their first
+        # parameter on) and the o_proj / gating / down projections
+        mats = [("model.embed_tokens.weight", cfg.vocab_size, cfg.hidden_size, self.ldv, None)]
+        for name, (_, shp) in layout.entries.items():
+            head, kind, _ = name.rsplit(".", 2)
+            if kind == "q_proj":
+                mats.append((name, shp[0] + 2 * layout.entries[head + ".k_proj.weight"][1][0], shp[1], None, head + ".qkv"))
+            elif kind == "gate_proj":
+                mats.append((name, 2 * shp[0], shp[1], None, head + ".gu"))
+            elif kind in ("o_proj", "gating", "down_proj"):
+                mats.append((name, shp[0], shp[1], None, None))
+        tab, toff, tile0 = [], 0, 0
+        for first, rows, cols, ldt, tkey in mats:
+            src, ldt = layout.entries[first][0], ldt or rows
+            tab += [src, src, toff, rows | (cols << 32), ldt | (tile0 << 32)]
             self.t_views[tkey or first] = (toff, (cols, ldt))
             toff += _round_up(cols * ldt, 8)
-
-        add("model.embed_tokens.weight", cfg.vocab_size, H, ldt=self.ldv)
-        for l in range(cfg.num_hidden_layers):
-            lp = f"model.layers.{l}."
-            cross = l in cfg.cross_attention_decoder
-            din = H + (cfg.behavior_embedding_dim if l in cfg.behavior_injection_decoder else 0)
-            for a in (["self_attn", "cross_attn"] if cross else ["self_attn"]):
-                add(lp + a + ".q_proj.weight", QKV, H, tkey=lp + a + ".qkv")
-                add(lp + a + ".o_proj.weight", H, nq * dh)
-                if a == "cross_attn":
-                    add(lp + a + ".gating.weight", H, H)
-            for e in range(E):              # gate_e | up_e are adjacent: one [2 I, din] matrix per expert, transposed [din, 2 I]
-                add(f"{lp}mlp.experts.expert_{e}.gate_proj.weight", 2 * I, din, tkey=f"{lp}mlp.experts.expert_{e}.gu")
-            for e in range(E):
-                add(f"{lp}mlp.experts.expert_{e}.down_proj.weight", H, I)
-        self.flatT = torch.zeros(toff, dtype=torch.bfloat16, device=dev)
-        tab, tile0 = [], 0
-        for src, rows, cols, ldt, dst_t in entries:
-            tab += [src, src, dst_t, rows | (cols << 32), ldt | (tile0 << 32)]
             tile0 += ((rows + 31) // 32) * ((cols + 31) // 32)
-        self.n_entries, self.n_tiles = len(entries), tile0
+        self.flatT = torch.zeros(toff, dtype=torch.bfloat16, device=dev)
+        self.n_entries, self.n_tiles = len(tab) // 5, tile0
         self.table = torch.tensor(tab, dtype=torch.int64, device=dev)
         self.params16 = layout.views(self.flat16)
 
@@ -257,15 +252,18 @@ class _Workspace:
     sample of each batch, ref:SeqRec/datasets/collator.py:59-67) reuse one allocation instead of freeing and
     re-creating tens of GB per micro-batch; ``Engine.reserve`` sizes it once for the largest batch up front.
     ``act`` is the dtype of the activations the GEMMs read and write: fp32, or bf16 for the AMP variant (the
-    residual stream, the normalisation statistics and everything the optimizer touches stay fp32)."""
+    residual stream, the normalisation statistics and everything the optimizer touches stay fp32).  The buffers are sized
+    from the config (its cross-attention and injecting layers); ``bind_masks(ws, B, S)`` adds the model's attention-mask
+    buffers (``Engine._bind_masks``)."""
 
-    def __init__(self, cfg: Qwen3MultiConfig, device, train: bool, act: torch.dtype = torch.float32, spill: bool = True):
+    def __init__(self, cfg, device, train: bool, act: torch.dtype = torch.float32, spill: bool = True, bind_masks=None):
         self.cfg, self.device, self.train, self.act, self.spill = cfg, device, train, act, spill
+        self.bind_masks = bind_masks
         self._store: Dict[str, torch.Tensor] = {}
         self.B = self.S = self.T = 0
         self.loss_sum = torch.zeros(1, dtype=torch.float32, device=device)
         self.count = torch.zeros(1, dtype=torch.float32, device=device)
-        self.session: Optional[dict] = None        # span_self / span_cross / pos_ids of the session variant
+        self.bad_label = torch.zeros(1, dtype=torch.int32, device=device)
 
     def _buf(self, name: str, shape, dtype=torch.float32) -> torch.Tensor:
         n = math.prod(shape)
@@ -283,33 +281,17 @@ class _Workspace:
         if (B, S) == (self.B, self.S):
             return self
         cfg, train, act = self.cfg, self.train, self.act
-        f32, i32 = torch.float32, torch.int32
+        f32 = torch.float32
         self.B, self.S, self.T = B, S, B * S
         T, H = self.T, cfg.hidden_size
         nq, nkv, dh, I = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.intermediate_size
         NQ, NKV = nq * dh, nkv * dh
         QKV = NQ + 2 * NKV
-        L, E = cfg.num_hidden_layers, cfg.num_experts
-        din_max = H + cfg.behavior_embedding_dim
-        n_t32 = (S + 31) // 32
+        L, crosses, injects = cfg.num_hidden_layers, cfg.cross_attention_decoder, cfg.behavior_injection_decoder
+        din_max = H + (cfg.behavior_embedding_dim if injects else 0)
         buf = self._buf
-        self.router = {k: buf("r_" + k, (B, S), i32) for k in
-                       ("expert", "beh_idx", "act_idx", "kl_self", "kl_cross", "ql_cross", "empty_self", "empty_cross")}
-        self.router["tile_empty_self"] = buf("r_tile_empty_self", (B, n_t32), i32)
-        self.router["tile_empty_cross"] = buf("r_tile_empty_cross", (B, n_t32), i32)
-        if "r_bad_token" not in self._store:
-            self._store["r_bad_token"] = torch.zeros(1, dtype=i32, device=self.device)
-            self._store["r_bad_label"] = torch.zeros(1, dtype=i32, device=self.device)
-        self.router["bad_token"] = self._store["r_bad_token"]
-        self.bad_label = self._store["r_bad_label"]
-        if self.session is not None:
-            self.session = None                    # rebuilt at the new shape by the next session forward
-        self.perm = buf("perm", (T,), i32)
-        self.slot = buf("slot", (T,), i32)
-        # query-row order of the cross attention (normal rows first, empty rows behind)
-        self.cross_order = (buf("co_perm", (B, S), i32), buf("co_kind", (B, n_t32), i32), buf("co_maxpos", (B, n_t32), i32))
-        self.offsets = buf("offsets", (E + 1,), i32)
-        self.work = buf("work", ((B + 1) * E,), i32)
+        if self.bind_masks is not None:
+            self.bind_masks(self, B, S)
         # logits [T, ldl]: fp32, or bf16 as the reference's autocast lm_head returns them; the bf16 row is padded to a
         # multiple of 64 columns (the head's dgrad contracts over the padded vocabulary) and the padding stays zero
         self.ldl = _round_up(cfg.vocab_size, 32 if act == f32 else 64)
@@ -325,7 +307,8 @@ class _Workspace:
         keep = train            # eval keeps one set of buffers and reuses it for every layer
         shared: Optional[dict] = None
         for l in range(L):
-            cross = l in cfg.cross_attention_decoder
+            # (eval: the shared set has the cross buffers if any layer has a cross attention)
+            cross = l in crosses or (not keep and bool(crosses))
             tag = f"l{l}_" if keep else "l_"
             if keep or shared is None:
                 d = dict(
@@ -333,7 +316,7 @@ class _Workspace:
                     k=buf(tag + "k", (T, NKV), act), ao=buf(tag + "ao", (T, NQ), act), lse=buf(tag + "lse", (B, nq, S), f32),
                     hin=buf(tag + "hin", (T, din_max), act), gu=buf(tag + "gu", (T, 2 * I), act),
                     hm=buf(tag + "hm", (T, I), act))
-                if cross or not keep:
+                if cross:
                     d.update(h2=buf(tag + "h2", (T, H), act), qkv_c=buf(tag + "qkv_c", (T, QKV), act),
                              q_c=buf(tag + "q_c", (T, NQ), act), k_c=buf(tag + "k_c", (T, NKV), act),
                              ao_c=buf(tag + "ao_c", (T, NQ), act), lse_c=buf(tag + "lse_c", (B, nq, S), f32),
@@ -341,9 +324,8 @@ class _Workspace:
                 shared = d
             self.layers.append(shared if not keep else d)
             if keep or l == 0:
-                xs = [buf(tag + "x0", (T, H), f32), buf(tag + "x1", (T, H), f32)]
-                xs.append(buf(tag + "x2", (T, H), f32) if (cross or not keep) else None)
-                self.x.append(xs)
+                self.x.append([buf(tag + "x0", (T, H), f32), buf(tag + "x1", (T, H), f32),
+                               buf(tag + "x2", (T, H), f32) if cross else None])
             else:
                 self.x.append(self.x[0])
         self.x_final = buf("x_final", (T, H), f32) if keep else self.x[0][0]
@@ -358,17 +340,39 @@ class _Workspace:
             self.dk = buf("dk", (T, NKV), act)
             self.dao = buf("dao", (T, NQ), act)
             self.delta = buf("delta", (B, nq, S), f32)
-            # one [2048, H] table of weight-gradient partial sums per RMSNorm backward of a pass (reduced together at its end),
-            # plus one scratch table for the ordered behaviour-table gradient
-            self.norm_partial = buf("norm_partial", (3 * L + 2, 2048, H), f32)
-            self.qk_partial = buf("qk_partial", (ops.qknorm_partial_numel(cfg.num_behavior + 1),), f32)
+            # one [2048, H] table of weight-gradient partial sums per RMSNorm backward of a pass (reduced together at its end):
+            # two per layer and the final norm's, one more per layer in a model with cross attention, plus one scratch
+            # table for the ordered behaviour-table gradient of the injecting layers
+            n_norm = (3 if crosses else 2) * L + 1 + (1 if injects else 0)
+            self.norm_partial = buf("norm_partial", (n_norm, 2048, H), f32)
+            # (the cross attention's q/k behaviour biases add their table gradients to the q/k-norm backward's partials)
+            self.qk_partial = buf("qk_partial", (ops.qknorm_partial_numel(cfg.num_behavior + 1 if crosses else 0),), f32)
             # dS spill of the attention backward (5 matmuls per tile pair instead of 7; gamer_attn_bwd):
             # 6.4 GB at B = 1024, shared by all layers.  GAMER_ATTN_SPILL=0 keeps the two recompute kernels.
-            import os
             self.ds_work = (buf("ds_work", (ops.attn_ds_work_numel(B, S, nq),), f32)
                             if (os.environ.get("GAMER_ATTN_SPILL", "1") != "0" and act == torch.float32 and self.spill)
                             else None)
         return self
+
+
+def _matmul_arg(dtype: str, matmul: Optional[str]) -> str:
+    if matmul is None:
+        # default of the fp32 path: products on the 16-bit matrix pipe from piece cuts (docs/DESIGN_rounds1-4.md sections 13, 15, 17);
+        # "f32" = fp32 MFMA
+        matmul = "split3" if dtype == "f32" else "f32"
+    if matmul not in ops.MATMUL_MODES:
+        raise ValueError(f"unknown matmul {matmul!r} ({sorted(ops.MATMUL_MODES)})")
+    return matmul
+
+
+def _check_split_dtype(dtype: str, matmul: str):
+    if dtype != "f32" and matmul != "f32":
+        raise ValueError("matmul='split3'/'split6'/'split9' is a form of the fp32 path; dtype='bf16' has its own GEMM")
+
+
+def _check_dtype(dtype: str):
+    if dtype not in ("f32", "bf16"):
+        raise ValueError(f"unknown dtype {dtype!r} (f32 or bf16; the reference's --fp16 is not built)")
 
 
 class Engine:
@@ -414,15 +418,38 @@ class Engine:
         uses instead of allocating its own - the nn.Module keeps one set of fp32 masters and runs them through the fp32 or the
         bf16 step depending on the caller's autocast state (gamer_amd/modeling.py)."""
         cfg.validate()
-        if matmul is None:
-            # default of the fp32 path: products on the 16-bit matrix pipe from piece cuts (docs/DESIGN_rounds1-4.md sections 13, 15, 17);
-            # "f32" = fp32 MFMA
-            matmul = "split3" if dtype == "f32" else "f32"
-        if matmul not in ops.MATMUL_MODES:
-            raise ValueError(f"unknown matmul {matmul!r} ({sorted(ops.MATMUL_MODES)})")
-        if dtype != "f32" and matmul != "f32":
-            raise ValueError("matmul='split3'/'split6'/'split9' is a form of the fp32 path; dtype='bf16' has its own GEMM")
-        self.matmul = matmul
+        matmul = _matmul_arg(dtype, matmul)
+        _check_split_dtype(dtype, matmul)
+        if variant not in ("multi", "session"):
+            raise ValueError(f"unknown variant {variant!r} (multi, session or qwen3)")
+        _check_dtype(dtype)
+        self._init_core(cfg, device, temperature, variant, dtype, matmul, share_buffers_of, deterministic)
+        if self._amax is not None and self._amax.planes is not None and cfg.hidden_size == 256 and \
+                os.environ.get("GAMER_GEMM_OSF", "0") == "1":
+            # GAMER_GEMM_OSF=1 (A/B): next to the split3 planes, the pieces of the TRANSPOSES of the weights with 256 output rows and a longer
+            # contraction (o_proj, the experts' down projection): their forward then runs on the output-stationary kernel
+            # (gamer_gemm_desc.b_planes_t).  MEASURED slower than the 128 x 128 kernel's residual epilogue (same box: 9.6
+            # against 9.4 ms per step for the sixteen launches, 210.8 against 210.2 ms per step) - off by default.
+            self._amax.planes_t = torch.zeros(_round_up(self.layout.numel, 4), dtype=torch.float32, device=self.device)
+        self.lut = cfg.behavior_lut().to(self.device)
+        # fp32 forms: the injecting layers' gate|up projection runs on the 256 hidden columns only; the behaviour-embedding columns'
+        # share (NB + 1 different rows per expert) is a table added where gate|up are consumed (csrc/inject.hip).  Rows are then
+        # sorted by (expert, behaviour).  GAMER_SPLIT_INJECT=0: the reference's concatenated [T, 320] input (A/B runs).
+        nb1 = cfg.num_behavior + 1
+        self.split_inject = bool(self.dtype != "bf16" and os.environ.get("GAMER_SPLIT_INJECT", "1") != "0" and
+                                 cfg.behavior_injection_decoder and cfg.num_experts * nb1 <= 64 and nb1 <= 16 and
+                                 cfg.behavior_embedding_dim % 4 == 0 and cfg.behavior_embedding_dim <= 256)
+
+    # the model's parts of the shared construction: parameter layout, per-layer weight views (fp32 / bf16 operands,
+    # transposed bf16 copies)
+    _layout_cls = ParamLayout
+    _layer_cls = _LayerW
+    _layer_t_cls = _LayerWT
+
+    def _init_core(self, cfg, device, temperature, variant, dtype, matmul, share_buffers_of, deterministic):
+        """What every model's constructor does once its arguments are checked: flat buffers, weight views, bf16 copies,
+        split-form planes and the A/B switches the shared forward / backward blocks read."""
+        self.matmul, self.variant, self.dtype = matmul, variant, dtype
         self.deterministic = (os.environ.get("GAMER_DETERMINISTIC", "0") == "1") if deterministic is None else bool(deterministic)
         # q / k RMSNorm + RoPE in the q|k|v projection's epilogue (gamer_gemm_desc.qk_*): built, parity-tested and measured
         # at batch 1024 - the 12 projections got 6.8 ms slower per step (their tiles now also store q_rot / k_rot, and
@@ -435,12 +462,6 @@ class Engine:
         self.fuse_qkv_bf16 = os.environ.get("GAMER_FUSE_QKV_BF16", "0") == "1"
         # attention products of the split forms on the bf16 pipe too (csrc/attention_split.hip); False keeps fp32-MFMA attention
         self.split_attention = True
-        if variant not in ("multi", "session"):
-            raise ValueError(f"unknown variant {variant!r} (multi, session or qwen3)")
-        if dtype not in ("f32", "bf16"):
-            raise ValueError(f"unknown dtype {dtype!r} (f32 or bf16; the reference's --fp16 is not built)")
-        self.variant = variant
-        self.dtype = dtype
         self.act_dtype = torch.float32 if dtype == "f32" else torch.bfloat16
         if not torch.cuda.is_available():
             raise RuntimeError("gamer_amd.Engine needs a HIP device (there is no CPU fallback)")
@@ -449,7 +470,7 @@ class Engine:
         self.cfg = cfg
         self.device = torch.device(device)
         self.temperature = float(temperature)
-        self.layout = ParamLayout(cfg)
+        self.layout = self._layout_cls(cfg)
         n = self.layout.numel
         if share_buffers_of is not None:
             if share_buffers_of.layout.numel != n or share_buffers_of.device != self.device:
@@ -463,15 +484,15 @@ class Engine:
         self.params = self.layout.views(self.flat_p)
         self.grads = self.layout.views(self.flat_g)
         L = cfg.num_hidden_layers
-        self.W = [_LayerW(cfg, self.layout, self.flat_p, l) for l in range(L)]
-        self.G = [_LayerW(cfg, self.layout, self.flat_g, l) for l in range(L)]
+        self.W = [self._layer_cls(cfg, self.layout, self.flat_p, l) for l in range(L)]
+        self.G = [self._layer_cls(cfg, self.layout, self.flat_g, l) for l in range(L)]
         # matrices the GEMMs read: the fp32 masters themselves, or their bf16 copies (+ transposed copies for dgrad)
         self.shadow: Optional[Bf16Shadow] = None
         self.Wm, self.WT = self.W, None
         if dtype == "bf16":
             self.shadow = Bf16Shadow(cfg, self.layout, self.flat_p)
-            self.Wm = [_LayerW(cfg, self.layout, self.shadow.flat16, l) for l in range(L)]
-            self.WT = [_LayerWT(cfg, self.shadow, l) for l in range(L)]
+            self.Wm = [self._layer_cls(cfg, self.layout, self.shadow.flat16, l) for l in range(L)]
+            self.WT = [self._layer_t_cls(cfg, self.shadow, l) for l in range(L)]
         # split forms, opt-in (GAMER_SPLIT_PLANES=1): the fp32 masters cut once per step into three bf16 planes - the B operand
         # of every forward / input-gradient GEMM is a weight, and without this every row tile of the activations cuts its weight
         # tile again (half of a K-step's cut instructions).  Bit-identical results (tests/test_ops_gpu.py); measured at batch
@@ -495,13 +516,6 @@ class Engine:
                 # the parameters' fp16 pieces, packed at their values' offsets and rebuilt at the start of every pass (98 MB read,
                 # 98 MB written): the B operand of the forward and input-gradient GEMMs is then staged without its cut
                 self._amax.planes = torch.zeros(_round_up(n, 4), dtype=torch.float32, device=self.device)
-                if cfg.hidden_size == 256 and os.environ.get("GAMER_GEMM_OSF", "0") == "1":
-                    # GAMER_GEMM_OSF=1 (A/B): ... and the pieces of the TRANSPOSES of the weights with 256 output rows and a longer
-                    # contraction (o_proj, the experts' down projection): their forward then runs on the output-stationary kernel
-                    # (gamer_gemm_desc.b_planes_t).  MEASURED slower than the 128 x 128 kernel's residual epilogue (same box: 9.6
-                    # against 9.4 ms per step for the sixteen launches, 210.8 against 210.2 ms per step) - off by default.
-                    self._amax.planes_t = torch.zeros(_round_up(n, 4), dtype=torch.float32, device=self.device)
-        self.lut = cfg.behavior_lut().to(self.device)
         self._rope: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._ws: Dict[bool, _Workspace] = {}
         self.ws: Optional[_Workspace] = None
@@ -512,13 +526,6 @@ class Engine:
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._norm_out_table = None                 # (addresses, device array) of the RMSNorm weight gradients in backward order
         self.fuse_swiglu_bwd = os.environ.get("GAMER_FUSE_SWIGLU_BWD", "1") != "0"     # (A/B switch; split3 only)
-        # fp32 forms: the injecting layers' gate|up projection runs on the 256 hidden columns only; the behaviour-embedding columns'
-        # share (NB + 1 different rows per expert) is a table added where gate|up are consumed (csrc/inject.hip).  Rows are then
-        # sorted by (expert, behaviour).  GAMER_SPLIT_INJECT=0: the reference's concatenated [T, 320] input (A/B runs).
-        nb1 = cfg.num_behavior + 1
-        self.split_inject = bool(self.dtype != "bf16" and os.environ.get("GAMER_SPLIT_INJECT", "1") != "0" and
-                                 cfg.behavior_injection_decoder and cfg.num_experts * nb1 <= 64 and nb1 <= 16 and
-                                 cfg.behavior_embedding_dim % 4 == 0 and cfg.behavior_embedding_dim <= 256)
         self.ordered_embedding_grad = os.environ.get("GAMER_EMBEDDING_ATOMICS", "0") == "0"   # (1: the float-atomics scatter)
         self._check_deterministic_embedding()
         self._saved = None
@@ -572,9 +579,31 @@ class Engine:
             # it - unless the session variant sends its span calls to the fp32-MFMA kernels
             # (the three-product form takes the session variant's key spans itself)
             spill = not (self.split_attention and self.matmul != "f32" and
-                         (self.variant == "multi" or (self.matmul == "split3" and self.h2_attention)))
-            self._ws[train] = _Workspace(self.cfg, self.device, train, self.act_dtype, spill=spill)
+                         (self.variant != "session" or (self.matmul == "split3" and self.h2_attention)))
+            self._ws[train] = _Workspace(self.cfg, self.device, train, self.act_dtype, spill, self._bind_masks)
         return self._ws[train].bind(B, S)
+
+    @staticmethod
+    def _bind_masks(ws: _Workspace, B: int, S: int):
+        """The router's outputs (attention masks, expert / behaviour / action indices), the expert lists and the query-row
+        order of the cross attention, at the workspace's new shape."""
+        i32 = torch.int32
+        T, E, n_t32 = B * S, ws.cfg.num_experts, (S + 31) // 32
+        buf = ws._buf
+        ws.router = {k: buf("r_" + k, (B, S), i32) for k in
+                     ("expert", "beh_idx", "act_idx", "kl_self", "kl_cross", "ql_cross", "empty_self", "empty_cross")}
+        ws.router["tile_empty_self"] = buf("r_tile_empty_self", (B, n_t32), i32)
+        ws.router["tile_empty_cross"] = buf("r_tile_empty_cross", (B, n_t32), i32)
+        if "r_bad_token" not in ws._store:
+            ws._store["r_bad_token"] = torch.zeros(1, dtype=i32, device=ws.device)
+        ws.router["bad_token"] = ws._store["r_bad_token"]
+        ws.session = None                          # span_self / span_cross / pos_ids of the session variant, rebuilt at the
+        ws.perm = buf("perm", (T,), i32)           # new shape by the next session forward
+        ws.slot = buf("slot", (T,), i32)
+        # query-row order of the cross attention (normal rows first, empty rows behind)
+        ws.cross_order = (buf("co_perm", (B, S), i32), buf("co_kind", (B, n_t32), i32), buf("co_maxpos", (B, n_t32), i32))
+        ws.offsets = buf("offsets", (E + 1,), i32)
+        ws.work = buf("work", ((B + 1) * E,), i32)
 
     def reserve(self, B: int, S: int, train: bool = True):
         """Size the workspace once for the largest batch that will be seen (e.g. S = (max_his_len + 1) * num_positions),
@@ -623,50 +652,17 @@ class Engine:
                              "(the router assumes item-aligned sequences, router.py:78-81)")
         if train and (act_zero_col is not None or uniform_len not in (0, S)):
             raise ValueError("act_zero_col / uniform_len are evaluation-only options")
-        if kv_dest is not None and train:
-            raise ValueError("kv_dest is an evaluation-only option (the backward reads the workspace's q|k|v and keys)")
-        if last_row_logits and (train or labels is not None):
-            raise ValueError("last_row_logits is an evaluation-only option")
-        if hidden_sink is not None and last_row_logits:
-            raise ValueError("hidden_sink needs the full-sequence forward")
-        bf16 = self.dtype == "bf16"
-        if bf16:
-            if last_row_logits or uniform_len not in (0, S):
-                raise NotImplementedError("generation (cached decode / re-run scoring) is built for dtype='f32' only")
-            self.shadow.refresh()                    # the masters may have been updated by any optimizer since the last call
-        if self.weight_planes is not None:
-            ops.split3_planes(self.flat_p, self.weight_planes)     # likewise: 98 MB read, 147 MB written, once per forward
-        T, H = B * S, cfg.hidden_size
-        nq, nkv, dh, I, E = (cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.intermediate_size,
-                             cfg.num_experts)
-        NQ, NKV = nq * dh, nkv * dh
-        QKV = NQ + 2 * NKV
-        eps = float(cfg.rms_norm_eps)
-        use_drop = train if dropout is None else dropout
-        p_res = float(cfg.dropout_rate) if use_drop else 0.0
-        p_att = float(cfg.attention_dropout) if use_drop else 0.0
-        if use_drop:
-            self.dropout_step += 1
-        ws = self.workspace(B, S, train)
-        self.ws = ws
-        if self._amax is not None:
-            # matmul="split3": maxima of the tensors that do not change between their first GEMM of this pass and the backward
-            # (saved GEMM inputs, the parameters) are measured once; everything else per GEMM (ops.amax_reuse)
-            self._amax.reset()
-            if train:       # (the evaluation workspace shares one set of buffers between the layers: nothing is stable there)
-                self._amax.stable(ws.xn, *[A[k] for A in ws.layers for k in ("h1", "h2", "ao", "ao_c", "hin", "hm") if k in A])
-                if self.h2_attention:       # the attention operands saved for the backward: q, k (after norm + RoPE) and the v columns
-                    self._amax.stable(*[A[k] for A in ws.layers for k in ("q", "k", "q_c", "k_c") if k in A],
-                                      *[A[k][:, NQ + NKV:] for A in ws.layers for k in ("qkv", "qkv_c") if k in A])
-        ids = input_ids.to(self.device, torch.int64).contiguous()
-        am = attention_mask.to(self.device, torch.int64).contiguous() if attention_mask is not None else None
+        c = self._prologue(input_ids, attention_mask, labels, train, dropout, cfg.dropout_rate, kv_dest, hidden_sink,
+                           last_row_logits, uniform_len,
+                           eval_only="last_row_logits is an evaluation-only option" if last_row_logits else None,
+                           f32_only=("generation (cached decode / re-run scoring) is built for dtype='f32' only"
+                                     if last_row_logits or uniform_len not in (0, S) else None))
+        ws, ids, am, bf16 = c.ws, c.ids, c.am, c.bf16
+        T, H, nq, nkv, I, E = c.T, c.H, c.nq, c.nkv, c.I, cfg.num_experts
+        NQ, NKV, QKV, eps, scale, cos, sin, p_res = c.NQ, c.NKV, c.QKV, c.eps, c.scale, c.cos, c.sin, c.p_res
         act = actions.to(self.device, torch.int64).contiguous() if actions is not None else None
-        lab = labels.to(self.device, torch.int64).contiguous() if labels is not None else None
         r = ws.router
         r["bad_token"].zero_()
-        if lab is not None:
-            ws.bad_label.zero_()
-            ops.check_labels(lab, cfg.vocab_size, IGNORE_INDEX, ws.bad_label)
         ops.router_fwd(ids, am, act, self.lut, cfg.num_positions, cfg.pad_token_id, cfg.eos_token_id, r)
         if act_zero_col is None and S % cfg.num_positions == 1:
             # the reference's router counts (S + 3) // 5 items (router.py:160-163), so a trailing behaviour token
@@ -717,72 +713,20 @@ class Engine:
             # (bf16: the rows without an allowed key - 70 % of them in the cross attention - output 0; sorted behind the
             # others they cost nothing)
             ops.attn_row_order(r["empty_cross"], *ws.cross_order)
-        cos, sin = self.rope(S)
-        scale = float(dh) ** -0.5
-        x = ws.x[0][0]
-        ops.embedding_fwd(ids, self.params["model.embed_tokens.weight"], x)
-        t0, t1 = ws.tmpH[0], ws.tmpH[1]
-        emb_m = self.shadow.params16["model.embed_tokens.weight"] if bf16 else self.params["model.embed_tokens.weight"]
+        ops.embedding_fwd(ids, self.params["model.embed_tokens.weight"], ws.x[0][0])
 
         # fp32: the q|k|v projection carries per-head RMSNorm + RoPE in its epilogue when its tiles are whole
         fuse_qkv = ((self.fuse_qkv_bf16 if bf16 else self.fuse_qkv) and ops.qkv_fused_ok(ws.layers[0]["h1"], T, QKV)
                     and cfg.head_dim == 64)
-
-        # matmul="split6" / "split9": the attention products run on the bf16 pipe as well (gamer_attn_fwd_split: exact
-        # three-way cuts, six piece products); the session variant's key spans and the evaluation re-run path stay on the
-        # fp32-MFMA kernels
-        split_attn = self.split_attention and self.matmul != "f32" and not bf16
-
-        # (three-product attention) max |v| out of the q|k|v projection's epilogue instead of a pass over the v columns; the cross
-        # attention adds its behaviour bias to v afterwards (qknorm_rope_fwd), so only the self attention's v can take it
-        h2_now = split_attn and self.h2_attention and self.matmul == "split3" and p_att < 0.75
-
-        # (three-product form) the SwiGLU forward as the epilogue of the experts' gate|up projection (gamer_gemm_desc.sw_hm); A/B switch
-        fuse_swiglu_fwd = (not bf16 and self.matmul == "split3" and os.environ.get("GAMER_FUSE_SWIGLU_FWD", "1") != "0")
-
-        def v_amax(qkv_buf):
-            return dict(c_amax=(qkv_buf[:, NQ + NKV:], NQ + NKV)) if (h2_now and not bf16 and self.gemm_c_amax) else {}
-
-        def attention(qb, kb, vb, kl_, ql_, empty_, tile_empty_, seed_, ob, lseb, order_, span_):
-            if split_attn and (span_ is None or h2_now):
-                # (per-query key spans - the session variant - are built for the three-product form; the six-product form sends
-                # those calls to the fp32-MFMA kernels below)
-                ops.attn_fwd_split(qb, NQ, kb, NKV, vb, QKV, kl_, ql_, empty_, B, S, nq, nkv, scale, p_att, seed_, ob, lseb,
-                                   order=order_, h2=h2_now, uniform_len=uniform_len, q_span=span_)
-            elif bf16:
-                ord16 = (order_[0], order_[2], empty_) if (order_ is not None and span_ is None) else None
-                ops.attn_fwd_bf16(qb, NQ, kb, NKV, vb, QKV, kl_, ql_, B, S, nq, nkv, scale, p_att, seed_, ob, lseb,
-                                  q_span=span_, order=ord16)
-            else:
-                ops.attn_fwd(qb, NQ, kb, NKV, vb, QKV, kl_, ql_, empty_, tile_empty_, B, S, nq, nkv, scale, p_att, seed_,
-                             ob, lseb, order=order_, uniform_len=uniform_len, q_span=span_)
+        attention = functools.partial(self._attention, c)
 
         for l in range(cfg.num_hidden_layers):
             W, A, xs = self.W[l], ws.layers[l], ws.x[l]
             Wm = self.Wm[l]                          # GEMM operands (fp32 masters or bf16 copies); W: norms, tables
             if hidden_sink is not None:
                 hidden_sink.append(xs[0].view(B, S, H).clone())
-            # ---- self attention (model.py:204-217) ----
-            ops.rmsnorm_fwd(xs[0], W.ln1, eps, A["h1"])
-            # (kv_dest: the q|k|v projection and the rotated keys of this layer are written where the caller keeps them - a
-            # generation's prompt caches - instead of the workspace's buffers and a copy)
-            qkv_s, k_s = kv_dest(l, "self") if kv_dest is not None else (A["qkv"], A["k"])
-            if fuse_qkv:
-                # per-head RMSNorm + RoPE of q / k in the projection's epilogue (model.py:88-101 in one kernel)
-                ops.gemm(A["h1"], H, 1, Wm.self_attn["qkv"], H, 1, qkv_s, QKV, T, QKV, H,
-                         qknorm=dict(wq=W.self_attn["qn"], wk=W.self_attn["kn"], eps=eps, cos=cos, sin=sin, q_rot=A["q"],
-                                     k_rot=k_s, pos_ids=pos_ids, S=S, nq=nq, nkv=nkv))
-            else:
-                ops.linear_fwd(A["h1"], H, Wm.self_attn["qkv"], H, qkv_s, QKV, T, QKV, H, **v_amax(qkv_s))
-                ops.qknorm_rope_fwd(qkv_s, S, nq, nkv, W.self_attn["qn"], W.self_attn["kn"], eps, cos, sin, A["q"], k_s,
-                                    pos_ids=pos_ids)
-            if kv_sink is not None:
-                kv_sink(l, "self", k_s, qkv_s[:, NQ + NKV:])
-            attention(A["q"], k_s, qkv_s[:, NQ + NKV:], r["kl_self"], None, r["empty_self"], r["tile_empty_self"],
-                      self._seed(l, 0), A["ao"], A["lse"], None, span_self)
-            # o_proj with the residual add + dropout fused into the GEMM epilogue (model.py:149,217)
-            ops.gemm(A["ao"], NQ, 1, Wm.self_attn["o"], NQ, 1, xs[1], H, T, H, NQ, resid=xs[0], p_drop=p_res,
-                     seed=self._seed(l, 1))
+            # ---- self attention (model.py:204-217), o_proj with the residual add + dropout (model.py:149,217) ----
+            self._self_attention(c, l, r, span_self, pos_ids, fuse_qkv, kv_dest, kv_sink)
             xcur = xs[1]
             # ---- behaviour-level "cross" attention (model.py:220-235) ----
             if W.cross:
@@ -864,7 +808,7 @@ class Engine:
                 ops.rmsnorm_fwd(xcur, W.ln3, eps, hin, H, ws.slot)
                 tb = ws._buf((f"l{l}_" if train else "l_") + "inject_tbl", (E * NB1, 2 * I))
                 ops.inject_table_fwd(W.beh, W.gu, din, H, E, 2 * I, tb)
-                if fuse_swiglu_fwd:
+                if c.fuse_swiglu_fwd:
                     # one call: gate|up AND hm (the SwiGLU forward as the projection's epilogue; rows grouped by (expert, behaviour))
                     ops.gemm(hin, H, 1, Wm.gu, din, 1, A["gu"], 2 * I, T, 2 * I, H, strideB=2 * I * din, groups=E * NB1,
                              group_offsets=ws.grp_offsets, group_div=NB1, p_drop=p_res, seed=self._seed(l, 4),
@@ -878,7 +822,7 @@ class Engine:
                     ops.rowtable_fwd(W.beh, r["beh_idx"], A["hin"], din, H, ws.slot)
                 # gate_proj and up_proj of the position's expert in ONE grouped GEMM against the stacked [2 I, din] weight (FFN.py:25-27:
                 # both read the same input): A["gu"][:, :I] = gate, [:, I:] = up
-                if fuse_swiglu_fwd and din == H:
+                if c.fuse_swiglu_fwd and din == H:
                     ops.gemm(A["hin"], din, 1, Wm.gu, din, 1, A["gu"], 2 * I, T, 2 * I, din, strideB=2 * I * din, p_drop=p_res,
                              seed=self._seed(l, 4), swiglu_fwd=(A["hm"], None, None), **grp)
                 else:
@@ -890,8 +834,123 @@ class Engine:
             ops.gemm(A["hm"], I, 1, Wm.down, I, 1, xnext, H, T, H, I, strideB=H * I, resid=xcur, row_map=ws.perm,
                      p_drop=p_res, seed=self._seed(l, 5), **grp)
         # ---- final norm, tied head, temperature CE (model.py:869,1001,904-922) ----
-        V = cfg.vocab_size
-        if last_row_logits:
+        return self._head(c, x_last if last_row_logits else None, num_items_in_batch, hidden_sink)
+
+    def _pass(self, B: int, S: int, p_res: float, p_att: float) -> SimpleNamespace:
+        """Shapes, dropout and kernel forms of one forward or backward pass (the context of the shared blocks below)."""
+        cfg = self.cfg
+        c = SimpleNamespace(B=B, S=S, T=B * S, H=cfg.hidden_size, nq=cfg.num_attention_heads, nkv=cfg.num_key_value_heads,
+                            dh=cfg.head_dim, I=cfg.intermediate_size, eps=float(cfg.rms_norm_eps), p_res=p_res, p_att=p_att,
+                            bf16=self.dtype == "bf16")
+        c.NQ, c.NKV = c.nq * c.dh, c.nkv * c.dh
+        c.QKV = c.NQ + 2 * c.NKV
+        c.scale = float(c.dh) ** -0.5
+        c.cos, c.sin = self.rope(S)
+        # matmul="split6" / "split9": the attention products run on the bf16 pipe as well (gamer_attn_fwd_split: exact
+        # three-way cuts, six piece products); the session variant's key spans and the evaluation re-run path stay on the
+        # fp32-MFMA kernels
+        c.split_attn = self.split_attention and self.matmul != "f32" and not c.bf16
+        # (three-product attention) max |v| out of the q|k|v projection's epilogue instead of a pass over the v columns
+        c.h2 = c.split_attn and self.h2_attention and self.matmul == "split3" and p_att < 0.75
+        # (three-product form) the SwiGLU forward as the epilogue of the gate|up projection (gamer_gemm_desc.sw_hm); A/B switch
+        c.fuse_swiglu_fwd = not c.bf16 and self.matmul == "split3" and os.environ.get("GAMER_FUSE_SWIGLU_FWD", "1") != "0"
+        c.fuse_swiglu_bwd = (c.bf16 or self.matmul == "split3") and self.fuse_swiglu_bwd
+        return c
+
+    def _prologue(self, input_ids, attention_mask, labels, train, dropout, dropout_rate, kv_dest, hidden_sink,
+                  last_row_logits, uniform_len, eval_only: Optional[str], f32_only: Optional[str]) -> SimpleNamespace:
+        """The start of every model's forward: argument checks (``eval_only`` / ``f32_only``: the model's message when one
+        of its evaluation-only / fp32-only options is set), bf16 copies or split planes of the masters, the dropout step,
+        the workspace, the split3 maxima, the inputs on the device and the label check.  ``dropout_rate``: the model's
+        residual dropout.  Returns the pass context (``_pass``) with ws, ids, am, lab and uniform_len."""
+        B, S = input_ids.shape
+        if kv_dest is not None and train:
+            raise ValueError("kv_dest is an evaluation-only option (the backward reads the workspace's q|k|v and keys)")
+        if eval_only and (train or labels is not None):
+            raise ValueError(eval_only)
+        if hidden_sink is not None and last_row_logits:
+            raise ValueError("hidden_sink needs the full-sequence forward")
+        if self.dtype == "bf16":
+            if f32_only:
+                raise NotImplementedError(f32_only)
+            self.shadow.refresh()                    # the masters may have been updated by any optimizer since the last call
+        if self.weight_planes is not None:
+            ops.split3_planes(self.flat_p, self.weight_planes)     # likewise: 98 MB read, 147 MB written, once per forward
+        use_drop = train if dropout is None else dropout
+        c = self._pass(B, S, float(dropout_rate) if use_drop else 0.0,
+                       float(self.cfg.attention_dropout) if use_drop else 0.0)
+        if use_drop:
+            self.dropout_step += 1
+        ws = c.ws = self.ws = self.workspace(B, S, train)
+        if self._amax is not None:
+            # matmul="split3": maxima of the tensors that do not change between their first GEMM of this pass and the backward
+            # (saved GEMM inputs, the parameters) are measured once; everything else per GEMM (ops.amax_reuse)
+            self._amax.reset()
+            if train:       # (the evaluation workspace shares one set of buffers between the layers: nothing is stable there)
+                self._amax.stable(ws.xn, *[A[k] for A in ws.layers for k in ("h1", "h2", "ao", "ao_c", "hin", "hm") if k in A])
+                if self.h2_attention:       # the attention operands saved for the backward: q, k (after norm + RoPE) and the v columns
+                    self._amax.stable(*[A[k] for A in ws.layers for k in ("q", "k", "q_c", "k_c") if k in A],
+                                      *[A[k][:, c.NQ + c.NKV:] for A in ws.layers for k in ("qkv", "qkv_c") if k in A])
+        c.ids = input_ids.to(self.device, torch.int64).contiguous()
+        c.am = attention_mask.to(self.device, torch.int64).contiguous() if attention_mask is not None else None
+        c.lab = labels.to(self.device, torch.int64).contiguous() if labels is not None else None
+        c.uniform_len, c.train = uniform_len, train
+        if c.lab is not None:
+            ws.bad_label.zero_()
+            ops.check_labels(c.lab, self.cfg.vocab_size, IGNORE_INDEX, ws.bad_label)
+        return c
+
+    def _attention(self, c, qb, kb, vb, kl_, ql_, empty_, tile_empty_, seed_, ob, lseb, order_, span_):
+        """Attention forward in the pass's form (three- / six-product split, bf16 or fp32 MFMA)."""
+        B, S, nq, nkv, NQ, NKV, QKV = c.B, c.S, c.nq, c.nkv, c.NQ, c.NKV, c.QKV
+        if c.split_attn and (span_ is None or c.h2):
+            # (per-query key spans - the session variant - are built for the three-product form; the six-product form sends
+            # those calls to the fp32-MFMA kernels below)
+            ops.attn_fwd_split(qb, NQ, kb, NKV, vb, QKV, kl_, ql_, empty_, B, S, nq, nkv, c.scale, c.p_att, seed_, ob, lseb,
+                               order=order_, h2=c.h2, uniform_len=c.uniform_len, q_span=span_)
+        elif c.bf16:
+            ord16 = (order_[0], order_[2], empty_) if (order_ is not None and span_ is None) else None
+            ops.attn_fwd_bf16(qb, NQ, kb, NKV, vb, QKV, kl_, ql_, B, S, nq, nkv, c.scale, c.p_att, seed_, ob, lseb,
+                              q_span=span_, order=ord16)
+        else:
+            ops.attn_fwd(qb, NQ, kb, NKV, vb, QKV, kl_, ql_, empty_, tile_empty_, B, S, nq, nkv, c.scale, c.p_att, seed_,
+                         ob, lseb, order=order_, uniform_len=c.uniform_len, q_span=span_)
+
+    def _self_attention(self, c, l: int, masks: dict, span, pos_ids, fuse_qkv: bool, kv_dest, kv_sink):
+        """Layer l's self-attention block: ws.x[l][1] = x + dropout(o_proj(attention(q/k-norm + RoPE of
+        q|k|v(input_layernorm(x))))), x = ws.x[l][0].  ``masks``: kl_self / empty_self / tile_empty_self; ``span`` /
+        ``pos_ids``: per-query key spans and RoPE positions (None: causal, 0..S-1)."""
+        W, Wm, A, xs = self.W[l], self.Wm[l], c.ws.layers[l], c.ws.x[l]
+        T, H, NQ, NKV, QKV, eps = c.T, c.H, c.NQ, c.NKV, c.QKV, c.eps
+        ops.rmsnorm_fwd(xs[0], W.ln1, eps, A["h1"])
+        # (kv_dest: the q|k|v projection and the rotated keys of this layer are written where the caller keeps them - a
+        # generation's prompt caches - instead of the workspace's buffers and a copy)
+        qkv_s, k_s = kv_dest(l, "self") if kv_dest is not None else (A["qkv"], A["k"])
+        if fuse_qkv:
+            # per-head RMSNorm + RoPE of q / k in the projection's epilogue (model.py:88-101 in one kernel)
+            ops.gemm(A["h1"], H, 1, Wm.self_attn["qkv"], H, 1, qkv_s, QKV, T, QKV, H,
+                     qknorm=dict(wq=W.self_attn["qn"], wk=W.self_attn["kn"], eps=eps, cos=c.cos, sin=c.sin, q_rot=A["q"],
+                                 k_rot=k_s, pos_ids=pos_ids, S=c.S, nq=c.nq, nkv=c.nkv))
+        else:
+            v_amax = dict(c_amax=(qkv_s[:, NQ + NKV:], NQ + NKV)) if (c.h2 and self.gemm_c_amax) else {}
+            ops.linear_fwd(A["h1"], H, Wm.self_attn["qkv"], H, qkv_s, QKV, T, QKV, H, **v_amax)
+            ops.qknorm_rope_fwd(qkv_s, c.S, c.nq, c.nkv, W.self_attn["qn"], W.self_attn["kn"], eps, c.cos, c.sin, A["q"], k_s,
+                                pos_ids=pos_ids)
+        if kv_sink is not None:
+            kv_sink(l, "self", k_s, qkv_s[:, NQ + NKV:])
+        self._attention(c, A["q"], k_s, qkv_s[:, NQ + NKV:], masks["kl_self"], None, masks["empty_self"],
+                        masks["tile_empty_self"], self._seed(l, 0), A["ao"], A["lse"], None, span)
+        # o_proj with the residual add + dropout fused into the GEMM epilogue
+        ops.gemm(A["ao"], NQ, 1, Wm.self_attn["o"], NQ, 1, xs[1], H, T, H, NQ, resid=xs[0], p_drop=c.p_res,
+                 seed=self._seed(l, 1))
+
+    def _head(self, c, x_last: Optional[torch.Tensor], num_items_in_batch, hidden_sink):
+        """Final norm, tied head and temperature CE of the pass; returns forward()'s (loss, logits).  ``x_last``: the
+        residual stream of every sample's last position after the last layer (a generation's prompt pass,
+        ``last_row_logits``) - the head then runs on those B rows only."""
+        ws, B, S, H, eps = c.ws, c.B, c.S, c.H, c.eps
+        V = self.cfg.vocab_size
+        if x_last is not None:
             xn = torch.empty_like(x_last)
             ops.rmsnorm_fwd(x_last, self.params["model.norm.weight"], eps, xn)
             small = torch.empty(B, ws.ldl, dtype=torch.float32, device=self.device)
@@ -902,10 +961,12 @@ class Engine:
         ops.rmsnorm_fwd(ws.x_final, self.params["model.norm.weight"], eps, ws.xn)
         if hidden_sink is not None:
             hidden_sink.append(ws.xn.view(B, S, H).clone())
+        emb_m = self.shadow.params16["model.embed_tokens.weight"] if c.bf16 else self.params["model.embed_tokens.weight"]
         # with labels the logits leave the head GEMM already divided by the temperature (its alpha; model.py:913 divides them in place):
         # the loss kernel then only reads them (fp32 engine; the bf16 head rounds to bf16 first, as the reference's autocast does)
+        lab = c.lab
         head_alpha = (1.0 / self.temperature) if (lab is not None and ws.logits.dtype == torch.float32) else 1.0
-        ops.linear_fwd(ws.xn, H, emb_m, H, ws.logits, ws.ldl, T, V, H, alpha=head_alpha)
+        ops.linear_fwd(ws.xn, H, emb_m, H, ws.logits, ws.ldl, c.T, V, H, alpha=head_alpha)
         loss = None
         if lab is not None:
             ops.ce_fwd(ws.logits, ws.ldl, lab, V, 1.0 if head_alpha != 1.0 else self.temperature, IGNORE_INDEX, ws.lse_ce,
@@ -918,10 +979,9 @@ class Engine:
                 loss = ws.loss_sum[0] / float(num_items_in_batch)
             else:
                 loss = ws.loss_sum[0] / ws.count[0]
-        self._saved = dict(ids=ids, labels=lab, num_items=num_items_in_batch, train=train, p_res=p_res, p_att=p_att,
+        self._saved = dict(ids=c.ids, labels=lab, num_items=num_items_in_batch, train=c.train, p_res=c.p_res, p_att=c.p_att,
                            B=B, S=S, dropout_step=self.dropout_step)
-        logits = ws.logits.view(B, S, ws.ldl)[:, :, :V]
-        return loss, logits
+        return loss, ws.logits.view(B, S, ws.ldl)[:, :, :V]
 
     def check_inputs(self):
         """Host-synchronising validation (what the reference would raise on): unknown behaviour tokens."""
@@ -944,114 +1004,36 @@ class Engine:
     def zero_grad(self):
         ops.fill(self.flat_g, 0.0)
 
+    @ops.scoped_f32_matmul(lambda self, *a: self.matmul, lambda self, *a: self._planes())
+    @ops.scoped_amax(lambda self, *a: self._amax)
     def backward(self, dloss: float = 1.0, layer_done=None, dloss_dev: Optional[torch.Tensor] = None):
+        sv = self._saved
+        if sv is None or not sv["train"] or sv["labels"] is None:
+            raise RuntimeError("backward() needs forward(train=True, labels=...) first")
         with ops.deterministic(True if self.deterministic else ops.DETERMINISTIC_WGRAD, bf16=True if self.deterministic else None):
             return self._backward(dloss, layer_done, dloss_dev)
 
-    @ops.scoped_f32_matmul(lambda self, *a: self.matmul, lambda self, *a: self._planes())
-    @ops.scoped_amax(lambda self, *a: self._amax)
     def _backward(self, dloss: float = 1.0, layer_done=None, dloss_dev: Optional[torch.Tensor] = None):
         """Accumulates d(loss)*dloss into the flat gradient buffer (call zero_grad() first for a fresh
         window).  Needs a forward(..., labels=..., train=True) before it.  ``dloss_dev``: fp32 device scalar that
         multiplies ``dloss`` (the module path hands autograd's incoming gradient over without reading it on the host).  ``layer_done(l)`` is called as
         soon as every kernel writing layer l's weight gradients has been enqueued (data-parallel
         all-reduce overlap, gamer_amd.dp)."""
-        sv = self._saved
-        if sv is None or not sv["train"] or sv["labels"] is None:
-            raise RuntimeError("backward() needs forward(train=True, labels=...) first")
-        cfg, ws = self.cfg, self.ws
-        B, S = sv["B"], sv["S"]
+        cfg = self.cfg
+        c = self._backward_head(dloss, dloss_dev, rows=self.ws.slot)
+        ws, B, S, T, H, I, E = c.ws, c.B, c.S, c.T, c.H, c.I, cfg.num_experts
+        nq, nkv, NQ, NKV, QKV, eps, cos, sin, p_res = c.nq, c.nkv, c.NQ, c.NKV, c.QKV, c.eps, c.cos, c.sin, c.p_res
+        NB1 = cfg.num_behavior + 1
         span_self = span_cross = pos_ids = None
         if self.variant == "session":
             span_self, span_cross, pos_ids = ws.session["span_self"], ws.session["span_cross"], ws.session["pos_ids"]
-        T, H = B * S, cfg.hidden_size
-        nq, nkv, dh, I, E = (cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.intermediate_size,
-                             cfg.num_experts)
-        NQ, NKV = nq * dh, nkv * dh
-        QKV = NQ + 2 * NKV
-        NB1 = cfg.num_behavior + 1
-        eps = float(cfg.rms_norm_eps)
-        p_res, p_att = sv["p_res"], sv["p_att"]
-        saved_step = self.dropout_step
-        self.dropout_step = sv["dropout_step"]          # regenerate exactly the forward's masks
         r = ws.router
-        cos, sin = self.rope(S)
-        scale = float(dh) ** -0.5
-        V = cfg.vocab_size
-        emb = self.params["model.embed_tokens.weight"]
-        demb = self.grads["model.embed_tokens.weight"]
         NP = ws.norm_partial[-1]                    # scratch table (rowtable_bwd); the norm backward takes the others in turn
-        norm_dws: List[torch.Tensor] = []
-        # delta = dO . O of the attention backward comes out of the o_proj dgrad GEMM (row-dot epilogue) when the dS-spill
-        # path is in use and every tile of that GEMM is full; otherwise gamer_attn_bwd computes it itself
-        bf16 = self.dtype == "bf16"
-        split_attn = self.split_attention and self.matmul != "f32" and not bf16
-        fuse_delta = (ws.ds_work is not None or bf16 or split_attn) and T % 128 == 0 and NQ % 128 == 0
-        # (three-product attention) max |dO| out of the o_proj input-gradient GEMM's epilogue instead of a pass over dO
-        do_amax = (dict(c_amax=(ws.dao, 0)) if (split_attn and self.h2_attention and self.matmul == "split3" and p_att < 0.75 and
-                                                   self.gemm_c_amax) else {})
-
-        fuse_swiglu_bwd = (bf16 or self.matmul == "split3") and self.fuse_swiglu_bwd
-
-        def dgrad(dy, lddy, Wf, Wt, ldw, dx, lddx, n_out, k_in, **kw):
-            """dx[T,k_in] (+)= dy[T,n_out] @ W[n_out,k_in]: fp32 reads W itself (row-contiguous B operand), bf16 the
-            transposed copy Wt [k_in, n_out] (k-contiguous on both sides); strideB is the same element count."""
-            if bf16:
-                ops.linear_dgrad_t(dy, lddy, Wt, Wt.shape[1], dx, lddx, T, n_out if Wt.shape[1] == n_out else Wt.shape[1],
-                                   k_in, **kw)
-            else:
-                ops.linear_dgrad(dy, lddy, Wf, ldw, dx, lddx, T, n_out, k_in, **kw)
-
-        def attention_bwd(qb, kb, vb, ob, lseb, kl_, ql_, empty_, tile_empty_, seed_, order_, span_):
-            h2_bwd = self.h2_attention and self.matmul == "split3" and p_att < 0.75
-            if split_attn and (span_ is None or h2_bwd):
-                ops.attn_bwd_split(qb, NQ, kb, NKV, vb, QKV, ob, ws.dao, lseb, kl_, ql_, empty_, tile_empty_, B, S, nq, nkv, scale,
-                                   p_att, seed_, ws.delta, ws.dq, NQ, ws.dk, NKV, ws.dqkv[:, NQ + NKV:], QKV, order=order_,
-                                   delta_ready=fuse_delta, dv_of=ws.dqkv,   # recompute form: measured faster than its dS spill
-                                   h2=h2_bwd, q_span=span_)
-            elif bf16:
-                ord16 = (order_[0], order_[2], empty_) if (order_ is not None and span_ is None) else None
-                ops.attn_bwd_bf16(qb, NQ, kb, NKV, vb, QKV, ob, ws.dao, lseb, kl_, ql_, B, S, nq, nkv, scale, p_att, seed_,
-                                  ws.delta, ws.dq, NQ, ws.dk, NKV, ws.dqkv[:, NQ + NKV:], QKV, q_span=span_,
-                                  delta_ready=fuse_delta, order=ord16)
-            else:
-                ops.attn_bwd(qb, NQ, kb, NKV, vb, QKV, ob, ws.dao, lseb, kl_, ql_, empty_, tile_empty_, B, S, nq, nkv, scale,
-                             p_att, seed_, ws.delta, ws.dq, NQ, ws.dk, NKV, ws.dqkv[:, NQ + NKV:], QKV, order=order_,
-                             ds_work=ws.ds_work, q_span=span_, delta_ready=fuse_delta and ws.ds_work is not None)
-
-        def norm_bwd(xin, w, dy, lddy, dw, accumulate_dx, dy_rows=None, branch=None):
-            """``branch`` = (seed, rows): the residual branch that consumes the updated dx next; its input gradient
-            dropout_mask(seed) * dx goes to t0 in the same pass (t0 must not be ``dy``)."""
-            part = ws.norm_partial[len(norm_dws)]       # dw itself is summed at the end of the pass (one launch for all norms:
-            norm_dws.append(dw)                         # they sit in the tail bucket of the gradient all-reduce)
-            if branch is None:
-                ops.rmsnorm_bwd(xin, w, dy, lddy, eps, ws.dx, part, accumulate_dx, dy_rows)
-            else:
-                ops.rmsnorm_bwd(xin, w, dy, lddy, eps, ws.dx, part, accumulate_dx, dy_rows, mask_out=ws.tmpH[0],
-                                mask_rows=branch[1], p=p_res, seed=branch[0])
-
-        # ---- loss -> logits -> final norm ----
-        if torch.is_tensor(sv["num_items"]):
-            ops.ce_bwd(ws.logits, ws.ldl, sv["labels"], V, self.temperature, IGNORE_INDEX, ws.lse_ce, sv["num_items"], 0.0,
-                       dloss, dloss_dev)
-        elif sv["num_items"] is not None:
-            ops.ce_bwd(ws.logits, ws.ldl, sv["labels"], V, self.temperature, IGNORE_INDEX, ws.lse_ce, None,
-                       float(sv["num_items"]), dloss, dloss_dev)
-        else:
-            ops.ce_bwd(ws.logits, ws.ldl, sv["labels"], V, self.temperature, IGNORE_INDEX, ws.lse_ce, ws.count, 0.0,
-                       dloss, dloss_dev)
-        import contextlib
-        # (matmul="split3") a gradient read by the weight- and the input-gradient GEMM of a site is measured once
-        hold = self._amax.hold if self._amax is not None else (lambda *t: contextlib.nullcontext())
+        hold, fuse_delta, do_amax, fuse_swiglu_bwd = c.hold, c.fuse_delta, c.do_amax, c.fuse_swiglu_bwd
+        dgrad, norm_bwd = functools.partial(self._dgrad, c), functools.partial(self._norm_bwd, c)
+        attention_bwd = functools.partial(self._attention_bwd, c)
         t0, t1, t2, t3 = ws.tmpH
-        L = cfg.num_hidden_layers
-        with hold(ws.logits):
-            ops.linear_wgrad(ws.logits, ws.ldl, ws.xn, H, demb, H, T, V, H)
-            dgrad(ws.logits, ws.ldl, emb, self.shadow.t("model.embed_tokens.weight") if bf16 else None, H, t3, H, V, H)
-        # every norm backward that completes dx also emits t0 = mask * dx for the branch that reads dx next
-        norm_bwd(ws.x_final, self.params["model.norm.weight"], t3, H, self.grads["model.norm.weight"], False,
-                 branch=(self._seed(L - 1, 5), ws.slot))
-
+        bf16 = c.bf16
         for l in reversed(range(cfg.num_hidden_layers)):
             W, G, A, xs = self.W[l], self.G[l], ws.layers[l], ws.x[l]
             WT = self.WT[l] if bf16 else None
@@ -1130,37 +1112,126 @@ class Engine:
                 dgrad(t2, H, C["gate"], CT["gate"], H, t3, H, H, H, accumulate=True)
                 hold_t2.__exit__(None, None, None)
                 norm_bwd(xs[1], W.ln2, t3, H, G.ln2, True, branch=(self._seed(l, 1), None))
-            # ---- self attention ----
-            SA, GS = W.self_attn, G.self_attn
-            ST = WT.self_attn if bf16 else dict(o=None, qkv=None)
-            # (t0 = mask * dx of this branch, written by the norm backward above)
-            with hold(t0):
-                ops.linear_wgrad(t0, H, A["ao"], NQ, GS["o"], NQ, T, H, NQ)
-                dgrad(t0, H, SA["o"], ST["o"], NQ, ws.dao, NQ, H, NQ, rowdot=(A["ao"], ws.delta, S) if fuse_delta else None,
-                      **do_amax)
-            attention_bwd(A["q"], A["k"], A["qkv"][:, NQ + NKV:], A["ao"], A["lse"], r["kl_self"], None, r["empty_self"],
-                          r["tile_empty_self"], self._seed(l, 0), None, span_self)
-            ops.qknorm_rope_bwd(A["qkv"], ws.dq, ws.dk, S, nq, nkv, SA["qn"], SA["kn"], eps, cos, sin, ws.dqkv, GS["qn"],
-                                GS["kn"], pos_ids=pos_ids, partial=ws.qk_partial)
-            with hold(ws.dqkv):
-                ops.linear_wgrad(ws.dqkv, QKV, A["h1"], H, GS["qkv"], H, T, QKV, H)
-                dgrad(ws.dqkv, QKV, SA["qkv"], ST["qkv"], H, t3, H, QKV, H)
-            norm_bwd(xs[0], W.ln1, t3, H, G.ln1, True, branch=(self._seed(l - 1, 5), ws.slot) if l > 0 else None)
+            self._self_attention_bwd(c, l, r, span_self, pos_ids, rows=ws.slot)
             if layer_done is not None:
                 layer_done(l)
+        self._backward_tail(c)
+
+    def _backward_head(self, dloss, dloss_dev, rows) -> SimpleNamespace:
+        """The start of every model's backward (after ``backward`` checked that a training forward ran): loss -> logits -> final norm (with t0 = dropout mask * dx for the last
+        layer's output branch, rows scattered through ``rows``).  Returns the pass context with the saved forward's
+        dropout step in effect."""
+        sv = self._saved
+        c = self._pass(sv["B"], sv["S"], sv["p_res"], sv["p_att"])
+        ws = c.ws = self.ws
+        c.saved_step = self.dropout_step
+        self.dropout_step = sv["dropout_step"]          # regenerate exactly the forward's masks
+        c.ids, c.norm_dws = sv["ids"], []
+        # delta = dO . O of the attention backward comes out of the o_proj dgrad GEMM (row-dot epilogue) when the dS-spill
+        # path is in use and every tile of that GEMM is full; otherwise gamer_attn_bwd computes it itself
+        c.fuse_delta = (ws.ds_work is not None or c.bf16 or c.split_attn) and c.T % 128 == 0 and c.NQ % 128 == 0
+        # (three-product attention) max |dO| out of the o_proj input-gradient GEMM's epilogue instead of a pass over dO
+        c.do_amax = dict(c_amax=(ws.dao, 0)) if (c.h2 and self.gemm_c_amax) else {}
+        # (matmul="split3") a gradient read by the weight- and the input-gradient GEMM of a site is measured once
+        c.hold = self._amax.hold if self._amax is not None else (lambda *t: contextlib.nullcontext())
+        V, H, T, L = self.cfg.vocab_size, c.H, c.T, self.cfg.num_hidden_layers
+        if torch.is_tensor(sv["num_items"]):
+            ops.ce_bwd(ws.logits, ws.ldl, sv["labels"], V, self.temperature, IGNORE_INDEX, ws.lse_ce, sv["num_items"], 0.0,
+                       dloss, dloss_dev)
+        elif sv["num_items"] is not None:
+            ops.ce_bwd(ws.logits, ws.ldl, sv["labels"], V, self.temperature, IGNORE_INDEX, ws.lse_ce, None,
+                       float(sv["num_items"]), dloss, dloss_dev)
+        else:
+            ops.ce_bwd(ws.logits, ws.ldl, sv["labels"], V, self.temperature, IGNORE_INDEX, ws.lse_ce, ws.count, 0.0,
+                       dloss, dloss_dev)
+        t3 = ws.tmpH[3]
+        with c.hold(ws.logits):
+            ops.linear_wgrad(ws.logits, ws.ldl, ws.xn, H, self.grads["model.embed_tokens.weight"], H, T, V, H)
+            self._dgrad(c, ws.logits, ws.ldl, self.params["model.embed_tokens.weight"],
+                        self.shadow.t("model.embed_tokens.weight") if c.bf16 else None, H, t3, H, V, H)
+        # every norm backward that completes dx also emits t0 = mask * dx for the branch that reads dx next
+        self._norm_bwd(c, ws.x_final, self.params["model.norm.weight"], t3, H, self.grads["model.norm.weight"], False,
+                       branch=(self._seed(L - 1, 5), rows))
+        return c
+
+    def _dgrad(self, c, dy, lddy, Wf, Wt, ldw, dx, lddx, n_out, k_in, **kw):
+        """dx[T,k_in] (+)= dy[T,n_out] @ W[n_out,k_in]: fp32 reads W itself (row-contiguous B operand), bf16 the
+        transposed copy Wt [k_in, n_out] (k-contiguous on both sides); strideB is the same element count."""
+        if c.bf16:
+            ops.linear_dgrad_t(dy, lddy, Wt, Wt.shape[1], dx, lddx, c.T, n_out if Wt.shape[1] == n_out else Wt.shape[1],
+                               k_in, **kw)
+        else:
+            ops.linear_dgrad(dy, lddy, Wf, ldw, dx, lddx, c.T, n_out, k_in, **kw)
+
+    def _norm_bwd(self, c, xin, w, dy, lddy, dw, accumulate_dx, dy_rows=None, branch=None):
+        """ws.dx (+)= the RMSNorm's input gradient.  ``branch`` = (seed, rows): the residual branch that consumes the
+        updated dx next; its input gradient dropout_mask(seed) * dx goes to t0 in the same pass (t0 must not be ``dy``)."""
+        ws = c.ws
+        part = ws.norm_partial[len(c.norm_dws)]     # dw itself is summed at the end of the pass (one launch for all norms:
+        c.norm_dws.append(dw)                       # they sit in the tail bucket of the gradient all-reduce)
+        if branch is None:
+            ops.rmsnorm_bwd(xin, w, dy, lddy, c.eps, ws.dx, part, accumulate_dx, dy_rows)
+        else:
+            ops.rmsnorm_bwd(xin, w, dy, lddy, c.eps, ws.dx, part, accumulate_dx, dy_rows, mask_out=ws.tmpH[0],
+                            mask_rows=branch[1], p=c.p_res, seed=branch[0])
+
+    def _attention_bwd(self, c, qb, kb, vb, ob, lseb, kl_, ql_, empty_, tile_empty_, seed_, order_, span_):
+        """Attention backward in the pass's form: dq, dk and the v columns of dqkv from dO = ws.dao."""
+        ws, B, S, nq, nkv, NQ, NKV, QKV = c.ws, c.B, c.S, c.nq, c.nkv, c.NQ, c.NKV, c.QKV
+        if c.split_attn and (span_ is None or c.h2):
+            ops.attn_bwd_split(qb, NQ, kb, NKV, vb, QKV, ob, ws.dao, lseb, kl_, ql_, empty_, tile_empty_, B, S, nq, nkv, c.scale,
+                               c.p_att, seed_, ws.delta, ws.dq, NQ, ws.dk, NKV, ws.dqkv[:, NQ + NKV:], QKV, order=order_,
+                               delta_ready=c.fuse_delta, dv_of=ws.dqkv,   # recompute form: measured faster than its dS spill
+                               h2=c.h2, q_span=span_)
+        elif c.bf16:
+            ord16 = (order_[0], order_[2], empty_) if (order_ is not None and span_ is None) else None
+            ops.attn_bwd_bf16(qb, NQ, kb, NKV, vb, QKV, ob, ws.dao, lseb, kl_, ql_, B, S, nq, nkv, c.scale, c.p_att, seed_,
+                              ws.delta, ws.dq, NQ, ws.dk, NKV, ws.dqkv[:, NQ + NKV:], QKV, q_span=span_,
+                              delta_ready=c.fuse_delta, order=ord16)
+        else:
+            ops.attn_bwd(qb, NQ, kb, NKV, vb, QKV, ob, ws.dao, lseb, kl_, ql_, empty_, tile_empty_, B, S, nq, nkv, c.scale,
+                         c.p_att, seed_, ws.delta, ws.dq, NQ, ws.dk, NKV, ws.dqkv[:, NQ + NKV:], QKV, order=order_,
+                         ds_work=ws.ds_work, q_span=span_, delta_ready=c.fuse_delta and ws.ds_work is not None)
+
+    def _self_attention_bwd(self, c, l: int, masks: dict, span, pos_ids, rows):
+        """Backward of layer l's self-attention block (t0 = mask * dx of its output branch, written by the norm backward
+        before it); the input norm's backward emits t0 for layer l - 1's output branch, rows scattered through ``rows``."""
+        W, G, A, xs, ws = self.W[l], self.G[l], c.ws.layers[l], c.ws.x[l], c.ws
+        T, H, NQ, NKV, QKV, S = c.T, c.H, c.NQ, c.NKV, c.QKV, c.S
+        SA, GS = W.self_attn, G.self_attn
+        ST = self.WT[l].self_attn if c.bf16 else dict(o=None, qkv=None)
+        t0, t3 = ws.tmpH[0], ws.tmpH[3]
+        with c.hold(t0):
+            ops.linear_wgrad(t0, H, A["ao"], NQ, GS["o"], NQ, T, H, NQ)
+            self._dgrad(c, t0, H, SA["o"], ST["o"], NQ, ws.dao, NQ, H, NQ,
+                        rowdot=(A["ao"], ws.delta, S) if c.fuse_delta else None, **c.do_amax)
+        self._attention_bwd(c, A["q"], A["k"], A["qkv"][:, NQ + NKV:], A["ao"], A["lse"], masks["kl_self"], None,
+                            masks["empty_self"], masks["tile_empty_self"], self._seed(l, 0), None, span)
+        ops.qknorm_rope_bwd(A["qkv"], ws.dq, ws.dk, S, c.nq, c.nkv, SA["qn"], SA["kn"], c.eps, c.cos, c.sin, ws.dqkv, GS["qn"],
+                            GS["kn"], pos_ids=pos_ids, partial=ws.qk_partial)
+        with c.hold(ws.dqkv):
+            ops.linear_wgrad(ws.dqkv, QKV, A["h1"], H, GS["qkv"], H, T, QKV, H)
+            self._dgrad(c, ws.dqkv, QKV, SA["qkv"], ST["qkv"], H, t3, H, QKV, H)
+        self._norm_bwd(c, xs[0], W.ln1, t3, H, G.ln1, True, branch=(self._seed(l - 1, 5), rows) if l > 0 else None)
+
+    def _backward_tail(self, c):
+        """The end of every model's backward: the embedding gradient, the RMSNorm weight gradients of the pass in one
+        reduce, and the dropout step the forward left."""
+        ws, V = c.ws, self.cfg.vocab_size
+        demb = self.grads["model.embed_tokens.weight"]
         self._check_deterministic_embedding()        # (raised in __init__ already: nothing has been written when it fires there)
         if self.ordered_embedding_grad and V <= 8191:
             # the scatter-add of the embedding gradient in a fixed order: a stable counting sort of the tokens by id, then sums in
             # token order (no float atomics: with the ordered weight gradients and table gradients every gradient of the step
             # has the same bits on every run); pad and out-of-range ids are skipped (padding_idx, model.py:263)
-            ops.embedding_bwd_ordered(sv["ids"], ws.dx, cfg.pad_token_id, demb)
+            ops.embedding_bwd_ordered(c.ids, ws.dx, self.cfg.pad_token_id, demb)
         else:
-            ops.embedding_bwd(sv["ids"], ws.dx, cfg.pad_token_id, demb)
-        key = tuple(d.data_ptr() for d in norm_dws)
+            ops.embedding_bwd(c.ids, ws.dx, self.cfg.pad_token_id, demb)
+        key = tuple(d.data_ptr() for d in c.norm_dws)
         if self._norm_out_table is None or self._norm_out_table[0] != key:
             self._norm_out_table = (key, torch.tensor(key, dtype=torch.int64, device=self.device))
-        ops.colsum_reduce_batched(ws.norm_partial, len(norm_dws), self._norm_out_table[1], accumulate=True)
-        self.dropout_step = saved_step
+        ops.colsum_reduce_batched(ws.norm_partial, len(c.norm_dws), self._norm_out_table[1], accumulate=True)
+        self.dropout_step = c.saved_step
 
     # ------------------------------------------------------------------------------------------
     def optimizer_step(self, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, max_norm=1.0,

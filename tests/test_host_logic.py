@@ -115,6 +115,40 @@ def test_flat_optimizer_state_of_an_older_parameter_order_is_adopted_by_name():
         new.adopt(flat_old[:-4], cfg, 1)
 
 
+@pytest.mark.parametrize("model", ["multi", "qwen3"])
+def test_engine_core_sizes_are_pinned(model):
+    """Both models build their layout, bf16 shadow and workspace from the shared engine code: the sizes, the order of the
+    parameters and the transpose table of the two models stay what they were when each model had its own copy."""
+    import hashlib
+    from gamer_amd.config import Qwen3Config
+    from gamer_amd.engine import Bf16Shadow, Engine, _Workspace
+    from gamer_amd.engine_qwen3 import Qwen3Engine, Qwen3Layout
+    if model == "multi":
+        cfg, layout, masks = synthetic_config(), ParamLayout(synthetic_config()), Engine._bind_masks
+        want = dict(numel=24535040, n_decay=24528128, entries="2028bddb88f7", n_entries=125, n_tiles=23944,
+                    flatT=24526848, table="76d76fec2b84",
+                    # (the label-check flag is allocated with loss_sum / count now, outside the counted store: 4 bytes less)
+                    ws={("f32", True, True): 14140428856, ("f32", True, False): 13335122488, ("f32", False, True): 2447306296,
+                        ("bf16", True, True): 7444091448, ("bf16", False, True): 1330327096})
+    else:
+        cfg = Qwen3Config(vocab_size=1040)
+        layout, masks = Qwen3Layout(cfg), Qwen3Engine._bind_masks
+        want = dict(numel=5776640, n_decay=5771264, entries="d9b30418910d", n_entries=33, n_tiles=5640, flatT=5783552,
+                    table="a662f0033f5e",
+                    ws={("f32", True, True): 11109705728, ("f32", True, False): 10304399360, ("f32", False, True): 1715554304,
+                        ("bf16", True, True): 5778565120, ("bf16", False, True): 929531904})
+    assert (layout.numel, layout.n_decay) == (want["numel"], want["n_decay"])
+    assert hashlib.sha256(repr(list(layout.entries.items())).encode()).hexdigest()[:12] == want["entries"]
+    sh = Bf16Shadow(cfg, layout, torch.zeros(layout.numel))
+    assert (sh.n_entries, sh.n_tiles, sh.flatT.numel()) == (want["n_entries"], want["n_tiles"], want["flatT"])
+    assert hashlib.sha256(sh.table.numpy().tobytes()).hexdigest()[:12] == want["table"]
+    for (dt, train, spill), n in want["ws"].items():
+        act = torch.float32 if dt == "f32" else torch.bfloat16
+        for sp in ((spill,) if dt == "f32" and train else (True, False)):      # (the spill flag only sizes the fp32 train step)
+            ws = _Workspace(cfg, "meta", train, act, sp, masks).bind(128, 505)
+            assert ws.allocated_bytes() == n, (dt, train, sp)
+
+
 def test_no_decay_rule_matches_hf_trainer(golden):
     """oracle.is_no_decay restates HF Trainer.get_decay_parameter_names for this model: every parameter of the reference
     model at a small configuration with the group the Trainer put it in (oracle/make_golden_no_decay.py)."""
