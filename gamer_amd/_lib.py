@@ -101,6 +101,7 @@ _SIGNATURES = {
     "gamer_router_fwd": [P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
     "gamer_expert_lists": [P, I, I, I, P, P, P, P, P],
     "gamer_causal_prep": [P, I, I, P, P, P, P, P, P],
+    "gamer_session_prep": [P, P, P, I, I, I, I, P, P, P, P, P, P, P],
     "gamer_embedding_fwd": [P, P, I, I, I, P, P],
     "gamer_embedding_bwd": [P, P, I, I, I, I, P, P],
     "gamer_embedding_bwd_ordered": [P, P, I, I, I, I, P, P, L, P],

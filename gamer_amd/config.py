@@ -272,3 +272,40 @@ class Qwen3Config:
             raise ValueError("lm_head is tied to embed_tokens in this model")
         if self.hidden_act != "silu" or self.attention_bias:
             raise ValueError("only hidden_act='silu' without attention bias is implemented")
+
+
+class Qwen3SessionConfig(Qwen3Config):
+    """Configuration of the Qwen3Session baseline (ref:SeqRec/models/generative/Qwen3Session/model.py: HF
+    ``Qwen3ForCausalLM`` with session-wise masks): ``Qwen3Config`` plus the two integer fields its model asserts
+    (model.py:16-17) and train_SMB_decoder.py:369-378 sets on the HF config - ``num_positions`` (tokens per item) and
+    ``model_max_length`` (the in-item mask covers ``(model_max_length // num_positions) * num_positions`` tokens)."""
+
+    REQUIRED = (("num_positions", "Config must have 'num_positions' attribute for Qwen3SessionModel."),
+                ("model_max_length", "Config must have 'model_max_length' attribute for Qwen3SessionModel."))
+
+    def __init__(self, **kwargs):
+        for key, msg in self.REQUIRED:
+            if not isinstance(kwargs.get(key), int) or isinstance(kwargs.get(key), bool):
+                raise ValueError(msg)
+        super().__init__(**kwargs)
+
+    @classmethod
+    def coerce(cls, config) -> "Qwen3SessionConfig":
+        """As ``Qwen3Config.coerce``; an HF config object must carry both run-time fields as attributes."""
+        if isinstance(config, cls) or isinstance(config, dict):
+            return super().coerce(config)
+        base = Qwen3Config.coerce(config).to_dict()
+        for key, _ in cls.REQUIRED:
+            if hasattr(config, key):
+                base[key] = getattr(config, key)
+        return cls(**base)
+
+    @property
+    def max_item_tokens(self) -> int:
+        """Length of the reference's in-item mask: the longest sequence its forward accepts."""
+        return (self.model_max_length // self.num_positions) * self.num_positions
+
+    def validate(self):
+        super().validate()
+        if self.num_positions <= 0:
+            raise ValueError("num_positions must be positive")

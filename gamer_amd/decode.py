@@ -459,12 +459,16 @@ class DecodeSession:
 
 
 class Qwen3DecodeSession(DecodeSession):
-    """K/V cache + single-token step of the plain Qwen3 baseline (``Engine(variant="qwen3")``): self attention only.
-    The prompt pass runs with transformers' generate() positions ``cumsum(attention_mask) - 1`` (gamer_causal_prep builds
-    them on the device) and writes every layer's q|k|v and rotated keys in place; the token generated at step t is
-    rotated by (number of kept prompt tokens) + t - 1, per row - a left-padded prompt by its own offset."""
+    """K/V cache + single-token step of the plain Qwen3 baselines (``Engine(variant="qwen3")`` / ``"qwen3_session"``): self
+    attention only.  The prompt pass runs with transformers' generate() positions ``cumsum(attention_mask) - 1``
+    (gamer_causal_prep builds them on the device) and writes every layer's q|k|v and rotated keys in place; the token
+    generated at step t is rotated by (number of kept prompt tokens) + t - 1, per row - a left-padded prompt by its own offset.
+    Qwen3Session (``session_ids`` / ``extended_session_ids`` [B, L0], required): the prompt pass runs with the session mask
+    and the extended ids as positions (gamer_session_prep); the generated tokens see every kept key and are rotated by
+    max(extended_session_ids[row]) + t, with no padding offset (Qwen3Session/model.py:293-309)."""
 
-    def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int):
+    def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int, session_ids=None,
+                 extended_session_ids=None):
         import os
         cfg, dev = engine.cfg, engine.device
         self.eng, self.nb, self.tmax = engine, num_beams, max_new_tokens
@@ -508,7 +512,16 @@ class Qwen3DecodeSession(DecodeSession):
                 sv = engine._amax.peek(v, (1, 0, T0, self.NKV, v.stride(0)))
                 if sk and sv:
                     prompt_amax[(layer, kind)] = (sk, sv)
-        engine.forward(ids0, am0, train=False, kv_sink=sink, kv_dest=dest, last_row_logits=True, rope_from_mask=True)
+        sessions = engine.variant == "qwen3_session"
+        if sessions:
+            if session_ids is None or extended_session_ids is None:
+                raise ValueError("a session engine needs session_ids and extended_session_ids")
+            ext0 = extended_session_ids.to(dev, torch.int64)
+            engine.forward(ids0, am0, train=False, kv_sink=sink, kv_dest=dest, last_row_logits=True,
+                           session_ids=session_ids.to(dev, torch.int64), extended_session_ids=ext0)
+            engine.check_inputs()
+        else:
+            engine.forward(ids0, am0, train=False, kv_sink=sink, kv_dest=dest, last_row_logits=True, rope_from_mask=True)
         self.prefill_logits = engine.last_logits_buf
 
         def keep(name, value):
@@ -520,8 +533,10 @@ class Qwen3DecodeSession(DecodeSession):
                 t.copy_(value)
             return t
         self.ok_self = keep("ok_self", am0.to(torch.int32))
-        # RoPE position of the token generated at step t: pos_last + t (next_pos = kept prompt tokens, gamer_causal_prep)
-        self.pos_last = keep("pos_last", (engine.ws.mask["next_pos"] - 1).repeat_interleave(nb))
+        # RoPE position of the token generated at step t: pos_last + t (next_pos = kept prompt tokens, gamer_causal_prep;
+        # Qwen3Session: the prompt's largest extended id)
+        last = ext0.max(dim=1).values.to(torch.int32) if sessions else engine.ws.mask["next_pos"] - 1
+        self.pos_last = keep("pos_last", last.repeat_interleave(nb))
         if st.gen is None:
             st.gen = {kk: (torch.zeros(N, max_new_tokens, self.NKV, **f32), torch.zeros(N, max_new_tokens, self.NKV, **f32))
                       for kk in self.kp}
@@ -610,7 +625,7 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     ``use_cache=False`` re-runs the whole sequence every step (the cross-check of the cache path; it has no slots, so
     it needs ``reorder_cross_cache=True``).  ``reorder_cross_cache``: see ``DecodeSession`` (False = the reference).
     ``session_ids`` / ``extended_session_ids`` [B, L0]: required by a "session" engine (see DecodeSession)."""
-    qwen3 = engine.variant == "qwen3"
+    qwen3 = engine.variant in ("qwen3", "qwen3_session")
     if not use_cache and not reorder_cross_cache and not qwen3:
         raise ValueError("use_cache=False re-computes every position for its own beam: it can only reproduce "
                          "reorder_cross_cache=True (the shipped reference's un-reordered cross cache needs the cache)")
@@ -633,7 +648,7 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     node, nxt = nxt, node
     scores = torch.empty(N, V, device=dev)
     final = None
-    sess_variant = engine.variant == "session"
+    sess_variant = engine.variant in ("session", "qwen3_session")
     if sess_variant:
         if session_ids is None or extended_session_ids is None:
             raise ValueError("a session engine needs session_ids and extended_session_ids")
@@ -653,7 +668,8 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     if not use_cache:
         session = None
     elif qwen3:
-        session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens)
+        session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens, session_ids if sess_variant else None,
+                                     extended_session_ids if sess_variant else None)
     else:
         session = DecodeSession(engine, ids0, am0, act0, nb, max_new_tokens, session_ids if sess_variant else None,
                                 extended_session_ids if sess_variant else None, reorder_cross_cache=reorder_cross_cache)
@@ -668,10 +684,15 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
                 logits2d = session.step(last_tok)
                 rows = torch.arange(N, device=dev, dtype=torch.int32)
         elif qwen3:
-            # the cache-free cross-check: the whole sequence again, positions from the (extended) attention mask
+            # the cache-free cross-check: the whole sequence again, positions from the (extended) attention mask or, for
+            # Qwen3Session, from the extended session ids
             flat = ids0 if step == 0 else seqs.reshape(N, cur)
             am = am0 if step == 0 else torch.cat([am0, am0.new_ones(B, step)], 1).repeat_interleave(nb, 0)
-            engine.forward(flat, am, train=False, rope_from_mask=True)
+            if sess_variant:
+                engine.forward(flat, am, train=False, **session_kw(step, step > 0))
+                engine.check_inputs()
+            else:
+                engine.forward(flat, am, train=False, rope_from_mask=True)
             rows = ((torch.arange(N, device=dev, dtype=torch.int32) // (nb if step == 0 else 1)) * cur + (cur - 1))
         elif step == 0:
             # all beams of a sample hold the same prompt: run it once (HF runs num_beams copies)

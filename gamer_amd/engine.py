@@ -382,11 +382,11 @@ class Engine:
     N_SUMSQ_PARTIAL = 1024
 
     def __new__(cls, *args, **kwargs):
-        # Engine(cfg, variant="qwen3") is the plain Qwen3 baseline's engine (gamer_amd/engine_qwen3.py)
+        # Engine(cfg, variant="qwen3") / variant="qwen3_session" are the plain Qwen3 baselines' engines (gamer_amd/engine_qwen3.py)
         variant = kwargs.get("variant", args[3] if len(args) > 3 else "multi")
-        if cls is Engine and variant == "qwen3":
-            from .engine_qwen3 import Qwen3Engine
-            cls = Qwen3Engine
+        if cls is Engine and variant in ("qwen3", "qwen3_session"):
+            from .engine_qwen3 import Qwen3Engine, Qwen3SessionEngine
+            cls = Qwen3Engine if variant == "qwen3" else Qwen3SessionEngine
         return super().__new__(cls)
 
     def __init__(self, cfg: Qwen3MultiConfig, device="cuda", temperature: float = 1.0, variant: str = "multi",
@@ -421,8 +421,9 @@ class Engine:
         matmul = _matmul_arg(dtype, matmul)
         _check_split_dtype(dtype, matmul)
         if variant not in ("multi", "session"):
-            raise ValueError(f"unknown variant {variant!r} (multi, session or qwen3)")
+            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3 or qwen3_session)")
         _check_dtype(dtype)
+        self.key_spans = variant == "session"
         self._init_core(cfg, device, temperature, variant, dtype, matmul, share_buffers_of, deterministic)
         if self._amax is not None and self._amax.planes is not None and cfg.hidden_size == 256 and \
                 os.environ.get("GAMER_GEMM_OSF", "0") == "1":
@@ -439,6 +440,10 @@ class Engine:
         self.split_inject = bool(self.dtype != "bf16" and os.environ.get("GAMER_SPLIT_INJECT", "1") != "0" and
                                  cfg.behavior_injection_decoder and cfg.num_experts * nb1 <= 64 and nb1 <= 16 and
                                  cfg.behavior_embedding_dim % 4 == 0 and cfg.behavior_embedding_dim <= 256)
+
+    # whether the model's self attention takes per-query key spans (session-wise masks): the kernel forms that take them
+    # decide whether the workspace needs the dS-spill scratch (``workspace``)
+    key_spans = False
 
     # the model's parts of the shared construction: parameter layout, per-layer weight views (fp32 / bf16 operands,
     # transposed bf16 copies)
@@ -576,10 +581,10 @@ class Engine:
         buffers); each is bound to the shape of the current batch without reallocating (grow-only storage)."""
         if train not in self._ws:
             # the 6.4 GB dS-spill scratch is the fp32-MFMA attention backward's; the split form (recompute) does not use
-            # it - unless the session variant sends its span calls to the fp32-MFMA kernels
-            # (the three-product form takes the session variant's key spans itself)
+            # it - unless a model with key spans (the session-wise masks) sends its span calls to the fp32-MFMA kernels
+            # (the three-product form takes the key spans itself)
             spill = not (self.split_attention and self.matmul != "f32" and
-                         (self.variant != "session" or (self.matmul == "split3" and self.h2_attention)))
+                         (not self.key_spans or (self.matmul == "split3" and self.h2_attention)))
             self._ws[train] = _Workspace(self.cfg, self.device, train, self.act_dtype, spill, self._bind_masks)
         return self._ws[train].bind(B, S)
 

@@ -11,7 +11,12 @@ token order, no ``row_map``, no group offsets).  The mask comes from ``gamer_cau
 ``rope_from_mask=True`` (the prompt pass of a generation) the same kernel builds transformers' per-row positions
 ``cumsum(attention_mask) - 1`` for left-padded prompts on the device.
 
-``Engine(cfg, variant="qwen3")`` constructs this class.  It brings its parameter layout, masks and per-layer loops with
+``Engine(cfg, variant="qwen3_session")`` constructs ``Qwen3SessionEngine``, the Qwen3Session baseline: the same model
+with session-wise masks and RoPE positions from ``extended_session_ids``, built by ``gamer_session_prep`` instead of
+``gamer_causal_prep``: besides its argument checks, the ``_self_mask`` hook is all it changes of the forward and backward
+loops.
+
+``Engine(cfg, variant="qwen3")`` constructs ``Qwen3Engine``.  It brings its parameter layout, masks and per-layer loops with
 the dense MLP; the construction, workspace, bf16 shadow, the shared forward / backward blocks and the update, accumulation-
 window and data-parallel surface are ``Engine``'s.
 """
@@ -23,7 +28,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .config import Qwen3Config
+from .config import Qwen3Config, Qwen3SessionConfig
 from .engine import Engine, _check_dtype, _check_split_dtype, _FlatLayout, _matmul_arg
 
 
@@ -92,13 +97,16 @@ class Qwen3Engine(Engine):
     _layout_cls = Qwen3Layout
     _layer_cls = _Qwen3LayerW
     _layer_t_cls = _Qwen3LayerWT
+    VARIANT = "qwen3"
+    _config_cls = Qwen3Config
 
-    def __init__(self, cfg: Qwen3Config, device="cuda", temperature: float = 1.0, variant: str = "qwen3",
+    def __init__(self, cfg: Qwen3Config, device="cuda", temperature: float = 1.0, variant: Optional[str] = None,
                  dtype: str = "f32", matmul: Optional[str] = None, share_buffers_of: Optional["Qwen3Engine"] = None,
                  deterministic: Optional[bool] = None):
-        if variant != "qwen3":
-            raise ValueError(f"Qwen3Engine is the 'qwen3' variant, not {variant!r}")
-        cfg = Qwen3Config.coerce(cfg)
+        variant = self.VARIANT if variant is None else variant
+        if variant != self.VARIANT:
+            raise ValueError(f"{type(self).__name__} is the {self.VARIANT!r} variant, not {variant!r}")
+        cfg = self._config_cls.coerce(cfg)
         cfg.validate()
         matmul = _matmul_arg(dtype, matmul)
         _check_dtype(dtype)
@@ -126,16 +134,14 @@ class Qwen3Engine(Engine):
         ``rope_from_mask`` transformers' generate() positions ``cumsum(attention_mask) - 1`` (0 at pads) - the prompt pass
         of a generation.  ``kv_dest`` / ``kv_sink`` / ``last_row_logits`` / ``hidden_sink``: see ``Engine.forward``
         (kinds "self" only)."""
-        del actions, session_ids, extended_session_ids
+        del actions
         c = self._prologue(input_ids, attention_mask, labels, train, dropout, 0.0, kv_dest, hidden_sink, last_row_logits, 0,
                            eval_only=("last_row_logits / rope_from_mask are evaluation-only options"
                                       if last_row_logits or rope_from_mask else None),
                            f32_only="generation (cached decode) is built for dtype='f32' only" if last_row_logits else None)
         cfg, ws, m = self.cfg, c.ws, c.ws.mask
         B, S, T, H, I, L, eps = c.B, c.S, c.T, c.H, c.I, cfg.num_hidden_layers, c.eps
-        ops.causal_prep(c.am, B, S, m["kl_self"], m["empty_self"], m["tile_empty_self"],
-                        pos_ids=m["pos_ids"] if rope_from_mask else None, next_pos=m["next_pos"])
-        pos_ids = m["pos_ids"] if rope_from_mask else None
+        span, pos_ids = ws.self_span = self._self_mask(c, rope_from_mask, session_ids, extended_session_ids)
         ops.embedding_fwd(c.ids, self.params["model.embed_tokens.weight"], ws.x[0][0])
         # the q|k|v projection with per-head RMSNorm + RoPE in its epilogue: opt-in in the train step (Engine.__init__), always
         # in a generation's prompt pass when its tiles are whole (it writes q and the rotated keys with the prompt's positions)
@@ -147,7 +153,7 @@ class Qwen3Engine(Engine):
             if hidden_sink is not None:
                 hidden_sink.append(xs[0].view(B, S, H).clone())
             # ---- self attention, o_proj with the residual add (no residual dropout in this model) ----
-            self._self_attention(c, l, m, None, pos_ids, fuse_qkv, kv_dest, kv_sink)
+            self._self_attention(c, l, m, span, pos_ids, fuse_qkv, kv_dest, kv_sink)
             # ---- dense SwiGLU MLP ----
             if last_row_logits and l == L - 1:
                 # prompt pass of a generation: the last layer's K/V are cached; of its MLP only the last position of every
@@ -173,6 +179,15 @@ class Qwen3Engine(Engine):
             ops.gemm(A["hm"], I, 1, Wm.down, I, 1, xnext, H, T, H, I, resid=xs[1])
         # ---- final norm, tied head, temperature CE ----
         return self._head(c, x_last, num_items_in_batch, hidden_sink)
+
+    def _self_mask(self, c, rope_from_mask: bool, session_ids, extended_session_ids):
+        """Builds the pass's self-attention mask into ``ws.mask`` and returns (per-query key spans, RoPE positions) for the
+        forward and the backward: the causal + key-padding mask, no spans, positions 0..S-1 or, with ``rope_from_mask``,
+        generate()'s ``cumsum(attention_mask) - 1``.  The session ids are not used here."""
+        m = c.ws.mask
+        ops.causal_prep(c.am, c.B, c.S, m["kl_self"], m["empty_self"], m["tile_empty_self"],
+                        pos_ids=m["pos_ids"] if rope_from_mask else None, next_pos=m["next_pos"])
+        return None, (m["pos_ids"] if rope_from_mask else None)
 
     def check_inputs(self):
         """Host-synchronising validation: labels outside the vocabulary (nn.CrossEntropyLoss raises on them)."""
@@ -209,7 +224,76 @@ class Qwen3Engine(Engine):
                 dgrad(A["gu"], 2 * I, W.gu, WT.gu if c.bf16 else None, H, ws.dhin, H, 2 * I, H)
             # (t0 = dx for the attention block's output: the dropout-mask pass with p = 0)
             self._norm_bwd(c, xs[1], W.ln2, ws.dhin, H, G.ln2, True, branch=(self._seed(l, 1), None))
-            self._self_attention_bwd(c, l, ws.mask, None, None, rows=None)
+            self._self_attention_bwd(c, l, ws.mask, *ws.self_span, rows=None)
             if layer_done is not None:
                 layer_done(l)
         self._backward_tail(c)
+
+
+class Qwen3SessionEngine(Qwen3Engine):
+    """The Qwen3Session baseline (``--backbone Qwen3Session``; ref:SeqRec/models/generative/Qwen3Session/model.py): HF
+    ``Qwen3ForCausalLM`` - the parameters, layers and loops of ``Qwen3Engine`` - with Qwen3SessionMulti's self mask (a token
+    sees its own item up to itself and every kept token of a strictly earlier session, model.py:28-80) and RoPE positions
+    ``extended_session_ids`` (model.py:293-309).  ``gamer_session_prep`` builds both on the device, without a router, as
+    per-query key spans; the attention kernels take them in every form (split3, split6, f32, bf16)."""
+
+    VARIANT = "qwen3_session"
+    _config_cls = Qwen3SessionConfig
+    key_spans = True
+
+    @staticmethod
+    def _bind_masks(ws, B: int, S: int):
+        """gamer_session_prep's outputs: key-padding levels, key spans, RoPE positions, empty rows / tiles, violations."""
+        i32 = torch.int32
+        if "m_violations" not in ws._store:
+            ws._store["m_violations"] = torch.zeros(1, dtype=i32, device=ws.device)
+        ws.mask = dict(kl_self=ws._buf("m_kl_self", (B, S), i32), empty_self=ws._buf("m_empty_self", (B, S), i32),
+                       tile_empty_self=ws._buf("m_tile_empty_self", (B, (S + 31) // 32), i32),
+                       span_self=ws._buf("m_span_self", (B, S, 4), i32), pos_ids=ws._buf("m_pos_ids", (B, S), i32),
+                       violations=ws._store["m_violations"])
+
+    def forward(self, input_ids, attention_mask=None, actions=None, labels=None, num_items_in_batch=None,
+                train: bool = False, dropout: Optional[bool] = None, kv_sink=None, kv_dest=None,
+                session_ids=None, extended_session_ids=None, last_row_logits: bool = False,
+                hidden_sink: Optional[list] = None):
+        """``Qwen3Engine.forward`` with the session-wise mask: ``session_ids`` [B,S] are required (the reference asserts
+        the same), ``extended_session_ids`` [B,S] are the RoPE positions (None: 0..S-1).  ``actions`` are ignored."""
+        if session_ids is None:
+            raise ValueError("Session IDs must be provided to generate session-wise causal mask.")
+        S = input_ids.shape[1]
+        # the reference's in-item mask has (model_max_length // num_positions) * num_positions rows: a longer sequence
+        # fails there; the mask kernel keeps a row's session ids in LDS up to 2048 tokens
+        if S > self.cfg.max_item_tokens:
+            raise ValueError(f"sequence length {S} exceeds the reference's in-item mask, (model_max_length // "
+                             f"num_positions) * num_positions = {self.cfg.max_item_tokens}")
+        if S > 2048:
+            raise ValueError(f"sequence length {S} > 2048: the session mask kernel (gamer_session_prep) is built for S <= 2048")
+        return super().forward(input_ids, attention_mask, labels=labels, num_items_in_batch=num_items_in_batch,
+                               train=train, dropout=dropout, kv_sink=kv_sink, kv_dest=kv_dest, session_ids=session_ids,
+                               extended_session_ids=extended_session_ids, last_row_logits=last_row_logits,
+                               hidden_sink=hidden_sink)
+
+    def _self_mask(self, c, rope_from_mask: bool, session_ids, extended_session_ids):
+        """The session-wise mask as key spans and the extended ids as positions (gamer_session_prep, one launch)."""
+        m = c.ws.mask
+        sid = session_ids.to(self.device, torch.int64).contiguous()
+        if tuple(sid.shape) != (c.B, c.S):
+            raise ValueError(f"session_ids has shape {tuple(sid.shape)}, input_ids {(c.B, c.S)}")
+        ext = None
+        if extended_session_ids is not None:
+            ext = extended_session_ids.to(self.device, torch.int64).contiguous()
+            if tuple(ext.shape) != (c.B, c.S):
+                raise ValueError(f"extended_session_ids has shape {tuple(ext.shape)}, input_ids {(c.B, c.S)}")
+        m["violations"].zero_()
+        ops.session_prep(sid, ext, c.am, self.cfg.num_positions, c.S, m)
+        return m["span_self"], m["pos_ids"]
+
+    def check_inputs(self):
+        """Labels outside the vocabulary, and rows whose session ids cannot be expressed as key spans (``forward`` has
+        already refused sequences longer than the reference's in-item mask or 2048 tokens)."""
+        super().check_inputs()
+        n = int(self.ws.mask["violations"].item())
+        if n:
+            raise ValueError(f"{n} row(s) with session ids that decrease along the sequence or RoPE positions "
+                             "outside [0, S): the session masks are built as causal key spans "
+                             "(gamer_session_prep), which needs the dataset's layout (SMB_dataset.py:194-222)")

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .config import Qwen3Config, Qwen3MultiConfig
+from .config import Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig
 from .engine import Engine
 
 
@@ -123,6 +123,8 @@ except Exception:                                             # noqa: BLE001
 class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
     VARIANT = "multi"
     CONFIG_CLASS = Qwen3MultiConfig
+    USES_ACTIONS = True             # the forward needs the behaviour levels (cross-attention mask)
+    USES_SESSIONS = False           # the forward passes session_ids / extended_session_ids on to the engine
 
     def __init__(self, config, device: str = "cuda", dtype: str = "f32", matmul: Optional[str] = None):
         """``config``: the object the reference constructs its model from - a transformers ``Qwen3MoeConfig`` loaded from
@@ -312,13 +314,13 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         if inputs_embeds is not None or past_key_values is not None or use_cache:
             raise NotImplementedError("gamer_amd implements the training/scoring forward (no KV cache, no inputs_embeds)")
-        if actions is None and self.VARIANT != "qwen3":
+        if actions is None and self.USES_ACTIONS:
             raise ValueError("Qwen3Multi needs `actions` (behaviour level per token) for the cross-attention mask")
         num_items = kwargs.get("num_items_in_batch", None)
         if torch.is_tensor(num_items):
             num_items = float(num_items)
         eng = self._engine_for_call()
-        sess = (session_ids, extended_session_ids) if self.VARIANT == "session" else (None, None)
+        sess = (session_ids, extended_session_ids) if self.USES_SESSIONS else (None, None)
         needs_grad = torch.is_grad_enabled() and labels is not None
         want_hidden = output_hidden_states if output_hidden_states is not None else bool(getattr(self.config, "output_hidden_states", False))
         hidden = [] if want_hidden else None
@@ -336,7 +338,7 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
                 # the engine's logits live in a workspace buffer that the next forward overwrites; callers keep
                 # module outputs across batches (HF Trainer.predict / evaluate with compute_metrics), so hand out a copy
                 logits = logits.clone()
-        if self.VARIANT == "session":
+        if self.USES_SESSIONS:
             eng.check_inputs()          # session ids out of order cannot be expressed as key spans: raise, do not guess
         if isinstance(logits_to_keep, int) and logits_to_keep > 0:
             logits = logits[:, -logits_to_keep:, :]
@@ -403,6 +405,7 @@ class Qwen3SessionMultiWithTemperature(Qwen3MultiWithTemperature):
     attention additionally needs a lower behaviour level) and RoPE positions = ``extended_session_ids``.
     ``forward`` needs ``session_ids`` (the reference asserts the same) and validates their order on the host."""
     VARIANT = "session"
+    USES_SESSIONS = True
 
 
 class Qwen3WithTemperature(Qwen3MultiWithTemperature):
@@ -415,6 +418,7 @@ class Qwen3WithTemperature(Qwen3MultiWithTemperature):
     ignores them, as the reference's ``**kwargs`` does."""
     VARIANT = "qwen3"
     CONFIG_CLASS = Qwen3Config
+    USES_ACTIONS = False
 
     @staticmethod
     def _check_config(config):
@@ -439,6 +443,19 @@ class Qwen3WithTemperature(Qwen3MultiWithTemperature):
             raise NotImplementedError("num_return_sequences must equal num_beams (what the evaluation task uses)")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
+        skw = dict(session_ids=kwargs.get("session_ids"), extended_session_ids=kwargs.get("extended_session_ids")) \
+            if self.USES_SESSIONS else {}
         seqs, scores = decode.beam_search(self.engine, input_ids, attention_mask, None, trie, num_beams, max_new_tokens,
-                                          use_cache=bool(kwargs.get("use_cache", True)))
+                                          use_cache=bool(kwargs.get("use_cache", True)), **skw)
         return CausalLMOutput(sequences=seqs, sequences_scores=scores)
+
+
+class Qwen3SessionWithTemperature(Qwen3WithTemperature):
+    """ref:SeqRec/models/generative/Qwen3Session/model.py - HF ``Qwen3ForCausalLM`` with the temperature loss and session-wise
+    self-attention masks (``--backbone Qwen3Session``, train_SMB_decoder.py:369-378): the parameters and surface of
+    ``Qwen3WithTemperature`` on ``Engine(variant="qwen3_session")``.  The config must carry integer ``num_positions`` and
+    ``model_max_length`` (the reference asserts both).  ``forward`` needs ``session_ids`` and takes the RoPE positions from
+    ``extended_session_ids``; ``generate`` takes both, as test_SMB_decoder.py:139-156 passes them, and no ``actions``."""
+    VARIANT = "qwen3_session"
+    CONFIG_CLASS = Qwen3SessionConfig
+    USES_SESSIONS = True

@@ -111,6 +111,20 @@ def causal_prep(attn_mask, B, S, kl_self, empty_self, tile_empty_self, pos_ids=N
          ptr(next_pos), stream_ptr())
 
 
+def session_prep(session_ids, extended_session_ids, attn_mask, num_positions, n_rope_positions, out: dict):
+    """Qwen3Session's self mask as per-query key spans plus its RoPE positions, without a router (gamer_session_prep).
+    ``out``: kl_self, span_self, pos_ids, empty_self, tile_empty_self, violations (incremented, not cleared)."""
+    B, S = session_ids.shape
+    _chk(session_ids, torch.int64, "session_ids")
+    if extended_session_ids is not None:
+        _chk(extended_session_ids, torch.int64, "extended_session_ids")
+    if attn_mask is not None:
+        _chk(attn_mask, torch.int64, "attention_mask")
+    call("gamer_session_prep", ptr(session_ids), ptr(extended_session_ids), ptr(attn_mask), B, S, num_positions,
+         n_rope_positions, ptr(out["kl_self"]), ptr(out["span_self"]), ptr(out["pos_ids"]), ptr(out["empty_self"]),
+         ptr(out["tile_empty_self"]), ptr(out["violations"]), stream_ptr())
+
+
 def expert_lists(expert, num_experts, perm, slot, offsets, work):
     B, S = expert.shape
     call("gamer_expert_lists", ptr(expert), B, S, num_experts, ptr(perm), ptr(slot), ptr(offsets), ptr(work),

@@ -18,6 +18,9 @@ are synthetic tensors of the same layout.
 
 ``--backbone Qwen3`` trains the plain Qwen3 baseline (train_SMB_decoder.py:317-320: the Qwen3-Light config with the
 vocabulary resized; ``Engine(variant="qwen3")``); its checkpoints load into ``gamer_amd.modeling.Qwen3WithTemperature``.
+``--backbone Qwen3Session`` trains its session-mask ablation (train_SMB_decoder.py:369-378: the same config plus
+``num_positions`` = tokens per item and ``model_max_length``; ``Engine(variant="qwen3_session")``, synthetic batches with
+sessions of mean 4 items); its checkpoints load into ``gamer_amd.modeling.Qwen3SessionWithTemperature``.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ import time
 import torch
 
 from . import synthetic
-from .config import Qwen3Config, synthetic_config
+from .config import Qwen3Config, Qwen3SessionConfig, synthetic_config
 from .dp import GradAllReducer, all_reduce_scalar_
 from .engine import Engine
 from .schedule import cosine_with_warmup, warmup_steps_for
@@ -54,7 +57,8 @@ def parse_args(argv=None):
     ap.add_argument("--dataset", type=str, default="")
     ap.add_argument("--index_file", type=str, default=".index.json")
     ap.add_argument("--tasks", type=str, default="smb_explicit_decoder_4")
-    ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti", "Qwen3"])
+    ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti", "Qwen3",
+                                                                                 "Qwen3Session"])
     ap.add_argument("--patience", type=int, default=10, help="early stopping: evaluations without a better eval_loss")
     ap.add_argument("--save_total_limit", type=int, default=2)
     ap.add_argument("--bf16", action="store_true",
@@ -158,7 +162,7 @@ def main(argv=None):
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl", init_method="env://", device_id=torch.device("cuda", local_rank))
-    variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3"}.get(args.backbone, "multi")
+    variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3", "Qwen3Session": "qwen3_session"}.get(args.backbone, "multi")
     accum = args.gradient_accumulation_steps
     real = None
     if args.data_path:
@@ -181,6 +185,10 @@ def main(argv=None):
         if variant == "qwen3":
             # the baseline's config: Qwen3-Light with the tokenizer's vocabulary, nothing else set at run time
             cfg = Qwen3Config(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id)
+        elif variant == "qwen3_session":
+            # Qwen3-Light plus the item length and the tokenizer's model_max_length (train_SMB_decoder.py:369-378)
+            cfg = Qwen3SessionConfig(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id,
+                                     num_positions=cfg.num_positions, model_max_length=cfg.model_max_length)
         per_step = args.per_device_batch_size * accum * world
         args.steps_per_epoch = max(1, len(samples) // per_step)            # drop_last, as the window needs equal shards
         real = dict(samples=samples, coll=coll, valid=ds.valid_samples(args.max_his_len), only_response=only_response)
@@ -189,6 +197,9 @@ def main(argv=None):
                               "steps_per_epoch": args.steps_per_epoch}), flush=True)
     elif variant == "qwen3":
         cfg = Qwen3Config(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID)
+    elif variant == "qwen3_session":
+        cfg = Qwen3SessionConfig(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID,
+                                 num_positions=synthetic.TOKENS_PER_ITEM, model_max_length=1024)
     else:
         cfg = synthetic_config(n_positions=args.max_his_len + 1)
     eng = Engine(cfg, device=f"cuda:{local_rank}", temperature=args.temperature, variant=variant,
@@ -229,7 +240,8 @@ def main(argv=None):
             return real_micro(step)
         return [synthetic.make_batch(args.per_device_batch_size, items, 256, 3, ragged=args.ragged,
                                      seed=args.seed + 7919 * (step * accum + a) + 104729 * rank,
-                                     session_mean=4.0 if variant == "session" else None) for a in range(accum)]
+                                     session_mean=4.0 if variant in ("session", "qwen3_session") else None)
+                for a in range(accum)]
 
     feed = Prefetcher(make_step, state["global_step"], total_steps, args.prefetch)
     while state["global_step"] < total_steps:

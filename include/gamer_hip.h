@@ -97,6 +97,18 @@ int gamer_session_spans(const int64_t* session_ids, const int64_t* extended_sess
                         int32_t* tile_empty_self, int32_t* tile_empty_cross, int32_t* violations,
                         void* stream);
 
+/* Session mask of the Qwen3Session baseline (HF Qwen3ForCausalLM with Qwen3SessionMulti's self mask and RoPE positions;
+ * ref:SeqRec/models/generative/Qwen3Session/model.py:28-80 mask, :293-309 positions) without a router: the self half of
+ * gamer_session_spans (the same kernel, no cross inputs or outputs).
+ *   kl_self int32 [B,S] = 0 for kept keys, INT32_MAX for padded ones (the self query level is the constant 1)
+ *   span_self [B,S,4], pos_ids [B,S], empty_self [B,S], tile_empty_self [B, ceil(S/32)], violations [1]: as
+ *   gamer_session_spans'.  extended_session_ids NULL: positions 0..S-1.  S <= 2048.
+ * Additive in ABI 9.                                                                                                */
+int gamer_session_prep(const int64_t* session_ids, const int64_t* extended_session_ids, const int64_t* attn_mask,
+                       int B, int S, int num_positions, int n_rope_positions, int32_t* kl_self, int32_t* span_self,
+                       int32_t* pos_ids, int32_t* empty_self, int32_t* tile_empty_self, int32_t* violations,
+                       void* stream);
+
 /* Causal + key-padding mask of the Qwen3 baseline (HF Qwen3ForCausalLM; ref:SeqRec/models/generative/Qwen3/model.py) in the
  * attention kernels' form, and its per-row RoPE positions.  No router: allowed(i,j) = j <= i && attention_mask[j] != 0.
  *   attn_mask int64 [B,S] (may be NULL = all ones)
