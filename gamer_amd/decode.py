@@ -22,6 +22,7 @@ test_SMB_decoder.py:470-500): the same sequences in the same order and the same 
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Sequence, Tuple
 
 import torch
@@ -145,7 +146,8 @@ class _DecodeStatic:
     MEASURED on MI355X / ROCm 7.2 (tools/decode_leg.py): the replay is no faster than the eager step - 2.45 against 2.40 ms per token
     at 16 users x 20 beams, 2.28 / 2.28 at 64, 4.08 / 3.98 at 256: a kernel node costs the ~7 us of dispatch an eager launch costs,
     and at 256 users the step is GPU time anyway (tools/decode_step_kernels.py: gamer_attn_decode 1.73 of 3.6 ms) - so the graph
-    is OFF by default; what would shorten the step is FEWER launches, not cheaper ones."""
+    is OFF by default; what would shorten the step is FEWER launches, not cheaper ones.
+    The buffers belong to the latest session of the shape: ``claims`` counts the sessions that have taken them."""
 
     def __init__(self):
         self.kp: Dict[Tuple[int, str], torch.Tensor] = {}
@@ -157,11 +159,21 @@ class _DecodeStatic:
         self.graphs: Dict[int, "torch.cuda.CUDAGraph"] = {}
         self.sessions = 0            # sessions of this shape that have run so far
         self.sig = None              # state of the engine's maxima cache the graphs were captured against
+        self.claims = 0              # sessions that have taken these buffers (the latest one owns them)
 
 
 def _graphs_enabled() -> bool:
-    import os
     return os.environ.get("GAMER_DECODE_GRAPH", "0") == "1"
+
+
+def _session_kw(engine, session_ids, extended_session_ids) -> dict:
+    """The session ids of a session engine ("session", "qwen3_session") on the device - required there - and {} for the others."""
+    if engine.variant not in ("session", "qwen3_session"):
+        return {}
+    if session_ids is None or extended_session_ids is None:
+        raise ValueError("a session engine needs session_ids and extended_session_ids")
+    return dict(session_ids=session_ids.to(engine.device, torch.int64),
+                extended_session_ids=extended_session_ids.to(engine.device, torch.int64))
 
 
 class DecodeSession:
@@ -171,7 +183,14 @@ class DecodeSession:
     once per sample; only the generated positions are per beam.  ``step`` pushes one token per beam through the
     layers with the ordinary row kernels (norms, GEMMs with M = B*num_beams rows, SwiGLU) - all new tokens of a
     step sit at the same position, hence in the same position-routed expert - and ``gamer_attn_decode``.
-    GAMER_DECODE_GRAPH=1: from the third session of a shape on the step is a hipGraph replay (``_DecodeStatic``: measured neutral)."""
+    GAMER_DECODE_GRAPH=1: from the third session of a shape on the step is a hipGraph replay (``_DecodeStatic``: measured neutral).
+    This class is Qwen3Multi's (and Qwen3SessionMulti's) session and the core every model shares; a model's own parts are the
+    hooks ``_eval_forward`` (its prompt pass), ``_row_inputs`` (the step's per-row inputs) and ``_layer_tail`` (a layer after
+    its self-attention block) - ``Qwen3DecodeSession`` overrides them for the plain Qwen3 baselines.
+    ONE LIVE SESSION PER SHAPE: the sessions of an engine with the same (batch, prompt length, beams, new tokens, model, cross
+    cache order, matmul form) share their buffers (``_DecodeStatic``).  Creating a session takes them over; ``step`` and
+    ``reorder`` of an older session of that shape then raise RuntimeError instead of attending over the newer one's caches
+    (``beam_search`` runs one session at a time)."""
 
     def __init__(self, engine, input_ids, attention_mask, actions, num_beams: int, max_new_tokens: int,
                  session_ids=None, extended_session_ids=None, reorder_cross_cache: bool = False):
@@ -190,22 +209,26 @@ class DecodeSession:
         self.eng, self.nb, self.tmax = engine, num_beams, max_new_tokens
         self.reorder_cross_cache = bool(reorder_cross_cache)
         self.B, self.L0 = input_ids.shape
-        B, L0, nb = self.B, self.L0, num_beams
-        self.N = N = B * nb
-        self.session = engine.variant == "session"
+        B, L0 = self.B, self.L0
+        self.N = N = B * num_beams
+        sess = _session_kw(engine, session_ids, extended_session_ids)
         statics = engine.__dict__.setdefault("_decode_static", {})
-        key = (B, L0, nb, max_new_tokens, engine.variant, self.reorder_cross_cache, engine.matmul)
+        key = (B, L0, num_beams, max_new_tokens, engine.variant, self.reorder_cross_cache, engine.matmul)
         st = statics.get(key)
         if st is None:
             if len(statics) >= 4:                     # (a few shapes at most: the buffers of a shape are ~2.5 GB at 256 users)
                 statics.pop(next(iter(statics)))
             st = statics[key] = _DecodeStatic()
         self.st = st
+        st.claims += 1                                # (before the prompt pass overwrites the caches of an older session)
+        self.claim = st.claims
         ids0 = input_ids.to(dev, torch.int64)
         am0 = attention_mask.to(dev, torch.int64)
-        act0 = actions.to(dev, torch.int64)
+        act0 = None if actions is None else actions.to(dev, torch.int64)
         nq, nkv, dh = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         self.NQ, self.NKV = nq * dh, nkv * dh
+        QKV = self.NQ + 2 * self.NKV
+        T0 = B * L0
         f32 = dict(dtype=torch.float32, device=dev)
         self.kp, self.vp = st.kp, st.vp
 
@@ -213,9 +236,6 @@ class DecodeSession:
         # (Engine.forward(kv_dest=...): the V cache is the v columns of the layer's own q|k|v buffer, row stride QKV) - no copy of 2 x
         # 98 MB per layer and kind - and the maxima the three-piece decode attention needs are the ones the prompt pass's own
         # attention used (the producers left them in the engine's maxima cache): no gamer_absmax_f32 pass over the caches either
-        import os
-        QKV = self.NQ + 2 * self.NKV
-        T0 = ids0.shape[0] * ids0.shape[1]
         direct = engine.dtype == "f32" and os.environ.get("GAMER_DECODE_DIRECT_KV", "1") != "0"      # (0: the copying path, A/B and tests)
         want_amax = (engine._amax is not None and engine.matmul == "split3" and os.environ.get("GAMER_DECODE_ATTN_SPLIT", "1") != "0")
         prompt_amax = {}
@@ -243,16 +263,8 @@ class DecodeSession:
             else:
                 st.kp[kk].copy_(k)
                 st.vp[kk].copy_(v)
-        if self.session and (session_ids is None or extended_session_ids is None):
-            raise ValueError("a session engine needs session_ids and extended_session_ids")
-        skw = {}
-        if self.session:
-            sid0 = session_ids.to(dev, torch.int64)
-            ext0 = extended_session_ids.to(dev, torch.int64)
-            skw = dict(session_ids=sid0, extended_session_ids=ext0)
-        engine.forward(ids0, am0, act0, train=False, act_zero_col=L0 - 1, uniform_len=L0, kv_sink=sink,
-                       kv_dest=dest if direct else None, last_row_logits=True, **skw)
-        if self.session:
+        self._eval_forward(engine, ids0, am0, act0, sess, L0, kv_sink=sink, kv_dest=dest if direct else None, last_row_logits=True)
+        if sess:
             engine.check_inputs()
         # last-row logits of every sample: the head ran on B rows, not on the whole prompt
         self.prefill_logits = engine.last_logits_buf
@@ -266,36 +278,28 @@ class DecodeSession:
             else:
                 t.copy_(value)
             return t
-        # masks of the new rows: self = kept keys; cross = kept keys of a lower level than the target behaviour
-        # (the cached last mask row, model.py:603-617); no allowed key -> uniform over every key
-        lv = act0[:, -1:]
         self.ok_self = keep("ok_self", am0.to(torch.int32))
-        ok_cross = (am0[:, :] != 0) & (act0 < lv)
+        # RoPE position of the token generated at step t, per beam row: pos_last + t - for a session model the prompt's largest
+        # extended id + t; None: position L0 + t - 1 for every row
         self.pos_last = None
-        if self.session:
-            ok_cross &= sid0 < sid0[:, -1:]              # Qwen3SessionMulti/model.py:582-584, last prompt row
-            # RoPE table row of the token generated at step t: the prompt's largest extended id + t
-            self.pos_last = keep("pos_last", ext0.max(dim=1).values.to(torch.int32).repeat_interleave(nb))
-        ok_cross[:, -1] = False
-        self.ok_cross = keep("ok_cross", ok_cross.to(torch.int32))
-        self.uniform_cross = keep("uniform_cross", (~ok_cross.any(1)).to(torch.int32))
-        # router outputs of the generated tokens (router.py:158-195 in decode mode): behaviour index + 1 of the
-        # target item's behaviour token, for the FFN injection and for the cross-attention biases
-        beh = engine.lut[ids0[:, -1]].to(torch.int32) + 1
-        self.beh = keep("beh", beh.repeat_interleave(nb))
+        if sess:
+            self.pos_last = keep("pos_last", sess["extended_session_ids"].max(dim=1).values.to(torch.int32).repeat_interleave(num_beams))
+        self._row_inputs(keep, ids0, am0, act0, sess)
         if st.gen is None:
             st.gen = {kk: (torch.zeros(N, max_new_tokens, self.NKV, **f32), torch.zeros(N, max_new_tokens, self.NKV, **f32))
                       for kk in self.kp}
             H, I = cfg.hidden_size, cfg.intermediate_size
-            QKV = self.NQ + 2 * self.NKV
-            din_max = H + cfg.behavior_embedding_dim
-            st.buf = dict(x=[torch.empty(N, H, **f32) for _ in range(3)], h=torch.empty(N, H, **f32),
+            st.buf = dict(x=[torch.empty(N, H, **f32) for _ in range(2)], h=torch.empty(N, H, **f32),
                           qkv=torch.empty(N, QKV, **f32), q=torch.empty(N, self.NQ, **f32), k=torch.empty(N, self.NKV, **f32),
-                          ao=torch.empty(N, self.NQ, **f32), op=torch.empty(N, H, **f32), gate=torch.empty(N, H, **f32),
-                          t0=torch.empty(N, H, **f32), hin=torch.empty(N, din_max, **f32), gu=torch.empty(N, 2 * I, **f32),
-                          hm=torch.empty(N, I, **f32), xn=torch.empty(N, H, **f32),
-                          logits=torch.empty(N, engine.ws.ldl, **f32),
+                          ao=torch.empty(N, self.NQ, **f32), gu=torch.empty(N, 2 * I, **f32), hm=torch.empty(N, I, **f32),
+                          xn=torch.empty(N, H, **f32), logits=torch.empty(N, engine.ws.ldl, **f32),
                           gen_tmp=torch.empty(N, max(1, max_new_tokens - 1), self.NKV, **f32))
+            if cfg.cross_attention_decoder or cfg.behavior_injection_decoder:
+                # Qwen3Multi's layers: the state after the cross block, its o_proj and gate outputs, and the FFN input widened
+                # by the injected behaviour embedding (without these layers the FFN reads h)
+                st.buf["x"].append(torch.empty(N, H, **f32))
+                st.buf.update(op=torch.empty(N, H, **f32), gate=torch.empty(N, H, **f32),
+                              hin=torch.empty(N, H + cfg.behavior_embedding_dim, **f32))
             st.small["tok"] = torch.zeros(N, dtype=torch.int64, device=dev)
             st.small["parent"] = torch.arange(N, dtype=torch.int64, device=dev)
         # (stale generated rows of an earlier session are never read: gamer_attn_decode takes the number of valid positions)
@@ -322,10 +326,37 @@ class DecodeSession:
             st.sessions = 0
         st.sessions += 1
 
+    @staticmethod
+    def _eval_forward(engine, ids, am, act, sess: dict, L0: int, **kw):
+        """The model's evaluation forward of prompts of length ``L0`` (+ generated tokens): a session's prompt pass and the
+        cache-free re-run of ``beam_search``.  Qwen3Multi: with the two things the reference's cache freezes, ``act_zero_col``
+        and ``uniform_len`` (Engine.forward)."""
+        engine.forward(ids, am, act, train=False, act_zero_col=L0 - 1, uniform_len=L0, **sess, **kw)
+
+    def _row_inputs(self, keep, ids0, am0, act0, sess: dict):
+        """The step's per-row inputs besides ``ok_self`` and a session model's ``pos_last``.  Qwen3Multi: the cross mask of the
+        new rows = kept keys of a lower level than the target behaviour (the cached last mask row, model.py:603-617; no allowed
+        key -> uniform over every key), and the router outputs of the generated tokens (router.py:158-195 in decode mode):
+        behaviour index + 1 of the target item's behaviour token, for the FFN injection and the cross-attention biases."""
+        ok_cross = (am0 != 0) & (act0 < act0[:, -1:])
+        if sess:
+            sid0 = sess["session_ids"]
+            ok_cross &= sid0 < sid0[:, -1:]              # Qwen3SessionMulti/model.py:582-584, last prompt row
+        ok_cross[:, -1] = False
+        self.ok_cross = keep("ok_cross", ok_cross.to(torch.int32))
+        self.uniform_cross = keep("uniform_cross", (~ok_cross.any(1)).to(torch.int32))
+        self.beh = keep("beh", (self.eng.lut[ids0[:, -1]].to(torch.int32) + 1).repeat_interleave(self.nb))
+
+    def _own(self):
+        if self.st.claims != self.claim:
+            raise RuntimeError("a newer DecodeSession of the same shape has taken this engine's decode buffers: only the latest "
+                               "session of a shape can step (one live session per shape)")
+
     def reorder(self, parent: torch.Tensor):
         """Beams were re-ordered: the generated part of the SELF cache follows its beam (the prompt part is shared);
         the cross cache only with ``reorder_cross_cache`` (see __init__).  The rows move at the start of the next step
         (in place, the positions generated so far only), so that the move is part of the captured step."""
+        self._own()
         self.st.small["parent"].copy_(parent)
         self._pending_reorder = True
 
@@ -336,6 +367,7 @@ class DecodeSession:
         (matmul="split3": runs inside the engine's maxima cache - the parameters keep the slots of the prompt pass, which
         measured them once (they cannot change during a generation), the producers of the step's activations hand their
         maxima to the GEMMs (gamer_amax_sink) - instead of two gamer_absmax_f32 launches per GEMM and token.)"""
+        self._own()
         st = self.st
         st.small["tok"].copy_(tokens)
         self.t += 1
@@ -365,14 +397,11 @@ class DecodeSession:
 
     def _step_body(self, t: int):
         eng, cfg, b = self.eng, self.eng.cfg, self.buf
-        N, B, nb, L0 = self.N, self.B, self.nb, self.L0
-        H, I, E = cfg.hidden_size, cfg.intermediate_size, cfg.num_experts
-        nq, nkv, NQ, NKV = cfg.num_attention_heads, cfg.num_key_value_heads, self.NQ, self.NKV
-        QKV = NQ + 2 * NKV
-        eps, scale = float(cfg.rms_norm_eps), float(cfg.head_dim) ** -0.5
-        tokens, parent = self.st.small["tok"], self.st.small["parent"]
+        N, L0, NQ, NKV = self.N, self.L0, self.NQ, self.NKV
+        H, eps = cfg.hidden_size, float(cfg.rms_norm_eps)
         if t >= 2:
             # the beams were re-ordered after the last step: the t - 1 generated positions follow them
+            parent = self.st.small["parent"]
             for key, (kg, vg) in self.gen.items():
                 if key[1] == "cross" and not self.reorder_cross_cache:
                     continue
@@ -381,86 +410,92 @@ class DecodeSession:
                 kg[:, :t - 1] = tmp
                 torch.index_select(vg[:, :t - 1], 0, parent, out=tmp)
                 vg[:, :t - 1] = tmp
-        p = L0 + t - 1                                   # position of the new token
         cos, sin = eng.rope(L0 + self.tmax)
-        pos_ids = None
-        if self.session:
-            pos_ids = (self.pos_last + t).contiguous()   # per beam row; the table is indexed through pos_ids
-        else:
-            cos, sin = cos[p:p + 1], sin[p:p + 1]
-        e = p % cfg.num_positions + 1                    # position-routed expert (router.py:83-104), same for every row
-        grp = None
-        if eng._amax is not None and eng.matmul == "split3":
-            key = f"expert_offsets_{e}"
-            if key not in self.st.small:           # rows [0, N) belong to expert e, every other group is empty
-                self.st.small[key] = torch.tensor([0] * (e + 1) + [N] * (E - e), dtype=torch.int32, device=tokens.device)
-            grp = dict(groups=E, group_offsets=self.st.small[key])
-        import os
-        fused_ok = eng.dtype == "f32" and os.environ.get("GAMER_DECODE_FUSE_QK", "1") != "0"
-        x, x1, x2 = b["x"]
-        ops.embedding_fwd(tokens, eng.params["model.embed_tokens.weight"], x)
-
+        if self.pos_last is None:                        # the table row of the new tokens' common position
+            p = L0 + t - 1
+            self._rope = (cos[p:p + 1], sin[p:p + 1], None)
+        else:                                            # per beam row; the table is indexed through pos_ids
+            self._rope = (cos, sin, (self.pos_last + t).contiguous())
         # the per-head RMSNorm + RoPE as the q|k|v projection's epilogue: at these row counts the projection runs on the 128 x 128 kernel
         # either way (the activation-stationary kernel starts at 16 k rows), so the epilogue only removes a launch and a pass per
         # attention and token (in the train step, where it would displace the faster kernel, it measured 9 ms slower)
-        fuse_qk = fused_ok and ops.qkv_fused_ok(b["h"], N, QKV)
-
-        def attend(kind, layer, Wa, hin, xin, xout, act_idx):
-            bias = dict(bias_q=Wa["bq"], bias_k=Wa["bk"], bias_v=Wa["bv"], act_idx=act_idx) if kind == "cross" else {}
-            if fuse_qk:
-                ops.gemm(hin, H, 1, Wa["qkv"], H, 1, b["qkv"], QKV, N, QKV, H,
-                         qknorm=dict(wq=Wa["qn"], wk=Wa["kn"], eps=eps, cos=cos, sin=sin, q_rot=b["q"], k_rot=b["k"], pos_ids=pos_ids,
-                                     S=1, nq=nq, nkv=nkv, **bias))
-            else:
-                ops.linear_fwd(hin, H, Wa["qkv"], H, b["qkv"], QKV, N, QKV, H)
-                ops.qknorm_rope_fwd(b["qkv"], 1, nq, nkv, Wa["qn"], Wa["kn"], eps, cos, sin, b["q"], b["k"], pos_ids=pos_ids, **bias)
-            kg, vg = self.gen[(layer, kind)]
-            ops.kv_append(b["k"], b["qkv"][:, NQ + NKV:], kg, vg, t - 1)
-            ops.attn_decode(b["q"], self.kp[(layer, kind)], self.vp[(layer, kind)],
-                            self.ok_self if kind == "self" else self.ok_cross, kg, vg, t, kind == "self",
-                            None if kind == "self" else self.uniform_cross, B, nb, L0, nq, nkv, scale, b["ao"],
-                            amax=self.kv_amax.get((layer, kind)))
-            if kind == "self":
-                ops.gemm(b["ao"], NQ, 1, Wa["o"], NQ, 1, xout, H, N, H, NQ, resid=xin)
-            else:
-                ops.linear_fwd(b["ao"], NQ, Wa["o"], NQ, b["op"], H, N, H, NQ)
-                ops.linear_fwd(hin, H, Wa["gate"], H, b["gate"], H, N, H, H)
-                ops.silu_gate_fwd(b["op"], b["gate"], xout, resid=xin)
-
-        # x holds the layer input and receives the layer output; x1 / x2 are the states after the self / cross block
+        self._fuse_qk = (eng.dtype == "f32" and os.environ.get("GAMER_DECODE_FUSE_QK", "1") != "0"
+                         and ops.qkv_fused_ok(b["h"], N, NQ + 2 * NKV))
+        x, x1 = b["x"][:2]
+        ops.embedding_fwd(self.st.small["tok"], eng.params["model.embed_tokens.weight"], x)
+        # x holds the layer input and receives the layer output; x1 is the state after the self-attention block
         for l in range(cfg.num_hidden_layers):
             W = eng.W[l]
             ops.rmsnorm_fwd(x, W.ln1, eps, b["h"])
-            attend("self", l, W.self_attn, b["h"], x, x1, None)
-            xc = x1
-            if W.cross:
-                ops.rmsnorm_fwd(x1, W.ln2, eps, b["h"])
-                attend("cross", l, W.cross_attn, b["h"], x1, x2, self.beh)
-                xc = x2
-            din = W.din
-            ops.rmsnorm_fwd(xc, W.ln3, eps, b["hin"], din)
-            if W.inject:
-                ops.rowtable_fwd(W.beh, self.beh, b["hin"], din, H)
-            if grp is not None:
-                # the whole stacked weight with every row in expert e's group: the tensor the prompt pass measured and cut (its maximum
-                # slot and packed pieces are reused; a row slice is another tensor to the maxima cache - two gamer_absmax_f32 launches
-                # and two cuts of the weight per layer and token)
-                ops.linear_fwd(b["hin"], din, W.gu, din, b["gu"], 2 * I, N, 2 * I, din, strideB=2 * I * din, **grp)
-                ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
-                ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, strideB=H * I, resid=xc, **grp)
-                continue
-            ops.linear_fwd(b["hin"], din, W.gu[e * 2 * I:(e + 1) * 2 * I], din, b["gu"], 2 * I, N, 2 * I, din)      # gate | up of expert e
-            ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
-            ops.gemm(b["hm"], I, 1, W.down[e * H:(e + 1) * H], I, 1, x, H, N, H, I, resid=xc)
-        cur = x
-        ops.rmsnorm_fwd(cur, eng.params["model.norm.weight"], eps, b["xn"])
+            self._attend(t, "self", l, W.self_attn)
+            ops.gemm(b["ao"], NQ, 1, W.self_attn["o"], NQ, 1, x1, H, N, H, NQ, resid=x)
+            self._layer_tail(t, l, W, x, x1)
+        ops.rmsnorm_fwd(x, eng.params["model.norm.weight"], eps, b["xn"])
         ops.linear_fwd(b["xn"], H, eng.params["model.embed_tokens.weight"], H, b["logits"], b["logits"].stride(0), N,
                        cfg.vocab_size, H)
+
+    def _attend(self, t: int, kind: str, layer: int, Wa: dict, act_idx=None):
+        """Attention of the new rows (input b["h"]) into b["ao"]: q|k|v with the per-head RMSNorm + RoPE, the new position
+        appended to the layer's generated K / V, ``gamer_attn_decode`` over the prompt's and the generated keys.  ``act_idx``:
+        the behaviour biases of a cross block."""
+        cfg, b = self.eng.cfg, self.buf
+        N, H, NQ, NKV = self.N, cfg.hidden_size, self.NQ, self.NKV
+        nq, nkv, QKV = cfg.num_attention_heads, cfg.num_key_value_heads, NQ + 2 * NKV
+        eps, scale = float(cfg.rms_norm_eps), float(cfg.head_dim) ** -0.5
+        cos, sin, pos_ids = self._rope
+        is_self = kind == "self"
+        bias = {} if is_self else dict(bias_q=Wa["bq"], bias_k=Wa["bk"], bias_v=Wa["bv"], act_idx=act_idx)
+        if self._fuse_qk:
+            ops.gemm(b["h"], H, 1, Wa["qkv"], H, 1, b["qkv"], QKV, N, QKV, H,
+                     qknorm=dict(wq=Wa["qn"], wk=Wa["kn"], eps=eps, cos=cos, sin=sin, q_rot=b["q"], k_rot=b["k"], pos_ids=pos_ids,
+                                 S=1, nq=nq, nkv=nkv, **bias))
+        else:
+            ops.linear_fwd(b["h"], H, Wa["qkv"], H, b["qkv"], QKV, N, QKV, H)
+            ops.qknorm_rope_fwd(b["qkv"], 1, nq, nkv, Wa["qn"], Wa["kn"], eps, cos, sin, b["q"], b["k"], pos_ids=pos_ids, **bias)
+        kg, vg = self.gen[(layer, kind)]
+        ops.kv_append(b["k"], b["qkv"][:, NQ + NKV:], kg, vg, t - 1)
+        ops.attn_decode(b["q"], self.kp[(layer, kind)], self.vp[(layer, kind)], self.ok_self if is_self else self.ok_cross,
+                        kg, vg, t, is_self, None if is_self else self.uniform_cross, self.B, self.nb, self.L0, nq, nkv,
+                        scale, b["ao"], amax=self.kv_amax.get((layer, kind)))
+
+    def _layer_tail(self, t: int, l: int, W, x, x1):
+        """Layer ``l`` after its self-attention block (output x1): the layer output into x.  Qwen3Multi: the cross block with
+        the behaviour biases and the output gate, the behaviour injection and the position-routed expert FFN."""
+        eng, cfg, b, N = self.eng, self.eng.cfg, self.buf, self.N
+        H, I, E, NQ, eps = cfg.hidden_size, cfg.intermediate_size, cfg.num_experts, self.NQ, float(cfg.rms_norm_eps)
+        xc = x1
+        if W.cross:
+            xc = b["x"][2]
+            ops.rmsnorm_fwd(x1, W.ln2, eps, b["h"])
+            self._attend(t, "cross", l, W.cross_attn, self.beh)
+            ops.linear_fwd(b["ao"], NQ, W.cross_attn["o"], NQ, b["op"], H, N, H, NQ)
+            ops.linear_fwd(b["h"], H, W.cross_attn["gate"], H, b["gate"], H, N, H, H)
+            ops.silu_gate_fwd(b["op"], b["gate"], xc, resid=x1)
+        hin, din = b.get("hin", b["h"]), W.din
+        ops.rmsnorm_fwd(xc, W.ln3, eps, hin, din)
+        if W.inject:
+            ops.rowtable_fwd(W.beh, self.beh, hin, din, H)
+        e = (self.L0 + t - 1) % cfg.num_positions + 1    # position-routed expert (router.py:83-104), same for every row
+        if eng._amax is not None and eng.matmul == "split3":
+            # the whole stacked weight with every row in expert e's group: the tensor the prompt pass measured and cut (its maximum
+            # slot and packed pieces are reused; a row slice is another tensor to the maxima cache - two gamer_absmax_f32 launches
+            # and two cuts of the weight per layer and token)
+            key = f"expert_offsets_{e}"
+            if key not in self.st.small:           # rows [0, N) belong to expert e, every other group is empty
+                self.st.small[key] = torch.tensor([0] * (e + 1) + [N] * (E - e), dtype=torch.int32, device=eng.device)
+            grp = dict(groups=E, group_offsets=self.st.small[key])
+            ops.linear_fwd(hin, din, W.gu, din, b["gu"], 2 * I, N, 2 * I, din, strideB=2 * I * din, **grp)
+            ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
+            ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, strideB=H * I, resid=xc, **grp)
+            return
+        ops.linear_fwd(hin, din, W.gu[e * 2 * I:(e + 1) * 2 * I], din, b["gu"], 2 * I, N, 2 * I, din)      # gate | up of expert e
+        ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
+        ops.gemm(b["hm"], I, 1, W.down[e * H:(e + 1) * H], I, 1, x, H, N, H, I, resid=xc)
 
 
 class Qwen3DecodeSession(DecodeSession):
     """K/V cache + single-token step of the plain Qwen3 baselines (``Engine(variant="qwen3")`` / ``"qwen3_session"``): self
-    attention only.  The prompt pass runs with transformers' generate() positions ``cumsum(attention_mask) - 1``
+    attention and a dense MLP per layer.  The prompt pass runs with transformers' generate() positions ``cumsum(attention_mask) - 1``
     (gamer_causal_prep builds them on the device) and writes every layer's q|k|v and rotated keys in place; the token
     generated at step t is rotated by (number of kept prompt tokens) + t - 1, per row - a left-padded prompt by its own offset.
     Qwen3Session (``session_ids`` / ``extended_session_ids`` [B, L0], required): the prompt pass runs with the session mask
@@ -469,149 +504,28 @@ class Qwen3DecodeSession(DecodeSession):
 
     def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int, session_ids=None,
                  extended_session_ids=None):
-        import os
-        cfg, dev = engine.cfg, engine.device
-        self.eng, self.nb, self.tmax = engine, num_beams, max_new_tokens
-        self.reorder_cross_cache = False
-        self.session = False
-        self.B, self.L0 = input_ids.shape
-        B, L0, nb = self.B, self.L0, num_beams
-        self.N = N = B * nb
-        statics = engine.__dict__.setdefault("_decode_static", {})
-        key = (B, L0, nb, max_new_tokens, engine.variant, False, engine.matmul)
-        st = statics.get(key)
-        if st is None:
-            if len(statics) >= 4:
-                statics.pop(next(iter(statics)))
-            st = statics[key] = _DecodeStatic()
-        self.st = st
-        ids0 = input_ids.to(dev, torch.int64)
-        am0 = attention_mask.to(dev, torch.int64)
-        nq, nkv, dh = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        self.NQ, self.NKV = nq * dh, nkv * dh
-        QKV = self.NQ + 2 * self.NKV
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.kp, self.vp = st.kp, st.vp
-        T0 = B * L0
         if engine.dtype != "f32":
             raise NotImplementedError("generation (cached decode) is built for dtype='f32' only")
-        want_amax = (engine._amax is not None and engine.matmul == "split3" and os.environ.get("GAMER_DECODE_ATTN_SPLIT", "1") != "0")
-        prompt_amax = {}
+        super().__init__(engine, input_ids, attention_mask, None, num_beams, max_new_tokens, session_ids, extended_session_ids)
 
-        def dest(layer, kind):
-            kk = (layer, kind)
-            if kk not in st.qkvp or st.qkvp[kk].shape[0] != T0:
-                st.qkvp[kk] = torch.empty(T0, QKV, **f32)
-                st.kp[kk] = torch.empty(T0, self.NKV, **f32)
-                st.vp[kk] = st.qkvp[kk][:, self.NQ + self.NKV:]
-            return st.qkvp[kk], st.kp[kk]
+    @staticmethod
+    def _eval_forward(engine, ids, am, act, sess: dict, L0: int, **kw):
+        """RoPE positions from the extended session ids (Qwen3Session) or, as transformers' generate(), from the attention mask."""
+        engine.forward(ids, am, train=False, **(sess or dict(rope_from_mask=True)), **kw)
 
-        def sink(layer, kind, k, v):
-            if want_amax:
-                sk = engine._amax.peek(k, (1, 0, T0, self.NKV, k.stride(0)))
-                sv = engine._amax.peek(v, (1, 0, T0, self.NKV, v.stride(0)))
-                if sk and sv:
-                    prompt_amax[(layer, kind)] = (sk, sv)
-        sessions = engine.variant == "qwen3_session"
-        if sessions:
-            if session_ids is None or extended_session_ids is None:
-                raise ValueError("a session engine needs session_ids and extended_session_ids")
-            ext0 = extended_session_ids.to(dev, torch.int64)
-            engine.forward(ids0, am0, train=False, kv_sink=sink, kv_dest=dest, last_row_logits=True,
-                           session_ids=session_ids.to(dev, torch.int64), extended_session_ids=ext0)
-            engine.check_inputs()
-        else:
-            engine.forward(ids0, am0, train=False, kv_sink=sink, kv_dest=dest, last_row_logits=True, rope_from_mask=True)
-        self.prefill_logits = engine.last_logits_buf
+    def _row_inputs(self, keep, ids0, am0, act0, sess: dict):
+        """The plain baseline's pos_last: the number of kept prompt tokens - 1 (gamer_causal_prep's next_pos - 1), per row."""
+        if not sess:
+            self.pos_last = keep("pos_last", (self.eng.ws.mask["next_pos"] - 1).repeat_interleave(self.nb))
 
-        def keep(name, value):
-            value = value.contiguous()
-            t = st.small.get(name)
-            if t is None or t.shape != value.shape or t.dtype != value.dtype:
-                st.small[name] = t = value.clone()
-            else:
-                t.copy_(value)
-            return t
-        self.ok_self = keep("ok_self", am0.to(torch.int32))
-        # RoPE position of the token generated at step t: pos_last + t (next_pos = kept prompt tokens, gamer_causal_prep;
-        # Qwen3Session: the prompt's largest extended id)
-        last = ext0.max(dim=1).values.to(torch.int32) if sessions else engine.ws.mask["next_pos"] - 1
-        self.pos_last = keep("pos_last", last.repeat_interleave(nb))
-        if st.gen is None:
-            st.gen = {kk: (torch.zeros(N, max_new_tokens, self.NKV, **f32), torch.zeros(N, max_new_tokens, self.NKV, **f32))
-                      for kk in self.kp}
-            H, I = cfg.hidden_size, cfg.intermediate_size
-            st.buf = dict(x=[torch.empty(N, H, **f32) for _ in range(2)], h=torch.empty(N, H, **f32),
-                          qkv=torch.empty(N, QKV, **f32), q=torch.empty(N, self.NQ, **f32), k=torch.empty(N, self.NKV, **f32),
-                          ao=torch.empty(N, self.NQ, **f32), gu=torch.empty(N, 2 * I, **f32), hm=torch.empty(N, I, **f32),
-                          xn=torch.empty(N, H, **f32), logits=torch.empty(N, engine.ws.ldl, **f32),
-                          gen_tmp=torch.empty(N, max(1, max_new_tokens - 1), self.NKV, **f32))
-            st.small["tok"] = torch.zeros(N, dtype=torch.int64, device=dev)
-            st.small["parent"] = torch.arange(N, dtype=torch.int64, device=dev)
-        self.gen, self.buf = st.gen, st.buf
-        self._pending_reorder = False
-        self.t = 0
-        self.kv_amax = {}
-        if want_amax:
-            if len(prompt_amax) == len(self.kp):
-                self.kv_amax = prompt_amax
-            else:
-                with ops.f32_matmul("split3"), engine._amax:
-                    for kk in self.kp:
-                        kpt, vpt = self.kp[kk], self.vp[kk]
-                        self.kv_amax[kk] = (ops.absmax_slot(kpt, 1, 0, kpt.shape[0], kpt.shape[1], kpt.stride(0)),
-                                            ops.absmax_slot(vpt, 1, 0, vpt.shape[0], vpt.shape[1], vpt.stride(0)))
-        am_ = engine._amax
-        self._sig = None if am_ is None else (len(am_._wkeys), am_.used, 0 if am_.planes is None else am_.planes.data_ptr())
-        if st.graphs and st.sig != self._sig:
-            st.graphs.clear()
-            st.sessions = 0
-        st.sessions += 1
-
-    def _step_body(self, t: int):
-        eng, cfg, b = self.eng, self.eng.cfg, self.buf
-        N, B, nb, L0 = self.N, self.B, self.nb, self.L0
+    def _layer_tail(self, t: int, l: int, W, x, x1):
+        """The dense SwiGLU MLP."""
+        cfg, b, N = self.eng.cfg, self.buf, self.N
         H, I = cfg.hidden_size, cfg.intermediate_size
-        nq, nkv, NQ, NKV = cfg.num_attention_heads, cfg.num_key_value_heads, self.NQ, self.NKV
-        QKV = NQ + 2 * NKV
-        eps, scale = float(cfg.rms_norm_eps), float(cfg.head_dim) ** -0.5
-        tokens, parent = self.st.small["tok"], self.st.small["parent"]
-        if t >= 2:
-            # the beams were re-ordered after the last step: the t - 1 generated positions follow them
-            for kg, vg in self.gen.values():
-                tmp = b["gen_tmp"].view(-1)[:N * (t - 1) * NKV].view(N, t - 1, NKV)
-                torch.index_select(kg[:, :t - 1], 0, parent, out=tmp)
-                kg[:, :t - 1] = tmp
-                torch.index_select(vg[:, :t - 1], 0, parent, out=tmp)
-                vg[:, :t - 1] = tmp
-        cos, sin = eng.rope(L0 + self.tmax)
-        pos_ids = (self.pos_last + t).contiguous()       # per beam row; the table is indexed through pos_ids
-        x, x1 = b["x"]
-        ops.embedding_fwd(tokens, eng.params["model.embed_tokens.weight"], x)
-        fuse_qk = ops.qkv_fused_ok(b["h"], N, QKV)
-        for l in range(cfg.num_hidden_layers):
-            W = eng.W[l]
-            Wa = W.self_attn
-            ops.rmsnorm_fwd(x, W.ln1, eps, b["h"])
-            if fuse_qk:
-                ops.gemm(b["h"], H, 1, Wa["qkv"], H, 1, b["qkv"], QKV, N, QKV, H,
-                         qknorm=dict(wq=Wa["qn"], wk=Wa["kn"], eps=eps, cos=cos, sin=sin, q_rot=b["q"], k_rot=b["k"],
-                                     pos_ids=pos_ids, S=1, nq=nq, nkv=nkv))
-            else:
-                ops.linear_fwd(b["h"], H, Wa["qkv"], H, b["qkv"], QKV, N, QKV, H)
-                ops.qknorm_rope_fwd(b["qkv"], 1, nq, nkv, Wa["qn"], Wa["kn"], eps, cos, sin, b["q"], b["k"], pos_ids=pos_ids)
-            kg, vg = self.gen[(l, "self")]
-            ops.kv_append(b["k"], b["qkv"][:, NQ + NKV:], kg, vg, t - 1)
-            ops.attn_decode(b["q"], self.kp[(l, "self")], self.vp[(l, "self")], self.ok_self, kg, vg, t, True, None,
-                            B, nb, L0, nq, nkv, scale, b["ao"], amax=self.kv_amax.get((l, "self")))
-            ops.gemm(b["ao"], NQ, 1, Wa["o"], NQ, 1, x1, H, N, H, NQ, resid=x)
-            ops.rmsnorm_fwd(x1, W.ln2, eps, b["h"])
-            ops.linear_fwd(b["h"], H, W.gu, H, b["gu"], 2 * I, N, 2 * I, H)
-            ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
-            ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, resid=x1)
-        ops.rmsnorm_fwd(x, eng.params["model.norm.weight"], eps, b["xn"])
-        ops.linear_fwd(b["xn"], H, eng.params["model.embed_tokens.weight"], H, b["logits"], b["logits"].stride(0), N,
-                       cfg.vocab_size, H)
+        ops.rmsnorm_fwd(x1, W.ln2, float(cfg.rms_norm_eps), b["h"])
+        ops.linear_fwd(b["h"], H, W.gu, H, b["gu"], 2 * I, N, 2 * I, H)
+        ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
+        ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, resid=x1)
 
 
 @torch.no_grad()
@@ -629,6 +543,7 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     if not use_cache and not reorder_cross_cache and not qwen3:
         raise ValueError("use_cache=False re-computes every position for its own beam: it can only reproduce "
                          "reorder_cross_cache=True (the shipped reference's un-reordered cross cache needs the cache)")
+    cls = Qwen3DecodeSession if qwen3 else DecodeSession
     dev = engine.device
     B, L0 = input_ids.shape
     V = engine.cfg.vocab_size
@@ -637,6 +552,7 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     ids0 = input_ids.to(dev, torch.int64)
     am0 = attention_mask.to(dev, torch.int64)
     act0 = actions.to(dev, torch.int64) if not qwen3 else None
+    sess0 = _session_kw(engine, session_ids, extended_session_ids)
     seqs = ids0[:, None, :].expand(B, nb, L0).contiguous()
     run_scores = torch.zeros(B, nb, device=dev)
     run_scores[:, 1:] = -1e9                       # only beam 0 is live at the first step (HF)
@@ -648,31 +564,12 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     node, nxt = nxt, node
     scores = torch.empty(N, V, device=dev)
     final = None
-    sess_variant = engine.variant in ("session", "qwen3_session")
-    if sess_variant:
-        if session_ids is None or extended_session_ids is None:
-            raise ValueError("a session engine needs session_ids and extended_session_ids")
-        sid0 = session_ids.to(dev, torch.int64)
-        ext0 = extended_session_ids.to(dev, torch.int64)
-
-    def session_kw(step, repeat):
-        """ids of prompt + ``step`` generated tokens for the full re-run: the generated tokens carry the behaviour
-        token's session id and the next extended ids, which makes the training masks equal to the cached ones"""
-        if not sess_variant:
-            return {}
-        sid = torch.cat([sid0, sid0[:, -1:].expand(B, step)], 1)
-        ext = torch.cat([ext0, ext0[:, -1:] + torch.arange(1, step + 1, device=dev)[None, :]], 1)
-        if repeat:
-            sid, ext = sid.repeat_interleave(nb, 0), ext.repeat_interleave(nb, 0)
-        return dict(session_ids=sid, extended_session_ids=ext)
     if not use_cache:
         session = None
     elif qwen3:
-        session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens, session_ids if sess_variant else None,
-                                     extended_session_ids if sess_variant else None)
+        session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens, **sess0)
     else:
-        session = DecodeSession(engine, ids0, am0, act0, nb, max_new_tokens, session_ids if sess_variant else None,
-                                extended_session_ids if sess_variant else None, reorder_cross_cache=reorder_cross_cache)
+        session = DecodeSession(engine, ids0, am0, act0, nb, max_new_tokens, reorder_cross_cache=reorder_cross_cache, **sess0)
     last_tok = None
     for step in range(max_new_tokens):
         cur = L0 + step
@@ -683,30 +580,26 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
             else:
                 logits2d = session.step(last_tok)
                 rows = torch.arange(N, device=dev, dtype=torch.int32)
-        elif qwen3:
-            # the cache-free cross-check: the whole sequence again, positions from the (extended) attention mask or, for
-            # Qwen3Session, from the extended session ids
-            flat = ids0 if step == 0 else seqs.reshape(N, cur)
-            am = am0 if step == 0 else torch.cat([am0, am0.new_ones(B, step)], 1).repeat_interleave(nb, 0)
-            if sess_variant:
-                engine.forward(flat, am, train=False, **session_kw(step, step > 0))
-                engine.check_inputs()
-            else:
-                engine.forward(flat, am, train=False, rope_from_mask=True)
-            rows = ((torch.arange(N, device=dev, dtype=torch.int32) // (nb if step == 0 else 1)) * cur + (cur - 1))
-        elif step == 0:
-            # all beams of a sample hold the same prompt: run it once (HF runs num_beams copies)
-            engine.forward(ids0, am0, act0, train=False, act_zero_col=L0 - 1, uniform_len=L0, **session_kw(0, False))
-            rows = (torch.arange(N, device=dev, dtype=torch.int32) // nb) * cur + (cur - 1)
         else:
-            flat = seqs.reshape(N, cur)
-            am = torch.cat([am0, am0.new_ones(B, step)], 1).repeat_interleave(nb, 0)
-            # generated tokens belong to the target item: same behaviour level as its behaviour token
-            act = torch.cat([act0, act0[:, -1:].expand(B, step)], 1).repeat_interleave(nb, 0)
-            engine.forward(flat, am, act, train=False, act_zero_col=L0 - 1, uniform_len=L0, **session_kw(step, True))
-            rows = torch.arange(N, device=dev, dtype=torch.int32) * cur + (cur - 1)
-        if session is None:
+            # the cache-free cross-check: the whole sequence again (the first step runs every sample's prompt once, HF runs
+            # num_beams copies).  The generated tokens belong to the target item: the behaviour level and session id of its
+            # behaviour token and the next extended ids, which makes the training masks equal to the cached ones
+            flat, am, act, sess = ids0, am0, act0, sess0
+            if step:
+                flat = seqs.reshape(N, cur)
+                am = torch.cat([am0, am0.new_ones(B, step)], 1).repeat_interleave(nb, 0)
+                if act0 is not None:
+                    act = torch.cat([act0, act0[:, -1:].expand(B, step)], 1).repeat_interleave(nb, 0)
+                if sess0:
+                    sid0, ext0 = sess0["session_ids"], sess0["extended_session_ids"]
+                    ext = torch.cat([ext0, ext0[:, -1:] + torch.arange(1, step + 1, device=dev)[None, :]], 1)
+                    sess = dict(session_ids=torch.cat([sid0, sid0[:, -1:].expand(B, step)], 1).repeat_interleave(nb, 0),
+                                extended_session_ids=ext.repeat_interleave(nb, 0))
+            cls._eval_forward(engine, flat, am, act, sess, L0)
+            if sess:
+                engine.check_inputs()
             logits2d = engine.ws.logits
+            rows = (torch.arange(N, device=dev, dtype=torch.int32) // (nb if step == 0 else 1)) * cur + (cur - 1)
         ops.trie_logprobs(logits2d, rows, run_scores.reshape(N).contiguous(), node, trie.child_start, trie.child_tok,
                           V, scores)
         top_s, top_i = torch.topk(scores.view(B, nb * V), K)

@@ -278,13 +278,9 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
         model.load_state_dict(sd)
         return model
 
-    @torch.no_grad()
-    def generate(self, input_ids=None, attention_mask=None, actions=None, max_new_tokens: int = 4, num_beams: int = 1,
-                 num_return_sequences=None, prefix_allowed_tokens_fn=None, trie=None, **kwargs):
-        """The call of test_SMB_decoder.py:163-180: trie-constrained beam search, all beams returned best first.
-        ``trie`` is a ``gamer_amd.decode.ItemTrie`` (or pass ``prefix_allowed_tokens_fn=decode.prefix_allowed_tokens(trie)``,
-        which carries it); arbitrary Python callables are not supported - the constraint runs on the device.
-        Returns an object with ``.sequences`` [B*num_beams, L0+max_new_tokens] and ``.sequences_scores``."""
+    def _generation_trie(self, input_ids, max_new_tokens, num_beams, num_return_sequences, prefix_allowed_tokens_fn, trie):
+        """The device trie of a ``generate`` call: ``trie`` (a ``gamer_amd.decode.ItemTrie``), the one a
+        ``decode.prefix_allowed_tokens(trie)`` callable carries, or the walk of an arbitrary ``prefix_allowed_tokens_fn``."""
         from . import decode
         if trie is None:
             trie = getattr(prefix_allowed_tokens_fn, "trie", None)
@@ -298,6 +294,17 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
                                       "of the SMB evaluation)")
         if num_return_sequences not in (None, num_beams):
             raise NotImplementedError("num_return_sequences must equal num_beams (what the evaluation task uses)")
+        return trie
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, attention_mask=None, actions=None, max_new_tokens: int = 4, num_beams: int = 1,
+                 num_return_sequences=None, prefix_allowed_tokens_fn=None, trie=None, **kwargs):
+        """The call of test_SMB_decoder.py:163-180: trie-constrained beam search, all beams returned best first.
+        ``trie`` is a ``gamer_amd.decode.ItemTrie`` (or pass ``prefix_allowed_tokens_fn=decode.prefix_allowed_tokens(trie)``,
+        which carries it); an arbitrary callable is walked once into a device trie - the constraint runs on the device.
+        Returns an object with ``.sequences`` [B*num_beams, L0+max_new_tokens] and ``.sequences_scores``."""
+        from . import decode
+        trie = self._generation_trie(input_ids, max_new_tokens, num_beams, num_return_sequences, prefix_allowed_tokens_fn, trie)
         if attention_mask is None or actions is None:
             raise ValueError("generate() needs attention_mask and actions")
         seqs, scores = decode.beam_search(self.engine, input_ids, attention_mask, actions, trie, num_beams, max_new_tokens,
@@ -431,22 +438,12 @@ class Qwen3WithTemperature(Qwen3MultiWithTemperature):
         beam search, all beams returned best first, RoPE positions from the attention mask as transformers' generate()
         builds them.  ``trie`` / ``prefix_allowed_tokens_fn`` as in ``Qwen3MultiWithTemperature.generate``."""
         from . import decode
-        if trie is None:
-            trie = getattr(prefix_allowed_tokens_fn, "trie", None)
-        if trie is None and callable(prefix_allowed_tokens_fn):
-            trie = decode.trie_from_callable(prefix_allowed_tokens_fn, input_ids, max_new_tokens,
-                                             device=self.engine.device, pad_token_id=self._cfg.pad_token_id)
-        if trie is None:
-            raise NotImplementedError("generate() needs trie=ItemTrie(...) or prefix_allowed_tokens_fn (constrained beam search "
-                                      "of the SMB evaluation)")
-        if num_return_sequences not in (None, num_beams):
-            raise NotImplementedError("num_return_sequences must equal num_beams (what the evaluation task uses)")
+        trie = self._generation_trie(input_ids, max_new_tokens, num_beams, num_return_sequences, prefix_allowed_tokens_fn, trie)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        skw = dict(session_ids=kwargs.get("session_ids"), extended_session_ids=kwargs.get("extended_session_ids")) \
-            if self.USES_SESSIONS else {}
         seqs, scores = decode.beam_search(self.engine, input_ids, attention_mask, None, trie, num_beams, max_new_tokens,
-                                          use_cache=bool(kwargs.get("use_cache", True)), **skw)
+                                          use_cache=bool(kwargs.get("use_cache", True)), session_ids=kwargs.get("session_ids"),
+                                          extended_session_ids=kwargs.get("extended_session_ids"))
         return CausalLMOutput(sequences=seqs, sequences_scores=scores)
 
 

@@ -550,3 +550,91 @@ def test_decode_step_graph_replay_equals_the_eager_step(reorder_cross, monkeypat
     assert torch.equal(seq3, ref1[0]) and torch.equal(sc3, ref1[1])
     if not reorder_cross:
         _check(seq3, sc3, fx, tb, "", torch.ones(ids.shape[0], dtype=torch.bool), beams, 1e-4)
+
+
+@pytest.mark.gpu
+def test_a_newer_session_of_the_same_shape_retires_the_older_one():
+    """Sessions of one engine and shape share their buffers (gamer_amd/decode.py: _DecodeStatic).  Once a second session has
+    been created, the first refuses to step or re-order instead of attending over the second's caches; the second steps to
+    the logits of a session created alone on its prompts."""
+    from gamer_amd.config import synthetic_config
+    from gamer_amd.decode import DecodeSession
+    from gamer_amd.engine import Engine
+    eng = Engine(synthetic_config(), temperature=0.7)
+    eng.init_weights(seed=3)
+    cat = synthetic.make_catalogue(300, 256, seed=3)
+    b1, b2 = (synthetic.make_eval_batch(5, 30, cat, 2, 256, 3, min_his=12, seed=s) for s in (9, 10))
+    nb = 4
+    tok = torch.randint(14, 14 + 256, (5 * nb,), device="cuda")
+
+    def session(b):
+        return DecodeSession(eng, b["input_ids"], b["attention_mask"], b["actions"], nb, 3)
+    alone = session(b2).step(tok).clone()
+    first = session(b1)
+    second = session(b2)
+    with pytest.raises(RuntimeError, match="newer DecodeSession"):
+        first.step(tok)
+    with pytest.raises(RuntimeError, match="newer DecodeSession"):
+        first.reorder(torch.arange(5 * nb, device="cuda"))
+    got = second.step(tok)
+    V = eng.cfg.vocab_size
+    assert float((got[:, :V] - alone[:, :V]).abs().max()) < 2e-5 * float(alone[:, :V].abs().max())
+
+
+def _decode_engine(model):
+    from gamer_amd.config import Qwen3Config, Qwen3SessionConfig, synthetic_config
+    from gamer_amd.engine import Engine
+    V = synthetic.vocab_size(256, 3)
+    if model == "qwen3":
+        eng = Engine(Qwen3Config(vocab_size=V, pad_token_id=synthetic.PAD_ID), temperature=0.7, variant="qwen3")
+    elif model == "qwen3_session":
+        eng = Engine(Qwen3SessionConfig(vocab_size=V, pad_token_id=synthetic.PAD_ID, num_positions=5, model_max_length=1024),
+                     temperature=0.7, variant="qwen3_session")
+    else:
+        eng = Engine(synthetic_config(), temperature=0.7, variant=model)
+    eng.init_weights(seed=3)
+    return eng
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model", ["multi", "session", "qwen3", "qwen3_session"])
+def test_fused_qk_decode_step_agrees_with_the_unfused_step(model, monkeypatch):
+    """32 users x 4 beams (N = 128 rows: whole tiles, so the decode step runs the per-head RMSNorm + RoPE as the q|k|v
+    projection's epilogue) against GAMER_DECODE_FUSE_QK=0 (its own kernel): a step, a beam re-order and a second step give
+    the generated K / V and both steps' logits to fp32 rounding, for every model's session."""
+    from gamer_amd import ops
+    from gamer_amd.decode import DecodeSession, Qwen3DecodeSession
+    eng = _decode_engine(model)
+    sessions = model in ("session", "qwen3_session")
+    cat = synthetic.make_catalogue(300, 256, seed=3)
+    B, nb = 32, 4
+    N = B * nb
+    b = synthetic.make_eval_batch(B, 30, cat, 2, 256, 3, min_his=12, seed=9, behavior_probs=[0.6, 0.3, 0.1],
+                                  session_mean=4.0 if sessions else None)
+    skw = dict(session_ids=b["session_ids"], extended_session_ids=b["extended_session_ids"]) if sessions else {}
+    g = torch.Generator().manual_seed(4)
+    tok1, tok2 = (torch.randint(14, 14 + 256, (N,), generator=g).cuda() for _ in range(2))
+    beam = torch.arange(N) % nb
+    parent = (torch.arange(N) - beam + (nb - 1 - beam)).cuda()          # every sample's beams in reverse order
+    out = {}
+    for fuse in ("1", "0"):
+        monkeypatch.setenv("GAMER_DECODE_FUSE_QK", fuse)
+        eng._decode_static = {}                      # (a fresh set of session buffers for either form)
+        if model.startswith("qwen3"):
+            s = Qwen3DecodeSession(eng, b["input_ids"], b["attention_mask"], nb, 3, **skw)
+        else:
+            s = DecodeSession(eng, b["input_ids"], b["attention_mask"], b["actions"], nb, 3, **skw)
+        assert ops.qkv_fused_ok(s.buf["h"], s.N, s.NQ + 2 * s.NKV)
+        first = s.step(tok1).clone()
+        s.reorder(parent)
+        second = s.step(tok2).clone()
+        gen = {kk: (kg[:, :2].clone(), vg[:, :2].clone()) for kk, (kg, vg) in s.gen.items()}
+        torch.cuda.synchronize()
+        out[fuse] = (first, second, gen)
+    V = eng.cfg.vocab_size
+    for i in (0, 1):
+        a, ref = out["1"][i][:, :V].double(), out["0"][i][:, :V].double()
+        assert float((a - ref).abs().max()) < 2e-5 * float(ref.abs().max()), i
+    for kk, pair in out["0"][2].items():
+        for a, ref in zip(out["1"][2][kk], pair):
+            assert float((a - ref).abs().max()) < 2e-5 * float(ref.abs().max()), kk
