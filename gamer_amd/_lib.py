@@ -142,6 +142,9 @@ _SIGNATURES = {
     "gamer_swiglu_bwd_ld": [P, L, I, I, P, F, U, P],
     "gamer_swiglu_fwd_ld_tbl": [P, L, I, I, F, U, P, P, P, P],
     "gamer_swiglu_bwd_ld_tbl": [P, L, I, I, P, F, U, P, P, P],
+    "gamer_silu_fwd_ld": [P, L, I, I, F, U, P, P],
+    "gamer_silu_bwd_ld": [P, L, I, I, P, F, U, P],
+    "gamer_router_position_table": [P, L, P, I, P],
     "gamer_inject_table_fwd": [P, P, L, I, I, I, I, I, P, P],
     "gamer_segment_colsum_ws_floats": [I, I, I],
     "gamer_segment_colsum": [P, L, I, I, P, I, P, L, P, P],
@@ -172,7 +175,7 @@ _SIGNATURES = {
 
 # bf16 twins: same argument kinds as the fp32 entry point (activation pointers are gamer_bf16* instead of float*)
 for _n in ("rmsnorm_fwd", "rmsnorm_bwd", "rowtable_fwd", "rowtable_bwd", "qknorm_rope_fwd", "qknorm_rope_bwd", "swiglu_fwd",
-           "swiglu_bwd", "swiglu_fwd_ld", "swiglu_bwd_ld", "silu_gate_fwd", "silu_gate_bwd", "ce_fwd", "ce_bwd"):
+           "swiglu_bwd", "swiglu_fwd_ld", "swiglu_bwd_ld", "silu_fwd_ld", "silu_bwd_ld", "silu_gate_fwd", "silu_gate_bwd", "ce_fwd", "ce_bwd"):
     _SIGNATURES[f"gamer_{_n}_bf16"] = _SIGNATURES[f"gamer_{_n}"]
 
 

@@ -61,6 +61,31 @@ _DEFAULTS: Dict[str, Any] = {
 }
 
 
+MLP_TYPES = ("Qwen3", "PBATransformer")
+
+
+def expected_num_experts(config) -> int:
+    """num_experts as train_SMB_decoder.py:344-351 sets it at run time: 2 under Moe_behavior_only (one expert for the
+    behaviour tokens, one for pad / eos), else num_positions + 1."""
+    return 2 if getattr(config, "Moe_behavior_only", False) else int(config.num_positions) + 1
+
+
+def apply_runtime_fields(config, num_behavior: int, behavior_maps: dict, num_positions: int = 5,
+                         n_positions: int = 101, model_max_length: int = 1024):
+    """The run-time mutation of a config read from config.json (train_SMB_decoder.py:321-360): the dataset's behaviours,
+    a behaviour token per item, no user token, and the expert count of the routing mode (``expected_num_experts``).
+    Works on this class and on any attribute bag (a transformers config); returns ``config``."""
+    config.num_behavior = int(num_behavior)
+    config.behavior_maps = {str(k): int(v) for k, v in behavior_maps.items()}
+    config.use_behavior_token = True
+    config.use_user_token = False
+    config.num_positions = int(num_positions)
+    config.n_positions = int(n_positions)
+    config.model_max_length = int(model_max_length)
+    config.num_experts = expected_num_experts(config)
+    return config
+
+
 class Qwen3MultiConfig:
     """Plain attribute bag with dict semantics (``'num_positions' in config`` works as in HF)."""
 
@@ -125,8 +150,6 @@ class Qwen3MultiConfig:
 
     # --- validation of what the HIP kernels are built for --------------------------------------
     def validate(self):
-        if self.mlp_type != "Qwen3":
-            raise ValueError("only mlp_type='Qwen3' (MyQwen3SparseMLP) is implemented")
         if self.head_dim != 64:
             raise ValueError("the attention kernels are built for head_dim=64")
         if self.behavior_embedding_dim != self.head_dim:
@@ -140,15 +163,46 @@ class Qwen3MultiConfig:
             raise ValueError("hidden_size must be a multiple of 4 and <= 1024")
         if self.num_behavior + 1 > 8:
             raise ValueError("at most 7 behaviours are supported by the bias-gradient kernels")
-        if sorted(self.sparse_layers_decoder) != list(range(self.num_hidden_layers)):
-            raise ValueError("every decoder layer must be sparse (position-routed experts)")
-        if self.Moe_behavior_only or self.use_user_token or not self.use_behavior_token:
-            raise ValueError("only the shipped routing mode is implemented "
-                             "(Moe_behavior_only=False, use_user_token=False, use_behavior_token=True)")
-        if self.num_experts != self.num_positions + 1:
-            raise ValueError("num_experts must be num_positions + 1")
+        if self.mlp_type not in MLP_TYPES:
+            raise ValueError(f"mlp_type must be one of {MLP_TYPES} (MyQwen3SparseMLP / PBATransformerSparseMLP)")
+        if self.hidden_act != "silu":
+            raise ValueError("only hidden_act='silu' is implemented")
+        if any(int(l) not in range(self.num_hidden_layers) for l in self.sparse_layers_decoder):
+            raise ValueError("sparse_layers_decoder must be a subset of range(num_hidden_layers)")
+        if self.use_user_token or not self.use_behavior_token:
+            raise ValueError("only the routing modes with a behaviour token and without a user token are implemented "
+                             "(use_user_token=False, use_behavior_token=True)")
+        if self.num_experts != expected_num_experts(self):
+            raise ValueError("num_experts must be num_positions + 1, or 2 with Moe_behavior_only "
+                             "(train_SMB_decoder.py:344-351)")
         if not self.tie_word_embeddings:
             raise ValueError("lm_head is tied to embed_tokens in this model")
+
+    # --- the FFN ablation switches (mlp_type, sparse_layers_decoder, Moe_behavior_only) -------------------
+    def is_sparse(self, layer: int) -> bool:
+        """Whether decoder layer ``layer`` runs position-routed experts (else one dense MLP over every token)."""
+        return layer in self.sparse_layers_decoder
+
+    @property
+    def gated_mlp(self) -> bool:
+        """mlp_type "Qwen3": SwiGLU experts (gate / up / down); "PBATransformer": wo(dropout(silu(wi(x))))."""
+        return self.mlp_type == "Qwen3"
+
+    @property
+    def shipped_ffn(self) -> bool:
+        """The FFN configuration of the shipped config.json: SwiGLU experts in every layer, one expert per position."""
+        return (self.gated_mlp and not self.Moe_behavior_only and
+                sorted(self.sparse_layers_decoder) == list(range(self.num_hidden_layers)))
+
+    def position_experts(self):
+        """Expert index of each position inside an item (router.py:28-54): 1..num_positions, or with
+        Moe_behavior_only 1 for the behaviour token and 2 for every semantic token.  Pad and eos go to expert 0.
+        With Moe_behavior_only and num_experts = 2 the semantic tokens' index names no expert: the reference's
+        MyQwen3SparseMLP / PBATransformerSparseMLP leave their FFN output at zero (only the residual passes)."""
+        P = int(self.num_positions)
+        if self.Moe_behavior_only:
+            return [1] + [2] * (P - 1)
+        return list(range(1, P + 1))
 
     def behavior_lut(self):
         """int32 table token id -> behaviour index (or -1), what the router kernel consumes."""
@@ -158,6 +212,20 @@ class Qwen3MultiConfig:
             if 0 <= int(tok) < self.vocab_size:
                 lut[int(tok)] = int(idx)
         return lut
+
+
+def base_model_config(path: str, vocab_size: int, num_behavior: int, behavior_maps: dict, num_positions: int,
+                      n_positions: int, pad_token_id: int = None, model_max_length: int = 1024) -> Qwen3MultiConfig:
+    """``--base_model DIR`` of train_SMB_decoder.py: DIR/config.json (any of the shipped Qwen3Multi configs, with its FFN
+    ablation switches mlp_type / sparse_layers_decoder / Moe_behavior_only as written there), the vocabulary resized to the
+    tokenizer's, then the run-time fields of train_SMB_decoder.py:321-360 (``apply_runtime_fields``).  A config.json without
+    ``mlp_type`` gets this class's default "Qwen3" - the reference's decoder layer falls back to "PBATransformer" then
+    (model.py:166-169)."""
+    cfg = Qwen3MultiConfig.from_pretrained(path)
+    cfg.vocab_size = int(vocab_size)
+    if pad_token_id is not None:
+        cfg.pad_token_id = int(pad_token_id)
+    return apply_runtime_fields(cfg, num_behavior, behavior_maps, num_positions, n_positions, model_max_length)
 
 
 def synthetic_config(codebook: int = 256, num_behavior: int = 3, **overrides) -> Qwen3MultiConfig:

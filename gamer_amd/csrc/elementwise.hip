@@ -2257,6 +2257,103 @@ extern "C" int gamer_residual_dropout_bwd(const float* dx, const int32_t* src_ro
     return 0;
 }
 
+// The non-gated FFN (mlp_type "PBATransformer": T5DenseActDense, ref:SeqRec/models/generative/Qwen3Moe/FFN.py:75-86):
+// hm = dropout(silu(h)) on the output h [T][ld] of the wi projection (columns 0 .. I - 1), hm [T][I] contiguous; the backward
+// writes dh = dropout_mask * dhm * silu'(h) over h in place.  One wave per row, as the SwiGLU _ld kernels: the dropout word of
+// element (t, c) is that of the flat index t * I + c (the same masks as gamer_swiglu_fwd_ld under the same seed).
+template <typename TA>
+__global__ void __launch_bounds__(EW_THREADS)
+silu_fwd_ld_kernel(const TA* __restrict__ h, int64_t ld, int T, int I4, float p, uint64_t seed, TA* __restrict__ hm,
+                   uint32_t* __restrict__ amax_out) {
+    __shared__ uint32_t amax_lds[4];
+    uint32_t am = 0;
+    const DropoutRng rng(p, seed);
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * EW_THREADS + threadIdx.x) >> 6, nwaves = (gridDim.x * EW_THREADS) >> 6;
+    for (int t = wave; t < T; t += nwaves) {
+        const TA* row = h + (int64_t)t * ld;
+        for (int c = lane; c < I4; c += 64) {
+            const float4 a = ld4(row + 4 * c);
+            const int64_t i = (int64_t)t * I4 + c;
+            float m[4];
+            rng.mult4((uint32_t)i, m);
+            float4 o;
+            o.x = m[0] * silu_f(a.x);
+            o.y = m[1] * silu_f(a.y);
+            o.z = m[2] * silu_f(a.z);
+            o.w = m[3] * silu_f(a.w);
+            st4(hm + 4 * i, o);
+            am = amax_f4(am, o);
+        }
+    }
+    amax_block_commit(am, amax_out, amax_lds);
+}
+
+template <typename TA>
+__global__ void __launch_bounds__(EW_THREADS)
+silu_bwd_ld_kernel(TA* __restrict__ h, int64_t ld, int T, int I4, const TA* __restrict__ dhm, float p, uint64_t seed,
+                   uint32_t* __restrict__ amax_out) {
+    __shared__ uint32_t amax_lds[4];
+    uint32_t am = 0;
+    const DropoutRng rng(p, seed);
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * EW_THREADS + threadIdx.x) >> 6, nwaves = (gridDim.x * EW_THREADS) >> 6;
+    for (int t = wave; t < T; t += nwaves) {
+        TA* row = h + (int64_t)t * ld;
+        for (int c = lane; c < I4; c += 64) {
+            const int64_t i = (int64_t)t * I4 + c;
+            const float4 a = ld4(row + 4 * c), d = ld4(dhm + 4 * i);
+            float m[4];
+            rng.mult4((uint32_t)i, m);
+            float4 o;
+            o.x = m[0] * d.x * dsilu_f(a.x);
+            o.y = m[1] * d.y * dsilu_f(a.y);
+            o.z = m[2] * d.z * dsilu_f(a.z);
+            o.w = m[3] * d.w * dsilu_f(a.w);
+            st4(row + 4 * c, o);
+            am = amax_f4(am, o);
+        }
+    }
+    amax_block_commit(am, amax_out, amax_lds);
+}
+
+template <typename TA>
+static int silu_fwd_ld_impl(const char* name, const TA* h, int64_t ld, int T, int I, float p_drop, uint64_t seed, TA* hm,
+                            void* stream) {
+    GAMER_CHECK_ARG(h && hm && T > 0 && I > 0 && I % 4 == 0 && ld >= (int64_t)I && ld % 4 == 0 && p_drop >= 0.f && p_drop < 1.f,
+                    "%s: bad arguments (T=%d I=%d ld=%lld)", name, T, I, (long long)ld);
+    GAMER_CHECK_ARG(aligned_vec4<TA>(h) && aligned_vec4<TA>(hm), "%s: pointers must be aligned to four elements", name);
+    hipLaunchKernelGGL(silu_fwd_ld_kernel<TA>, dim3(grid_for_waves(T)), dim3(EW_THREADS), 0, ST(stream), h, ld, T, I / 4,
+                       p_drop, seed, hm, take_amax_sink().out[0]);
+    GAMER_CHECK_LAUNCH(name);
+    return 0;
+}
+template <typename TA>
+static int silu_bwd_ld_impl(const char* name, TA* h, int64_t ld, int T, int I, const TA* dhm, float p_drop, uint64_t seed,
+                            void* stream) {
+    GAMER_CHECK_ARG(h && dhm && T > 0 && I > 0 && I % 4 == 0 && ld >= (int64_t)I && ld % 4 == 0 && p_drop >= 0.f && p_drop < 1.f,
+                    "%s: bad arguments (T=%d I=%d ld=%lld)", name, T, I, (long long)ld);
+    GAMER_CHECK_ARG(aligned_vec4<TA>(h) && aligned_vec4<TA>(dhm), "%s: pointers must be aligned to four elements", name);
+    hipLaunchKernelGGL(silu_bwd_ld_kernel<TA>, dim3(grid_for_waves(T)), dim3(EW_THREADS), 0, ST(stream), h, ld, T, I / 4, dhm,
+                       p_drop, seed, take_amax_sink().out[0]);
+    GAMER_CHECK_LAUNCH(name);
+    return 0;
+}
+extern "C" int gamer_silu_fwd_ld(const float* h, int64_t ld, int T, int I, float p_drop, uint64_t seed, float* hm, void* stream) {
+    return silu_fwd_ld_impl<float>("gamer_silu_fwd_ld", h, ld, T, I, p_drop, seed, hm, stream);
+}
+extern "C" int gamer_silu_fwd_ld_bf16(const gamer_bf16* h, int64_t ld, int T, int I, float p_drop, uint64_t seed, gamer_bf16* hm,
+                                      void* stream) {
+    return silu_fwd_ld_impl<bf16_t>("gamer_silu_fwd_ld_bf16", (const bf16_t*)h, ld, T, I, p_drop, seed, (bf16_t*)hm, stream);
+}
+extern "C" int gamer_silu_bwd_ld(float* h, int64_t ld, int T, int I, const float* dhm, float p_drop, uint64_t seed, void* stream) {
+    return silu_bwd_ld_impl<float>("gamer_silu_bwd_ld", h, ld, T, I, dhm, p_drop, seed, stream);
+}
+extern "C" int gamer_silu_bwd_ld_bf16(gamer_bf16* h, int64_t ld, int T, int I, const gamer_bf16* dhm, float p_drop, uint64_t seed,
+                                      void* stream) {
+    return silu_bwd_ld_impl<bf16_t>("gamer_silu_bwd_ld_bf16", (bf16_t*)h, ld, T, I, (const bf16_t*)dhm, p_drop, seed, stream);
+}
+
 template <typename TA>
 static int swiglu_fwd_impl(const char* name, const TA* g, const TA* u, int64_t n, float p_drop, uint64_t seed, TA* hm,
                            void* stream) {

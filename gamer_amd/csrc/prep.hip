@@ -215,7 +215,8 @@ __global__ void expert_count_kernel(const int32_t* __restrict__ expert, int S, i
     if (threadIdx.x < 64) cnt[threadIdx.x] = 0;
     __syncthreads();
     for (int t = threadIdx.x; t < S; t += blockDim.x) {
-        atomicAdd(&cnt[expert[(int64_t)b * S + t]], 1);
+        const int e = expert[(int64_t)b * S + t];
+        if ((unsigned)e < (unsigned)E) atomicAdd(&cnt[e], 1);     // rows past the last expert are in no group
     }
     __syncthreads();
     if (threadIdx.x < E) work[(int64_t)b * E + threadIdx.x] = cnt[threadIdx.x];
@@ -270,21 +271,46 @@ expert_scan_kernel(int B, int E, int T, int32_t* __restrict__ work, int32_t* __r
     }
 }
 
-// pass 3: one wave per sequence; lane e (< E) walks the sequence in token order and emits slots.
+// pass 3: one wave per sequence; lane e (< E) walks the sequence in token order and emits slots.  Lane E emits the rows whose
+// expert index is outside [0, E) - in no group - behind the last group, in token order: slots offsets[E] .. T - 1, so that perm
+// and slot stay permutations of [0, T).  Its base is offsets[E] plus the ungrouped rows of the sequences before b (b S minus
+// their grouped rows, which the scanned work table gives per expert).
 __global__ void expert_emit_kernel(const int32_t* __restrict__ expert, int S, int E,
-                                   const int32_t* __restrict__ work,
+                                   const int32_t* __restrict__ work, const int32_t* __restrict__ offsets,
                                    int32_t* __restrict__ perm, int32_t* __restrict__ slot) {
     const int b = blockIdx.x;
     const int e = threadIdx.x;
-    if (e >= E) return;
-    int next = work[(int64_t)b * E + e];
+    if (e > E) return;
     const int64_t base = (int64_t)b * S;
+    if (e == E) {
+        int64_t grouped_before = 0;
+        for (int g = 0; g < E; ++g) grouped_before += work[(int64_t)b * E + g] - offsets[g];
+        int next = (int)(offsets[E] + base - grouped_before);
+        for (int t = 0; t < S; ++t) {
+            if ((unsigned)expert[base + t] >= (unsigned)E) {
+                perm[next] = (int32_t)(base + t);
+                slot[base + t] = next;
+                ++next;
+            }
+        }
+        return;
+    }
+    int next = work[(int64_t)b * E + e];
     for (int t = 0; t < S; ++t) {
         if (expert[base + t] == e) {
             perm[next] = (int32_t)(base + t);
             slot[base + t] = next;
             ++next;
         }
+    }
+}
+
+// The router's position table (router.py:28-54): expert[i] <- table[expert[i]] for 0 <= expert[i] < n_table.
+__global__ void __launch_bounds__(256)
+position_table_kernel(int32_t* __restrict__ expert, int64_t n, const int32_t* __restrict__ table, int n_table) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int e = expert[i];
+        if ((unsigned)e < (unsigned)n_table) expert[i] = table[e];
     }
 }
 
@@ -383,8 +409,19 @@ extern "C" int gamer_expert_lists(const int32_t* expert, int B, int S, int num_e
     GAMER_CHECK_LAUNCH("gamer_expert_lists/count");
     hipLaunchKernelGGL(expert_scan_kernel, dim3(1), dim3(1024), 0, st, B, num_experts, B * S, work, offsets);
     GAMER_CHECK_LAUNCH("gamer_expert_lists/scan");
-    hipLaunchKernelGGL(expert_emit_kernel, dim3(B), dim3(64), 0, st, expert, S, num_experts, work, perm, slot);
+    hipLaunchKernelGGL(expert_emit_kernel, dim3(B), dim3(num_experts < 64 ? 64 : 128), 0, st, expert, S, num_experts, work,
+                       offsets, perm, slot);
     GAMER_CHECK_LAUNCH("gamer_expert_lists/emit");
+    return 0;
+}
+
+extern "C" int gamer_router_position_table(int32_t* expert, int64_t n, const int32_t* table, int n_table, void* stream) {
+    GAMER_CHECK_ARG(expert && table && n > 0 && n_table > 0 && n_table <= 4096,
+                    "gamer_router_position_table: bad arguments n=%lld n_table=%d", (long long)n, n_table);
+    int64_t blocks = (n + 256 * 4 - 1) / (256 * 4);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(position_table_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, expert, n, table, n_table);
+    GAMER_CHECK_LAUNCH("gamer_router_position_table");
     return 0;
 }
 

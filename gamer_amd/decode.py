@@ -471,11 +471,17 @@ class DecodeSession:
             ops.linear_fwd(b["ao"], NQ, W.cross_attn["o"], NQ, b["op"], H, N, H, NQ)
             ops.linear_fwd(b["h"], H, W.cross_attn["gate"], H, b["gate"], H, N, H, H)
             ops.silu_gate_fwd(b["op"], b["gate"], xc, resid=x1)
+        # the expert of the new tokens' common position (router.py:28-54 table, the same for every row); a dense layer's one MLP
+        pos = (self.L0 + t - 1) % cfg.num_positions
+        if not (W.sparse and W.gated and not cfg.Moe_behavior_only):
+            # the FFN ablation forms (dense layer, PBATransformer experts, behaviour-only routing: semantic tokens have no expert)
+            eng.ffn_rows(W, pos, xc, self.beh if W.inject else None, x)
+            return
         hin, din = b.get("hin", b["h"]), W.din
         ops.rmsnorm_fwd(xc, W.ln3, eps, hin, din)
         if W.inject:
             ops.rowtable_fwd(W.beh, self.beh, hin, din, H)
-        e = (self.L0 + t - 1) % cfg.num_positions + 1    # position-routed expert (router.py:83-104), same for every row
+        e = pos + 1                                      # position-routed expert (router.py:83-104), same for every row
         if eng._amax is not None and eng.matmul == "split3":
             # the whole stacked weight with every row in expert e's group: the tensor the prompt pass measured and cut (its maximum
             # slot and packed pieces are reused; a row slice is another tensor to the maxima cache - two gamer_absmax_f32 launches

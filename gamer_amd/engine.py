@@ -102,16 +102,21 @@ class ParamLayout(_FlatLayout):
                               (ap + "k_behavior_embedding.weight", (NB1, nkv * Eb)),
                               (ap + "v_behavior_embedding.weight", (NB1, nkv * Eb))]
             din = H + (Eb if inject else 0)
-            if version == 1:
+            # the FFN ablation switches: a dense layer's one MLP is mlp.mlp.*, a sparse layer's experts mlp.experts.expert_{e}.*;
+            # mlp_type "PBATransformer" (T5DenseActDense) has wi [I, din] / wo [H, I] instead of gate / up / down
+            mlps = [f"{lp}mlp.experts.expert_{e}." for e in range(E)] if cfg.is_sparse(l) else [f"{lp}mlp.mlp."]
+            if not cfg.gated_mlp:
+                decay += [(m + "wi.weight", (I, din)) for m in mlps] + [(m + "wo.weight", (H, I)) for m in mlps]
+            elif version == 1:
                 for kind, shp in (("gate_proj", (I, din)), ("up_proj", (I, din)), ("down_proj", (H, I))):
-                    for e in range(E):
-                        decay.append((f"{lp}mlp.experts.expert_{e}.{kind}.weight", shp))
+                    for m in mlps:
+                        decay.append((f"{m}{kind}.weight", shp))
             else:
-                for e in range(E):
-                    decay.append((f"{lp}mlp.experts.expert_{e}.gate_proj.weight", (I, din)))
-                    decay.append((f"{lp}mlp.experts.expert_{e}.up_proj.weight", (I, din)))
-                for e in range(E):
-                    decay.append((f"{lp}mlp.experts.expert_{e}.down_proj.weight", (H, I)))
+                for m in mlps:
+                    decay.append((f"{m}gate_proj.weight", (I, din)))
+                    decay.append((f"{m}up_proj.weight", (I, din)))
+                for m in mlps:
+                    decay.append((f"{m}down_proj.weight", (H, I)))
             if inject:
                 decay.append((lp + "mlp.behavior_embedding.weight", (NB1, Eb)))
             nodecay.append((lp + "input_layernorm.weight", (H,)))
@@ -164,10 +169,16 @@ class _LayerW:
         self.ln1 = v[lp + "input_layernorm.weight"]
         self.ln2 = v[lp + "post_self_attention_layernorm.weight"] if self.cross else None
         self.ln3 = v[lp + "post_cross_attention_layernorm.weight"]
-        # rows [e 2I, e 2I + I) = gate_proj of expert e, [e 2I + I, (e + 1) 2I) = its up_proj
-        self.gu = layout.span(flat, f"{lp}mlp.experts.expert_0.gate_proj.weight", E * 2 * I, self.din)
+        # the FFN: ``ne`` experts (1 = the dense MLP of a layer outside sparse_layers_decoder), each with an input projection of
+        # ``nI`` rows - gated: rows [e 2I, e 2I + I) = gate_proj of expert e, [e 2I + I, (e + 1) 2I) = its up_proj; PBATransformer:
+        # rows [e I, (e + 1) I) = its wi - and an output projection of H rows (down_proj / wo)
+        self.sparse, self.gated = cfg.is_sparse(l), cfg.gated_mlp
+        self.ne = E if self.sparse else 1
+        self.nI = 2 * I if self.gated else I
+        m0 = f"{lp}mlp.experts.expert_0." if self.sparse else f"{lp}mlp.mlp."
+        self.gu = layout.span(flat, m0 + ("gate_proj.weight" if self.gated else "wi.weight"), self.ne * self.nI, self.din)
         self.I = I
-        self.down = layout.span(flat, f"{lp}mlp.experts.expert_0.down_proj.weight", E * H, I)
+        self.down = layout.span(flat, m0 + ("down_proj.weight" if self.gated else "wo.weight"), self.ne * H, I)
         self.beh = v[lp + "mlp.behavior_embedding.weight"] if self.inject else None
 
     def gate_e(self, e: int) -> torch.Tensor:
@@ -202,7 +213,9 @@ class Bf16Shadow:
                 mats.append((name, shp[0] + 2 * layout.entries[head + ".k_proj.weight"][1][0], shp[1], None, head + ".qkv"))
             elif kind == "gate_proj":
                 mats.append((name, 2 * shp[0], shp[1], None, head + ".gu"))
-            elif kind in ("o_proj", "gating", "down_proj"):
+            elif kind == "wi":                       # (the non-gated FFN's input projection: the same role, I rows)
+                mats.append((name, shp[0], shp[1], None, head + ".gu"))
+            elif kind in ("o_proj", "gating", "down_proj", "wo"):
                 mats.append((name, shp[0], shp[1], None, None))
         tab, toff, tile0 = [], 0, 0
         for first, rows, cols, ldt, tkey in mats:
@@ -240,8 +253,9 @@ class _LayerWT:
         self.self_attn = attn("self_attn")
         self.cross_attn = attn("cross_attn") if cross else None
         # expert e's transposed matrix sits e * (cols * rows) behind expert 0's (consecutive add() calls, sizes % 8 == 0)
-        self.gu = sh.t(f"{lp}mlp.experts.expert_0.gu")
-        self.down = sh.t(f"{lp}mlp.experts.expert_0.down_proj.weight")
+        m0 = f"{lp}mlp.experts.expert_0." if cfg.is_sparse(l) else f"{lp}mlp.mlp."
+        self.gu = sh.t(m0 + "gu")
+        self.down = sh.t(m0 + ("down_proj.weight" if cfg.gated_mlp else "wo.weight"))
 
 
 class _Workspace:
@@ -439,7 +453,10 @@ class Engine:
         nb1 = cfg.num_behavior + 1
         self.split_inject = bool(self.dtype != "bf16" and os.environ.get("GAMER_SPLIT_INJECT", "1") != "0" and
                                  cfg.behavior_injection_decoder and cfg.num_experts * nb1 <= 64 and nb1 <= 16 and
-                                 cfg.behavior_embedding_dim % 4 == 0 and cfg.behavior_embedding_dim <= 256)
+                                 cfg.behavior_embedding_dim % 4 == 0 and cfg.behavior_embedding_dim <= 256 and cfg.shipped_ffn)
+        # Moe_behavior_only: the router's position table [1, 2, 2, ...] (pad / eos 0) over gamer_router_fwd's [1, 2, 3, ...]
+        self.position_table = (torch.tensor([0] + cfg.position_experts(), dtype=torch.int32, device=self.device)
+                               if cfg.Moe_behavior_only else None)
 
     # whether the model's self attention takes per-query key spans (session-wise masks): the kernel forms that take them
     # decide whether the workspace needs the dS-spill scratch (``workspace``)
@@ -669,6 +686,8 @@ class Engine:
         r = ws.router
         r["bad_token"].zero_()
         ops.router_fwd(ids, am, act, self.lut, cfg.num_positions, cfg.pad_token_id, cfg.eos_token_id, r)
+        if self.position_table is not None:
+            ops.router_position_table(r["expert"], self.position_table)
         if act_zero_col is None and S % cfg.num_positions == 1:
             # the reference's router counts (S + 3) // 5 items (router.py:160-163), so a trailing behaviour token
             # - an evaluation prompt - gets action index 0
@@ -692,7 +711,7 @@ class Engine:
         if self._amax is not None and self._amax.planes_t is not None:
             for Wl in self.W:
                 self._amax.register_transposed(Wl.self_attn["o"], 1, H, NQ)
-                self._amax.register_transposed(Wl.down, E, H, I)
+                self._amax.register_transposed(Wl.down, Wl.ne, H, I)
                 if Wl.cross:
                     self._amax.register_transposed(Wl.cross_attn["o"], 1, H, NQ)
         span_self = span_cross = pos_ids = None
@@ -793,19 +812,16 @@ class Engine:
                 # sample is still needed; its FFN is one dense expert on B rows (the prompt ends with a real token,
                 # so the expert is the position's: router.py:83-104)
                 rows = torch.arange(B, device=self.device) * S + (S - 1)
-                e = (S - 1) % cfg.num_positions + 1
                 xl = x_cross_last if (W.cross and x_cross_last is not None) else xcur.index_select(0, rows).contiguous()
                 f32 = dict(dtype=torch.float32, device=self.device)
-                hin = torch.empty(B, din, **f32)
-                ops.rmsnorm_fwd(xl, W.ln3, eps, hin, din)
-                if W.inject:
-                    ops.rowtable_fwd(W.beh, r["beh_idx"].view(-1).index_select(0, rows).contiguous(), hin, din, H)
-                gu, hm = torch.empty(B, 2 * I, **f32), torch.empty(B, I, **f32)
-                ops.linear_fwd(hin, din, W.gu[e * 2 * I:(e + 1) * 2 * I], din, gu, 2 * I, B, 2 * I, din)
-                ops.swiglu_fwd_ld(gu, 2 * I, B, I, 0.0, 0, hm)
+                beh = r["beh_idx"].view(-1).index_select(0, rows).contiguous() if W.inject else None
                 x_last = torch.empty(B, H, **f32)
-                ops.gemm(hm, I, 1, W.down[e * H:(e + 1) * H], I, 1, x_last, H, B, H, I, resid=xl)
+                self.ffn_rows(W, (S - 1) % cfg.num_positions, xl, beh, x_last)
                 break
+            xnext = ws.x[l + 1][0] if l + 1 < cfg.num_hidden_layers else ws.x_final
+            if not self._shipped_ffn_layer(W):
+                self._ffn_fwd_plain(c, l, xcur, xnext)
+                continue
             grp = dict(groups=E, group_offsets=ws.offsets)
             if W.inject and self.split_inject:
                 # K = 256 of the 320 input columns; the embedding columns' share comes from the (expert, behaviour) table
@@ -833,13 +849,103 @@ class Engine:
                 else:
                     ops.linear_fwd(A["hin"], din, Wm.gu, din, A["gu"], 2 * I, T, 2 * I, din, strideB=2 * I * din, **grp)
                     ops.swiglu_fwd_ld(A["gu"], 2 * I, T, I, p_res, self._seed(l, 4), A["hm"])
-            xnext = ws.x[l + 1][0] if l + 1 < cfg.num_hidden_layers else ws.x_final
             # down projection: rows are in expert-sorted order, the epilogue scatters them back to token
             # order through perm while adding the residual and applying dropout (FFN.py:25-27, model.py:241)
             ops.gemm(A["hm"], I, 1, Wm.down, I, 1, xnext, H, T, H, I, strideB=H * I, resid=xcur, row_map=ws.perm,
                      p_drop=p_res, seed=self._seed(l, 5), **grp)
         # ---- final norm, tied head, temperature CE (model.py:869,1001,904-922) ----
         return self._head(c, x_last if last_row_logits else None, num_items_in_batch, hidden_sink)
+
+    def _shipped_ffn_layer(self, W) -> bool:
+        """Whether layer W's FFN has the shipped form the fused paths are built for: SwiGLU experts, one per position."""
+        return W.sparse and W.gated and not self.cfg.Moe_behavior_only
+
+    def _ffn_rows(self, l: int):
+        """Row order of layer l's FFN tensors (what the norm backward scatters its branch gradient through): expert-sorted
+        for a sparse layer, token order for a dense one."""
+        return self.ws.slot if self.W[l].sparse else None
+
+    def _ffn_fwd_plain(self, c, l: int, xcur, xnext):
+        """Layer l's FFN outside the shipped form - a dense layer (one MLP over every token, pad and eos included,
+        FFN.py:69-70), PBATransformer experts (wo(dropout(silu(wi(x)))), FFN.py:75-86) or behaviour-only routing - from
+        standalone kernels: norm (+ behaviour columns), the input projection (grouped by expert in a sparse layer, one
+        GEMM in a dense one), the activation with its dropout, the output projection with the residual add + dropout.
+        Behaviour-only routing: the semantic tokens' expert index (2) names no expert; their rows are in no group, so
+        their FFN output is 0 and xnext = xcur there exactly (MyQwen3SparseMLP leaves them at zeros_like)."""
+        ws, W, Wm, A = c.ws, self.W[l], self.Wm[l], c.ws.layers[l]
+        T, H, I, din, nI = c.T, c.H, c.I, W.din, W.nI
+        slot = ws.slot if W.sparse else None
+        grp = dict(groups=W.ne, group_offsets=ws.offsets) if W.sparse else {}
+        phantom = W.sparse and self.cfg.Moe_behavior_only
+        ops.rmsnorm_fwd(xcur, W.ln3, c.eps, A["hin"], din, slot)
+        if W.inject:
+            ops.rowtable_fwd(W.beh, ws.router["beh_idx"], A["hin"], din, H, slot)
+        gu = A["gu"].view(-1)[:T * nI].view(T, nI)
+        if phantom:
+            gu.zero_()          # (rows in no group are never written by the GEMM: zeros keep the activation's maximum finite)
+        ops.linear_fwd(A["hin"], din, Wm.gu, din, gu, nI, T, nI, din, **(dict(strideB=nI * din) if W.sparse else {}), **grp)
+        if W.gated:
+            ops.swiglu_fwd_ld(gu, nI, T, I, c.p_res, self._seed(l, 4), A["hm"])
+        else:
+            ops.silu_fwd_ld(gu, nI, T, I, c.p_res, self._seed(l, 4), A["hm"])
+        if phantom:
+            xnext.copy_(xcur)   # (the down projection below overwrites the grouped rows)
+        ops.gemm(A["hm"], I, 1, Wm.down, I, 1, xnext, H, T, H, I, resid=xcur, p_drop=c.p_res, seed=self._seed(l, 5),
+                 **(dict(strideB=H * I, row_map=ws.perm) if W.sparse else {}), **grp)
+
+    def _ffn_bwd_plain(self, c, l: int, xlast):
+        """Backward of ``_ffn_fwd_plain`` (t0 = mask * dx of the FFN branch in the layer's row order): ws.dx += the norm's
+        input gradient, weight gradients of both projections, of the behaviour table and of the norm."""
+        ws, W, G, A = c.ws, self.W[l], self.G[l], c.ws.layers[l]
+        WT = self.WT[l] if c.bf16 else None
+        T, H, I, din, nI = c.T, c.H, c.I, W.din, W.nI
+        t0 = ws.tmpH[0]
+        slot = ws.slot if W.sparse else None
+        grp = dict(groups=W.ne, group_offsets=ws.offsets) if W.sparse else {}
+        sB = (lambda n: dict(strideB=n)) if W.sparse else (lambda n: {})
+        sC = (lambda n: dict(strideC=n)) if W.sparse else (lambda n: {})
+        if W.sparse and self.cfg.Moe_behavior_only:
+            ws.dhm.zero_()      # (the rows in no group: their input gradients are zero; the GEMMs below do not write them)
+            ws.dhin.zero_()
+        with c.hold(t0):
+            ops.linear_wgrad(t0, H, A["hm"], I, G.down, I, T, H, I, **sC(H * I), **grp)
+            self._dgrad(c, t0, H, W.down, WT.down if c.bf16 else None, I, ws.dhm, I, H, I, **sB(H * I), **grp)
+        gu = A["gu"].view(-1)[:T * nI].view(T, nI)
+        if W.gated:
+            ops.swiglu_bwd_ld(gu, nI, T, I, ws.dhm, c.p_res, self._seed(l, 4))
+        else:
+            ops.silu_bwd_ld(gu, nI, T, I, ws.dhm, c.p_res, self._seed(l, 4))
+        with c.hold(gu):
+            ops.linear_wgrad(gu, nI, A["hin"], din, G.gu, din, T, nI, din, **sC(nI * din), **grp)
+            self._dgrad(c, gu, nI, W.gu, WT.gu if c.bf16 else None, din, ws.dhin, din, nI, din, **sB(nI * din), **grp)
+        if W.inject:
+            ops.rowtable_bwd(ws.dhin, din, H, ws.router["beh_idx"], G.beh, slot, partial=ws.norm_partial[-1])
+        self._norm_bwd(c, xlast, W.ln3, ws.dhin, din, G.ln3, True, slot,
+                       branch=None if W.cross else (self._seed(l, 1), None))
+
+    def ffn_rows(self, W, pos: int, x, beh, out):
+        """The FFN of layer W on rows that all sit at item position ``pos`` (fp32, no dropout): out = x + FFN(x) - a
+        generation's prompt pass (its last position) and decode step.  ``beh``: the rows' behaviour indices (injecting
+        layers).  A sparse layer runs the position's expert (config.position_experts); behaviour-only routing gives the
+        semantic positions no expert, so out = x there."""
+        cfg = self.cfg
+        B, H, I, din, nI = x.shape[0], cfg.hidden_size, cfg.intermediate_size, W.din, W.nI
+        e = cfg.position_experts()[pos] if W.sparse else 0
+        if e >= W.ne:
+            out.copy_(x)
+            return
+        f32 = dict(dtype=torch.float32, device=self.device)
+        hin = torch.empty(B, din, **f32)
+        ops.rmsnorm_fwd(x, W.ln3, float(cfg.rms_norm_eps), hin, din)
+        if W.inject:
+            ops.rowtable_fwd(W.beh, beh, hin, din, H)
+        gu, hm = torch.empty(B, nI, **f32), torch.empty(B, I, **f32)
+        ops.linear_fwd(hin, din, W.gu[e * nI:(e + 1) * nI], din, gu, nI, B, nI, din)
+        if W.gated:
+            ops.swiglu_fwd_ld(gu, nI, B, I, 0.0, 0, hm)
+        else:
+            ops.silu_fwd_ld(gu, nI, B, I, 0.0, 0, hm)
+        ops.gemm(hm, I, 1, W.down[e * H:(e + 1) * H], I, 1, out, H, B, H, I, resid=x)
 
     def _pass(self, B: int, S: int, p_res: float, p_att: float) -> SimpleNamespace:
         """Shapes, dropout and kernel forms of one forward or backward pass (the context of the shared blocks below)."""
@@ -1025,7 +1131,7 @@ class Engine:
         soon as every kernel writing layer l's weight gradients has been enqueued (data-parallel
         all-reduce overlap, gamer_amd.dp)."""
         cfg = self.cfg
-        c = self._backward_head(dloss, dloss_dev, rows=self.ws.slot)
+        c = self._backward_head(dloss, dloss_dev, rows=self._ffn_rows(cfg.num_hidden_layers - 1))
         ws, B, S, T, H, I, E = c.ws, c.B, c.S, c.T, c.H, c.I, cfg.num_experts
         nq, nkv, NQ, NKV, QKV, eps, cos, sin, p_res = c.nq, c.nkv, c.NQ, c.NKV, c.QKV, c.eps, c.cos, c.sin, c.p_res
         NB1 = cfg.num_behavior + 1
@@ -1046,51 +1152,54 @@ class Engine:
             grp = dict(groups=E, group_offsets=ws.offsets)
             xlast = xs[2] if W.cross else xs[1]
             # ---- experts ----   (t0 = d out_sorted, written by the norm backward that completed dx)
-            split_inj = W.inject and self.split_inject
-            tb = ws._buf(f"l{l}_inject_tbl", (E * NB1, 2 * I)) if split_inj else None
-            with hold(t0):
-                ops.linear_wgrad(t0, H, A["hm"], I, G.down, I, T, H, I, strideC=H * I, **grp)
-                if fuse_swiglu_bwd and split_inj:
-                    # (rows grouped by (expert, behaviour): a tile's rows share one table row; NB1 consecutive groups share an expert)
-                    ops.gemm(t0, H, 1, W.down, 1, I, ws.dhm, I, T, I, H, strideB=H * I, p_drop=p_res, seed=self._seed(l, 4),
-                             swiglu_bwd=(A["gu"], 2 * I), groups=E * NB1, group_offsets=ws.grp_offsets, group_div=NB1, sw_tbl=tb)
-                elif fuse_swiglu_bwd:
-                    # the down projection's input gradient with the SwiGLU backward in its epilogue: d(hm) = t0 W_down never goes
-                    # to memory, A["gu"] <- d gate | d up (gamer_gemm_desc.sw_gu; ws.dhm is only the descriptor's C)
-                    if bf16:
-                        ops.linear_dgrad_t(t0, H, WT.down, WT.down.shape[1], ws.dhm, I, T, H, I, strideB=H * I, p_drop=p_res,
-                                           seed=self._seed(l, 4), swiglu_bwd=(A["gu"], 2 * I), **grp)
-                    else:
-                        ops.gemm(t0, H, 1, W.down, 1, I, ws.dhm, I, T, I, H, strideB=H * I, p_drop=p_res, seed=self._seed(l, 4),
-                                 swiglu_bwd=(A["gu"], 2 * I), **grp)
-                else:
-                    dgrad(t0, H, W.down, WT.down if bf16 else None, I, ws.dhm, I, H, I, strideB=H * I, **grp)
-            if not fuse_swiglu_bwd:
-                if split_inj:
-                    ops.swiglu_bwd_ld_tbl(A["gu"], 2 * I, T, I, ws.dhm, p_res, self._seed(l, 4), tb, ws.row_group)
-                else:
-                    ops.swiglu_bwd_ld(A["gu"], 2 * I, T, I, ws.dhm, p_res, self._seed(l, 4))    # gu <- d gate | d up
-            if split_inj:
-                hin = A["hin"].view(-1)[:T * H].view(T, H)
-                dhin = ws.dhin.view(-1)[:T * H].view(T, H)
-                with hold(A["gu"]):
-                    ops.linear_wgrad(A["gu"], 2 * I, hin, H, G.gu, din, T, 2 * I, H, strideC=2 * I * din, **grp)
-                    dgrad(A["gu"], 2 * I, W.gu, None, din, dhin, H, 2 * I, H, strideB=2 * I * din, **grp)
-                # the embedding columns' weight gradient and the embedding gradient from the (expert, behaviour) sums of d(gate|up)
-                seg = ws._buf("inject_segsum", (E * NB1, 2 * I))
-                seg_ws = ws._buf("inject_seg_ws", (ops.segment_colsum_ws_floats(T, 2 * I, E * NB1),))
-                ops.segment_colsum(A["gu"], 2 * I, T, 2 * I, ws.grp_offsets, E * NB1, seg_ws, seg)
-                ops.inject_table_bwd(seg, W.beh, W.gu, din, H, E, 2 * I, G.gu, G.beh,
-                                     ws._buf("inject_scratch", (NB1 * E * cfg.behavior_embedding_dim,)))
-                norm_bwd(xlast, W.ln3, dhin, H, G.ln3, True, ws.slot, branch=None if W.cross else (self._seed(l, 1), None))
+            if not self._shipped_ffn_layer(W):
+                self._ffn_bwd_plain(c, l, xlast)
             else:
-                with hold(A["gu"]):
-                    ops.linear_wgrad(A["gu"], 2 * I, A["hin"], din, G.gu, din, T, 2 * I, din, strideC=2 * I * din, **grp)
-                    dgrad(A["gu"], 2 * I, W.gu, WT.gu if bf16 else None, din, ws.dhin, din, 2 * I, din, strideB=2 * I * din, **grp)
-                if W.inject:
-                    ops.rowtable_bwd(ws.dhin, din, H, r["beh_idx"], G.beh, ws.slot, partial=NP)
-                norm_bwd(xlast, W.ln3, ws.dhin, din, G.ln3, True, ws.slot,
-                         branch=None if W.cross else (self._seed(l, 1), None))
+                split_inj = W.inject and self.split_inject
+                tb = ws._buf(f"l{l}_inject_tbl", (E * NB1, 2 * I)) if split_inj else None
+                with hold(t0):
+                    ops.linear_wgrad(t0, H, A["hm"], I, G.down, I, T, H, I, strideC=H * I, **grp)
+                    if fuse_swiglu_bwd and split_inj:
+                        # (rows grouped by (expert, behaviour): a tile's rows share one table row; NB1 consecutive groups share an expert)
+                        ops.gemm(t0, H, 1, W.down, 1, I, ws.dhm, I, T, I, H, strideB=H * I, p_drop=p_res, seed=self._seed(l, 4),
+                                 swiglu_bwd=(A["gu"], 2 * I), groups=E * NB1, group_offsets=ws.grp_offsets, group_div=NB1, sw_tbl=tb)
+                    elif fuse_swiglu_bwd:
+                        # the down projection's input gradient with the SwiGLU backward in its epilogue: d(hm) = t0 W_down never goes
+                        # to memory, A["gu"] <- d gate | d up (gamer_gemm_desc.sw_gu; ws.dhm is only the descriptor's C)
+                        if bf16:
+                            ops.linear_dgrad_t(t0, H, WT.down, WT.down.shape[1], ws.dhm, I, T, H, I, strideB=H * I, p_drop=p_res,
+                                               seed=self._seed(l, 4), swiglu_bwd=(A["gu"], 2 * I), **grp)
+                        else:
+                            ops.gemm(t0, H, 1, W.down, 1, I, ws.dhm, I, T, I, H, strideB=H * I, p_drop=p_res, seed=self._seed(l, 4),
+                                     swiglu_bwd=(A["gu"], 2 * I), **grp)
+                    else:
+                        dgrad(t0, H, W.down, WT.down if bf16 else None, I, ws.dhm, I, H, I, strideB=H * I, **grp)
+                if not fuse_swiglu_bwd:
+                    if split_inj:
+                        ops.swiglu_bwd_ld_tbl(A["gu"], 2 * I, T, I, ws.dhm, p_res, self._seed(l, 4), tb, ws.row_group)
+                    else:
+                        ops.swiglu_bwd_ld(A["gu"], 2 * I, T, I, ws.dhm, p_res, self._seed(l, 4))    # gu <- d gate | d up
+                if split_inj:
+                    hin = A["hin"].view(-1)[:T * H].view(T, H)
+                    dhin = ws.dhin.view(-1)[:T * H].view(T, H)
+                    with hold(A["gu"]):
+                        ops.linear_wgrad(A["gu"], 2 * I, hin, H, G.gu, din, T, 2 * I, H, strideC=2 * I * din, **grp)
+                        dgrad(A["gu"], 2 * I, W.gu, None, din, dhin, H, 2 * I, H, strideB=2 * I * din, **grp)
+                    # the embedding columns' weight gradient and the embedding gradient from the (expert, behaviour) sums of d(gate|up)
+                    seg = ws._buf("inject_segsum", (E * NB1, 2 * I))
+                    seg_ws = ws._buf("inject_seg_ws", (ops.segment_colsum_ws_floats(T, 2 * I, E * NB1),))
+                    ops.segment_colsum(A["gu"], 2 * I, T, 2 * I, ws.grp_offsets, E * NB1, seg_ws, seg)
+                    ops.inject_table_bwd(seg, W.beh, W.gu, din, H, E, 2 * I, G.gu, G.beh,
+                                         ws._buf("inject_scratch", (NB1 * E * cfg.behavior_embedding_dim,)))
+                    norm_bwd(xlast, W.ln3, dhin, H, G.ln3, True, ws.slot, branch=None if W.cross else (self._seed(l, 1), None))
+                else:
+                    with hold(A["gu"]):
+                        ops.linear_wgrad(A["gu"], 2 * I, A["hin"], din, G.gu, din, T, 2 * I, din, strideC=2 * I * din, **grp)
+                        dgrad(A["gu"], 2 * I, W.gu, WT.gu if bf16 else None, din, ws.dhin, din, 2 * I, din, strideB=2 * I * din, **grp)
+                    if W.inject:
+                        ops.rowtable_bwd(ws.dhin, din, H, r["beh_idx"], G.beh, ws.slot, partial=NP)
+                    norm_bwd(xlast, W.ln3, ws.dhin, din, G.ln3, True, ws.slot,
+                             branch=None if W.cross else (self._seed(l, 1), None))
             # ---- cross attention ----
             if W.cross:
                 C, GC = W.cross_attn, G.cross_attn
@@ -1117,7 +1226,7 @@ class Engine:
                 dgrad(t2, H, C["gate"], CT["gate"], H, t3, H, H, H, accumulate=True)
                 hold_t2.__exit__(None, None, None)
                 norm_bwd(xs[1], W.ln2, t3, H, G.ln2, True, branch=(self._seed(l, 1), None))
-            self._self_attention_bwd(c, l, r, span_self, pos_ids, rows=ws.slot)
+            self._self_attention_bwd(c, l, r, span_self, pos_ids, rows=self._ffn_rows(l - 1) if l > 0 else None)
             if layer_done is not None:
                 layer_done(l)
         self._backward_tail(c)

@@ -125,6 +125,13 @@ def session_prep(session_ids, extended_session_ids, attn_mask, num_positions, n_
          ptr(out["tile_empty_self"]), ptr(out["violations"]), stream_ptr())
 
 
+def router_position_table(expert, table):
+    """expert[i] <- table[expert[i]] in place (gamer_router_position_table; int32 tensors on the device)."""
+    _chk(expert, torch.int32, "expert")
+    _chk(table, torch.int32, "table")
+    call("gamer_router_position_table", ptr(expert), expert.numel(), ptr(table), table.numel(), stream_ptr())
+
+
 def expert_lists(expert, num_experts, perm, slot, offsets, work):
     B, S = expert.shape
     call("gamer_expert_lists", ptr(expert), B, S, num_experts, ptr(perm), ptr(slot), ptr(offsets), ptr(work),
@@ -1067,6 +1074,19 @@ def swiglu_bwd_ld(gu, ld, T, I, dhm, p, seed):
         geom = (1, 0, 1, T * ld, T * ld)
         _arm_sink((gu, geom, False), (gu, geom, True))
     call("gamer_swiglu_bwd_ld" + _sfx(gu), ptr(gu), ld, T, I, ptr(dhm), p, seed, stream_ptr())
+
+
+def silu_fwd_ld(h, ld, T, I, p, seed, hm):
+    """hm[T, I] = drop(silu(h[:, :I])) on the output of a non-gated FFN's wi projection (row stride ld; mlp_type "PBATransformer")."""
+    _arm_sink((hm, (1, 0, 1, T * I, T * I), False))
+    call("gamer_silu_fwd_ld" + _sfx(h), ptr(h), ld, T, I, p, seed, ptr(hm), stream_ptr())
+
+
+def silu_bwd_ld(h, ld, T, I, dhm, p, seed):
+    """In place: h[:, :I] <- drop_mask * dhm * silu'(h)."""
+    if ld == I:
+        _arm_sink((h, (1, 0, 1, T * I, T * I), False))
+    call("gamer_silu_bwd_ld" + _sfx(h), ptr(h), ld, T, I, ptr(dhm), p, seed, stream_ptr())
 
 
 def swiglu_fwd_ld_tbl(gu, ld, T, I, p, seed, hm, tbl, row_group):

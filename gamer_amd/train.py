@@ -21,6 +21,8 @@ vocabulary resized; ``Engine(variant="qwen3")``); its checkpoints load into ``ga
 ``--backbone Qwen3Session`` trains its session-mask ablation (train_SMB_decoder.py:369-378: the same config plus
 ``num_positions`` = tokens per item and ``model_max_length``; ``Engine(variant="qwen3_session")``, synthetic batches with
 sessions of mean 4 items); its checkpoints load into ``gamer_amd.modeling.Qwen3SessionWithTemperature``.
+``--base_model DIR`` reads DIR/config.json for Qwen3Multi / Qwen3SessionMulti (train_SMB_decoder.py's argument): the FFN
+ablation configurations of the reference's configs (mlp_type, sparse_layers_decoder, Moe_behavior_only) train as written there.
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ import time
 import torch
 
 from . import synthetic
-from .config import Qwen3Config, Qwen3SessionConfig, synthetic_config
+from .config import Qwen3Config, Qwen3SessionConfig, base_model_config, synthetic_config
 from .dp import GradAllReducer, all_reduce_scalar_
 from .engine import Engine
 from .schedule import cosine_with_warmup, warmup_steps_for
@@ -69,9 +71,20 @@ def parse_args(argv=None):
                     help="fp32 runs: how matrix products are formed (default: the engine's, split3 = Linear sites as three fp16 piece "
                          "products scaled per tensor; split6 = exact bf16 piece products with fp32 accumulation; f32 = the fp32 MFMA)")
     ap.add_argument("--prefetch", type=int, default=2, help="optimizer steps collated ahead on a background thread")
+    ap.add_argument("--base_model", type=str, default="",
+                    help="directory with the model's config.json (Qwen3Multi / Qwen3SessionMulti: its FFN ablation switches "
+                         "mlp_type, sparse_layers_decoder and Moe_behavior_only are honoured; the run-time fields of "
+                         "train_SMB_decoder.py:321-360 are set on top)")
     ap.add_argument("--output_dir", type=str, default="")
     ap.add_argument("--resume_from_checkpoint", type=str, default="")
     return ap.parse_args(argv)
+
+
+def synthetic_base_model_config(path: str, max_his_len: int):
+    """``--base_model DIR`` with synthetic batches: DIR/config.json with the vocabulary, behaviours and item length of
+    ``gamer_amd.synthetic`` set at run time (config.base_model_config)."""
+    return base_model_config(path, synthetic.vocab_size(256, 3), 3, synthetic.behavior_maps(256, 3), synthetic.TOKENS_PER_ITEM,
+                             max_his_len + 1, pad_token_id=synthetic.PAD_ID)
 
 
 def save_checkpoint(eng: Engine, path: str, state: dict):
@@ -152,6 +165,8 @@ class Prefetcher:
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti"):
+        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti backbones")
     if args.fp16:
         raise SystemExit("--fp16 is not built (the MI355X path has fp32 and bf16; the reference's recipe uses neither "
                          "loss scaling nor fp16 kernels of its own)")
@@ -182,6 +197,9 @@ def main(argv=None):
             raise NotImplementedError(f"tasks={args.tasks}: smb_explicit and smb_explicit_decoder[_N] are built")
         coll = gdata.Collator(ds)
         cfg = gdata.model_config(ds, args.max_his_len)
+        if args.base_model and variant in ("multi", "session"):
+            cfg = base_model_config(args.base_model, cfg.vocab_size, cfg.num_behavior, cfg.behavior_maps, cfg.num_positions,
+                                    cfg.n_positions, pad_token_id=cfg.pad_token_id)
         if variant == "qwen3":
             # the baseline's config: Qwen3-Light with the tokenizer's vocabulary, nothing else set at run time
             cfg = Qwen3Config(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id)
@@ -200,6 +218,8 @@ def main(argv=None):
     elif variant == "qwen3_session":
         cfg = Qwen3SessionConfig(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID,
                                  num_positions=synthetic.TOKENS_PER_ITEM, model_max_length=1024)
+    elif args.base_model:
+        cfg = synthetic_base_model_config(args.base_model, args.max_his_len)
     else:
         cfg = synthetic_config(n_positions=args.max_his_len + 1)
     eng = Engine(cfg, device=f"cuda:{local_rank}", temperature=args.temperature, variant=variant,

@@ -128,6 +128,15 @@ int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t* kl_self, 
  *   offsets int32 [num_experts+1]; work int32 [(B+1)*num_experts] scratch.                     */
 int gamer_expert_lists(const int32_t* expert, int B, int S, int num_experts,
                        int32_t* perm, int32_t* slot, int32_t* offsets, int32_t* work, void* stream);
+/* Rows whose expert index is outside [0, num_experts) belong to no group (Moe_behavior_only: the semantic tokens' index 2 names
+ * no expert when num_experts = 2, and MyQwen3SparseMLP leaves their FFN output at zero): with num_experts < 64 they take the slots
+ * offsets[num_experts] .. T - 1 in token order (perm / slot stay permutations); the grouped GEMMs never visit them.
+
+ * (additive in ABI 9) The router's position table (ref:SeqRec/models/generative/Qwen3Multi/router.py:28-54) applied to
+ * gamer_router_fwd's `expert` output in place: expert[i] <- table[expert[i]] for 0 <= expert[i] < n_table (int32 [n_table], on the
+ * device).  gamer_router_fwd emits the shipped table (position p of an item -> p + 1, pad / eos -> 0); Moe_behavior_only's is
+ * table = [0, 1, 2, 2, ..., 2] (behaviour token -> 1, semantic tokens -> 2).                                                     */
+int gamer_router_position_table(int32_t* expert, int64_t n, const int32_t* table, int n_table, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Embedding (nn.Embedding(vocab,H,padding_idx), ref:.../Qwen3Multi/model.py:263,779).
@@ -676,6 +685,19 @@ int gamer_swiglu_fwd_ld_bf16(const gamer_bf16* gu, int64_t ld, int T, int I, flo
                              void* stream);
 int gamer_swiglu_bwd_ld_bf16(gamer_bf16* gu, int64_t ld, int T, int I, const gamer_bf16* dhm, float p_drop, uint64_t seed,
                              void* stream);
+/* (additive in ABI 9) The non-gated FFN of mlp_type "PBATransformer" (T5DenseActDense, ref:SeqRec/models/generative/Qwen3Moe/FFN.py:
+ * 75-86: wo(dropout(silu(wi(x))))): h [T][ld] is the output of the wi projection (columns 0 .. I - 1, ld >= I, a multiple of 4),
+ * hm / dhm [T][I] contiguous.
+ *   gamer_silu_fwd_ld   hm = drop(silu(h))
+ *   gamer_silu_bwd_ld   in place: h <- drop_mask * dhm * silu'(h)
+ * Same dropout masks as gamer_swiglu_fwd_ld under the same seed (element (t, c) <-> flat index t I + c).  gamer_amax_sink: out0 =
+ * max |hm| (forward), max |dh| (backward).                                                                                        */
+int gamer_silu_fwd_ld(const float* h, int64_t ld, int T, int I, float p_drop, uint64_t seed, float* hm, void* stream);
+int gamer_silu_bwd_ld(float* h, int64_t ld, int T, int I, const float* dhm, float p_drop, uint64_t seed, void* stream);
+int gamer_silu_fwd_ld_bf16(const gamer_bf16* h, int64_t ld, int T, int I, float p_drop, uint64_t seed, gamer_bf16* hm,
+                           void* stream);
+int gamer_silu_bwd_ld_bf16(gamer_bf16* h, int64_t ld, int T, int I, const gamer_bf16* dhm, float p_drop, uint64_t seed,
+                           void* stream);
 /* out = a * silu(gate)  (cross-attention output gate, model.py:147); with resid != NULL the block's residual add
  * is fused in: out = resid + drop(a * silu(gate)) (model.py:235), same mask as gamer_residual_dropout_fwd(seed)  */
 int gamer_silu_gate_fwd(const float* a, const float* gate, int64_t n, float* out, const float* resid,
