@@ -169,14 +169,18 @@ class Qwen3MultiConfig:
             raise ValueError("only hidden_act='silu' is implemented")
         if any(int(l) not in range(self.num_hidden_layers) for l in self.sparse_layers_decoder):
             raise ValueError("sparse_layers_decoder must be a subset of range(num_hidden_layers)")
-        if self.use_user_token or not self.use_behavior_token:
-            raise ValueError("only the routing modes with a behaviour token and without a user token are implemented "
-                             "(use_user_token=False, use_behavior_token=True)")
+        self._check_routing_mode()
         if self.num_experts != expected_num_experts(self):
             raise ValueError("num_experts must be num_positions + 1, or 2 with Moe_behavior_only "
                              "(train_SMB_decoder.py:344-351)")
         if not self.tie_word_embeddings:
             raise ValueError("lm_head is tied to embed_tokens in this model")
+
+    def _check_routing_mode(self):
+        """The router modes the model runs (Qwen3Multi: a behaviour token per item, no user token)."""
+        if self.use_user_token or not self.use_behavior_token:
+            raise ValueError("only the routing modes with a behaviour token and without a user token are implemented "
+                             "(use_user_token=False, use_behavior_token=True)")
 
     # --- the FFN ablation switches (mlp_type, sparse_layers_decoder, Moe_behavior_only) -------------------
     def is_sparse(self, layer: int) -> bool:
@@ -377,3 +381,122 @@ class Qwen3SessionConfig(Qwen3Config):
         super().validate()
         if self.num_positions <= 0:
             raise ValueError("num_positions must be positive")
+
+
+_QWEN3MOE_DEFAULTS: Dict[str, Any] = {
+    # ref:config/s2s-models/Qwen3Moe/config.json: Qwen3Multi's schema without cross attention (no cross_attention_decoder key),
+    # residual and attention dropout 0.1, the router's auxiliary-loss coefficient (multiplied by an aux loss of 0)
+    "architectures": ["Qwen3MoeForCausalLM"],
+    "model_type": "qwen3_moe",
+    "router_aux_loss_coef": 0.001,
+    "cross_attention_decoder": [],
+    "dropout_rate": 0.1,
+    "attention_dropout": 0.1,
+}
+
+
+class Qwen3MoeConfig(Qwen3MultiConfig):
+    """Configuration of the Qwen3Moe model (ref:SeqRec/models/generative/Qwen3Moe/model.py; train_MB_decoder.py:317-364 builds
+    ``Qwen3MoeWithTemperature`` from it): Qwen3Multi's schema and FFN switches, no cross attention, and besides the shipped
+    routing mode the one of a dataset without behaviour tokens (task ``mb``): ``use_behavior_token = False``, no behaviours,
+    no injection, behaviour index 0 everywhere.  ``mlp_type`` absent from a config.json or an HF config object falls back to
+    "PBATransformer", as the reference's decoder layer does (model.py:50-53); keyword construction takes config.json's values."""
+
+    def __init__(self, **kwargs):
+        d = copy.deepcopy(_QWEN3MOE_DEFAULTS)
+        d.update(kwargs)
+        super().__init__(**d)
+
+    @classmethod
+    def from_pretrained(cls, path: str) -> "Qwen3MoeConfig":
+        f = os.path.join(path, "config.json") if os.path.isdir(path) else path
+        with open(f) as fh:
+            d = json.load(fh)
+        d.setdefault("mlp_type", "PBATransformer")
+        return cls(**d)
+
+    @classmethod
+    def coerce(cls, config) -> "Qwen3MoeConfig":
+        """As ``Qwen3MultiConfig.coerce``; an HF config object without ``mlp_type`` gets "PBATransformer" (model.py:50-53)."""
+        if isinstance(config, cls):
+            return config
+        if isinstance(config, dict):
+            return cls(**config)
+        d = {key: copy.deepcopy(getattr(config, key)) for key in _DEFAULTS if hasattr(config, key)}
+        if "rope_theta" not in d:
+            rp = getattr(config, "rope_parameters", None)
+            if isinstance(rp, dict) and "rope_theta" in rp:
+                d["rope_theta"] = rp["rope_theta"]
+        missing = [k for k in ("num_positions", "num_behavior", "behavior_maps", "n_positions") if k not in d]
+        if missing:
+            raise ValueError(f"config object lacks the run-time fields {missing} (train_MB_decoder.py:319-362 sets them "
+                             "before the model is constructed)")
+        d["router_aux_loss_coef"] = getattr(config, "router_aux_loss_coef", _QWEN3MOE_DEFAULTS["router_aux_loss_coef"])
+        d["cross_attention_decoder"] = list(getattr(config, "cross_attention_decoder", []) or [])
+        if not hasattr(config, "mlp_type"):
+            d["mlp_type"] = "PBATransformer"
+        return cls(**d)
+
+    def expected_num_experts(self) -> int:
+        """train_MB_decoder.py:354-361: num_positions + 1, or 2 under Moe_behavior_only."""
+        return 2 if self.Moe_behavior_only else int(self.num_positions) + 1
+
+    def validate(self):
+        if self.cross_attention_decoder:
+            raise ValueError("Qwen3Moe has no cross attention (cross_attention_decoder must be empty)")
+        if not self.use_behavior_token:
+            # task "mb" (train_MB_decoder.py:343-350): no behaviour tokens, no behaviours, no injection
+            if self.num_behavior or self.behavior_maps:
+                raise ValueError("use_behavior_token=False: num_behavior must be 0 and behavior_maps empty "
+                                 "(train_MB_decoder.py:343-344)")
+            if self.behavior_injection_decoder:
+                raise ValueError("use_behavior_token=False: behavior_injection_decoder must be empty "
+                                 "(train_MB_decoder.py:346-350)")
+        super().validate()
+        if int(self.n_positions) < 1:
+            raise ValueError("n_positions (the router's item count, max_his_len + 1) must be positive")
+
+    def _check_routing_mode(self):
+        """Qwen3Moe's router also runs without behaviour tokens (task "mb", checked in ``validate``); no user token."""
+        if self.use_user_token:
+            raise ValueError("the routing modes with a user token are not implemented (use_user_token=False)")
+
+    def position_experts(self):
+        """Expert index of each position inside an item (router.py:29-54): 1..num_positions; Moe_behavior_only: [1, 2, .., 2]
+        with a behaviour token, [1, .., 1] without one (no +1 there)."""
+        P = int(self.num_positions)
+        if self.Moe_behavior_only and not self.use_behavior_token:
+            return [1] * P
+        return super().position_experts()
+
+
+def apply_mb_runtime_fields(config, num_behavior: int, behavior_maps: dict, use_behavior_token: bool, num_positions: int,
+                            max_his_len: int = 20):
+    """The run-time mutation train_MB_decoder.py:319-362 applies to a Qwen3Moe config read from config.json: the dataset's
+    behaviours (none without behaviour tokens, and then no injection), the item's token count, the expert count of the
+    routing mode, ``n_positions = max_his_len + 1`` and no user token.  Returns ``config``."""
+    config.use_behavior_token = bool(use_behavior_token)
+    if config.use_behavior_token:
+        config.num_behavior = int(num_behavior)
+        config.behavior_maps = {str(k): int(v) for k, v in behavior_maps.items()}
+    else:
+        config.num_behavior = 0
+        config.behavior_maps = {}
+        config.behavior_injection = False
+        config.behavior_injection_decoder = []
+    config.num_positions = int(num_positions)
+    config.num_experts = 2 if config.Moe_behavior_only else config.num_positions + 1
+    config.n_positions = int(max_his_len) + 1
+    config.use_user_token = False
+    return config
+
+
+def base_model_config_moe(path: str, vocab_size: int, num_behavior: int, behavior_maps: dict, use_behavior_token: bool,
+                          num_positions: int, max_his_len: int = 20, pad_token_id: int = None) -> Qwen3MoeConfig:
+    """``--base_model DIR`` of train_MB_decoder.py for ``--backbone Qwen3Moe``: DIR/config.json (mlp_type absent -> the
+    reference's "PBATransformer"), the vocabulary resized to the tokenizer's, then ``apply_mb_runtime_fields``."""
+    cfg = Qwen3MoeConfig.from_pretrained(path)
+    cfg.vocab_size = int(vocab_size)
+    if pad_token_id is not None:
+        cfg.pad_token_id = int(pad_token_id)
+    return apply_mb_runtime_fields(cfg, num_behavior, behavior_maps, use_behavior_token, num_positions, max_his_len)

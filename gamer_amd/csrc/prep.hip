@@ -491,3 +491,91 @@ extern "C" int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t
     GAMER_CHECK_LAUNCH("gamer_causal_prep");
     return 0;
 }
+
+// ---- Qwen3Moe router + causal mask (one launch) -----------------------------------------------------------------------
+// ref:SeqRec/models/generative/Qwen3Moe/router.py (Qwen3Multi's router without action indices) with the model's
+// cache_position = arange(S) (model.py:222-230), and its causal + key-padding mask (model.py:310-460).  Per token t of row b:
+//   expert[t]  = table[t % P] for t < n_items P, 0 for the trailing eos slot t = n_items P (router.py:28-60);
+//                0 at pad / eos tokens.  table == NULL: t % P + 1 (the shipped table, and that of use_behavior_token = False)
+//   beh_idx[t] = behaviour tokens (use_beh != 0): lut[ids[item start]] + 1, 0 on the behaviour token itself, at pad / eos and
+//                in the eos slot (router.py:97-154); a non-special item start outside behavior_maps is counted in bad_token
+//                (the reference fails in its embedding there) and gets 0.  use_beh == 0: 0 everywhere.
+//   kl_self / empty_self / tile_empty_self / pos_ids / next_pos: as causal_prep_kernel.
+// One workgroup per sequence; LDS holds the kept-flag prefix sum (2 S int32).
+__global__ void __launch_bounds__(ROUTER_THREADS)
+moe_router_prep_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ attn_mask,
+                       const int32_t* __restrict__ lut, int vocab, const int32_t* __restrict__ table, int S, int P,
+                       int n_items, int use_beh, int pad_id, int eos_id,
+                       int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx, int32_t* __restrict__ kl_self,
+                       int32_t* __restrict__ empty_self, int32_t* __restrict__ tile_empty_self,
+                       int32_t* __restrict__ pos_ids, int32_t* __restrict__ next_pos, int32_t* __restrict__ bad_token) {
+    extern __shared__ __attribute__((aligned(16))) int32_t ms[];
+    int32_t* a = ms;            // [S] scan ping-pong
+    int32_t* bb = ms + S;       // [S]
+    const int b = blockIdx.x;
+    const int64_t base = (int64_t)b * S;
+    const int n_tiles = (S + 31) / 32;
+    const int slots = n_items * P;
+    int bad = 0;
+    for (int t = threadIdx.x; t < S; t += blockDim.x) {
+        const int64_t id = ids[base + t];
+        const bool special = (id == pad_id) || (id == eos_id);
+        const int p = t % P;
+        int e = 0, bi = 0;
+        if (!special && t < slots) {
+            e = table ? table[p] : p + 1;
+            if (use_beh && p != 0) {
+                const int64_t btok = ids[base + t - p];
+                if (btok >= 0 && btok < vocab && lut[btok] >= 0) bi = lut[btok] + 1;
+            }
+        }
+        if (use_beh && p == 0 && !special && t < slots && !(id >= 0 && id < vocab && lut[id] >= 0)) ++bad;
+        expert[base + t] = e;
+        beh_idx[base + t] = bi;
+        const int keep = attn_mask ? (attn_mask[base + t] != 0 ? 1 : 0) : 1;
+        kl_self[base + t] = keep ? 0 : INT_BIG;
+        a[t] = keep;
+    }
+    if (bad) atomicAdd(bad_token, bad);
+    __syncthreads();
+    for (int off = 1; off < S; off <<= 1) {
+        for (int t = threadIdx.x; t < S; t += blockDim.x) bb[t] = a[t] + (t >= off ? a[t - off] : 0);
+        __syncthreads();
+        int32_t* sw = a; a = bb; bb = sw;
+    }
+    for (int t = threadIdx.x; t < S; t += blockDim.x) {
+        const int c = a[t];
+        empty_self[base + t] = c == 0 ? 1 : 0;
+        if (pos_ids) {
+            const int keep = attn_mask ? (attn_mask[base + t] != 0 ? 1 : 0) : 1;
+            pos_ids[base + t] = keep ? c - 1 : 0;
+        }
+    }
+    for (int qt = threadIdx.x; qt < n_tiles; qt += blockDim.x)
+        tile_empty_self[(int64_t)b * n_tiles + qt] = a[qt * 32] == 0 ? 1 : 0;
+    if (next_pos && threadIdx.x == 0) next_pos[b] = a[S - 1];
+}
+
+extern "C" int gamer_moe_router_prep(const int64_t* ids, const int64_t* attn_mask, const int32_t* behavior_lut, int vocab,
+                                     const int32_t* position_table, int B, int S, int num_positions, int n_items,
+                                     int use_behavior_token, int pad_id, int eos_id, int32_t* expert, int32_t* beh_idx,
+                                     int32_t* kl_self, int32_t* empty_self, int32_t* tile_empty_self, int32_t* pos_ids,
+                                     int32_t* next_pos, int32_t* bad_token, void* stream) {
+    GAMER_CHECK_ARG(ids && expert && beh_idx && kl_self && empty_self && tile_empty_self && bad_token,
+                    "gamer_moe_router_prep: null pointer");
+    GAMER_CHECK_ARG(!use_behavior_token || (behavior_lut && vocab > 0),
+                    "gamer_moe_router_prep: use_behavior_token needs the behaviour table");
+    GAMER_CHECK_ARG(B > 0 && S > 0 && num_positions > 0 && n_items > 0,
+                    "gamer_moe_router_prep: bad shape B=%d S=%d P=%d n_items=%d", B, S, num_positions, n_items);
+    GAMER_CHECK_ARG(S <= 8192, "gamer_moe_router_prep: S=%d > 8192 unsupported", S);
+    GAMER_CHECK_ARG((int64_t)n_items * num_positions + 1 >= S,
+                    "gamer_moe_router_prep: S=%d is longer than the router's table (n_items * P + 1 = %lld)", S,
+                    (long long)n_items * num_positions + 1);
+    const size_t shmem = (size_t)2 * S * sizeof(int32_t);
+    hipLaunchKernelGGL(moe_router_prep_kernel, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
+                       ids, attn_mask, behavior_lut, vocab, position_table, S, num_positions, n_items,
+                       use_behavior_token ? 1 : 0, pad_id, eos_id, expert, beh_idx, kl_self, empty_self, tile_empty_self,
+                       pos_ids, next_pos, bad_token);
+    GAMER_CHECK_LAUNCH("gamer_moe_router_prep");
+    return 0;
+}

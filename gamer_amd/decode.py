@@ -534,6 +534,45 @@ class Qwen3DecodeSession(DecodeSession):
         ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, resid=x1)
 
 
+def _check_moe_generation(engine, L0: int, max_new_tokens: int):
+    """What a Qwen3Moe generation is built for: prompts ending with the target behaviour token (the trie starts there and the
+    generated tokens take its behaviour), and columns inside the router's table (the reference indexes past it)."""
+    if not engine.cfg.use_behavior_token:
+        raise NotImplementedError("generation needs behaviour tokens (the prompt ends with the target behaviour token); "
+                                  "a model trained with use_behavior_token=False is trained and scored, not generated from")
+    if L0 + max_new_tokens - 1 > engine.max_len():
+        raise ValueError(f"prompt of {L0} tokens + {max_new_tokens} new ones exceeds the router's table, n_positions * "
+                         f"num_positions + 1 = {engine.max_len()} (router.py:46-60)")
+
+
+class Qwen3MoeDecodeSession(DecodeSession):
+    """K/V cache + single-token step of Qwen3Moe (``Engine(variant="qwen3moe")``): Qwen3Multi's layers without a cross block,
+    so no cross caches.  The prompt pass runs with the causal + key-padding mask and generate()'s positions
+    ``cumsum(attention_mask) - 1`` (gamer_moe_router_prep builds both); the token generated at step t is rotated by (number
+    of kept prompt tokens) + t - 1 per row, routed to the expert of its column L0 + t - 1 (the reference router's
+    ``cache_position`` rule) and, with behaviour tokens, injected with the behaviour of the prompt's last token (the target
+    item's behaviour token)."""
+
+    def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int):
+        if engine.dtype != "f32":
+            raise NotImplementedError("generation (cached decode) is built for dtype='f32' only")
+        _check_moe_generation(engine, input_ids.shape[1], max_new_tokens)
+        super().__init__(engine, input_ids, attention_mask, None, num_beams, max_new_tokens)
+
+    @staticmethod
+    def _eval_forward(engine, ids, am, act, sess: dict, L0: int, **kw):
+        engine.forward(ids, am, train=False, rope_from_mask=True, **kw)
+
+    def _row_inputs(self, keep, ids0, am0, act0, sess: dict):
+        eng = self.eng
+        self.pos_last = keep("pos_last", (eng.next_pos - 1).repeat_interleave(self.nb))
+        if eng.cfg.use_behavior_token:
+            beh = (eng.lut[ids0[:, -1]].to(torch.int32) + 1).clamp_(min=0)
+        else:
+            beh = torch.zeros(self.B, dtype=torch.int32, device=eng.device)
+        self.beh = keep("beh", beh.repeat_interleave(self.nb))
+
+
 @torch.no_grad()
 def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, actions: torch.Tensor, trie: ItemTrie,
                 num_beams: int, max_new_tokens: int = 4, use_cache: bool = True, session_ids=None,
@@ -546,10 +585,13 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     it needs ``reorder_cross_cache=True``).  ``reorder_cross_cache``: see ``DecodeSession`` (False = the reference).
     ``session_ids`` / ``extended_session_ids`` [B, L0]: required by a "session" engine (see DecodeSession)."""
     qwen3 = engine.variant in ("qwen3", "qwen3_session")
-    if not use_cache and not reorder_cross_cache and not qwen3:
+    moe = engine.variant == "qwen3moe"          # (no behaviour levels either: no actions, no cross cache)
+    if not use_cache and not reorder_cross_cache and not (qwen3 or moe):
         raise ValueError("use_cache=False re-computes every position for its own beam: it can only reproduce "
                          "reorder_cross_cache=True (the shipped reference's un-reordered cross cache needs the cache)")
-    cls = Qwen3DecodeSession if qwen3 else DecodeSession
+    cls = Qwen3DecodeSession if qwen3 else (Qwen3MoeDecodeSession if moe else DecodeSession)
+    if moe:
+        _check_moe_generation(engine, input_ids.shape[1], max_new_tokens)
     dev = engine.device
     B, L0 = input_ids.shape
     V = engine.cfg.vocab_size
@@ -557,7 +599,7 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     N = B * nb
     ids0 = input_ids.to(dev, torch.int64)
     am0 = attention_mask.to(dev, torch.int64)
-    act0 = actions.to(dev, torch.int64) if not qwen3 else None
+    act0 = actions.to(dev, torch.int64) if not (qwen3 or moe) else None
     sess0 = _session_kw(engine, session_ids, extended_session_ids)
     seqs = ids0[:, None, :].expand(B, nb, L0).contiguous()
     run_scores = torch.zeros(B, nb, device=dev)
@@ -574,6 +616,8 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
         session = None
     elif qwen3:
         session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens, **sess0)
+    elif moe:
+        session = Qwen3MoeDecodeSession(engine, ids0, am0, nb, max_new_tokens)
     else:
         session = DecodeSession(engine, ids0, am0, act0, nb, max_new_tokens, reorder_cross_cache=reorder_cross_cache, **sess0)
     last_tok = None

@@ -79,6 +79,7 @@ class ParamLayout(_FlatLayout):
     """
 
     VERSION = 2          # 1 (rounds 1-3): the experts' gate / up / down weights of a layer stacked per kind
+    FFN_NORM = "post_cross_attention_layernorm.weight"        # (the norm in front of the FFN; Qwen3Moe names it differently)
 
     def __init__(self, cfg: Qwen3MultiConfig, version: int = 2):
         H, dh = cfg.hidden_size, cfg.head_dim
@@ -122,7 +123,7 @@ class ParamLayout(_FlatLayout):
             nodecay.append((lp + "input_layernorm.weight", (H,)))
             if cross:
                 nodecay.append((lp + "post_self_attention_layernorm.weight", (H,)))
-            nodecay.append((lp + "post_cross_attention_layernorm.weight", (H,)))
+            nodecay.append((lp + self.FFN_NORM, (H,)))
         nodecay.append(("model.norm.weight", (H,)))
         super().__init__(decay, nodecay)
 
@@ -168,7 +169,7 @@ class _LayerW:
         self.cross_attn = attn(lp + "cross_attn.") if self.cross else None
         self.ln1 = v[lp + "input_layernorm.weight"]
         self.ln2 = v[lp + "post_self_attention_layernorm.weight"] if self.cross else None
-        self.ln3 = v[lp + "post_cross_attention_layernorm.weight"]
+        self.ln3 = v[lp + layout.FFN_NORM]
         # the FFN: ``ne`` experts (1 = the dense MLP of a layer outside sparse_layers_decoder), each with an input projection of
         # ``nI`` rows - gated: rows [e 2I, e 2I + I) = gate_proj of expert e, [e 2I + I, (e + 1) 2I) = its up_proj; PBATransformer:
         # rows [e I, (e + 1) I) = its wi - and an output projection of H rows (down_proj / wo)
@@ -401,6 +402,9 @@ class Engine:
         if cls is Engine and variant in ("qwen3", "qwen3_session"):
             from .engine_qwen3 import Qwen3Engine, Qwen3SessionEngine
             cls = Qwen3Engine if variant == "qwen3" else Qwen3SessionEngine
+        elif cls is Engine and variant == "qwen3moe":       # Qwen3Moe (gamer_amd/engine_qwen3moe.py)
+            from .engine_qwen3moe import Qwen3MoeEngine
+            cls = Qwen3MoeEngine
         return super().__new__(cls)
 
     def __init__(self, cfg: Qwen3MultiConfig, device="cuda", temperature: float = 1.0, variant: str = "multi",
@@ -434,8 +438,8 @@ class Engine:
         cfg.validate()
         matmul = _matmul_arg(dtype, matmul)
         _check_split_dtype(dtype, matmul)
-        if variant not in ("multi", "session"):
-            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3 or qwen3_session)")
+        if variant not in self._VARIANTS:
+            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3, qwen3_session or qwen3moe)")
         _check_dtype(dtype)
         self.key_spans = variant == "session"
         self._init_core(cfg, device, temperature, variant, dtype, matmul, share_buffers_of, deterministic)
@@ -457,6 +461,11 @@ class Engine:
         # Moe_behavior_only: the router's position table [1, 2, 2, ...] (pad / eos 0) over gamer_router_fwd's [1, 2, 3, ...]
         self.position_table = (torch.tensor([0] + cfg.position_experts(), dtype=torch.int32, device=self.device)
                                if cfg.Moe_behavior_only else None)
+
+    # the variants this class runs (Engine: Qwen3Multi and Qwen3SessionMulti)
+    _VARIANTS = ("multi", "session")
+    # whether a training sequence must be a whole number of items (the router kernel of Qwen3Multi assumes it)
+    _item_aligned = True
 
     # whether the model's self attention takes per-query key spans (session-wise masks): the kernel forms that take them
     # decide whether the workspace needs the dS-spill scratch (``workspace``)
@@ -645,7 +654,7 @@ class Engine:
     def forward(self, input_ids, attention_mask=None, actions=None, labels=None, num_items_in_batch=None,
                 train: bool = False, dropout: Optional[bool] = None, act_zero_col: Optional[int] = None,
                 uniform_len: int = 0, kv_sink=None, kv_dest=None, session_ids=None, extended_session_ids=None,
-                last_row_logits: bool = False, hidden_sink: Optional[list] = None):
+                last_row_logits: bool = False, hidden_sink: Optional[list] = None, rope_from_mask: bool = False):
         """Returns (loss or None, logits view [B,S,V]).  With labels the logits are divided by the
         temperature in place, as the reference does (model.py:913).  The view aliases a workspace
         buffer: backward() overwrites it with d(logits), the next forward() with new logits.  ``train`` keeps every activation
@@ -666,14 +675,17 @@ class Engine:
 
         ``hidden_sink``: a list that receives copies [B, S, H] of the residual stream at the entry of every decoder layer and of
         the final norm's output - HF's ``output_hidden_states`` tuple (model.py:822-873).  fp32 in both dtypes (the residual
-        stream is kept in fp32), except the last entry, which has the activation dtype."""
+        stream is kept in fp32), except the last entry, which has the activation dtype.
+
+        ``rope_from_mask`` (evaluation, models without behaviour levels only - Qwen3Moe): RoPE positions
+        ``cumsum(attention_mask) - 1`` per row, as transformers' generate() gives a left-padded prompt."""
         cfg = self.cfg
         B, S = input_ids.shape
-        if train and S % cfg.num_positions != 0:
+        if train and self._item_aligned and S % cfg.num_positions != 0:
             raise ValueError(f"sequence length {S} is not a multiple of num_positions={cfg.num_positions} "
                              "(the router assumes item-aligned sequences, router.py:78-81)")
-        if train and (act_zero_col is not None or uniform_len not in (0, S)):
-            raise ValueError("act_zero_col / uniform_len are evaluation-only options")
+        if train and (act_zero_col is not None or uniform_len not in (0, S) or rope_from_mask):
+            raise ValueError("act_zero_col / uniform_len / rope_from_mask are evaluation-only options")
         c = self._prologue(input_ids, attention_mask, labels, train, dropout, cfg.dropout_rate, kv_dest, hidden_sink,
                            last_row_logits, uniform_len,
                            eval_only="last_row_logits is an evaluation-only option" if last_row_logits else None,
@@ -682,18 +694,9 @@ class Engine:
         ws, ids, am, bf16 = c.ws, c.ids, c.am, c.bf16
         T, H, nq, nkv, I, E = c.T, c.H, c.nq, c.nkv, c.I, cfg.num_experts
         NQ, NKV, QKV, eps, scale, cos, sin, p_res = c.NQ, c.NKV, c.QKV, c.eps, c.scale, c.cos, c.sin, c.p_res
-        act = actions.to(self.device, torch.int64).contiguous() if actions is not None else None
         r = ws.router
         r["bad_token"].zero_()
-        ops.router_fwd(ids, am, act, self.lut, cfg.num_positions, cfg.pad_token_id, cfg.eos_token_id, r)
-        if self.position_table is not None:
-            ops.router_position_table(r["expert"], self.position_table)
-        if act_zero_col is None and S % cfg.num_positions == 1:
-            # the reference's router counts (S + 3) // 5 items (router.py:160-163), so a trailing behaviour token
-            # - an evaluation prompt - gets action index 0
-            act_zero_col = S - 1
-        if act_zero_col is not None:
-            r["act_idx"][:, act_zero_col] = 0
+        pos_ids = self._route(c, actions, act_zero_col, rope_from_mask)
         NB1 = cfg.num_behavior + 1
         if self.split_inject:
             # rows sorted by (expert, behaviour): group g = expert * NB1 + behaviour; the experts' segments are every NB1-th offset
@@ -714,7 +717,7 @@ class Engine:
                 self._amax.register_transposed(Wl.down, Wl.ne, H, I)
                 if Wl.cross:
                     self._amax.register_transposed(Wl.cross_attn["o"], 1, H, NQ)
-        span_self = span_cross = pos_ids = None
+        span_self = span_cross = None
         if self.variant == "session":
             # Qwen3SessionMulti/model.py:784-806: both masks are rebuilt from session_ids on every forward
             if session_ids is None:
@@ -855,6 +858,25 @@ class Engine:
                      p_drop=p_res, seed=self._seed(l, 5), **grp)
         # ---- final norm, tied head, temperature CE (model.py:869,1001,904-922) ----
         return self._head(c, x_last if last_row_logits else None, num_items_in_batch, hidden_sink)
+
+    def _route(self, c, actions, act_zero_col, rope_from_mask: bool):
+        """The router's outputs into ``ws.router`` (expert / behaviour / action indices, self and cross masks); returns the
+        pass's RoPE positions (None: 0..S-1).  Qwen3Multi: gamer_router_fwd, its position table, and the action index of a
+        trailing behaviour token."""
+        if rope_from_mask:
+            raise ValueError("rope_from_mask is an option of the models without behaviour levels")
+        cfg, r, S = self.cfg, c.ws.router, c.S
+        act = actions.to(self.device, torch.int64).contiguous() if actions is not None else None
+        ops.router_fwd(c.ids, c.am, act, self.lut, cfg.num_positions, cfg.pad_token_id, cfg.eos_token_id, r)
+        if self.position_table is not None:
+            ops.router_position_table(r["expert"], self.position_table)
+        if act_zero_col is None and S % cfg.num_positions == 1:
+            # the reference's router counts (S + 3) // 5 items (router.py:160-163), so a trailing behaviour token
+            # - an evaluation prompt - gets action index 0
+            act_zero_col = S - 1
+        if act_zero_col is not None:
+            r["act_idx"][:, act_zero_col] = 0
+        return None
 
     def _shipped_ffn_layer(self, W) -> bool:
         """Whether layer W's FFN has the shipped form the fused paths are built for: SwiGLU experts, one per position."""

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .config import Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig
+from .config import Qwen3MoeConfig, Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig
 from .engine import Engine
 
 
@@ -456,3 +456,23 @@ class Qwen3SessionWithTemperature(Qwen3WithTemperature):
     VARIANT = "qwen3_session"
     CONFIG_CLASS = Qwen3SessionConfig
     USES_SESSIONS = True
+
+
+class Qwen3MoeWithTemperature(Qwen3WithTemperature):
+    """ref:SeqRec/models/generative/Qwen3Moe/model.py - Qwen3Multi's position-routed experts without the behaviour-level cross
+    attention, with the temperature loss (``--backbone Qwen3Moe``, train_MB_decoder.py:317-364) - on the HIP engine
+    (``Engine(variant="qwen3moe")``, gamer_amd/engine_qwen3moe.py).  The surface of the other ``*WithTemperature`` classes:
+    ``set_hyper``, the reference's state-dict names, ``from_pretrained`` / ``save_pretrained``, the autograd forward, bf16
+    autocast, ``fused_optimizer``, ``enable_dp_overlap`` and ``generate`` (no ``actions``: left-padded prompts, RoPE positions
+    from the attention mask).  ``actions`` and session ids are accepted and ignored.  As the reference's forward (model.py:
+    583-591) the output carries ``aux_loss = 0`` (the loss gains ``router_aux_loss_coef * 0``) and one
+    ``(tensor([0]),)`` router entry per layer in ``router_logits``."""
+    VARIANT = "qwen3moe"
+    CONFIG_CLASS = Qwen3MoeConfig
+
+    def forward(self, *args, output_router_logits=True, **kwargs):
+        out = super().forward(*args, **kwargs)
+        if output_router_logits:
+            out["aux_loss"] = 0
+            out["router_logits"] = tuple((torch.zeros(1, dtype=torch.int64),) for _ in range(self._cfg.num_hidden_layers))
+        return out

@@ -111,6 +111,27 @@ def causal_prep(attn_mask, B, S, kl_self, empty_self, tile_empty_self, pos_ids=N
          ptr(next_pos), stream_ptr())
 
 
+def moe_router_prep(ids, attn_mask, behavior_lut, position_table, num_positions, n_items, use_behavior_token, pad_id,
+                    eos_id, out: dict, pos_ids=None, next_pos=None):
+    """Qwen3Moe's router outputs and causal + key-padding mask in one launch (gamer_moe_router_prep).  ``out``: expert,
+    beh_idx, kl_self, empty_self, tile_empty_self, bad_token (incremented, not cleared).  ``position_table``: int32
+    [num_positions] on the device or None (position p -> expert p + 1).  ``pos_ids`` / ``next_pos``: generate()'s per-row
+    RoPE positions of a left-padded prompt (see causal_prep), or None."""
+    B, S = ids.shape
+    _chk(ids, torch.int64, "input_ids")
+    if attn_mask is not None:
+        _chk(attn_mask, torch.int64, "attention_mask")
+    if position_table is not None:
+        _chk(position_table, torch.int32, "position_table")
+        if position_table.numel() != num_positions:
+            raise ValueError(f"position_table has {position_table.numel()} entries, num_positions is {num_positions}")
+    call("gamer_moe_router_prep", ptr(ids), ptr(attn_mask), ptr(behavior_lut),
+         behavior_lut.numel() if behavior_lut is not None else 0, ptr(position_table), B, S, num_positions, n_items,
+         1 if use_behavior_token else 0, pad_id, eos_id, ptr(out["expert"]), ptr(out["beh_idx"]), ptr(out["kl_self"]),
+         ptr(out["empty_self"]), ptr(out["tile_empty_self"]), ptr(pos_ids), ptr(next_pos), ptr(out["bad_token"]),
+         stream_ptr())
+
+
 def session_prep(session_ids, extended_session_ids, attn_mask, num_positions, n_rope_positions, out: dict):
     """Qwen3Session's self mask as per-query key spans plus its RoPE positions, without a router (gamer_session_prep).
     ``out``: kl_self, span_self, pos_ids, empty_self, tile_empty_self, violations (incremented, not cleared)."""

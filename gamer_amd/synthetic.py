@@ -283,3 +283,36 @@ def write_smb_dataset(root: str, name: str, n_users: int = 40, n_items: int = 60
         with open(os.path.join(d, name + suffix), "w") as f:
             json.dump(obj, f)
     return d
+
+
+def write_mb_dataset(root: str, name: str, n_users: int = 30, n_items: int = 50, codebook: int = 16,
+                     behavior_level: Optional[Dict[str, int]] = None, min_len: int = 4, max_len: int = 14,
+                     seed: int = 0) -> str:
+    """Write a small multi-behaviour dataset in the reference's MB ON-DISK format (ref:SeqRec/datasets/MB_dataset.py:56-74):
+    ``<root>/<name>/<name>.MB.inter.json`` (user -> item ids), ``.MB.behavior.json`` (user -> behaviour names),
+    ``.behavior_level.json`` and ``.index.json`` (item -> 4 semantic-ID tokens).  Every user has min_len..max_len
+    interactions (at least 4: training uses the interactions before the last two, and needs two of them); some items repeat
+    at other behaviours, which ``filter_target`` acts on.  Returns the dataset directory."""
+    import json
+    import os
+    import random
+    rng = random.Random(seed)
+    if behavior_level is None:
+        behavior_level = {"click": 0, "cart": 1, "buy": 2}
+    names = list(behavior_level)
+    d = os.path.join(root, name)
+    os.makedirs(d, exist_ok=True)
+    index = {str(i): [f"<{c}_{rng.randrange(codebook)}>" for c in "abcd"] for i in range(n_items)}
+    inter, beh = {}, {}
+    for u in range(n_users):
+        n = rng.randint(min_len, max_len)
+        items, bs = [], []
+        for _ in range(n):
+            items.append(rng.choice(items) if items and rng.random() < 0.25 else rng.randrange(n_items))
+            bs.append(rng.choices(names, weights=[6, 2, 1][:len(names)] + [1] * max(0, len(names) - 3))[0])
+        inter[str(u)], beh[str(u)] = items, bs
+    for suffix, obj in ((".MB.inter.json", inter), (".MB.behavior.json", beh), (".behavior_level.json", behavior_level),
+                        (".index.json", index)):
+        with open(os.path.join(d, name + suffix), "w") as f:
+            json.dump(obj, f)
+    return d

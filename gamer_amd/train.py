@@ -23,6 +23,11 @@ vocabulary resized; ``Engine(variant="qwen3")``); its checkpoints load into ``ga
 sessions of mean 4 items); its checkpoints load into ``gamer_amd.modeling.Qwen3SessionWithTemperature``.
 ``--base_model DIR`` reads DIR/config.json for Qwen3Multi / Qwen3SessionMulti (train_SMB_decoder.py's argument): the FFN
 ablation configurations of the reference's configs (mlp_type, sparse_layers_decoder, Moe_behavior_only) train as written there.
+MB data (train_MB_decoder): ``--tasks`` one of mb, mb_explicit, mb_explicit_filter, mb_explicit_decoder[_N], mb_explicit_back
+reads ``<dataset>.MB.*.json`` (gamer_amd/mb_data.py) for ``--backbone Qwen3Moe`` (``Engine(variant="qwen3moe")``, config.json
+of Qwen3Moe or ``--base_model DIR`` plus train_MB_decoder.py:319-362's run-time fields; mb_explicit_back is refused, its
+behaviour token ends the item) or ``--backbone Qwen3``; checkpoints load into ``Qwen3MoeWithTemperature`` /
+``Qwen3WithTemperature``.
 """
 from __future__ import annotations
 
@@ -34,7 +39,8 @@ import time
 import torch
 
 from . import synthetic
-from .config import Qwen3Config, Qwen3SessionConfig, base_model_config, synthetic_config
+from .config import (Qwen3Config, Qwen3MoeConfig, Qwen3SessionConfig, apply_mb_runtime_fields, base_model_config,
+                     synthetic_config)
 from .dp import GradAllReducer, all_reduce_scalar_
 from .engine import Engine
 from .schedule import cosine_with_warmup, warmup_steps_for
@@ -60,7 +66,7 @@ def parse_args(argv=None):
     ap.add_argument("--index_file", type=str, default=".index.json")
     ap.add_argument("--tasks", type=str, default="smb_explicit_decoder_4")
     ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti", "Qwen3",
-                                                                                 "Qwen3Session"])
+                                                                                 "Qwen3Session", "Qwen3Moe"])
     ap.add_argument("--patience", type=int, default=10, help="early stopping: evaluations without a better eval_loss")
     ap.add_argument("--save_total_limit", type=int, default=2)
     ap.add_argument("--bf16", action="store_true",
@@ -120,7 +126,7 @@ def evaluate_loss(eng: Engine, samples, coll, batch_size: int, rank: int, world:
     tot = torch.zeros(2, dtype=torch.float64, device=eng.device)
     for idx in gdata.batches(len(samples), batch_size, rank=rank, world=world):
         b = coll.train(samples, idx)
-        loss, _ = eng.forward(b["input_ids"], b["attention_mask"], b["actions"], labels=b["labels"], train=False,
+        loss, _ = eng.forward(b["input_ids"], b["attention_mask"], b.get("actions"), labels=b["labels"], train=False,
                               session_ids=b.get("session_ids"), extended_session_ids=b.get("extended_session_ids"))
         tot[0] += loss.double() * len(idx)
         tot[1] += len(idx)
@@ -165,8 +171,8 @@ class Prefetcher:
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti"):
-        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti backbones")
+    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti", "Qwen3Moe"):
+        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti / Qwen3Moe backbones")
     if args.fp16:
         raise SystemExit("--fp16 is not built (the MI355X path has fp32 and bf16; the reference's recipe uses neither "
                          "loss scaling nor fp16 kernels of its own)")
@@ -177,10 +183,32 @@ def main(argv=None):
     if world > 1:
         import torch.distributed as dist
         dist.init_process_group("nccl", init_method="env://", device_id=torch.device("cuda", local_rank))
-    variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3", "Qwen3Session": "qwen3_session"}.get(args.backbone, "multi")
+    variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3", "Qwen3Session": "qwen3_session",
+               "Qwen3Moe": "qwen3moe"}.get(args.backbone, "multi")
+    mb = args.tasks.lower().startswith("mb")
     accum = args.gradient_accumulation_steps
     real = None
-    if args.data_path:
+    if args.data_path and mb:
+        # load_MB_datasets(..., tasks) of the MB decoder harness (loading_MB.py:9-135, train_MB_decoder.py:240-364): the
+        # Qwen3Moe model or the plain Qwen3 baseline
+        from . import mb_data
+        if variant not in ("qwen3moe", "qwen3"):
+            raise SystemExit("MB tasks train --backbone Qwen3Moe or Qwen3 (the decoder-only backbones of train_MB_decoder)")
+        ds = mb_data.MBData(args.data_path, args.dataset, args.tasks, args.index_file)
+        samples = ds.train_samples(args.max_his_len)
+        coll = mb_data.MBCollator(ds)
+        if variant == "qwen3moe":
+            cfg = mb_data.qwen3moe_config(ds, args.max_his_len, base_model=args.base_model or None)
+        else:
+            cfg = Qwen3Config(vocab_size=len(ds.tokens), pad_token_id=ds.tokens.pad_id)
+        per_step = args.per_device_batch_size * accum * world
+        args.steps_per_epoch = max(1, len(samples) // per_step)
+        real = dict(samples=samples, coll=coll, valid=ds.valid_samples(args.max_his_len),
+                    only_response=ds.only_train_response)
+        if rank == 0:
+            print(json.dumps({"dataset": args.dataset, "train_samples": len(samples), "vocab_size": cfg.vocab_size,
+                              "steps_per_epoch": args.steps_per_epoch}), flush=True)
+    elif args.data_path:
         # load_SMB_datasets(..., tasks) for the explicit-decoder task family (loading_SMB.py:39-55)
         from . import data as gdata
         task = args.tasks.lower()
@@ -215,6 +243,11 @@ def main(argv=None):
                               "steps_per_epoch": args.steps_per_epoch}), flush=True)
     elif variant == "qwen3":
         cfg = Qwen3Config(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID)
+    elif variant == "qwen3moe":
+        # synthetic batches (behaviour token + 4 semantic tokens per item) on config.json's architecture
+        cfg = Qwen3MoeConfig.from_pretrained(args.base_model) if args.base_model else Qwen3MoeConfig()
+        cfg.vocab_size, cfg.pad_token_id = synthetic.vocab_size(256, 3), synthetic.PAD_ID
+        apply_mb_runtime_fields(cfg, 3, synthetic.behavior_maps(256, 3), True, synthetic.TOKENS_PER_ITEM, args.max_his_len)
     elif variant == "qwen3_session":
         cfg = Qwen3SessionConfig(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID,
                                  num_positions=synthetic.TOKENS_PER_ITEM, model_max_length=1024)

@@ -121,6 +121,28 @@ int gamer_session_prep(const int64_t* session_ids, const int64_t* extended_sessi
 int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t* kl_self, int32_t* empty_self,
                       int32_t* tile_empty_self, int32_t* pos_ids, int32_t* next_pos, void* stream);
 
+/* Router + causal mask of the Qwen3Moe model (ref:SeqRec/models/generative/Qwen3Moe/router.py, model.py:310-460): what
+ * gamer_router_fwd + gamer_causal_prep give Qwen3Multi and the Qwen3 baseline, for a model without actions or cross attention,
+ * in one launch.  Routing as the reference's router with cache_position = arange(S):
+ *   ids int64 [B,S]; attn_mask int64 [B,S] (may be NULL = all ones)
+ *   behavior_lut int32 [vocab] (token -> behaviour index or -1; may be NULL when use_behavior_token == 0)
+ *   position_table int32 [num_positions] on the device (may be NULL): the expert of each position inside an item; NULL = p + 1
+ *           (the shipped table; also use_behavior_token = 0).  Moe_behavior_only: [1, 2, .., 2] with a behaviour token,
+ *           [1, .., 1] without (router.py:29-45)
+ *   n_items: the router's item count (config.n_positions); position n_items * num_positions is the table's eos slot (expert 0),
+ *           S > n_items * num_positions + 1 is refused (the reference indexes past its table there)
+ *   expert int32 [B,S]: table entry of the token's position, 0 at pad / eos and in the eos slot
+ *   beh_idx int32 [B,S]: use_behavior_token: behaviour index + 1 of the token's item (its first token), 0 on that token, at pad
+ *           / eos and in the eos slot; 0 everywhere without behaviour tokens
+ *   kl_self, empty_self, tile_empty_self, pos_ids (may be NULL), next_pos (may be NULL): as gamer_causal_prep's
+ *   bad_token int32 [1]: incremented by the number of non-special item starts outside behavior_maps (use_behavior_token only)
+ * No host synchronisation (graph-capture safe).  S <= 8192.  Additive in ABI 9.                                           */
+int gamer_moe_router_prep(const int64_t* ids, const int64_t* attn_mask, const int32_t* behavior_lut, int vocab,
+                          const int32_t* position_table, int B, int S, int num_positions, int n_items,
+                          int use_behavior_token, int pad_id, int eos_id, int32_t* expert, int32_t* beh_idx,
+                          int32_t* kl_self, int32_t* empty_self, int32_t* tile_empty_self, int32_t* pos_ids,
+                          int32_t* next_pos, int32_t* bad_token, void* stream);
+
 /* Expert token lists for the position-routed FFN (replaces the boolean-mask gather/scatter loop of
  * MyQwen3SparseMLP.forward, ref:SeqRec/models/generative/Qwen3Moe/FFN.py:63-68, and its 6 host
  * syncs per layer).  Deterministic order: expert-major, then token order.
