@@ -171,6 +171,15 @@ _SIGNATURES = {
     "gamer_kv_append": [P, I, P, I, P, P, I, I, I, I, I, P],
     "gamer_attn_decode": [P, I, P, I, P, I, P, P, P, I, I, I, I, P, I, I, I, I, I, F, P, P],
     "gamer_attn_decode_split": [P, I, P, I, P, I, P, P, P, I, I, I, I, P, I, I, I, I, I, F, P, P, P, P],
+    "gamer_catalog_ws_bytes": [I, I, I, I],
+    "gamer_catalog_ce_fwd": [P, L, P, I, I, P, I, I, P, P, P, P, P, L, P],
+    "gamer_catalog_ce_bwd": [P, L, P, I, I, P, I, I, P, P, P, F, P, P, L, P, L, P],
+    "gamer_catalog_topk": [P, L, P, I, I, P, I, I, I, I, I, P, P, P, L, P],
+    "gamer_embedding_bwd_large_ws_bytes": [I, I, I],
+    "gamer_embedding_bwd_large": [P, P, I, I, I, I, P, P, L, P],
+    "gamer_position_bwd_ws_floats": [I, I, I],
+    "gamer_position_bwd": [P, I, I, I, P, P, L, P],
+    "gamer_seq_embed_ln_fwd": [P, P, I, P, I, I, I, P, P, F, F, U, P, P, P, P, P],
 }
 
 
@@ -209,6 +218,8 @@ def load(build_if_missing: bool = False) -> C.CDLL:
         fn.argtypes = args
     lib.gamer_embedding_bwd_ordered_ws_bytes.restype = c_int64      # (a size, not an error code: call it on the library object)
     lib.gamer_segment_colsum_ws_floats.restype = c_int64
+    for name in ("gamer_catalog_ws_bytes", "gamer_embedding_bwd_large_ws_bytes", "gamer_position_bwd_ws_floats"):
+        getattr(lib, name).restype = c_int64
     _lib = lib
     return lib
 

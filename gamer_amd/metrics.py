@@ -63,3 +63,35 @@ def get_metrics_results(topk: List[List[int]], metrics: Sequence[str],
         else:
             raise NotImplementedError(m)
     return res
+
+
+def topk_rank_metrics(top: "np.ndarray", targets: list, metrics: list) -> dict:
+    """Per-sample values of ``hit@k`` / ``recall@k`` / ``ndcg@k`` (SMBRec.Trainer.evaluate, ref:SeqRec/trainers/SMBRec.py)
+    from the first K >= max(k) columns of each row's full ranking (``top`` [N, K]).  As the reference: ``set(targets)``,
+    recall the mean over the targets, idcg over min(len(targets), k); a target counts only at a rank below k, so K columns
+    give the same numbers as the full argsort."""
+    import numpy as np
+    out = {m: [] for m in metrics}
+    for m in metrics:
+        name, k = m.split("@")
+        k = int(k)
+        if k > top.shape[1]:
+            raise ValueError(f"{m}: needs the first {k} ranks, got {top.shape[1]}")
+        for ranks, tg in zip(top, targets):
+            tg = list(set(tg))
+            head = ranks[:k]
+            if name == "hit":
+                out[m].append(float(np.any(np.isin(tg, head))))
+            elif name == "recall":
+                out[m].append(np.mean(np.isin(tg, head).astype(float)))
+            elif name == "ndcg":
+                dcg = 0.0
+                for t in tg:
+                    pos = np.where(head == t)[0]
+                    if len(pos):
+                        dcg += 1.0 / np.log2(pos[0] + 2)
+                idcg = sum(1.0 / np.log2(i + 2) for i in range(min(len(tg), k)))
+                out[m].append(dcg / idcg if idcg > 0 else 0.0)
+            else:
+                raise ValueError(f"Unsupported metric: {m}")
+    return out

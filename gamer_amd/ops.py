@@ -1275,3 +1275,121 @@ def attn_dense_bwd(q, k, v, mask, B, S, H, dh, scale, p_drop, seed, o, d_o, lse,
     call("gamer_attn_dense_bwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(m), st, B, S, H, dh,
          scale, p_drop, seed, ptr(o), ptr(d_o), o.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0),
          ptr(dv), dv.stride(0), stream_ptr())
+
+
+# ---- catalogue-wide head of the discriminative baselines (csrc/catalog.hip) --------------------------------------------------
+_CAT_WS = {}
+
+
+def _ws(key, device, nbytes):
+    """a cached uint8 device workspace of at least nbytes (one per (key, device))"""
+    ws = _CAT_WS.get((key, device))
+    if ws is None or ws.numel() < nbytes:
+        _CAT_WS[(key, device)] = None
+        ws = _CAT_WS[(key, device)] = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _dense(t, dtype, name):
+    """a contiguous device tensor of dtype (the kernels read flat rows)"""
+    _chk(t, dtype, name)
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+    return t
+
+
+def _rows(h, row_idx):
+    """(row-strided 2-d view of h, index pointer, idx64, R)"""
+    _chk(h, torch.float32, "h")
+    h2 = h.reshape(-1, h.shape[-1])
+    if h2.stride(1) != 1:
+        raise RuntimeError("catalogue head: h rows must be contiguous")
+    if row_idx is None:
+        return h2, None, 0, h2.shape[0]
+    if row_idx.dtype not in (torch.int32, torch.int64) or not row_idx.is_contiguous():
+        raise RuntimeError("catalogue head: row_idx must be a contiguous int32 / int64 tensor")
+    return h2, row_idx, 1 if row_idx.dtype == torch.int64 else 0, row_idx.numel()
+
+
+def catalog_ce_fwd(h, row_idx, E, target, lse, loss, bad):
+    """lse [R], loss (0-d) = mean CE of the rows h[row_idx] against target over the whole table E (gamer_catalog_ce_fwd)."""
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
+    _dense(loss, torch.float32, "loss"), _dense(bad, torch.int32, "bad")
+    if target.numel() != R or lse.numel() != R:
+        raise RuntimeError(f"catalog_ce_fwd: target / lse must hold R = {R} values")
+    V, H = E.shape
+    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
+    ws = _ws("ce", h.device, n)
+    call("gamer_catalog_ce_fwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(target), ptr(lse), ptr(loss), ptr(bad),
+         ptr(ws), ws.numel(), stream_ptr())
+
+
+def catalog_ce_bwd(h, row_idx, E, target, lse, dloss, scale, dE=None, dh=None):
+    """dE += G^T h, dh rows (at row_idx of dh's row view) <- G E, G = (softmax - onehot) * dloss * scale (gamer_catalog_ce_bwd)."""
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
+    if dloss is not None:
+        _dense(dloss, torch.float32, "dloss")
+    if dE is not None and (_dense(dE, torch.float32, "dE").shape != E.shape):
+        raise RuntimeError("catalog_ce_bwd: dE must have E's shape")
+    V, H = E.shape
+    if dh is not None:
+        _dense(dh, torch.float32, "dh")                 # (a reshape of a strided dh would be a copy: the writes would be lost)
+        if dh.shape[-1] != H or (row_idx is None and dh.numel() // H < R):
+            raise RuntimeError("catalog_ce_bwd: dh must be rows of H values covering the gathered rows")
+    dh2 = dh.reshape(-1, dh.shape[-1]) if dh is not None else None
+    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
+    ws = _ws("ce", h.device, n)
+    call("gamer_catalog_ce_bwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(target), ptr(lse), ptr(dloss),
+         float(scale), ptr(dE), ptr(dh2), dh2.stride(0) if dh2 is not None else 0, ptr(ws), ws.numel(), stream_ptr())
+
+
+def catalog_topk(h, E, k, start=0, end=None, row_idx=None):
+    """(indices int64 [R, k], scores [R, k]): the k best items of [start, end) per row, ties to the lower index, -1 past the range."""
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E")
+    V, H = E.shape
+    end = V if end is None else int(end)
+    n = int(_lib.load().gamer_catalog_ws_bytes(R, max(end - start, 1), H, k))
+    ws = _ws("topk", h.device, n)
+    out_i = torch.empty(R, k, dtype=torch.int64, device=h.device)
+    out_s = torch.empty(R, k, dtype=torch.float32, device=h.device)
+    call("gamer_catalog_topk", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, int(start), end, int(k), ptr(out_i), ptr(out_s),
+         ptr(ws), ws.numel(), stream_ptr())
+    return out_i, out_s
+
+
+def embedding_bwd_large(ids, dx, pad_id, dW):
+    """dW[id] += dx rows in token order, pad_id skipped, any table size (gamer_embedding_bwd_large)."""
+    _dense(ids, torch.int64, "ids"), _dense(dx, torch.float32, "dx"), _dense(dW, torch.float32, "dW")
+    T = ids.numel()
+    V, H = dW.shape
+    if dx.numel() != T * H:
+        raise RuntimeError("embedding_bwd_large: dx must hold one row of H values per id")
+    ws = _ws("emb_large", dx.device, int(_lib.load().gamer_embedding_bwd_large_ws_bytes(V, T, H)))
+    call("gamer_embedding_bwd_large", ptr(ids), ptr(dx), V, T, H, pad_id, ptr(dW), ptr(ws), ws.numel(), stream_ptr())
+
+
+def position_bwd(dx, dP):
+    """dP [S, H] += dx [B, S, H] summed over the batch in order (gamer_position_bwd)."""
+    _dense(dx, torch.float32, "dx"), _dense(dP, torch.float32, "dP")
+    B, S, H = dx.shape
+    if dP.shape != (S, H):
+        raise RuntimeError(f"position_bwd: dP must be [{S}, {H}]")
+    nf = int(_lib.load().gamer_position_bwd_ws_floats(B, S, H))
+    ws = _ws("pos", dx.device, 4 * nf)
+    call("gamer_position_bwd", ptr(dx), B, S, H, ptr(dP), ptr(ws), nf, stream_ptr())
+
+
+def seq_embed_ln_fwd(ids, E, P, w, b, eps, p, seed, v, y, mean, rstd):
+    """y = dropout(LayerNorm(E[ids] + P[s])) for ids [B, S] (gamer_seq_embed_ln_fwd); v / mean / rstd for the backward."""
+    _dense(ids, torch.int64, "ids")
+    for t, n in ((E, "E"), (P, "P"), (w, "w"), (b, "b"), (v, "v"), (y, "y"), (mean, "mean"), (rstd, "rstd")):
+        _dense(t, torch.float32, n)
+    B, S = ids.shape
+    V, H = E.shape
+    if P.shape[0] < S or P.shape[1] != H:
+        raise RuntimeError(f"seq_embed_ln_fwd: the position table must have >= {S} rows of {H}")
+    call("gamer_seq_embed_ln_fwd", ptr(ids), ptr(E), V, ptr(P), B, S, H, ptr(w), ptr(b), float(eps), float(p), int(seed), ptr(v), ptr(y),
+         ptr(mean), ptr(rstd), stream_ptr())

@@ -1,0 +1,171 @@
+"""``python -m gamer_amd.train_rec``: train and test SASRec on session-wise multi-behaviour data (``train_SMB_rec``).
+
+Mirrors ``TrainSMBRec.invoke`` (ref:SeqRec/tasks/train_SMB_rec.py) and ``SMBRec.Trainer`` (ref:SeqRec/trainers/SMBRec.py):
+evaluate before training, then per epoch a shuffled pass over the training samples and an evaluation on the target
+behaviour's validation set; the best model by the last metric goes to ``best_model.pth`` (patience as the reference).  The
+step is AdamW (betas 0.9 / 0.999, eps 1e-8, decay on every parameter, no clipping) on ``gamer_adamw``.  Test: every
+behaviour of the test split plus the "Merged Behavior" entry weighted by the behaviours' sample counts, written to
+``result-{test_task}.json`` in the reference's layout.  Ranking uses ``SASRec.full_sort_topk`` with K = the largest k of
+``--metrics``.  Single device, no wandb.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+from . import ops, smb_dis_data
+from .metrics import topk_rank_metrics
+from .sasrec import SASRec, SASRecConfig
+
+DEFAULT_METRICS = "hit@1,hit@5,hit@10,recall@1,recall@5,recall@10,ndcg@5,ndcg@10"
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m gamer_amd.train_rec")
+    ap.add_argument("--backbone", default="SASRec")
+    ap.add_argument("--base_model", default="./config/dis-models/SASRec")
+    ap.add_argument("--data_path", default="./data")
+    ap.add_argument("--dataset", default="Retail_Beh")
+    ap.add_argument("--tasks", default="smb_dis")
+    ap.add_argument("--test_task", default="smb_dis")
+    ap.add_argument("--max_his_len", type=int, default=20)
+    ap.add_argument("--optim", default="adamw")
+    ap.add_argument("--epochs", type=int, default=200)
+    ap.add_argument("--learning_rate", type=float, default=5e-4)
+    ap.add_argument("--batch_size", type=int, default=256)
+    ap.add_argument("--weight_decay", type=float, default=0.01)
+    ap.add_argument("--patience", type=int, default=20)
+    ap.add_argument("--metrics", default=DEFAULT_METRICS)
+    ap.add_argument("--output_dir", default="./checkpoint/SMB-recommender")
+    ap.add_argument("--result_dir", default="./results")
+    ap.add_argument("--only_test", action="store_true")
+    ap.add_argument("--seed", type=int, default=42)
+    a = ap.parse_args(argv)
+    if a.backbone != "SASRec":
+        raise NotImplementedError(f"--backbone {a.backbone}: only SASRec runs on the HIP path")
+    if a.optim.lower() != "adamw":
+        raise NotImplementedError(f"--optim {a.optim}: only adamw (gamer_adamw) runs on the HIP path")
+    return a
+
+
+class AdamW:
+    """torch.optim.AdamW's update (decay on every parameter, no clipping) with gamer_adamw, one launch pair per tensor."""
+
+    def __init__(self, params, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8):
+        self.params = [p for p in params if p.requires_grad]
+        self.lr, self.wd, self.betas, self.eps, self.step_n = lr, weight_decay, betas, eps, 0
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.v = [torch.zeros_like(p) for p in self.params]
+        dev = self.params[0].device
+        self.partial = torch.empty(64, dtype=torch.float32, device=dev)
+        self.norm = torch.empty(1, dtype=torch.float32, device=dev)
+
+    def step(self):
+        self.step_n += 1
+        for p, m, v in zip(self.params, self.m, self.v):
+            if p.grad is None:          # (a parameter no loss reaches: torch's AdamW skips it too)
+                continue
+            g = p.grad.contiguous()
+            ops.sumsq(g, self.partial)
+            ops.adamw(p.data, g, m, v, p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_n, 0.0,
+                      1.0, self.partial, self.norm)
+
+
+def _to(batch, dev):
+    return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in batch.items()}
+
+
+def evaluate(model, data, batch_size, metrics, dev):
+    """mean of every metric over the samples of ``data`` (valid / test: lists of targets)"""
+    model.eval()
+    K = max(int(m.split("@")[1]) for m in metrics)
+    vals = {m: [] for m in metrics}
+    with torch.no_grad():
+        for i in range(0, len(data.samples), batch_size):
+            batch, targets = smb_dis_data.collate(data.samples[i:i + batch_size], test=True)
+            idx, _ = model.full_sort_topk(_to(batch, dev), K)
+            for m, v in topk_rank_metrics(idx.cpu().numpy(), targets, metrics).items():
+                vals[m].extend(v)
+    return {m: float(np.mean(v)) for m, v in vals.items()}
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    random.seed(a.seed)
+    np.random.seed(a.seed)
+    torch.manual_seed(a.seed)
+    dev = torch.device("cuda")
+    metrics = a.metrics.split(",")
+    os.makedirs(a.output_dir, exist_ok=True)
+    config = SASRecConfig.from_pretrained(a.base_model)
+    trains, valid = smb_dis_data.load_train_valid(a.data_path, a.dataset, a.max_his_len, a.tasks)
+    valid = valid.filter_by_behavior(valid.target_behavior)
+    first = trains[0]
+    model = SASRec(config, n_items=first.num_items, max_his_len=a.max_his_len).to(dev)
+    ckpt = os.path.join(a.output_dir, "best_model.pth")
+    if not a.only_test:
+        train_samples = [s for t in trains for s in t.samples]
+        opt = AdamW(model.parameters(), a.learning_rate, a.weight_decay)
+        g = torch.Generator().manual_seed(a.seed)
+        best = evaluate(model, valid, a.batch_size, metrics, dev)[metrics[-1]]
+        print(f"[train_rec] before training: {metrics[-1]} {best:.4f}", flush=True)
+        patience, saved = 0, False
+        for epoch in range(a.epochs):
+            model.train()
+            order = torch.randperm(len(train_samples), generator=g).tolist()
+            losses = []
+            for i in range(0, len(order), a.batch_size):
+                batch = _to(smb_dis_data.collate([train_samples[j] for j in order[i:i + a.batch_size]]), dev)
+                for p in model.parameters():
+                    p.grad = None
+                loss = model.calculate_loss(batch)
+                loss.backward()
+                opt.step()
+                losses.append(loss.detach())
+            loss = float(torch.stack(losses).mean())
+            res = evaluate(model, valid, a.batch_size, metrics, dev)
+            print(f"[train_rec] epoch {epoch + 1}/{a.epochs} loss {loss:.4f} " +
+                  " ".join(f"{m} {v:.4f}" for m, v in res.items()), flush=True)
+            if res[metrics[-1]] > best:
+                best, patience, saved = res[metrics[-1]], 0, True
+                torch.save(model.state_dict(), ckpt)
+            else:
+                patience += 1
+                if patience >= a.patience:
+                    print(f"[train_rec] early stopping on epoch {epoch + 1}", flush=True)
+                    break
+        if not saved:
+            # no epoch beat the evaluation before training: the reference's test step would fail on the missing file; the
+            # last model is tested instead
+            torch.save(model.state_dict(), ckpt)
+    test = smb_dis_data.load_test(a.data_path, a.dataset, a.max_his_len, a.test_task)
+    model.load_state_dict(torch.load(ckpt, map_location="cpu"))
+    results, merged, total = [], {m: 0.0 for m in metrics}, 0
+    for b in first.behaviors:
+        part = test.filter_by_behavior(b)
+        r = evaluate(model, part, a.batch_size, metrics, dev) if len(part) else {m: float("nan") for m in metrics}
+        r["eval_type"] = f"Behavior {b}"
+        results.append(r)
+        for m in metrics:
+            merged[m] += r[m] * len(part) if len(part) else 0.0
+        total += len(part)
+    for m in metrics:
+        merged[m] /= total
+    merged["eval_type"] = "Merged Behavior"
+    results.append(merged)
+    os.makedirs(a.result_dir, exist_ok=True)
+    out = os.path.join(a.result_dir, f"result-{a.test_task}.json")
+    with open(out, "w") as f:
+        json.dump(results, f, indent=4)
+    print(f"[train_rec] results saved to {out}", flush=True)
+    return results
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

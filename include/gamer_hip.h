@@ -832,6 +832,42 @@ int gamer_attn_decode_split(const float* q, int ldq, const float* kp, int ldkp, 
                             const int32_t* uniform, int B, int nb, int L0, int nq, int nkv, float scale, float* o,
                             const uint32_t* amax_k, const uint32_t* amax_v, void* stream);
 
+/* (ABI 9) Catalogue-wide head of the discriminative baselines (csrc/catalog.hip; SASRec's CE loss and full-sort ranking,
+ * ref:SeqRec/modules/model_base/seq_model.py:67-122).  h rows r = 0..R-1 are h + row_idx[r] * ldh (row_idx int32 when idx64 == 0,
+ * int64 otherwise, NULL = r); E [V][H] row-major, H % 4 == 0, H <= 256, any R and V.  fp32 MFMA (v_mfma_f32_16x16x4_f32) score
+ * tiles, no [R][V] tensor in HBM, no float atomics (the same bits on every call).  Bounds: a training step is 8 R H V FLOP (forward
+ * 2, the backward's two recomputes 4, dE and dh 2 + 2) against the 157 TFLOP/s fp32 MFMA peak; DESIGN.md section 10c.
+ * ws: gamer_catalog_ws_bytes(R, V, H, 0) bytes for ce_fwd / ce_bwd, gamer_catalog_ws_bytes(R, end - start, H, K) for topk. */
+int64_t gamer_catalog_ws_bytes(int R, int V, int H, int K);
+/* lse[R] = logsumexp_v(h_r . E_v); *loss = mean_r (lse_r - h_r . E_target[r]) (nn.CrossEntropyLoss()); a target outside [0, V) adds 1
+ * to *bad (the host raises on it) and counts 0 in the mean. */
+int gamer_catalog_ce_fwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                         const int64_t* target, float* lse, float* loss, int* bad, void* ws, int64_t ws_bytes, void* stream);
+/* G = (softmax - onehot(target)) * dloss[0] * scale (dloss a device scalar or NULL = 1; scale = 1 / R for the mean), recomputed
+ * tile by tile: dE [V][H] += G^T h (accumulated: one workgroup per 64 items sweeps the rows in order), dh + row_idx[r] * lddh <- G E
+ * (written; per-chunk partials summed in chunk order; row indices distinct).  Either of dE / dh may be NULL. */
+int gamer_catalog_ce_bwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                         const int64_t* target, const float* lse, const float* dloss, float scale, float* dE, float* dh, int64_t lddh,
+                         void* ws, int64_t ws_bytes, void* stream);
+/* top K (1..64) of h_r . E_v over v in [start, end) per row: out_idx int64 [R][K] (absolute item indices), out_score [R][K]; score
+ * descending, lower index first on ties (a stable argsort of -scores); fewer than K items: index -1, score -inf. */
+int gamer_catalog_topk(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H, int start,
+                       int end, int K, int64_t* out_idx, float* out_score, void* ws, int64_t ws_bytes, void* stream);
+/* dW[id] += the dx rows of the tokens with that id, in token order, ids == pad_id (and outside [0, V)) skipped; any V: the tokens
+ * are grouped with integer atomics and put in token order (ranks from 64-token chunks), ids of more than 64 tokens are summed in
+ * 64-row pieces, then the pieces in order (no float atomics). */
+int64_t gamer_embedding_bwd_large_ws_bytes(int V, int T, int H);
+int gamer_embedding_bwd_large(const int64_t* ids, const float* dx, int V, int T, int H, int pad_id, float* dW, void* ws,
+                              int64_t ws_bytes, void* stream);
+/* dP [S][H] += sum over b of dx [B][S][H] (batch order) */
+int64_t gamer_position_bwd_ws_floats(int B, int S, int H);
+int gamer_position_bwd(const float* dx, int B, int S, int H, float* dP, float* ws, int64_t ws_floats, void* stream);
+/* input block: v = E[ids] + P[s] (P [S][H] broadcast over the batch), y = dropout(LayerNorm(v) * w + b) with the mask of
+ * gamer_residual_dropout_bwd(seed); v, mean, rstd [B*S] kept for gamer_layernorm_bwd.  H % 4 == 0, H <= 256. */
+int gamer_seq_embed_ln_fwd(const int64_t* ids, const float* E, int V, const float* P, int B, int S, int H, const float* w,
+                           const float* b, float eps, float p_drop, uint64_t seed, float* v, float* y, float* mean, float* rstd,
+                           void* stream);
+
 /* misc */
 int gamer_fill_f32(float* p, int64_t n, float value, void* stream);
 
