@@ -180,6 +180,9 @@ _SIGNATURES = {
     "gamer_position_bwd_ws_floats": [I, I, I],
     "gamer_position_bwd": [P, I, I, I, P, P, L, P],
     "gamer_seq_embed_ln_fwd": [P, P, I, P, I, I, I, P, P, F, F, U, P, P, P, P, P],
+    "gamer_gru_gates_floats": [I, I, I],
+    "gamer_gru_fwd": [P, P, P, I, I, I, P, P, P],
+    "gamer_gru_bwd": [P, P, P, P, P, I, I, I, P, P, P],
 }
 
 
@@ -218,7 +221,8 @@ def load(build_if_missing: bool = False) -> C.CDLL:
         fn.argtypes = args
     lib.gamer_embedding_bwd_ordered_ws_bytes.restype = c_int64      # (a size, not an error code: call it on the library object)
     lib.gamer_segment_colsum_ws_floats.restype = c_int64
-    for name in ("gamer_catalog_ws_bytes", "gamer_embedding_bwd_large_ws_bytes", "gamer_position_bwd_ws_floats"):
+    for name in ("gamer_catalog_ws_bytes", "gamer_embedding_bwd_large_ws_bytes", "gamer_position_bwd_ws_floats",
+                 "gamer_gru_gates_floats"):
         getattr(lib, name).restype = c_int64
     _lib = lib
     return lib

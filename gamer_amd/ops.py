@@ -1393,3 +1393,45 @@ def seq_embed_ln_fwd(ids, E, P, w, b, eps, p, seed, v, y, mean, rstd):
         raise RuntimeError(f"seq_embed_ln_fwd: the position table must have >= {S} rows of {H}")
     call("gamer_seq_embed_ln_fwd", ptr(ids), ptr(E), V, ptr(P), B, S, H, ptr(w), ptr(b), float(eps), float(p), int(seed), ptr(v), ptr(y),
          ptr(mean), ptr(rstd), stream_ptr())
+
+
+# ---- GRU recurrence of GRU4Rec (csrc/gru.hip) ----------------------------------------------------------------------------------
+def _gru_check(B, L, H, lens):
+    if not (B >= 1 and L >= 1 and 16 <= H <= 256 and H % 16 == 0):
+        raise RuntimeError(f"gru: B={B} L={L} H={H} (B, L >= 1; H % 16 == 0, 16 <= H <= 256)")
+    if lens is not None:
+        _dense(lens, torch.int64, "lens")
+        if lens.numel() != B:
+            raise RuntimeError(f"gru: lens must hold B = {B} values")
+    return ptr(lens) if lens is not None else None
+
+
+def gru_gates_floats(B, L, H):
+    return int(_lib.load().gamer_gru_gates_floats(B, L, H))
+
+
+def gru_fwd(gi, w_hh, h, gates=None, lens=None):
+    """h [B, L, H] = the GRU's h_t of every step from gi [B, L, 3H] = x W_ih^T (gamer_gru_fwd); gates [B, L, 4, H] (training)
+    keeps r, z, n and W_hn h_{t-1} for gru_bwd."""
+    _dense(gi, torch.float32, "gi"), _dense(w_hh, torch.float32, "w_hh"), _dense(h, torch.float32, "h")
+    B, L, H = h.shape
+    lp = _gru_check(B, L, H, lens)
+    if gi.shape != (B, L, 3 * H) or w_hh.shape != (3 * H, H):
+        raise RuntimeError(f"gru_fwd: gi must be [{B}, {L}, {3 * H}] and w_hh [{3 * H}, {H}]")
+    if gates is not None and (_dense(gates, torch.float32, "gates").numel() != gru_gates_floats(B, L, H)):
+        raise RuntimeError(f"gru_fwd: gates must hold {gru_gates_floats(B, L, H)} floats")
+    call("gamer_gru_fwd", ptr(gi), ptr(w_hh), lp, B, L, H, ptr(h), ptr(gates), stream_ptr())
+
+
+def gru_bwd(dy, h, gates, w_hh, dgi, dgh_next, lens=None):
+    """dgi, dgh_next [B, L, 3H] from the upstream gradient dy [B, L, H] of every h_t (gamer_gru_bwd): dW_ih = dgi^T x,
+    dW_hh = dgh_next^T h, dx = dgi W_ih."""
+    for t, n in ((dy, "dy"), (h, "h"), (gates, "gates"), (w_hh, "w_hh"), (dgi, "dgi"), (dgh_next, "dgh_next")):
+        _dense(t, torch.float32, n)
+    B, L, H = h.shape
+    lp = _gru_check(B, L, H, lens)
+    if dy.shape != h.shape or w_hh.shape != (3 * H, H) or dgi.shape != (B, L, 3 * H) or dgh_next.shape != (B, L, 3 * H):
+        raise RuntimeError(f"gru_bwd: dy [{B}, {L}, {H}], w_hh [{3 * H}, {H}], dgi / dgh_next [{B}, {L}, {3 * H}]")
+    if gates.numel() != gru_gates_floats(B, L, H):
+        raise RuntimeError(f"gru_bwd: gates must hold {gru_gates_floats(B, L, H)} floats")
+    call("gamer_gru_bwd", ptr(dy), ptr(h), ptr(gates), ptr(w_hh), lp, B, L, H, ptr(dgi), ptr(dgh_next), stream_ptr())

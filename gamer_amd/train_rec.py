@@ -1,12 +1,13 @@
-"""``python -m gamer_amd.train_rec``: train and test SASRec on session-wise multi-behaviour data (``train_SMB_rec``).
+"""``python -m gamer_amd.train_rec``: train and test SASRec or GRU4Rec on session-wise multi-behaviour data (``train_SMB_rec``).
 
 Mirrors ``TrainSMBRec.invoke`` (ref:SeqRec/tasks/train_SMB_rec.py) and ``SMBRec.Trainer`` (ref:SeqRec/trainers/SMBRec.py):
 evaluate before training, then per epoch a shuffled pass over the training samples and an evaluation on the target
 behaviour's validation set; the best model by the last metric goes to ``best_model.pth`` (patience as the reference).  The
 step is AdamW (betas 0.9 / 0.999, eps 1e-8, decay on every parameter, no clipping) on ``gamer_adamw``.  Test: every
 behaviour of the test split plus the "Merged Behavior" entry weighted by the behaviours' sample counts, written to
-``result-{test_task}.json`` in the reference's layout.  Ranking uses ``SASRec.full_sort_topk`` with K = the largest k of
-``--metrics``.  Single device, no wandb.
+``result-{test_task}.json`` in the reference's layout.  Ranking uses the model's ``full_sort_topk`` with K = the largest k of
+``--metrics``.  ``--base_model`` defaults to ``./config/dis-models/{backbone}``, as the reference's launcher sets it.  Single
+device, no wandb.
 """
 from __future__ import annotations
 
@@ -20,16 +21,18 @@ import numpy as np
 import torch
 
 from . import ops, smb_dis_data
+from .gru4rec import GRU4Rec, GRU4RecConfig
 from .metrics import topk_rank_metrics
 from .sasrec import SASRec, SASRecConfig
 
 DEFAULT_METRICS = "hit@1,hit@5,hit@10,recall@1,recall@5,recall@10,ndcg@5,ndcg@10"
+BACKBONES = {"SASRec": (SASRec, SASRecConfig), "GRU4Rec": (GRU4Rec, GRU4RecConfig)}
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m gamer_amd.train_rec")
     ap.add_argument("--backbone", default="SASRec")
-    ap.add_argument("--base_model", default="./config/dis-models/SASRec")
+    ap.add_argument("--base_model", default=None, help="default: ./config/dis-models/{backbone}")
     ap.add_argument("--data_path", default="./data")
     ap.add_argument("--dataset", default="Retail_Beh")
     ap.add_argument("--tasks", default="smb_dis")
@@ -47,8 +50,10 @@ def parse_args(argv=None):
     ap.add_argument("--only_test", action="store_true")
     ap.add_argument("--seed", type=int, default=42)
     a = ap.parse_args(argv)
-    if a.backbone != "SASRec":
-        raise NotImplementedError(f"--backbone {a.backbone}: only SASRec runs on the HIP path")
+    if a.backbone not in BACKBONES:
+        raise NotImplementedError(f"--backbone {a.backbone}: only {', '.join(BACKBONES)} run on the HIP path")
+    if a.base_model is None:
+        a.base_model = f"./config/dis-models/{a.backbone}"
     if a.optim.lower() != "adamw":
         raise NotImplementedError(f"--optim {a.optim}: only adamw (gamer_adamw) runs on the HIP path")
     return a
@@ -103,11 +108,12 @@ def main(argv=None):
     dev = torch.device("cuda")
     metrics = a.metrics.split(",")
     os.makedirs(a.output_dir, exist_ok=True)
-    config = SASRecConfig.from_pretrained(a.base_model)
+    model_cls, config_cls = BACKBONES[a.backbone]
+    config = config_cls.from_pretrained(a.base_model)
     trains, valid = smb_dis_data.load_train_valid(a.data_path, a.dataset, a.max_his_len, a.tasks)
     valid = valid.filter_by_behavior(valid.target_behavior)
     first = trains[0]
-    model = SASRec(config, n_items=first.num_items, max_his_len=a.max_his_len).to(dev)
+    model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len).to(dev)
     ckpt = os.path.join(a.output_dir, "best_model.pth")
     if not a.only_test:
         train_samples = [s for t in trains for s in t.samples]

@@ -868,6 +868,21 @@ int gamer_seq_embed_ln_fwd(const int64_t* ids, const float* E, int V, const floa
                            const float* b, float eps, float p_drop, uint64_t seed, float* v, float* y, float* mean, float* rstd,
                            void* stream);
 
+/* (ABI 9) GRU recurrence of GRU4Rec (csrc/gru.hip; nn.GRU(bias=False, batch_first=True), gate order r, z, n, h_{-1} = 0).
+ * One layer, all L steps in one launch each way; rows are independent (16-row blocks, no grid barrier), fp32 MFMA products, fp32
+ * expf / tanhf gates, no atomics (the same bits on every call).  Layouts, row-major: gi / dgi / dgh_next [B][L][3H] (r | z | n),
+ * h / dy [B][L][H], gates [B][L][4][H] (r, z, n, W_hn h_{t-1}), w_hh [3H][H].  16 <= H <= 256, H % 16 == 0, any B, L >= 1.
+ * lens (int64 [B], or NULL = L for every row): a 16-row block stops after its longest row and h is zero past it; the backward
+ * ignores dy at t >= lens[row].  Bound: DESIGN.md section 10d. */
+int64_t gamer_gru_gates_floats(int B, int L, int H);
+/* h = the h_t of every step, from gi = x W_ih^T; gates (B L 4 H floats, NULL in evaluation) keeps what the backward reads */
+int gamer_gru_fwd(const float* gi, const float* w_hh, const int64_t* lens, int B, int L, int H, float* h, float* gates,
+                  void* stream);
+/* dy: the upstream gradient of every h_t.  dgi = d(gi); dgh_next[b][t] = d(W_hh h_t) of step t + 1 (zero at t = L - 1), so
+ * dW_hh = dgh_next^T h and dW_ih = dgi^T x and dx = dgi W_ih are GEMMs over the B L rows. */
+int gamer_gru_bwd(const float* dy, const float* h, const float* gates, const float* w_hh, const int64_t* lens, int B, int L, int H,
+                  float* dgi, float* dgh_next, void* stream);
+
 /* misc */
 int gamer_fill_f32(float* p, int64_t n, float value, void* stream);
 
