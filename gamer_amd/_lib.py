@@ -175,6 +175,11 @@ _SIGNATURES = {
     "gamer_catalog_ce_fwd": [P, L, P, I, I, P, I, I, P, P, P, P, P, L, P],
     "gamer_catalog_ce_bwd": [P, L, P, I, I, P, I, I, P, P, P, F, P, P, L, P, L, P],
     "gamer_catalog_topk": [P, L, P, I, I, P, I, I, I, I, I, P, P, P, L, P],
+    "gamer_catalog_ce_bias_fwd": [P, L, P, I, I, P, I, I, P, P, P, P, P, P, L, P],
+    "gamer_catalog_ce_bias_bwd": [P, L, P, I, I, P, I, I, P, P, P, P, F, P, P, L, P, P, L, P],
+    "gamer_catalog_topk_bias": [P, L, P, I, I, P, I, I, P, I, I, I, P, P, P, L, P],
+    "gamer_cloze_mask_ws_bytes": [I, I],
+    "gamer_cloze_mask": [P, P, I, I, F, F, L, I, U, P, P, P, P, P, P, P, L, P],
     "gamer_embedding_bwd_large_ws_bytes": [I, I, I],
     "gamer_embedding_bwd_large": [P, P, I, I, I, I, P, P, L, P],
     "gamer_position_bwd_ws_floats": [I, I, I],
@@ -222,7 +227,7 @@ def load(build_if_missing: bool = False) -> C.CDLL:
     lib.gamer_embedding_bwd_ordered_ws_bytes.restype = c_int64      # (a size, not an error code: call it on the library object)
     lib.gamer_segment_colsum_ws_floats.restype = c_int64
     for name in ("gamer_catalog_ws_bytes", "gamer_embedding_bwd_large_ws_bytes", "gamer_position_bwd_ws_floats",
-                 "gamer_gru_gates_floats"):
+                 "gamer_gru_gates_floats", "gamer_cloze_mask_ws_bytes"):
         getattr(lib, name).restype = c_int64
     _lib = lib
     return lib

@@ -1,6 +1,8 @@
 // Catalogue-wide kernels of the discriminative baselines (SASRec: ref:SeqRec/modules/model_base/seq_model.py:67-122).
 //   gamer_catalog_ce_fwd / _bwd   nn.CrossEntropyLoss over h @ E^T ([R, V] scores) without writing the scores to HBM
 //   gamer_catalog_topk            top K of h @ E[start:end]^T per row (full_sort_predict + argsort, first K columns)
+//   gamer_catalog_*_bias          the three above with a per-item bias added to every score (BERT4Rec's head) and its gradient
+//   gamer_cloze_mask              BERT4Rec's cloze masking and the row-major compaction of the masked positions
 //   gamer_embedding_bwd_large     item-embedding gradient without float atomics, tables of up to 2^31 - 1 rows
 //   gamer_position_bwd            position-embedding gradient (per-position sums over the batch)
 //   gamer_seq_embed_ln_fwd        dropout(LayerNorm(E[ids] + P[s])), the model's input block
@@ -84,11 +86,27 @@ __device__ __forceinline__ void score_tiles_t(f32x4v (&s)[4], const float (&hreg
     }
 }
 
+// BIAS instantiations: score(row, item v) += bias[v] for the S^T tiles of the block at v0 (the plain instantiations are the code
+// without it: same instructions, same bits as before the bias existed)
+template <bool BIAS>
+__device__ __forceinline__ void add_bias_t(f32x4v (&s)[4], const float* __restrict__ bias, int v0, int v_end) {
+    if (!BIAS || !bias) return;
+    const int g = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = v0 + 16 * j + 4 * g + i;
+            if (v < v_end) s[j][i] += bias[v];
+        }
+}
+
 // ---- cross entropy, forward: per (row block, chunk) running max / sum of exp -> ws; then the fixed-order merge -------------
-template <int HP>
+template <int HP, bool BIAS>
 __global__ void __launch_bounds__(CAT_THREADS)
 cat_ce_partial_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, int idx64, int R, const float* __restrict__ E,
-                      int V, int H, int per_chunk, float* __restrict__ pmax, float* __restrict__ psum) {
+                      int V, int H, int per_chunk, float* __restrict__ pmax, float* __restrict__ psum,
+                      const float* __restrict__ bias) {
     __shared__ float lds[CAT_ITEMS * (HP + 4)];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
     const int r = blockIdx.x * CAT_ROWS + 16 * w + c;
@@ -102,6 +120,7 @@ cat_ce_partial_kernel(const float* __restrict__ h, int64_t ldh, const void* idx,
         __syncthreads();
         f32x4v t[4];
         score_tiles_t<HP>(t, hreg, lds);
+        add_bias_t<BIAS>(t, bias, v0, v_end);
         float bm = -INFINITY;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -134,11 +153,12 @@ cat_ce_partial_kernel(const float* __restrict__ h, int64_t ldh, const void* idx,
 }
 
 // one thread per row: chunks merged in order; lse, the row's loss; bad targets counted
-template <int HP>
+template <int HP, bool BIAS>
 __global__ void __launch_bounds__(CAT_THREADS)
 cat_ce_merge_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, int idx64, int R, const float* __restrict__ E, int V,
                     int H, const int64_t* __restrict__ target, int chunks, const float* __restrict__ pmax,
-                    const float* __restrict__ psum, float* __restrict__ lse, float* __restrict__ row_loss, int* __restrict__ bad) {
+                    const float* __restrict__ psum, float* __restrict__ lse, float* __restrict__ row_loss, int* __restrict__ bad,
+                    const float* __restrict__ bias) {
     const int r = blockIdx.x * CAT_THREADS + threadIdx.x;
     if (r >= R) return;
     float m = -INFINITY, s = 0.f;
@@ -161,6 +181,7 @@ cat_ce_merge_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, i
     const float* er = E + t * H;
     float z = 0.f;
     for (int k = 0; k < H; ++k) z = fmaf(er[k], hr[k], z);
+    if (BIAS && bias) z += bias[t];
     row_loss[r] = l - z;
 }
 
@@ -188,11 +209,13 @@ __device__ __forceinline__ float cat_grad(float s, float lse, int v, int64_t tgt
 // dE: one workgroup per 64 items (16 per wave), sweeping every row in order; dE += G^T h, the row sum an MFMA chain.
 // Score tiles here are S (A = h rows from LDS, B = the wave's items from registers): s[t][i] = score(row 16 t + 4 g + i, item c).
 // The k-step (t, i) of dE^T = h^T G takes rows 16 t + 4 g + i, so G's register i is the B operand as it stands.
-template <int HP>
+// BIAS: dbias[item] = the column sum of G: every lane adds its 16 rows of each row block in (t, i) order as the blocks go by, then the
+// four lanes of an item in g order - one fixed order, written (not accumulated).  dE may be NULL then (dbias alone).
+template <int HP, bool BIAS>
 __global__ void __launch_bounds__(CAT_THREADS)
 cat_ce_bwd_de_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, int idx64, int R, const float* __restrict__ E, int V,
                      int H, const int64_t* __restrict__ target, const float* __restrict__ lse, const float* __restrict__ dloss,
-                     float scale, float* __restrict__ dE) {
+                     float scale, float* __restrict__ dE, const float* __restrict__ bias, float* __restrict__ dbias) {
     constexpr int LD = HP + 4, C4 = HP / 4;
     __shared__ float hl[CAT_ROWS * LD];
     __shared__ float lse_l[CAT_ROWS];
@@ -203,6 +226,8 @@ cat_ce_bwd_de_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, 
     float ereg[C4];
 #pragma unroll
     for (int k = 0; k < C4; ++k) ereg[k] = (v < V && 4 * k + g < H) ? E[(int64_t)v * H + 4 * k + g] : 0.f;
+    const float bv = (BIAS && bias && v < V) ? bias[v] : 0.f;
+    float gsum = 0.f;
     f32x4v acc[HP / 16];
 #pragma unroll
     for (int m = 0; m < HP / 16; ++m) acc[m] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -236,8 +261,10 @@ cat_ce_bwd_de_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int rr = 16 * t + 4 * g + i;
-                s[t][i] = (r0 + rr < R && v < V) ? cat_grad(s[t][i], lse_l[rr], v, tgt_l[rr], coef) : 0.f;
+                s[t][i] = (r0 + rr < R && v < V) ? cat_grad(BIAS ? s[t][i] + bv : s[t][i], lse_l[rr], v, tgt_l[rr], coef) : 0.f;
+                if (BIAS) gsum += s[t][i];
             }
+        if (BIAS && !dE) continue;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -246,8 +273,12 @@ cat_ce_bwd_de_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, 
                 for (int m = 0; m < HP / 16; ++m)
                     acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(hl[(16 * t + 4 * g + i) * LD + 16 * m + c], s[t][i], acc[m], 0, 0, 0);
     }
+    if (BIAS && dbias) {
+        const float g1 = __shfl(gsum, c + 16, 64), g2 = __shfl(gsum, c + 32, 64), g3 = __shfl(gsum, c + 48, 64);
+        if (g == 0 && v < V) dbias[v] = ((gsum + g1) + g2) + g3;
+    }
     // lane (g, c), register i: dE[item c][16 m + 4 g + i]
-    if (v < V) {
+    if (v < V && (!BIAS || dE)) {
 #pragma unroll
         for (int m = 0; m < HP / 16; ++m) {
             const int col = 16 * m + 4 * g;
@@ -262,11 +293,11 @@ cat_ce_bwd_de_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, 
 }
 
 // dh partials: per (row block, chunk), dh^T = E^T G^T over the chunk's items (k-step (j, i) = items 16 j + 4 g + i of a block)
-template <int HP>
+template <int HP, bool BIAS>
 __global__ void __launch_bounds__(CAT_THREADS)
 cat_ce_bwd_dh_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, int idx64, int R, const float* __restrict__ E, int V,
                      int H, const int64_t* __restrict__ target, const float* __restrict__ lse, const float* __restrict__ dloss,
-                     float scale, int per_chunk, float* __restrict__ part) {
+                     float scale, int per_chunk, float* __restrict__ part, const float* __restrict__ bias) {
     constexpr int LD = HP + 4;
     __shared__ float lds[CAT_ITEMS * LD];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
@@ -286,6 +317,7 @@ cat_ce_bwd_dh_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, 
         __syncthreads();
         f32x4v s[4];
         score_tiles_t<HP>(s, hreg, lds);
+        add_bias_t<BIAS>(s, bias, v0, v_end);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -341,10 +373,11 @@ __device__ __forceinline__ void cat_insert(float* ls, int* li, int& n, int K, fl
 }
 
 // per (row block, chunk of [start, end)): every lane offers its 16 scores of row c to the row's list, the four lanes of a row in turn
-template <int HP>
+template <int HP, bool BIAS>
 __global__ void __launch_bounds__(CAT_THREADS)
 cat_topk_partial_kernel(const float* __restrict__ h, int64_t ldh, const void* idx, int idx64, int R, const float* __restrict__ E, int H,
-                        int start, int end, int per_chunk, int K, float* __restrict__ cs, int* __restrict__ ci) {
+                        int start, int end, int per_chunk, int K, float* __restrict__ cs, int* __restrict__ ci,
+                        const float* __restrict__ bias) {
     __shared__ float lds[CAT_ITEMS * (HP + 4)];
     __shared__ float ls[CAT_ROWS * CAT_KMAX];
     __shared__ int li[CAT_ROWS * CAT_KMAX];
@@ -362,6 +395,7 @@ cat_topk_partial_kernel(const float* __restrict__ h, int64_t ldh, const void* id
         __syncthreads();
         f32x4v s[4];
         score_tiles_t<HP>(s, hreg, lds);
+        add_bias_t<BIAS>(s, bias, v0, v_end);
         for (int gg = 0; gg < 4; ++gg) {
             if (g == gg) {
 #pragma unroll
@@ -602,6 +636,101 @@ seq_embed_ln_kernel(const int64_t* __restrict__ ids, const float* __restrict__ E
     }
 }
 
+// ---- BERT4Rec's cloze masking (ref:SeqRec/models/discriminative/BERT4Rec/model.py reconstruct_train_data) ----------------------
+// ft[b] = word(B L + b) < ft_ratio 2^32; m[b, s] = word(b L + s) < mask_ratio 2^32 and ids != 0 and not ft[b]; m[b, p_b] |= ft[b],
+// p_b = min(seq_len[b], max_seq_length - 1); labels = ids * m; masked = m ? mask_token : ids.  word(i) is the 32-bit word of
+// DropoutRng::mult(i) (a ratio >= 1 always masks).  The masked positions with a label (labels != 0) are compacted in row-major
+// order without atomics: a wave per 64-token chunk counts them (ballot), one workgroup turns the chunk counts into offsets, a
+// wave per chunk places its tokens at offset + rank.
+struct ClozeRng {
+    uint32_t k0, k1;
+    __device__ __forceinline__ explicit ClozeRng(uint64_t seed) {
+        const DropoutRng r(0.f, seed);
+        k0 = r.k0;
+        k1 = r.k1;
+    }
+    __device__ __forceinline__ uint32_t word(uint32_t idx) const { return mix32(mix32(idx ^ k0) + k1); }
+};
+static inline uint32_t cloze_thr(float ratio) {
+    const float t = ratio * 4294967296.f;
+    return t >= 4294967040.f ? 0xffffffffU : (t <= 0.f ? 0u : (uint32_t)t);
+}
+constexpr int CLOZE_CHUNK = 64;
+
+__global__ void __launch_bounds__(CAT_THREADS)
+cloze_mask_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ seq_len, int B, int L, uint32_t thr_mask, int all_mask,
+                  uint32_t thr_ft, int all_ft, int64_t mask_token, int max_seq_length, uint64_t seed, int64_t* __restrict__ masked,
+                  int64_t* __restrict__ labels, int* __restrict__ chunk_count, int64_t* __restrict__ words) {
+    const ClozeRng rng(seed);
+    const int T = B * L;
+    const int lane = threadIdx.x & 63;
+    const int chunk = (blockIdx.x * CAT_THREADS + threadIdx.x) >> 6;
+    const int t = chunk * CLOZE_CHUNK + lane;
+    bool has = false;
+    if (t < T) {
+        const int b = t / L, s = t % L;
+        const uint32_t wr = rng.word((uint32_t)(T + b)), wp = rng.word((uint32_t)t);
+        const bool ft = all_ft || wr < thr_ft;
+        const int64_t n = seq_len[b], id = ids[t];
+        const int64_t p = n < max_seq_length - 1 ? n : max_seq_length - 1;
+        const bool m = ((all_mask || wp < thr_mask) && id != 0 && !ft) || (ft && s == p);
+        masked[t] = m ? mask_token : id;
+        labels[t] = m ? id : 0;
+        has = m && id != 0;
+        if (words) {
+            words[t] = (int64_t)wp;
+            if (s == 0) words[T + b] = (int64_t)wr;
+        }
+    }
+    const uint64_t bal = __ballot(has);
+    if (lane == 0 && chunk * CLOZE_CHUNK < T) chunk_count[chunk] = __popcll(bal);
+}
+
+// one workgroup: chunk counts -> exclusive offsets (in place), the total -> count[0]
+__global__ void __launch_bounds__(CAT_THREADS)
+cloze_scan_kernel(int* __restrict__ chunk_count, int nchunks, int* __restrict__ count) {
+    __shared__ int part[CAT_THREADS];
+    const int per = (nchunks + CAT_THREADS - 1) / CAT_THREADS;
+    const int c0 = min(nchunks, (int)threadIdx.x * per), c1 = min(nchunks, c0 + per);
+    int a = 0;
+    for (int c = c0; c < c1; ++c) a += chunk_count[c];
+    part[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int i = 0; i < CAT_THREADS; ++i) {
+            const int x = part[i];
+            part[i] = run;
+            run += x;
+        }
+        count[0] = run;
+    }
+    __syncthreads();
+    int run = part[threadIdx.x];
+    for (int c = c0; c < c1; ++c) {
+        const int x = chunk_count[c];
+        chunk_count[c] = run;
+        run += x;
+    }
+}
+
+__global__ void __launch_bounds__(CAT_THREADS)
+cloze_place_kernel(const int64_t* __restrict__ labels, int T, const int* __restrict__ chunk_off, int64_t* __restrict__ rows,
+                   int64_t* __restrict__ targets) {
+    const int lane = threadIdx.x & 63;
+    const int chunk = (blockIdx.x * CAT_THREADS + threadIdx.x) >> 6;
+    const int t = chunk * CLOZE_CHUNK + lane;
+    const int64_t lab = t < T ? labels[t] : 0;
+    const uint64_t bal = __ballot(lab != 0);
+    if (lab != 0) {
+        const int q = chunk_off[chunk] + __popcll(bal & ((1ull << lane) - 1ull));
+        if (q < T) {
+            rows[q] = t;
+            targets[q] = lab;
+        }
+    }
+}
+
 }  // namespace gamer
 
 using namespace gamer;
@@ -627,56 +756,78 @@ extern "C" int64_t gamer_catalog_ws_bytes(int R, int V, int H, int K) {
     return ((a > b ? a : b) * 4 + 15) / 16 * 16 + 16;
 }
 
-#define CAT_DISPATCH(HP_, KERNEL, GRID, ...)                                                                      \
-    do {                                                                                                           \
-        if ((HP_) == 64) hipLaunchKernelGGL(KERNEL<64>, GRID, dim3(CAT_THREADS), 0, st, __VA_ARGS__);              \
-        else if ((HP_) == 128) hipLaunchKernelGGL(KERNEL<128>, GRID, dim3(CAT_THREADS), 0, st, __VA_ARGS__);       \
-        else hipLaunchKernelGGL(KERNEL<256>, GRID, dim3(CAT_THREADS), 0, st, __VA_ARGS__);                         \
+#define CAT_DISPATCH_B(HP_, B_, KERNEL, GRID, ...)                                                                       \
+    do {                                                                                                                  \
+        if ((HP_) == 64) hipLaunchKernelGGL((KERNEL<64, B_>), GRID, dim3(CAT_THREADS), 0, st, __VA_ARGS__);               \
+        else if ((HP_) == 128) hipLaunchKernelGGL((KERNEL<128, B_>), GRID, dim3(CAT_THREADS), 0, st, __VA_ARGS__);        \
+        else hipLaunchKernelGGL((KERNEL<256, B_>), GRID, dim3(CAT_THREADS), 0, st, __VA_ARGS__);                          \
+    } while (0)
+// BIAS_: whether the call has a bias (or a bias gradient); without one the plain instantiation runs
+#define CAT_DISPATCH(HP_, BIAS_, KERNEL, GRID, ...)                                  \
+    do {                                                                             \
+        if (BIAS_) CAT_DISPATCH_B(HP_, true, KERNEL, GRID, __VA_ARGS__);             \
+        else CAT_DISPATCH_B(HP_, false, KERNEL, GRID, __VA_ARGS__);                  \
     } while (0)
 
-extern "C" int gamer_catalog_ce_fwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
-                                    const int64_t* target, float* lse, float* loss, int* bad, void* ws, int64_t ws_bytes,
-                                    void* stream) {
-    GAMER_CHECK_ARG(h && E && target && lse && loss && bad && ws, "gamer_catalog_ce_fwd: null pointer");
-    if (cat_shape_ok("gamer_catalog_ce_fwd", R, V, H, ldh)) return -1;
+// (the entry points without a bias call these with bias = NULL: the plain instantiations, the launches they always made)
+static int catalog_ce_fwd(const char* name, const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V,
+                          int H, const float* bias, const int64_t* target, float* lse, float* loss, int* bad, void* ws,
+                          int64_t ws_bytes, void* stream) {
+    GAMER_CHECK_ARG(h && E && target && lse && loss && bad && ws, "%s: null pointer", name);
+    if (cat_shape_ok(name, R, V, H, ldh)) return -1;
     GAMER_CHECK_ARG(aligned16(E) && aligned16(ws) && ws_bytes >= gamer_catalog_ws_bytes(R, V, H, 0),
-                    "gamer_catalog_ce_fwd: E / ws must be 16-byte aligned and ws hold %lld bytes",
+                    "%s: E / ws must be 16-byte aligned and ws hold %lld bytes", name,
                     (long long)gamer_catalog_ws_bytes(R, V, H, 0));
+    const bool hb = bias != nullptr;
     const int ch = ce_chunks(R, V), per = cat_per_chunk(V, ch), hp = cat_hp(H);
     float* pmax = (float*)ws;
     float* psum = pmax + (int64_t)ch * R;
     float* row_loss = psum + (int64_t)ch * R;
     hipStream_t st = ST(stream);
-    CAT_DISPATCH(hp, cat_ce_partial_kernel, dim3((R + CAT_ROWS - 1) / CAT_ROWS, ch), h, ldh, row_idx, idx64, R, E, V, H, per, pmax, psum);
+    CAT_DISPATCH(hp, hb, cat_ce_partial_kernel, dim3((R + CAT_ROWS - 1) / CAT_ROWS, ch), h, ldh, row_idx, idx64, R, E, V, H, per, pmax,
+                 psum, bias);
     GAMER_CHECK_LAUNCH("gamer_catalog_ce_fwd/partial");
-    CAT_DISPATCH(hp, cat_ce_merge_kernel, dim3((R + CAT_THREADS - 1) / CAT_THREADS), h, ldh, row_idx, idx64, R, E, V, H, target, ch,
-                 pmax, psum, lse, row_loss, bad);
+    CAT_DISPATCH(hp, hb, cat_ce_merge_kernel, dim3((R + CAT_THREADS - 1) / CAT_THREADS), h, ldh, row_idx, idx64, R, E, V, H, target, ch,
+                 pmax, psum, lse, row_loss, bad, bias);
     GAMER_CHECK_LAUNCH("gamer_catalog_ce_fwd/merge");
     hipLaunchKernelGGL(cat_mean_kernel, dim3(1), dim3(CAT_THREADS), 0, st, row_loss, R, loss);
     GAMER_CHECK_LAUNCH("gamer_catalog_ce_fwd/mean");
     return 0;
 }
+extern "C" int gamer_catalog_ce_fwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                                    const int64_t* target, float* lse, float* loss, int* bad, void* ws, int64_t ws_bytes,
+                                    void* stream) {
+    return catalog_ce_fwd("gamer_catalog_ce_fwd", h, ldh, row_idx, idx64, R, E, V, H, nullptr, target, lse, loss, bad, ws, ws_bytes,
+                          stream);
+}
+extern "C" int gamer_catalog_ce_bias_fwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V,
+                                         int H, const float* bias, const int64_t* target, float* lse, float* loss, int* bad, void* ws,
+                                         int64_t ws_bytes, void* stream) {
+    return catalog_ce_fwd("gamer_catalog_ce_bias_fwd", h, ldh, row_idx, idx64, R, E, V, H, bias, target, lse, loss, bad, ws, ws_bytes,
+                          stream);
+}
 
-extern "C" int gamer_catalog_ce_bwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
-                                    const int64_t* target, const float* lse, const float* dloss, float scale, float* dE, float* dh,
-                                    int64_t lddh, void* ws, int64_t ws_bytes, void* stream) {
-    GAMER_CHECK_ARG(h && E && target && lse && ws && (dE || dh), "gamer_catalog_ce_bwd: null pointer");
-    if (cat_shape_ok("gamer_catalog_ce_bwd", R, V, H, ldh)) return -1;
-    GAMER_CHECK_ARG(!dh || lddh >= H, "gamer_catalog_ce_bwd: lddh=%lld < H=%d", (long long)lddh, H);
+static int catalog_ce_bwd(const char* name, const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V,
+                          int H, const float* bias, const int64_t* target, const float* lse, const float* dloss, float scale,
+                          float* dE, float* dh, int64_t lddh, float* dbias, void* ws, int64_t ws_bytes, void* stream) {
+    GAMER_CHECK_ARG(h && E && target && lse && ws && (dE || dh || dbias), "%s: null pointer", name);
+    if (cat_shape_ok(name, R, V, H, ldh)) return -1;
+    GAMER_CHECK_ARG(!dh || lddh >= H, "%s: lddh=%lld < H=%d", name, (long long)lddh, H);
     GAMER_CHECK_ARG(aligned16(E) && aligned16(ws) && (!dE || aligned16(dE)) && ws_bytes >= gamer_catalog_ws_bytes(R, V, H, 0),
-                    "gamer_catalog_ce_bwd: E / dE / ws must be 16-byte aligned and ws hold %lld bytes",
+                    "%s: E / dE / ws must be 16-byte aligned and ws hold %lld bytes", name,
                     (long long)gamer_catalog_ws_bytes(R, V, H, 0));
     const int ch = ce_chunks(R, V), per = cat_per_chunk(V, ch), hp = cat_hp(H);
+    const bool hb = bias != nullptr;
     hipStream_t st = ST(stream);
-    if (dE) {
-        CAT_DISPATCH(hp, cat_ce_bwd_de_kernel, dim3((V + CAT_ITEMS - 1) / CAT_ITEMS), h, ldh, row_idx, idx64, R, E, V, H, target, lse,
-                     dloss, scale, dE);
+    if (dE || dbias) {
+        CAT_DISPATCH(hp, hb || dbias, cat_ce_bwd_de_kernel, dim3((V + CAT_ITEMS - 1) / CAT_ITEMS), h, ldh, row_idx, idx64, R, E, V, H,
+                     target, lse, dloss, scale, dE, bias, dbias);
         GAMER_CHECK_LAUNCH("gamer_catalog_ce_bwd/dE");
     }
     if (dh) {
         float* part = (float*)ws;
-        CAT_DISPATCH(hp, cat_ce_bwd_dh_kernel, dim3((R + CAT_ROWS - 1) / CAT_ROWS, ch), h, ldh, row_idx, idx64, R, E, V, H, target, lse,
-                     dloss, scale, per, part);
+        CAT_DISPATCH(hp, hb, cat_ce_bwd_dh_kernel, dim3((R + CAT_ROWS - 1) / CAT_ROWS, ch), h, ldh, row_idx, idx64, R, E, V, H, target,
+                     lse, dloss, scale, per, part, bias);
         GAMER_CHECK_LAUNCH("gamer_catalog_ce_bwd/dh");
         const int64_t n = (int64_t)R * H;
         hipLaunchKernelGGL(cat_dh_reduce_kernel, dim3((unsigned)((n + CAT_THREADS - 1) / CAT_THREADS)), dim3(CAT_THREADS), 0, st, part,
@@ -685,31 +836,57 @@ extern "C" int gamer_catalog_ce_bwd(const float* h, int64_t ldh, const void* row
     }
     return 0;
 }
+extern "C" int gamer_catalog_ce_bwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                                    const int64_t* target, const float* lse, const float* dloss, float scale, float* dE, float* dh,
+                                    int64_t lddh, void* ws, int64_t ws_bytes, void* stream) {
+    GAMER_CHECK_ARG(dE || dh, "gamer_catalog_ce_bwd: null pointer");
+    return catalog_ce_bwd("gamer_catalog_ce_bwd", h, ldh, row_idx, idx64, R, E, V, H, nullptr, target, lse, dloss, scale, dE, dh, lddh,
+                          nullptr, ws, ws_bytes, stream);
+}
+extern "C" int gamer_catalog_ce_bias_bwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V,
+                                         int H, const float* bias, const int64_t* target, const float* lse, const float* dloss,
+                                         float scale, float* dE, float* dh, int64_t lddh, float* dbias, void* ws, int64_t ws_bytes,
+                                         void* stream) {
+    return catalog_ce_bwd("gamer_catalog_ce_bias_bwd", h, ldh, row_idx, idx64, R, E, V, H, bias, target, lse, dloss, scale, dE, dh, lddh,
+                          dbias, ws, ws_bytes, stream);
+}
 
-extern "C" int gamer_catalog_topk(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
-                                  int start, int end, int K, int64_t* out_idx, float* out_score, void* ws, int64_t ws_bytes,
-                                  void* stream) {
-    GAMER_CHECK_ARG(h && E && out_idx && out_score && ws, "gamer_catalog_topk: null pointer");
-    if (cat_shape_ok("gamer_catalog_topk", R, V, H, ldh)) return -1;
-    GAMER_CHECK_ARG(K > 0 && K <= CAT_KMAX && start >= 0 && start < end && end <= V,
-                    "gamer_catalog_topk: K=%d (1..%d), range [%d, %d) of V=%d", K, CAT_KMAX, start, end, V);
+static int catalog_topk(const char* name, const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V,
+                        int H, const float* bias, int start, int end, int K, int64_t* out_idx, float* out_score, void* ws,
+                        int64_t ws_bytes, void* stream) {
+    GAMER_CHECK_ARG(h && E && out_idx && out_score && ws, "%s: null pointer", name);
+    if (cat_shape_ok(name, R, V, H, ldh)) return -1;
+    GAMER_CHECK_ARG(K > 0 && K <= CAT_KMAX && start >= 0 && start < end && end <= V, "%s: K=%d (1..%d), range [%d, %d) of V=%d", name,
+                    K, CAT_KMAX, start, end, V);
     const int n = end - start;
     GAMER_CHECK_ARG(aligned16(E) && aligned16(ws) && ws_bytes >= gamer_catalog_ws_bytes(R, n, H, K),
-                    "gamer_catalog_topk: E / ws must be 16-byte aligned and ws hold %lld bytes",
-                    (long long)gamer_catalog_ws_bytes(R, n, H, K));
+                    "%s: E / ws must be 16-byte aligned and ws hold %lld bytes", name, (long long)gamer_catalog_ws_bytes(R, n, H, K));
+    const bool hb = bias != nullptr;
     const int ch = topk_chunks(R, n), per = cat_per_chunk(n, ch), hp = cat_hp(H);
     float* cs = (float*)ws;
     int* ci = (int*)(cs + (int64_t)ch * R * K);
     float* ms = (float*)(ci + (int64_t)ch * R * K);
     int* mi = (int*)(ms + (int64_t)R * K);
     hipStream_t st = ST(stream);
-    CAT_DISPATCH(hp, cat_topk_partial_kernel, dim3((R + CAT_ROWS - 1) / CAT_ROWS, ch), h, ldh, row_idx, idx64, R, E, H, start, end, per,
-                 K, cs, ci);
+    CAT_DISPATCH(hp, hb, cat_topk_partial_kernel, dim3((R + CAT_ROWS - 1) / CAT_ROWS, ch), h, ldh, row_idx, idx64, R, E, H, start, end,
+                 per, K, cs, ci, bias);
     GAMER_CHECK_LAUNCH("gamer_catalog_topk/partial");
     hipLaunchKernelGGL(cat_topk_merge_kernel, dim3((R + CAT_THREADS - 1) / CAT_THREADS), dim3(CAT_THREADS), 0, st, R, K, ch, cs, ci,
                        out_idx, out_score, ms, mi);
     GAMER_CHECK_LAUNCH("gamer_catalog_topk/merge");
     return 0;
+}
+extern "C" int gamer_catalog_topk(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                                  int start, int end, int K, int64_t* out_idx, float* out_score, void* ws, int64_t ws_bytes,
+                                  void* stream) {
+    return catalog_topk("gamer_catalog_topk", h, ldh, row_idx, idx64, R, E, V, H, nullptr, start, end, K, out_idx, out_score, ws,
+                        ws_bytes, stream);
+}
+extern "C" int gamer_catalog_topk_bias(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                                       const float* bias, int start, int end, int K, int64_t* out_idx, float* out_score, void* ws,
+                                       int64_t ws_bytes, void* stream) {
+    return catalog_topk("gamer_catalog_topk_bias", h, ldh, row_idx, idx64, R, E, V, H, bias, start, end, K, out_idx, out_score, ws,
+                        ws_bytes, stream);
 }
 
 extern "C" int64_t gamer_embedding_bwd_large_ws_bytes(int V, int T, int H) {
@@ -794,5 +971,32 @@ extern "C" int gamer_seq_embed_ln_fwd(const int64_t* ids, const float* E, int V,
     hipLaunchKernelGGL(seq_embed_ln_kernel, dim3((unsigned)(((int64_t)T * 64 + CAT_THREADS - 1) / CAT_THREADS)), dim3(CAT_THREADS), 0,
                        ST(stream), ids, E, V, P, T, S, H, w, b, eps, p_drop, seed, v, y, mean, rstd);
     GAMER_CHECK_LAUNCH("gamer_seq_embed_ln_fwd");
+    return 0;
+}
+
+extern "C" int64_t gamer_cloze_mask_ws_bytes(int B, int L) {
+    if (B <= 0 || L <= 0 || (int64_t)B * L > (int64_t)1 << 30) return -1;
+    return ((int64_t)((B * L + CLOZE_CHUNK - 1) / CLOZE_CHUNK) * 4 + 15) / 16 * 16;
+}
+extern "C" int gamer_cloze_mask(const int64_t* ids, const int64_t* seq_len, int B, int L, float mask_ratio, float ft_ratio,
+                                int64_t mask_token, int max_seq_length, uint64_t seed, int64_t* masked, int64_t* labels, int64_t* rows,
+                                int64_t* targets, int* count, int64_t* words, void* ws, int64_t ws_bytes, void* stream) {
+    GAMER_CHECK_ARG(ids && seq_len && masked && labels && rows && targets && count && ws, "gamer_cloze_mask: null pointer");
+    GAMER_CHECK_ARG(B > 0 && L > 0 && (int64_t)B * L <= (int64_t)1 << 30 && max_seq_length >= 1 && mask_ratio >= 0.f && ft_ratio >= 0.f,
+                    "gamer_cloze_mask: bad arguments B=%d L=%d max_seq_length=%d mask_ratio=%f ft_ratio=%f", B, L, max_seq_length,
+                    mask_ratio, ft_ratio);
+    GAMER_CHECK_ARG(ws_bytes >= gamer_cloze_mask_ws_bytes(B, L), "gamer_cloze_mask: ws must hold %lld bytes",
+                    (long long)gamer_cloze_mask_ws_bytes(B, L));
+    const int T = B * L, nchunks = (T + CLOZE_CHUNK - 1) / CLOZE_CHUNK;
+    int* chunk_count = (int*)ws;
+    hipStream_t st = ST(stream);
+    const dim3 g((unsigned)(((int64_t)nchunks * 64 + CAT_THREADS - 1) / CAT_THREADS)), b(CAT_THREADS);
+    hipLaunchKernelGGL(cloze_mask_kernel, g, b, 0, st, ids, seq_len, B, L, cloze_thr(mask_ratio), (int)(mask_ratio >= 1.f),
+                       cloze_thr(ft_ratio), (int)(ft_ratio >= 1.f), mask_token, max_seq_length, seed, masked, labels, chunk_count, words);
+    GAMER_CHECK_LAUNCH("gamer_cloze_mask/mask");
+    hipLaunchKernelGGL(cloze_scan_kernel, dim3(1), b, 0, st, chunk_count, nchunks, count);
+    GAMER_CHECK_LAUNCH("gamer_cloze_mask/scan");
+    hipLaunchKernelGGL(cloze_place_kernel, g, b, 0, st, (const int64_t*)labels, T, (const int*)chunk_count, rows, targets);
+    GAMER_CHECK_LAUNCH("gamer_cloze_mask/place");
     return 0;
 }

@@ -1360,6 +1360,103 @@ def catalog_topk(h, E, k, start=0, end=None, row_idx=None):
     return out_i, out_s
 
 
+def _bias(bias, V):
+    if bias is not None and _dense(bias, torch.float32, "bias").numel() < V:
+        raise RuntimeError(f"catalogue head: bias must hold V = {V} values")
+    return bias
+
+
+def _head_v(E, V):
+    """the number of table rows the head scores: E's rows, or fewer (BERT4Rec's table ends with the <MASK> row)"""
+    V = E.shape[0] if V is None else int(V)
+    if not 0 < V <= E.shape[0]:
+        raise RuntimeError(f"catalogue head: V = {V} outside (0, {E.shape[0]}]")
+    return V
+
+
+def catalog_ce_bias_fwd(h, row_idx, E, bias, target, lse, loss, bad, V=None):
+    """catalog_ce_fwd with score(r, v) = h_r . E_v + bias[v] over the first V rows of E (gamer_catalog_ce_bias_fwd);
+    bias None: the same kernels and bits as catalog_ce_fwd."""
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
+    _dense(loss, torch.float32, "loss"), _dense(bad, torch.int32, "bad")
+    if target.numel() != R or lse.numel() != R:
+        raise RuntimeError(f"catalog_ce_bias_fwd: target / lse must hold R = {R} values")
+    V, H = _head_v(E, V), E.shape[1]
+    _bias(bias, V)
+    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
+    ws = _ws("ce", h.device, n)
+    call("gamer_catalog_ce_bias_fwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(bias), ptr(target), ptr(lse),
+         ptr(loss), ptr(bad), ptr(ws), ws.numel(), stream_ptr())
+
+
+def catalog_ce_bias_bwd(h, row_idx, E, bias, target, lse, dloss, scale, dE=None, dh=None, dbias=None, V=None):
+    """catalog_ce_bwd with the bias in the scores; dE rows [0, V) += G^T h, dh <- G E, dbias [V] <- the column sums of G (written)."""
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
+    if dloss is not None:
+        _dense(dloss, torch.float32, "dloss")
+    if dE is not None and (_dense(dE, torch.float32, "dE").shape != E.shape):
+        raise RuntimeError("catalog_ce_bias_bwd: dE must have E's shape")
+    V, H = _head_v(E, V), E.shape[1]
+    _bias(bias, V)
+    if dbias is not None and _dense(dbias, torch.float32, "dbias").numel() < V:
+        raise RuntimeError(f"catalog_ce_bias_bwd: dbias must hold V = {V} values")
+    if dh is not None:
+        _dense(dh, torch.float32, "dh")                 # (a reshape of a strided dh would be a copy: the writes would be lost)
+        if dh.shape[-1] != H or (row_idx is None and dh.numel() // H < R):
+            raise RuntimeError("catalog_ce_bias_bwd: dh must be rows of H values covering the gathered rows")
+    dh2 = dh.reshape(-1, dh.shape[-1]) if dh is not None else None
+    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
+    ws = _ws("ce", h.device, n)
+    call("gamer_catalog_ce_bias_bwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(bias), ptr(target), ptr(lse),
+         ptr(dloss), float(scale), ptr(dE), ptr(dh2), dh2.stride(0) if dh2 is not None else 0, ptr(dbias), ptr(ws), ws.numel(),
+         stream_ptr())
+
+
+def catalog_topk_bias(h, E, bias, k, start=0, end=None, row_idx=None, V=None):
+    """catalog_topk with score(r, v) = h_r . E_v + bias[v], over [start, end) of the first V rows of E (gamer_catalog_topk_bias)."""
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E")
+    V, H = _head_v(E, V), E.shape[1]
+    _bias(bias, V)
+    end = V if end is None else int(end)
+    n = int(_lib.load().gamer_catalog_ws_bytes(R, max(end - start, 1), H, k))
+    ws = _ws("topk", h.device, n)
+    out_i = torch.empty(R, k, dtype=torch.int64, device=h.device)
+    out_s = torch.empty(R, k, dtype=torch.float32, device=h.device)
+    call("gamer_catalog_topk_bias", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(bias), int(start), end, int(k),
+         ptr(out_i), ptr(out_s), ptr(ws), ws.numel(), stream_ptr())
+    return out_i, out_s
+
+
+def cloze_threshold(ratio: float) -> int:
+    """the 32-bit threshold gamer_cloze_mask compares a word against: word < threshold (a ratio >= 1 is always true)"""
+    t = float(torch.tensor(float(ratio), dtype=torch.float32)) * 4294967296.0
+    return 0xFFFFFFFF if t >= 4294967040.0 else max(int(t), 0)
+
+
+def cloze_mask(ids, seq_len, mask_ratio, ft_ratio, mask_token, max_seq_length, seed, want_words=False):
+    """BERT4Rec's cloze masking (gamer_cloze_mask): (masked [B, L], labels [B, L], rows [B L], targets [B L], count [1] int32[,
+    words [B L + B]]).  rows / targets hold count[0] entries: the flat positions with labels != 0 in row-major order and their
+    labels.  The caller checks seq_len against L and max_seq_length (a position outside the row is ignored here)."""
+    _dense(ids, torch.int64, "ids"), _dense(seq_len, torch.int64, "seq_len")
+    if ids.dim() != 2 or seq_len.shape != (ids.shape[0],):
+        raise RuntimeError("cloze_mask: ids [B, L] and seq_len [B]")
+    B, L = ids.shape
+    dev = ids.device
+    masked, labels = torch.empty_like(ids), torch.empty_like(ids)
+    rows = torch.empty(B * L, dtype=torch.int64, device=dev)
+    targets = torch.empty(B * L, dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    words = torch.empty(B * L + B, dtype=torch.int64, device=dev) if want_words else None
+    ws = _ws("cloze", dev, int(_lib.load().gamer_cloze_mask_ws_bytes(B, L)))
+    call("gamer_cloze_mask", ptr(ids), ptr(seq_len), B, L, float(mask_ratio), float(ft_ratio), int(mask_token), int(max_seq_length),
+         int(seed), ptr(masked), ptr(labels), ptr(rows), ptr(targets), ptr(count), ptr(words), ptr(ws), ws.numel(), stream_ptr())
+    out = (masked, labels, rows, targets, count)
+    return out + (words,) if want_words else out
+
+
 def embedding_bwd_large(ids, dx, pad_id, dW):
     """dW[id] += dx rows in token order, pad_id skipped, any table size (gamer_embedding_bwd_large)."""
     _dense(ids, torch.int64, "ids"), _dense(dx, torch.float32, "dx"), _dense(dW, torch.float32, "dW")

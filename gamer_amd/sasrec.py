@@ -129,35 +129,47 @@ class _InputBlockFn(torch.autograd.Function):
 
 
 class _CatalogCEFn(torch.autograd.Function):
-    """mean over rows r of CE(out[rows[r]] @ E^T, target[r]): the [R, V] scores exist only as register tiles."""
+    """mean over rows r of CE(out[rows[r]] @ E^T, target[r]): the [R, V] scores exist only as register tiles.  With ``bias`` (any
+    shape holding V values; BERT4Rec's head) the scores are out @ E[:V]^T + bias and the bias gets its gradient."""
 
     @staticmethod
-    def forward(ctx, out, rows, E, target, shared=None):
+    def forward(ctx, out, rows, E, target, shared=None, bias=None, V=None):
         H = out.shape[-1]
         x = out.reshape(-1, H)
         R = rows.numel()
         f32 = dict(dtype=torch.float32, device=out.device)
         lse, loss = torch.empty(R, **f32), torch.empty((), **f32)
         bad = torch.zeros(1, dtype=torch.int32, device=out.device)
-        ops.catalog_ce_fwd(x, rows, E, target, lse, loss, bad)
+        if bias is None and V is None:
+            ops.catalog_ce_fwd(x, rows, E, target, lse, loss, bad)
+        else:
+            ops.catalog_ce_bias_fwd(x, rows, E, None if bias is None else bias.detach().reshape(-1), target, lse, loss, bad, V)
         n_bad = int(bad.item())
         if n_bad:
-            raise IndexError(f"SASRec.calculate_loss: {n_bad} target(s) outside [0, {E.shape[0]})")
-        ctx.save_for_backward(x, rows, E, target, lse)
+            raise IndexError(f"SASRec.calculate_loss: {n_bad} target(s) outside [0, {E.shape[0] if V is None else V})")
+        ctx.save_for_backward(x, rows, E, target, lse, bias)
         ctx.out_shape = out.shape
         ctx.shared = shared
+        ctx.V = V
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        x, rows, E, target, lse = ctx.saved_tensors
+        x, rows, E, target, lse, bias = ctx.saved_tensors
         dx = torch.zeros(ctx.out_shape, dtype=torch.float32, device=x.device)
         dE = torch.zeros_like(E)
-        ops.catalog_ce_bwd(x, rows, E, target, lse, dloss.float().contiguous(), 1.0 / rows.numel(), dE=dE, dh=dx)
+        dbias = None
+        if bias is None and ctx.V is None:
+            ops.catalog_ce_bwd(x, rows, E, target, lse, dloss.float().contiguous(), 1.0 / rows.numel(), dE=dE, dh=dx)
+        else:
+            dbias = torch.empty_like(bias) if bias is not None and ctx.needs_input_grad[5] else None
+            ops.catalog_ce_bias_bwd(x, rows, E, None if bias is None else bias.detach().reshape(-1), target, lse,
+                                    dloss.float().contiguous(), 1.0 / rows.numel(), dE=dE, dh=dx,
+                                    dbias=None if dbias is None else dbias.view(-1), V=ctx.V)
         if ctx.shared is not None:
             ctx.shared.dE = dE                   # the input block's backward adds the gather's rows and returns it
-            return dx, None, None, None, None
-        return dx, None, dE, None, None
+            return dx, None, None, None, None, dbias, None
+        return dx, None, dE, None, None, dbias, None
 
 
 class SASRec(nn.Module):

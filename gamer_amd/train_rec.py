@@ -8,6 +8,9 @@ behaviour of the test split plus the "Merged Behavior" entry weighted by the beh
 ``result-{test_task}.json`` in the reference's layout.  Ranking uses the model's ``full_sort_topk`` with K = the largest k of
 ``--metrics``.  ``--base_model`` defaults to ``./config/dis-models/{backbone}``, as the reference's launcher sets it.  Single
 device, no wandb.
+
+``run`` is that loop with the model class, the config class and the data functions as arguments: ``main`` here calls it with the
+``smb_dis`` data layer, ``python -m gamer_amd.train_bert4rec`` with BERT4Rec and ``smb_dis_target_data``.
 """
 from __future__ import annotations
 
@@ -29,14 +32,17 @@ DEFAULT_METRICS = "hit@1,hit@5,hit@10,recall@1,recall@5,recall@10,ndcg@5,ndcg@10
 BACKBONES = {"SASRec": (SASRec, SASRecConfig), "GRU4Rec": (GRU4Rec, GRU4RecConfig)}
 
 
-def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m gamer_amd.train_rec")
-    ap.add_argument("--backbone", default="SASRec")
+def parse_args(argv=None, prog="python -m gamer_amd.train_rec", backbone="SASRec", backbones=None, tasks="smb_dis",
+               test_task="smb_dis"):
+    """The command's arguments; a command of another backbone family (train_bert4rec) passes its own defaults and names."""
+    backbones = BACKBONES if backbones is None else backbones
+    ap = argparse.ArgumentParser(prog=prog)
+    ap.add_argument("--backbone", default=backbone)
     ap.add_argument("--base_model", default=None, help="default: ./config/dis-models/{backbone}")
     ap.add_argument("--data_path", default="./data")
     ap.add_argument("--dataset", default="Retail_Beh")
-    ap.add_argument("--tasks", default="smb_dis")
-    ap.add_argument("--test_task", default="smb_dis")
+    ap.add_argument("--tasks", default=tasks)
+    ap.add_argument("--test_task", default=test_task)
     ap.add_argument("--max_his_len", type=int, default=20)
     ap.add_argument("--optim", default="adamw")
     ap.add_argument("--epochs", type=int, default=200)
@@ -50,8 +56,8 @@ def parse_args(argv=None):
     ap.add_argument("--only_test", action="store_true")
     ap.add_argument("--seed", type=int, default=42)
     a = ap.parse_args(argv)
-    if a.backbone not in BACKBONES:
-        raise NotImplementedError(f"--backbone {a.backbone}: only {', '.join(BACKBONES)} run on the HIP path")
+    if a.backbone not in backbones:
+        raise NotImplementedError(f"--backbone {a.backbone}: only {', '.join(backbones)} run on the HIP path")
     if a.base_model is None:
         a.base_model = f"./config/dis-models/{a.backbone}"
     if a.optim.lower() != "adamw":
@@ -86,31 +92,31 @@ def _to(batch, dev):
     return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in batch.items()}
 
 
-def evaluate(model, data, batch_size, metrics, dev):
+def evaluate(model, data, batch_size, metrics, dev, collate=smb_dis_data.collate):
     """mean of every metric over the samples of ``data`` (valid / test: lists of targets)"""
     model.eval()
     K = max(int(m.split("@")[1]) for m in metrics)
     vals = {m: [] for m in metrics}
     with torch.no_grad():
         for i in range(0, len(data.samples), batch_size):
-            batch, targets = smb_dis_data.collate(data.samples[i:i + batch_size], test=True)
+            batch, targets = collate(data.samples[i:i + batch_size], test=True)
             idx, _ = model.full_sort_topk(_to(batch, dev), K)
             for m, v in topk_rank_metrics(idx.cpu().numpy(), targets, metrics).items():
                 vals[m].extend(v)
     return {m: float(np.mean(v)) for m, v in vals.items()}
 
 
-def main(argv=None):
-    a = parse_args(argv)
+def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="train_rec"):
+    """The loop of ``TrainSMBRec.invoke`` for the parsed arguments ``a``: the model and config classes, the data functions
+    (train / valid loader, test loader, collate) and the tag of the printed lines are the command's (train_rec, train_bert4rec)."""
     random.seed(a.seed)
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
     dev = torch.device("cuda")
     metrics = a.metrics.split(",")
     os.makedirs(a.output_dir, exist_ok=True)
-    model_cls, config_cls = BACKBONES[a.backbone]
     config = config_cls.from_pretrained(a.base_model)
-    trains, valid = smb_dis_data.load_train_valid(a.data_path, a.dataset, a.max_his_len, a.tasks)
+    trains, valid = load_train_valid(a.data_path, a.dataset, a.max_his_len, a.tasks)
     valid = valid.filter_by_behavior(valid.target_behavior)
     first = trains[0]
     model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len).to(dev)
@@ -119,15 +125,15 @@ def main(argv=None):
         train_samples = [s for t in trains for s in t.samples]
         opt = AdamW(model.parameters(), a.learning_rate, a.weight_decay)
         g = torch.Generator().manual_seed(a.seed)
-        best = evaluate(model, valid, a.batch_size, metrics, dev)[metrics[-1]]
-        print(f"[train_rec] before training: {metrics[-1]} {best:.4f}", flush=True)
+        best = evaluate(model, valid, a.batch_size, metrics, dev, collate)[metrics[-1]]
+        print(f"[{tag}] before training: {metrics[-1]} {best:.4f}", flush=True)
         patience, saved = 0, False
         for epoch in range(a.epochs):
             model.train()
             order = torch.randperm(len(train_samples), generator=g).tolist()
             losses = []
             for i in range(0, len(order), a.batch_size):
-                batch = _to(smb_dis_data.collate([train_samples[j] for j in order[i:i + a.batch_size]]), dev)
+                batch = _to(collate([train_samples[j] for j in order[i:i + a.batch_size]]), dev)
                 for p in model.parameters():
                     p.grad = None
                 loss = model.calculate_loss(batch)
@@ -135,8 +141,8 @@ def main(argv=None):
                 opt.step()
                 losses.append(loss.detach())
             loss = float(torch.stack(losses).mean())
-            res = evaluate(model, valid, a.batch_size, metrics, dev)
-            print(f"[train_rec] epoch {epoch + 1}/{a.epochs} loss {loss:.4f} " +
+            res = evaluate(model, valid, a.batch_size, metrics, dev, collate)
+            print(f"[{tag}] epoch {epoch + 1}/{a.epochs} loss {loss:.4f} " +
                   " ".join(f"{m} {v:.4f}" for m, v in res.items()), flush=True)
             if res[metrics[-1]] > best:
                 best, patience, saved = res[metrics[-1]], 0, True
@@ -144,18 +150,18 @@ def main(argv=None):
             else:
                 patience += 1
                 if patience >= a.patience:
-                    print(f"[train_rec] early stopping on epoch {epoch + 1}", flush=True)
+                    print(f"[{tag}] early stopping on epoch {epoch + 1}", flush=True)
                     break
         if not saved:
             # no epoch beat the evaluation before training: the reference's test step would fail on the missing file; the
             # last model is tested instead
             torch.save(model.state_dict(), ckpt)
-    test = smb_dis_data.load_test(a.data_path, a.dataset, a.max_his_len, a.test_task)
+    test = load_test(a.data_path, a.dataset, a.max_his_len, a.test_task)
     model.load_state_dict(torch.load(ckpt, map_location="cpu"))
     results, merged, total = [], {m: 0.0 for m in metrics}, 0
     for b in first.behaviors:
         part = test.filter_by_behavior(b)
-        r = evaluate(model, part, a.batch_size, metrics, dev) if len(part) else {m: float("nan") for m in metrics}
+        r = evaluate(model, part, a.batch_size, metrics, dev, collate) if len(part) else {m: float("nan") for m in metrics}
         r["eval_type"] = f"Behavior {b}"
         results.append(r)
         for m in metrics:
@@ -169,8 +175,13 @@ def main(argv=None):
     out = os.path.join(a.result_dir, f"result-{a.test_task}.json")
     with open(out, "w") as f:
         json.dump(results, f, indent=4)
-    print(f"[train_rec] results saved to {out}", flush=True)
+    print(f"[{tag}] results saved to {out}", flush=True)
     return results
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    return run(a, *BACKBONES[a.backbone], smb_dis_data.load_train_valid, smb_dis_data.load_test, smb_dis_data.collate)
 
 
 if __name__ == "__main__":

@@ -853,6 +853,29 @@ int gamer_catalog_ce_bwd(const float* h, int64_t ldh, const void* row_idx, int i
  * descending, lower index first on ties (a stable argsort of -scores); fewer than K items: index -1, score -inf. */
 int gamer_catalog_topk(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H, int start,
                        int end, int K, int64_t* out_idx, float* out_score, void* ws, int64_t ws_bytes, void* stream);
+/* (additions to ABI 9) The three entry points above with a per-item bias (BERT4Rec's head, ref:SeqRec/modules/layers/transformer.py
+ * DotProductPredictionHead): score(r, v) = h_r . E_v + bias[v], bias [V] or NULL (then the same kernels and bits as the entry points
+ * above).  V may be smaller than E's allocation: rows >= V are never read or scored.  ce_bias_bwd also writes (not accumulates)
+ * dbias[v] = sum_r G[r, v] (the dE kernel's sweep, one fixed order; NULL = not wanted); any of dE / dh / dbias may be NULL. */
+int gamer_catalog_ce_bias_fwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                              const float* bias, const int64_t* target, float* lse, float* loss, int* bad, void* ws, int64_t ws_bytes,
+                              void* stream);
+int gamer_catalog_ce_bias_bwd(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                              const float* bias, const int64_t* target, const float* lse, const float* dloss, float scale, float* dE,
+                              float* dh, int64_t lddh, float* dbias, void* ws, int64_t ws_bytes, void* stream);
+int gamer_catalog_topk_bias(const float* h, int64_t ldh, const void* row_idx, int idx64, int R, const float* E, int V, int H,
+                            const float* bias, int start, int end, int K, int64_t* out_idx, float* out_score, void* ws,
+                            int64_t ws_bytes, void* stream);
+/* BERT4Rec's cloze masking of ids [B][L] (ref:SeqRec/models/discriminative/BERT4Rec/model.py reconstruct_train_data):
+ * ft[b] = word(B L + b) < ft_ratio 2^32; m[b][s] = word(b L + s) < mask_ratio 2^32 and ids != 0 and not ft[b];
+ * m[b][min(seq_len[b], max_seq_length - 1)] |= ft[b] (a position >= L is ignored: the host refuses such a batch);
+ * labels = ids * m, masked = m ? mask_token : ids.  word(i) is the 32-bit word of the counter hash of the dropout masks under seed
+ * (a ratio >= 1 is always true).  rows / targets [B L]: the flat indices and labels of the positions with labels != 0 in row-major
+ * order, count[0] of them (no atomics).  words: NULL or [B L + B], the words drawn (tests).  ws: gamer_cloze_mask_ws_bytes(B, L). */
+int64_t gamer_cloze_mask_ws_bytes(int B, int L);
+int gamer_cloze_mask(const int64_t* ids, const int64_t* seq_len, int B, int L, float mask_ratio, float ft_ratio, int64_t mask_token,
+                     int max_seq_length, uint64_t seed, int64_t* masked, int64_t* labels, int64_t* rows, int64_t* targets, int* count,
+                     int64_t* words, void* ws, int64_t ws_bytes, void* stream);
 /* dW[id] += the dx rows of the tokens with that id, in token order, ids == pad_id (and outside [0, V)) skipped; any V: the tokens
  * are grouped with integer atomics and put in token order (ranks from 64-token chunks), ids of more than 64 tokens are summed in
  * 64-row pieces, then the pieces in order (no float atomics). */

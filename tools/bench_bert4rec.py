@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""BERT4Rec on one GPU: train step, the biased catalogue head on the M masked rows against a materialised composition, the
+output chain's share of the step, and top-10 ranking.
+
+  * train step (``calculate_loss`` + backward; forward and backward only) of the reference's shipped config (hidden 64,
+    2 layers, 2 heads, inner 256, dropout 0.2, mask_ratio 0.2, ft_ratio 0.5) at batch ``--batch`` x 20 on synthetic catalogues
+    (full-length rows; M, the number of masked rows, is read from each step and reported as its median);
+  * the head alone on M rows, H = 64: gamer_catalog_ce_bias_fwd + _bwd against torch.matmul + bias + F.cross_entropy and
+    autograd's gradients in the same process, time and peak allocated memory;
+  * the output chain (output_ffn, GELU, output_ln, head.out, ReLU on the M gathered rows, forward + backward) alone, as a
+    share of the step;
+  * the cloze-mask kernel alone;
+  * evaluation: users/s of top-10 full ranking (gamer_catalog_topk_bias) against materialised scores + bias + torch.topk.
+Medians of ``--steps`` device-event timings after ``--warmup``.  Prints one JSON line per batch size.
+
+  python tools/bench_bert4rec.py --batch 4096,256 --steps 10 --warmup 3 --items 16384,100000,1000000
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from gamer_amd import bert4rec, ops, sasrec  # noqa: E402
+from gamer_amd.bert4rec import BERT4Rec, BERT4RecConfig  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def peak(fn, reset):
+    fn()
+    reset()                                           # (drop the gradients of the warm-up call before the baseline)
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2**20
+
+
+def bench(B, S, items, a):
+    out = dict(batch=B, seq=S, hidden=64)
+    for n_items in items:
+        key = f"items_{n_items}"
+        g = torch.Generator().manual_seed(n_items)
+        torch.manual_seed(0)
+        model = BERT4Rec(BERT4RecConfig(), n_items, S).to(DEV).train()
+        V, H = n_items + 1, model.hidden_size
+        with torch.no_grad():
+            model.head.bias.normal_(0.0, 0.5)
+        inter = dict(inputs=torch.randint(1, n_items + 1, (B, S), generator=g).to(DEV), seq_len=torch.full((B,), S, device=DEV))
+        counts = []
+
+        def step():
+            model.zero_grad(set_to_none=True)
+            model.calculate_loss(inter).backward()
+            counts.append(model.last_masked_count)
+        ms = timed(step, a.steps, a.warmup)
+        M = int(statistics.median(counts))
+        r = dict(step_ms=round(ms, 3), sequences_per_s=round(B / ms * 1e3, 1), masked_rows=M,
+                 step_peak_mib=round(peak(step, lambda: model.zero_grad(set_to_none=True)), 1))
+        r["cloze_mask_ms"] = round(timed(lambda: model.reconstruct_train_data(inter["inputs"], inter["seq_len"]), a.steps, a.warmup), 4)
+        # the head alone, on M rows
+        h = (torch.randn(M, H, generator=g) * 0.3).abs().to(DEV).requires_grad_(True)
+        E = model.item_embedding.weight.detach().clone().requires_grad_(True)
+        bias = model.head.bias.detach().clone().requires_grad_(True)
+        target = torch.randint(1, V, (M,), generator=g).to(DEV)
+        rows = torch.arange(M, device=DEV)
+
+        def drop():
+            E.grad = None
+            h.grad = None
+            bias.grad = None
+
+        def fused():
+            drop()
+            sasrec._CatalogCEFn.apply(h, rows, E, target, None, bias, V).backward()
+
+        def materialised():
+            drop()
+            F.cross_entropy(torch.matmul(h, E[:V].t()) + bias, target).backward()
+        r["head_fused_ms"] = round(timed(fused, a.steps, a.warmup), 3)
+        r["head_fused_peak_mib"] = round(peak(fused, drop), 1)
+        try:
+            r["head_materialised_ms"] = round(timed(materialised, a.steps, a.warmup), 3)
+            r["head_materialised_peak_mib"] = round(peak(materialised, drop), 1)
+        except torch.cuda.OutOfMemoryError:
+            r["head_materialised_ms"] = "out of memory"
+        drop()
+        torch.cuda.empty_cache()
+        # the output chain alone (forward + backward on M gathered rows of B S)
+        x = torch.randn(B, S, H, device=DEV, requires_grad=True)
+        crow = torch.randperm(B * S, generator=g)[:M].sort().values.to(DEV)
+        lin = model.head.out[0]
+
+        def chain():
+            model.zero_grad(set_to_none=True)
+            x.grad = None
+            y = bert4rec._OutputChainFn.apply(x, crow, model.output_ffn.weight, model.output_ffn.bias, model.output_ln.weight,
+                                              model.output_ln.bias, model.layer_norm_eps, lin.weight, lin.bias)
+            y.backward(torch.ones_like(y))
+        r["output_chain_ms"] = round(timed(chain, a.steps, a.warmup), 3)
+        r["output_chain_share_of_step"] = round(r["output_chain_ms"] / r["step_ms"], 3)
+        # evaluation: top-10 over the whole table
+        U = a.eval_users
+        hu = (torch.randn(U, H, generator=g) * 0.3).abs().to(DEV)
+        Ed, bd = E.detach(), bias.detach().reshape(-1)
+        t_fused = timed(lambda: ops.catalog_topk_bias(hu, Ed, bd, 10, 0, V, V=V), a.steps, a.warmup)
+
+        def topk_mat():
+            torch.topk(torch.matmul(hu, Ed[:V].t()) + bd, 10, dim=1)
+        t_mat = timed(topk_mat, a.steps, a.warmup)
+        r["topk_fused_users_per_s"] = round(U / t_fused * 1e3, 1)
+        r["topk_materialised_users_per_s"] = round(U / t_mat * 1e3, 1)
+        out[key] = r
+        del model, E, h, hu, Ed, x, bias
+        torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", default="4096,256")
+    ap.add_argument("--seq", type=int, default=20)
+    ap.add_argument("--items", default="16384,100000,1000000")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--eval_users", type=int, default=4096)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_bert4rec.py needs the GPU")
+    items = [int(x) for x in a.items.split(",")]
+    for B in [int(x) for x in a.batch.split(",")]:
+        print(json.dumps(bench(B, a.seq, items, a)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
