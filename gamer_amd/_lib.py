@@ -188,6 +188,13 @@ _SIGNATURES = {
     "gamer_gru_gates_floats": [I, I, I],
     "gamer_gru_fwd": [P, P, P, I, I, I, P, P, P],
     "gamer_gru_bwd": [P, P, P, P, P, I, I, I, P, P, P],
+    "gamer_mbs_mix_fwd": [P, P, I, I, I, P, P],
+    "gamer_mbs_mix_bwd": [P, P, P, I, I, I, P, P, P],
+    "gamer_mbs_attn_fwd": [P, I, P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, F, F, U, P, I, P, P],
+    "gamer_mbs_attn_bwd": [P, I, P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, F, F, U, P, P, I, P, P, I, P, I, P, I, P, P, P, I, P],
+    "gamer_mbs_bias_fold": [P, P, I, I, I, I, P, P],
+    "gamer_mbs_gate_mix_fwd": [P, I, P, P, I, I, I, P, P, P],
+    "gamer_mbs_gate_mix_bwd": [P, P, P, I, I, I, P, P, I, P],
 }
 
 

@@ -1532,3 +1532,131 @@ def gru_bwd(dy, h, gates, w_hh, dgi, dgh_next, lens=None):
     if gates.numel() != gru_gates_floats(B, L, H):
         raise RuntimeError(f"gru_bwd: gates must hold {gru_gates_floats(B, L, H)} floats")
     call("gamer_gru_bwd", ptr(dy), ptr(h), ptr(gates), ptr(w_hh), lp, B, L, H, ptr(dgi), ptr(dgh_next), stream_ptr())
+
+
+# ---- MBSTR's behaviour-aware attention and CGC head (csrc/mbs_attention.hip) -----------------------------------------------------
+MBS_MAX_L, MBS_MAX_D, MBS_MAX_B, MBS_MAX_E = 128, 64, 8, 16
+
+
+def mbs_check_limits(L, H, d, b):
+    """The limits of the MBSTR kernels, refused on the host before any launch."""
+    if L > MBS_MAX_L or d > MBS_MAX_D or H > 256 or H % 4 or b > MBS_MAX_B or L < 1 or b < 1:
+        raise NotImplementedError(f"MBSTR on the HIP path: L <= {MBS_MAX_L}, head size <= {MBS_MAX_D}, hidden size <= 256 and "
+                                  f"divisible by 4, n_behaviors <= {MBS_MAX_B} (got L={L}, head size={d}, hidden size={H}, "
+                                  f"n_behaviors={b})")
+
+
+def mbs_mix_fwd(W, alpha, Wm):
+    """Wm [b b + 1, h, d, d] = sum_j softmax_j(alpha [b b + 1, b, h]) W [b, h, d, d] (gamer_mbs_mix_fwd)."""
+    for t, n in ((W, "W"), (alpha, "alpha"), (Wm, "Wm")):
+        _dense(t, torch.float32, n)
+    b, h, d, _ = W.shape
+    if alpha.shape != (b * b + 1, b, h) or Wm.shape != (b * b + 1, h, d, d):
+        raise RuntimeError(f"mbs_mix_fwd: alpha [{b * b + 1}, {b}, {h}] and Wm [{b * b + 1}, {h}, {d}, {d}]")
+    call("gamer_mbs_mix_fwd", ptr(W), ptr(alpha), b, h, d, ptr(Wm), stream_ptr())
+
+
+def mbs_mix_bwd(W, alpha, dWm, dW, dalpha):
+    for t, n in ((W, "W"), (alpha, "alpha"), (dWm, "dWm"), (dW, "dW"), (dalpha, "dalpha")):
+        _dense(t, torch.float32, n)
+    b, h, d, _ = W.shape
+    if alpha.shape != (b * b + 1, b, h) or dWm.shape != (b * b + 1, h, d, d) or dW.shape != W.shape or dalpha.shape != alpha.shape:
+        raise RuntimeError("mbs_mix_bwd: shapes of mbs_mix_fwd")
+    call("gamer_mbs_mix_bwd", ptr(W), ptr(alpha), ptr(dWm), b, h, d, ptr(dW), ptr(dalpha), stream_ptr())
+
+
+def _mbs_common(q, k, v, types, w1m, w2m, rel, bucket, B, L, h, d, b):
+    mbs_check_limits(L, h * d, d, b)
+    C_ = b * b + 1
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, torch.float32, n)
+        if t.dim() != 2 or t.shape[0] != B * L or t.shape[1] != h * d or t.stride(1) != 1:
+            raise RuntimeError(f"mbs attention: {n} must be a [{B * L}, {h * d}] row-strided view")
+    _dense(types, torch.int32, "types"), _dense(w1m, torch.float32, "w1m"), _dense(w2m, torch.float32, "w2m")
+    if types.shape != (B, L) or w1m.shape != (C_, h, d, d) or w2m.shape != (C_, h, d, d):
+        raise RuntimeError(f"mbs attention: types [{B}, {L}], w1m / w2m [{C_}, {h}, {d}, {d}]")
+    nb = 0
+    if rel is not None:
+        _dense(rel, torch.float32, "rel"), _dense(bucket, torch.int32, "bucket")
+        nb = rel.shape[1]
+        if rel.shape != (C_, nb, h) or bucket.shape != (2 * L - 1,):
+            raise RuntimeError(f"mbs attention: rel [{C_}, num_buckets, {h}] and bucket [{2 * L - 1}]")
+    return nb
+
+
+def mbs_attn_fwd(q, k, v, types, w1m, w2m, rel, bucket, B, L, h, d, b, scale, p_drop, seed, o, lse):
+    """gamer_mbs_attn_fwd: q / k / v / o [B L, h d] (row-strided views), types int32 [B, L], rel [b b + 1, num_buckets, h] or None,
+    bucket int32 [2 L - 1] (values in [0, num_buckets): checked by the caller), lse [B, h, L]."""
+    nb = _mbs_common(q, k, v, types, w1m, w2m, rel, bucket, B, L, h, d, b)
+    _chk(o, torch.float32, "o"), _dense(lse, torch.float32, "lse")
+    if o.shape != (B * L, h * d) or o.stride(1) != 1 or lse.numel() != B * h * L:
+        raise RuntimeError("mbs_attn_fwd: o [B L, h d] and lse [B, h, L]")
+    call("gamer_mbs_attn_fwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(types), ptr(w1m), ptr(w2m), ptr(rel),
+         ptr(bucket) if rel is not None else None, nb, B, L, h, d, b, float(scale), float(p_drop), int(seed), ptr(o), o.stride(0),
+         ptr(lse), stream_ptr())
+
+
+def mbs_n_partial(B, h, d, b):
+    """Slabs of the attention backward's parameter gradients: n h workgroups, one per CU (256) when the slab sets allow it - at
+    most 24 MB each (two of them, W1m's and W2m's)."""
+    n = max(1, min(B, 256 // max(1, h)))
+    while n > 1 and n * (b * b + 1) * h * d * d * 4 > (24 << 20):
+        n //= 2
+    return n
+
+
+def mbs_attn_bwd(q, k, v, types, w1m, w2m, rel, bucket, B, L, h, d, b, scale, p_drop, seed, o, d_o, lse, dq, dk, dv, dw1m_partial,
+                 dw2m_partial, drel_partial):
+    """gamer_mbs_attn_bwd: dq / dk / dv and the three partial slab sets must be zero on entry; dw*_partial [n, b b + 1, h, d, d],
+    drel_partial [n, b b + 1, 2 L - 1, h] (None iff rel is None)."""
+    nb = _mbs_common(q, k, v, types, w1m, w2m, rel, bucket, B, L, h, d, b)
+    C_ = b * b + 1
+    for t, n in ((o, "o"), (d_o, "d_o"), (dq, "dq"), (dk, "dk"), (dv, "dv")):
+        _chk(t, torch.float32, n)
+        if t.shape != (B * L, h * d) or t.stride(1) != 1:
+            raise RuntimeError(f"mbs_attn_bwd: {n} must be a [{B * L}, {h * d}] row-strided view")
+    if o.stride(0) != d_o.stride(0):
+        raise RuntimeError("mbs_attn_bwd: o and d_o must share their row stride")
+    _dense(lse, torch.float32, "lse"), _dense(dw1m_partial, torch.float32, "dw1m_partial"), _dense(dw2m_partial, torch.float32, "dw2m_partial")
+    n = dw1m_partial.shape[0]
+    if dw1m_partial.shape != (n, C_, h, d, d) or dw2m_partial.shape != (n, C_, h, d, d) or lse.numel() != B * h * L:
+        raise RuntimeError("mbs_attn_bwd: partial slabs [n, b b + 1, h, d, d], lse [B, h, L]")
+    if (rel is None) != (drel_partial is None):
+        raise RuntimeError("mbs_attn_bwd: drel_partial goes with the bias table")
+    if drel_partial is not None and (_dense(drel_partial, torch.float32, "drel_partial").shape != (n, C_, 2 * L - 1, h)):
+        raise RuntimeError(f"mbs_attn_bwd: drel_partial [{n}, {C_}, {2 * L - 1}, {h}]")
+    call("gamer_mbs_attn_bwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(types), ptr(w1m), ptr(w2m), ptr(rel),
+         ptr(bucket) if rel is not None else None, nb, B, L, h, d, b, float(scale), float(p_drop), int(seed), ptr(o), ptr(d_o),
+         o.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv), dv.stride(0), ptr(dw1m_partial),
+         ptr(dw2m_partial), ptr(drel_partial), n, stream_ptr())
+
+
+def mbs_bias_fold(drel, bucket, dbias):
+    """dbias [C, num_buckets, h] from the per-offset sums drel [C, 2 L - 1, h] (gamer_mbs_bias_fold)."""
+    _dense(drel, torch.float32, "drel"), _dense(bucket, torch.int32, "bucket"), _dense(dbias, torch.float32, "dbias")
+    C_, R, h = drel.shape
+    if bucket.shape != (R,) or dbias.shape[0] != C_ or dbias.shape[2] != h:
+        raise RuntimeError("mbs_bias_fold: drel [C, 2 L - 1, h], bucket [2 L - 1], dbias [C, num_buckets, h]")
+    call("gamer_mbs_bias_fold", ptr(drel), ptr(bucket), (R + 1) // 2, C_, dbias.shape[1], h, ptr(dbias), stream_ptr())
+
+
+def mbs_gate_mix_fwd(logits, outs, types, gates, mix):
+    """gates [M, E] = softmax(logits [M, >= E][:, :E]); mix [M, H] = sum_e gates_e outs [M, E, H]; rows of type 0: zeros."""
+    _chk(logits, torch.float32, "logits"), _dense(outs, torch.float32, "outs"), _dense(types, torch.int32, "types")
+    _dense(gates, torch.float32, "gates"), _dense(mix, torch.float32, "mix")
+    M, E, H = outs.shape
+    if E > MBS_MAX_E or logits.shape[0] != M or logits.shape[1] < E or logits.stride(1) != 1 or types.shape != (M,) or gates.shape != (M, E) \
+            or mix.shape != (M, H):
+        raise RuntimeError(f"mbs_gate_mix_fwd: bad shapes (E <= {MBS_MAX_E})")
+    call("gamer_mbs_gate_mix_fwd", ptr(logits), logits.stride(0), ptr(outs), ptr(types), M, E, H, ptr(gates), ptr(mix), stream_ptr())
+
+
+def mbs_gate_mix_bwd(gates, outs, dmix, douts, dlogits):
+    for t, n in ((gates, "gates"), (outs, "outs"), (dmix, "dmix"), (douts, "douts")):
+        _dense(t, torch.float32, n)
+    _chk(dlogits, torch.float32, "dlogits")
+    M, E, H = outs.shape
+    if gates.shape != (M, E) or dmix.shape != (M, H) or douts.shape != outs.shape or dlogits.shape[0] != M or dlogits.shape[1] < E \
+            or dlogits.stride(1) != 1:
+        raise RuntimeError("mbs_gate_mix_bwd: bad shapes")
+    call("gamer_mbs_gate_mix_bwd", ptr(gates), ptr(outs), ptr(dmix), M, E, H, ptr(douts), ptr(dlogits), dlogits.stride(0), stream_ptr())

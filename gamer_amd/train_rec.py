@@ -119,7 +119,8 @@ def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="tra
     trains, valid = load_train_valid(a.data_path, a.dataset, a.max_his_len, a.tasks)
     valid = valid.filter_by_behavior(valid.target_behavior)
     first = trains[0]
-    model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len).to(dev)
+    # (n_behaviors: read by the behaviour-aware backbones; the others take it in **kwargs)
+    model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len, n_behaviors=len(first.behaviors)).to(dev)
     ckpt = os.path.join(a.output_dir, "best_model.pth")
     if not a.only_test:
         train_samples = [s for t in trains for s in t.samples]

@@ -906,6 +906,39 @@ int gamer_gru_fwd(const float* gi, const float* w_hh, const int64_t* lens, int B
 int gamer_gru_bwd(const float* dy, const float* h, const float* gates, const float* w_hh, const int64_t* lens, int B, int L, int H,
                   float* dgi, float* dgh_next, void* stream);
 
+/* (ABI 9) MBSTR's behaviour-aware attention (csrc/mbs_attention.hip; ref:SeqRec/modules/layers/mbs_transformer.py).  b = n_behaviors
+ * (<= 8), C = b b + 1 pair indices c(q, k) = 0 if t_q = 0 or t_k = 0, else (t_q - 1) b + t_k; types int32 [B][L] in [0, b], 0 = padding.
+ * Wm [C][H][d][d] = sum_j softmax_j(alpha [C][b][H]) W [b][H][d][d]: the mixed W1 / W2 of one layer. */
+int gamer_mbs_mix_fwd(const float* W, const float* alpha, int n_behaviors, int H, int head_dim, float* Wm, void* stream);
+int gamer_mbs_mix_bwd(const float* W, const float* alpha, const float* dWm, int n_behaviors, int H, int head_dim, float* dW,
+                      float* dalpha, void* stream);
+/* o[q] = sum_k dropout(softmax_k(Q_q^T W1m[c] K_k scale + rel[c][bucket[k - q + L - 1]][head] + keymask_k))[q, k] W2m[c]^T V_k, one
+ * workgroup per (batch row, head), q / k / v / o as gamer_attn_dense_fwd; keys of type 0 are masked (additive finfo.min); rel
+ * [C][num_buckets][H] or NULL (no position bias); bucket int32 [2 L - 1]; dropout mask of element (b, h, q, k) as
+ * gamer_attn_dense_fwd; lse [B][H][L].  L <= 128, head_dim <= 64.  Nothing of size L^2 is written to memory. */
+int gamer_mbs_attn_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* types,
+                       const float* w1m, const float* w2m, const float* rel, const int32_t* bucket, int num_buckets, int B, int L,
+                       int H, int head_dim, int n_behaviors, float scale, float p_drop, uint64_t seed, float* o, int ldo, float* lse,
+                       void* stream);
+/* dk / dv must be ZERO on entry (the rows of padding keys are not written); dq is written.  The parameter gradients leave as
+ * n_partial slabs, each ZERO on entry: workgroup (slab, head) walks the rows slab, slab + n_partial, ... in order and ADDS every
+ * row's sums into its own slab (read-modify-write by the one thread that owns an element): dw1m_partial / dw2m_partial [n_partial][C][H][d][d],
+ * drel_partial [n_partial][C][2 L - 1][H] (sums of dS per pair index and k - q; NULL iff rel is NULL).  gamer_colsum_reduce adds
+ * the slabs in order: no float atomics, the same bits on every run. */
+int gamer_mbs_attn_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* types,
+                       const float* w1m, const float* w2m, const float* rel, const int32_t* bucket, int num_buckets, int B, int L,
+                       int H, int head_dim, int n_behaviors, float scale, float p_drop, uint64_t seed, const float* o,
+                       const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
+                       float* dw1m_partial, float* dw2m_partial, float* drel_partial, int n_partial, void* stream);
+/* dbias [n_pairs][num_buckets][H] = sum over the offsets r with bucket[r] == bucket of drel [n_pairs][2 L - 1][H] (in order) */
+int gamer_mbs_bias_fold(const float* drel, const int32_t* bucket, int L, int n_pairs, int num_buckets, int H, float* dbias,
+                        void* stream);
+/* CGC head: gates [M][E] = softmax(logits [M][ldl >= E]), mix [M][H] = sum_e gates_e outs [M][E][H]; a row of type 0: zeros.  E <= 16. */
+int gamer_mbs_gate_mix_fwd(const float* logits, int ldl, const float* outs, const int32_t* types, int M, int E, int H, float* gates,
+                           float* mix, void* stream);
+int gamer_mbs_gate_mix_bwd(const float* gates, const float* outs, const float* dmix, int M, int E, int H, float* douts,
+                           float* dlogits, int lddl, void* stream);
+
 /* misc */
 int gamer_fill_f32(float* p, int64_t n, float value, void* stream);
 
