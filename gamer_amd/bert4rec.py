@@ -10,13 +10,13 @@ gets no gradient; saved and loaded), ``item_embedding`` [n_items + 2, H] (row 0 
 Every step runs as HIP kernels, with no PyTorch fallback:
   masking       reconstruct_train_data: gamer_cloze_mask (masked sequence, labels, and the row-major list of the M masked
                 positions with their targets, which the head consumes)
-  input block   SASRec's: gamer_seq_embed_ln_fwd and its backward, the item table's gradient buffer shared with the head
+  input block   rec_common.InputBlockFn (SASRec's too): gamer_seq_embed_ln_fwd and its backward, the item table's gradient buffer shared with the head
   encoder       gamer_amd.modules.TransformerEncoder with the bidirectional (key padding only) additive mask
   output chain  head.out(output_ln(gelu(output_ffn(x)))) then ReLU, on the M gathered rows only (the reference applies
                 output_ffn to all B L rows and gathers afterwards: the same values and gradients): fp32 GEMMs,
                 gamer_bias_act_fwd / _bwd, gamer_layernorm_fwd / _bwd
   head          nn.CrossEntropyLoss()(y @ E[:n_items + 1]^T + head.bias, target): gamer_catalog_ce_bias_fwd / _bwd, which never
-                write the [M, n_items + 1] scores; ranking: gamer_catalog_topk_bias
+                write the [M, n_items + 1] scores; ranking: gamer_catalog_topk_bias (rec_common.ClozeMixin, shared with MBSTR)
 
 Reference behaviour kept on purpose:
   * ``apply(_init_weights)`` reaches the item table through ``item_embedding`` and through ``head.token_embeddings`` (nn.Module.apply
@@ -34,19 +34,19 @@ Reference behaviour kept on purpose:
 from __future__ import annotations
 
 import dataclasses
-import json
-import os
 
 import torch
 from torch import nn
 
 from . import modules, ops
-from .sasrec import _CatalogCEFn, _InputBlockFn, _next_seed, _SharedGrad
+from .rec_common import (ClozeMixin, DotProductPredictionHead, DropUnknownConfig, InputBlockFn, _next_seed, layernorm_bwd,
+                         linear_act_bwd)
 
 
 @dataclasses.dataclass(init=False)
-class BERT4RecConfig:
-    """The fields and defaults of the reference's BERT4RecConfig (ref:SeqRec/models/discriminative/BERT4Rec/config.py)."""
+class BERT4RecConfig(DropUnknownConfig):
+    """The fields and defaults of the reference's BERT4RecConfig (ref:SeqRec/models/discriminative/BERT4Rec/config.py); unknown keys
+    are dropped, as the reference's pydantic model does (the point GRU4RecConfig makes)."""
     n_layers: int = 2
     n_heads: int = 2
     hidden_size: int = 64
@@ -58,37 +58,6 @@ class BERT4RecConfig:
     mask_ratio: float = 0.2
     ft_ratio: float = 0.5
     loss_type: str = "CE"
-
-    def __init__(self, **kwargs):
-        # unknown keys are dropped, as the reference's pydantic model does (the point GRU4RecConfig makes)
-        for f in dataclasses.fields(self):
-            setattr(self, f.name, kwargs.get(f.name, f.default))
-
-    @classmethod
-    def from_dict(cls, d: dict) -> "BERT4RecConfig":
-        return cls(**d)
-
-    @classmethod
-    def from_pretrained(cls, path: str) -> "BERT4RecConfig":
-        f = os.path.join(path, "config.json")
-        if not os.path.exists(f):
-            raise ValueError(f"Can't find a configuration file at {f}.")
-        with open(f, encoding="utf-8") as fh:
-            return cls.from_dict(json.load(fh))
-
-    def to_dict(self) -> dict:
-        return dataclasses.asdict(self)
-
-
-class DotProductPredictionHead(nn.Module):
-    """Parameter holder with the reference's names: ``out.0`` (Linear + ReLU), ``bias`` [1, n_items + 1] and the shared table."""
-
-    def __init__(self, d_model: int, n_items: int, token_embeddings: nn.Embedding):
-        super().__init__()
-        self.token_embeddings = token_embeddings
-        self.vocab_size = n_items + 1
-        self.out = nn.Sequential(nn.Linear(d_model, d_model), nn.ReLU())
-        self.bias = nn.Parameter(torch.zeros(1, self.vocab_size))
 
 
 class _OutputChainFn(torch.autograd.Function):
@@ -118,37 +87,15 @@ class _OutputChainFn(torch.autograd.Function):
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def backward(ctx, dout):
         xg, rows, w1, pre1, a1, lnw, mean, rstd, y1, w2, pre2 = ctx.saved_tensors
-        M, H = xg.shape
-        f32 = dict(dtype=torch.float32, device=xg.device)
-
-        def colsum(partial):
-            out = torch.empty(H, **f32)
-            ops.colsum_reduce(partial, out)
-            return out
-        g = dout.contiguous().float().clone()
-        pb = torch.empty(modules._N_PARTIAL, H, **f32)
-        ops.bias_act_bwd(pre2, g, ops.ACTIVATIONS["relu"], g, pb)
-        db2 = colsum(pb)
-        dw2 = torch.zeros_like(w2)
-        ops.linear_wgrad(g, H, y1, H, dw2, H, M, H, H)
-        dy1 = torch.empty(M, H, **f32)
-        ops.linear_dgrad(g, H, w2, H, dy1, H, M, H, H)
-        da1 = torch.empty(M, H, **f32)
-        pw, pb2 = torch.empty(modules._N_PARTIAL, H, **f32), torch.empty(modules._N_PARTIAL, H, **f32)
-        ops.layernorm_bwd(a1, lnw, mean, rstd, dy1, da1, pw, pb2)
-        dlnw, dlnb = colsum(pw), colsum(pb2)
-        ops.bias_act_bwd(pre1, da1, ops.ACTIVATIONS["gelu"], da1, pb)
-        db1 = colsum(pb)
-        dw1 = torch.zeros_like(w1)
-        ops.linear_wgrad(da1, H, xg, H, dw1, H, M, H, H)
-        dxg = torch.empty(M, H, **f32)
-        ops.linear_dgrad(da1, H, w1, H, dxg, H, M, H, H)
-        dx = torch.zeros(ctx.x_shape, **f32)
-        dx.view(-1, H)[rows] = dxg                                  # (rows are distinct positions)
+        dy1, dw2, db2 = linear_act_bwd(dout.contiguous().float().clone(), pre2, y1, w2, ops.ACTIVATIONS["relu"])
+        da1, dlnw, dlnb = layernorm_bwd(a1, lnw, mean, rstd, dy1)
+        dxg, dw1, db1 = linear_act_bwd(da1, pre1, xg, w1, ops.ACTIVATIONS["gelu"])
+        dx = torch.zeros(ctx.x_shape, dtype=torch.float32, device=xg.device)
+        dx.view(-1, xg.shape[1])[rows] = dxg                        # (rows are distinct positions)
         return dx, None, dw1, db1, dlnw, dlnb, None, dw2, db2
 
 
-class BERT4Rec(nn.Module):
+class BERT4Rec(ClozeMixin, nn.Module):
     def __init__(self, config: BERT4RecConfig, n_items: int, max_his_len: int, **kwargs):
         super().__init__()
         if config.loss_type != "CE":
@@ -192,8 +139,7 @@ class BERT4Rec(nn.Module):
 
     # ---- masking ---------------------------------------------------------------------------------------------------------------
     def _cloze(self, item_seq: torch.Tensor, seq_len: torch.Tensor, seed=None, want_words=False):
-        if not item_seq.is_cuda:
-            raise RuntimeError("gamer_amd.bert4rec runs on the HIP device only (no CPU fallback)")
+        self._require_device(item_seq)
         B, L = item_seq.shape
         n = seq_len.to(item_seq.device).long().contiguous()
         lo, hi = torch.stack([seq_len.min(), seq_len.max()]).tolist() if seq_len.shape == (B,) else (0, 0)     # (one host read)
@@ -220,13 +166,12 @@ class BERT4Rec(nn.Module):
         return (1.0 - keep) * torch.finfo(torch.float32).min
 
     def _encode(self, item_seq: torch.Tensor, shared=None) -> torch.Tensor:
-        if not item_seq.is_cuda:
-            raise RuntimeError("gamer_amd.bert4rec runs on the HIP device only (no CPU fallback)")
+        self._require_device(item_seq)
         if item_seq.size(1) > self.max_seq_length:
             raise ValueError(f"sequence length {item_seq.size(1)} > max_his_len {self.max_seq_length}")
         p = self.dropout_prob if self.training else 0.0
-        x = _InputBlockFn.apply(item_seq.long().contiguous(), self.item_embedding.weight, self.position_embedding.weight,
-                                self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps, p, _next_seed(), shared)
+        x = InputBlockFn.apply(item_seq.long().contiguous(), self.item_embedding.weight, self.position_embedding.weight,
+                               self.LayerNorm.weight, self.LayerNorm.bias, self.layer_norm_eps, p, _next_seed(), shared)
         return self.trm_encoder(x, self.get_attention_mask(item_seq))
 
     def _head_input(self, item_seq: torch.Tensor, rows: torch.Tensor, shared=None) -> torch.Tensor:
@@ -236,79 +181,22 @@ class BERT4Rec(nn.Module):
         return _OutputChainFn.apply(x, rows, self.output_ffn.weight, self.output_ffn.bias, self.output_ln.weight,
                                     self.output_ln.bias, self.layer_norm_eps, lin.weight, lin.bias)
 
-    def _logits(self, y: torch.Tensor) -> torch.Tensor:
-        V, H = self.n_items + 1, self.hidden_size
-        M = y.shape[0]
-        out = torch.empty(M, V, dtype=torch.float32, device=y.device)
-        with ops.f32_matmul("f32"):
-            ops.linear_fwd(y.contiguous(), H, self.item_embedding.weight[:V].detach(), H, out, V, M, V, H)
-        return out + self.head.bias.detach()
-
+    # ---- the cloze task (ClozeMixin: _loss, calculate_loss, full_sort_predict, full_sort_topk) -----------------------------------
     def forward(self, item_seq: torch.Tensor, labels: torch.Tensor, candidates=None):
         """(valid_logits [M, n_items + 1], valid_labels [M]) of the positions with labels != 0, the scores materialised (tests and
         small catalogues; no gradient flows through the scores: training goes through calculate_loss)."""
-        if candidates is not None:
-            raise NotImplementedError("BERT4Rec.forward: candidates (the negative-sampling tasks) are not supported on the HIP path")
-        flat = labels.to(item_seq.device).flatten()
-        rows = (flat != 0).nonzero()[:, 0]
-        if rows.numel() == 0:
-            return torch.empty(0, self.n_items + 1, device=item_seq.device), flat[rows]
-        with torch.no_grad():
-            y = self._head_input(item_seq, rows)
-            return self._logits(y), flat[rows]
+        self._refuse_candidates(candidates)
+        return self._scores_at_labels(item_seq, labels)
 
-    # ---- training --------------------------------------------------------------------------------------------------------------
-    def _loss(self, masked: torch.Tensor, rows: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
-        if rows.numel() == 0:
-            # what nn.CrossEntropyLoss gives for no rows: NaN, with an all-zero gradient for every parameter of the graph
-            params = [p for n, p in self.named_parameters() if n != "output_bias" and "feed_forward.LayerNorm" not in n]
-            return sum((p * 0.0).sum() for p in params) + float("nan")
-        shared = _SharedGrad() if torch.is_grad_enabled() and self.item_embedding.weight.requires_grad else None
-        y = self._head_input(masked, rows, shared)
-        all_rows = torch.arange(y.shape[0], device=y.device)
-        return _CatalogCEFn.apply(y, all_rows, self.item_embedding.weight, targets, shared, self.head.bias, self.n_items + 1)
+    def _extra(self, item_seq, interaction):
+        self._require_device(item_seq)
+        return ()
 
-    def calculate_loss(self, interaction: dict, masked_labels=None) -> torch.Tensor:
-        """The cloze loss of one batch.  ``masked_labels`` = (masked_item_seq, labels) injects the masking (parity tests); by
-        default gamer_cloze_mask draws it.  One host read (the number of masked positions M) per step.  M = 0: NaN, and
-        backward() leaves every parameter gradient exactly zero, as the reference."""
-        if masked_labels is None:
-            masked, _, rows, targets, count = self._cloze(interaction["inputs"], interaction["seq_len"])
-            M = int(count.item())
-            rows, targets = rows[:M], targets[:M]
-        else:
-            masked, labels = masked_labels
-            if not masked.is_cuda:
-                raise RuntimeError("gamer_amd.bert4rec runs on the HIP device only (no CPU fallback)")
-            flat = labels.to(masked.device).long().flatten()
-            rows = (flat != 0).nonzero()[:, 0]
-            targets = flat[rows]
-        self.last_masked_count = int(rows.numel())
-        return self._loss(masked.long().contiguous(), rows.contiguous(), targets.contiguous())
+    def _draw_cloze(self, interaction: dict):
+        masked, _, rows, targets, count = self._cloze(interaction["inputs"], interaction["seq_len"])
+        M = int(count.item())                              # (the step's host read: the number of masked positions)
+        return masked, (), rows[:M], targets[:M]
 
-    # ---- ranking ---------------------------------------------------------------------------------------------------------------
     @staticmethod
-    def _last_rows(item_seq, item_seq_len):
-        B, S = item_seq.shape
-        n = item_seq_len.to(item_seq.device).long()
-        if n.shape != (B,) or int(n.min()) < 1 or int(n.max()) > S:
-            raise IndexError(f"seq_len must hold {B} values in [1, {S}]")
-        return torch.arange(B, device=item_seq.device) * S + (n - 1)
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction: dict) -> torch.Tensor:
-        """[B, n_items + 1] scores (bias added) from position seq_len - 1 of the input as given: the evaluation data already ends
-        with the mask token.  ``item_range`` is ignored, as in the reference.  Small catalogues and tests."""
-        item_seq = interaction["inputs"]
-        rows = self._last_rows(item_seq, interaction["seq_len"])
-        return self._logits(self._head_input(item_seq, rows))
-
-    @torch.no_grad()
-    def full_sort_topk(self, interaction: dict, k: int):
-        """(indices [B, k], scores [B, k]) of the k best of items [0, n_items + 1), as a stable argsort of full_sort_predict reads
-        them (lower index on ties); the scores are never materialised (gamer_catalog_topk_bias); <MASK> is never scored."""
-        item_seq = interaction["inputs"]
-        rows = self._last_rows(item_seq, interaction["seq_len"])
-        y = self._head_input(item_seq, rows)
-        V = self.n_items + 1
-        return ops.catalog_topk_bias(y, self.item_embedding.weight.detach(), self.head.bias.detach().reshape(-1), k, 0, V, V=V)
+    def _in_graph(name: str) -> bool:
+        return name != "output_bias" and "feed_forward.LayerNorm" not in name

@@ -10,8 +10,8 @@ Every step runs as HIP kernels, with no PyTorch fallback (nn.GRU's forward is ne
                 gamer_embedding_bwd_large (padding row skipped) into the head's item-table gradient
   GRU layer     gi = x W_ih^T (fp32 GEMM over B L rows), then gamer_gru_fwd: all L steps in one launch; backward: gamer_gru_bwd
                 (one launch), dW_ih = dgi^T x, dW_hh = dgh_next^T h, dx = dgi W_ih (fp32 GEMMs)
-  dense         on the gathered rows (position seq_len - 1) only: the only rows the output reads
-  head          sasrec's catalogue-wide CE (gamer_catalog_ce_fwd / _bwd) and top K (gamer_catalog_topk), one shared [V, E]
+  dense         on the gathered rows (position seq_len - 1) only: the only rows the output reads (rec_common.GatherLinearFn)
+  head          rec_common's catalogue-wide CE (gamer_catalog_ce_fwd / _bwd) and top K (gamer_catalog_topk), one shared [V, E]
                 item-table gradient
 
 Reference behaviour kept on purpose:
@@ -25,81 +25,25 @@ Reference behaviour kept on purpose:
 from __future__ import annotations
 
 import dataclasses
-import json
-import os
-import warnings
 
 import torch
 from torch import nn
 from torch.nn.init import xavier_normal_, xavier_uniform_
 
-from . import modules, ops
-from .sasrec import SASRec, _CatalogCEFn, _next_seed, _SharedGrad
+from . import ops
+from .rec_common import CatalogCEFn, ConfigBase, EmbedDropoutFn, GatherLinearFn, SeqRecMixin, _next_seed
 
 
 @dataclasses.dataclass
-class GRU4RecConfig:
-    """The fields and defaults of the reference's GRU4RecConfig (ref:SeqRec/models/discriminative/GRU4Rec/config.py)."""
+class GRU4RecConfig(ConfigBase):
+    """The fields and defaults of the reference's GRU4RecConfig (ref:SeqRec/models/discriminative/GRU4Rec/config.py).  The
+    reference's pydantic model drops unknown keys without a word; from_dict says which ones are dropped."""
     embedding_size: int = 64
     hidden_size: int = 128
     n_layers: int = 1
     dropout: float = 0.3
     loss_type: str = "CE"
-
-    @classmethod
-    def from_dict(cls, d: dict) -> "GRU4RecConfig":
-        names = {f.name for f in dataclasses.fields(cls)}
-        unknown = sorted(set(d) - names)
-        if unknown:
-            # the reference's pydantic model drops unknown keys without a word; say which ones are dropped
-            warnings.warn(f"GRU4RecConfig: ignoring unknown keys {unknown} (as the reference does)", stacklevel=2)
-        return cls(**{k: v for k, v in d.items() if k in names})
-
-    @classmethod
-    def from_pretrained(cls, path: str) -> "GRU4RecConfig":
-        f = os.path.join(path, "config.json")
-        if not os.path.exists(f):
-            raise ValueError(f"Can't find a configuration file at {f}.")
-        with open(f, encoding="utf-8") as fh:
-            return cls.from_dict(json.load(fh))
-
-    def to_dict(self) -> dict:
-        return dataclasses.asdict(self)
-
-
-class _EmbedDropoutFn(torch.autograd.Function):
-    """emb_dropout(E[ids]) for ids [B, L]; the gradient of E (padding row 0 skipped) into the shared table gradient."""
-
-    @staticmethod
-    def forward(ctx, ids, E, p, seed, shared=None):
-        B, L = ids.shape
-        D = E.shape[1]
-        x = torch.empty(B * L, D, dtype=torch.float32, device=E.device)
-        ops.embedding_fwd(ids, E, x)
-        if p > 0:
-            y = torch.zeros_like(x)
-            ops.residual_dropout_fwd(y, x, p, seed)               # y = 0 + drop(x)
-            x = y
-        ctx.meta = (p, seed, E.shape)
-        ctx.shared = shared
-        ctx.save_for_backward(ids)
-        return x.view(B, L, D)
-
-    @staticmethod
-    def backward(ctx, dx):
-        ids, = ctx.saved_tensors
-        p, seed, e_shape = ctx.meta
-        g = dx.reshape(-1, e_shape[1]).contiguous().float()
-        if p > 0:
-            gm = torch.empty_like(g)
-            ops.residual_dropout_bwd(g, p, seed, gm)
-            g = gm
-        dE = ctx.shared.dE if ctx.shared is not None and ctx.shared.dE is not None else \
-            torch.zeros(e_shape, dtype=torch.float32, device=g.device)
-        if ctx.shared is not None:
-            ctx.shared.dE = None
-        ops.embedding_bwd_large(ids, g, 0, dE)
-        return None, dE, None, None, None
+    _unknown_keys = "warn"
 
 
 class _GRULayerFn(torch.autograd.Function):
@@ -142,45 +86,7 @@ class _GRULayerFn(torch.autograd.Function):
         return dx, dw_ih, dw_hh, None, None
 
 
-class _GatherDenseFn(torch.autograd.Function):
-    """dense(h[rows]) for the rows of h's [B L, H] view: [R, E]; dh is zero outside the gathered rows."""
-
-    @staticmethod
-    @ops.scoped_f32_matmul(lambda *a: "f32")
-    def forward(ctx, h, rows, w, b):
-        H = h.shape[-1]
-        E = w.shape[0]
-        hl = h.reshape(-1, H)[rows].contiguous()
-        R = hl.shape[0]
-        out = torch.empty(R, E, dtype=torch.float32, device=h.device)
-        ops.linear_fwd(hl, H, w, H, out, E, R, E, H)
-        ops.bias_act_fwd(out, b, 0)
-        ctx.save_for_backward(hl, rows, w)
-        ctx.h_shape = h.shape
-        return out
-
-    @staticmethod
-    @ops.scoped_f32_matmul(lambda *a: "f32")
-    def backward(ctx, dout):
-        hl, rows, w = ctx.saved_tensors
-        R, H = hl.shape
-        E = w.shape[0]
-        f32 = dict(dtype=torch.float32, device=hl.device)
-        g = dout.contiguous().float().clone()
-        pb = torch.empty(modules._N_PARTIAL, E, **f32)
-        ops.bias_act_bwd(None, g, 0, g, pb)
-        db = torch.empty(E, **f32)
-        ops.colsum_reduce(pb, db)
-        dw = torch.zeros_like(w)
-        ops.linear_wgrad(g, E, hl, H, dw, H, R, E, H)
-        dhl = torch.empty(R, H, **f32)
-        ops.linear_dgrad(g, E, w, H, dhl, H, R, E, H)
-        dh = torch.zeros(ctx.h_shape, **f32)
-        dh.view(-1, H)[rows] = dhl                                  # (rows are distinct: one per sequence)
-        return dh, None, dw, db
-
-
-class GRU4Rec(nn.Module):
+class GRU4Rec(SeqRecMixin, nn.Module):
     def __init__(self, config: GRU4RecConfig, n_items: int, **kwargs):
         super().__init__()
         if config.loss_type == "BPR":
@@ -213,19 +119,16 @@ class GRU4Rec(nn.Module):
             xavier_uniform_(module.weight_hh_l0)
             xavier_uniform_(module.weight_ih_l0)
 
-    _last_rows = staticmethod(SASRec._last_rows)
-
     def _encode(self, item_seq: torch.Tensor, rows: torch.Tensor, lens: torch.Tensor, shared=None) -> torch.Tensor:
         """dense(GRU(emb_dropout(E[ids])))[rows]: [R, E]"""
-        if not item_seq.is_cuda:
-            raise RuntimeError("gamer_amd.gru4rec runs on the HIP device only (no CPU fallback)")
+        self._require_device(item_seq)
         p = self.dropout_prob if self.training else 0.0
-        x = _EmbedDropoutFn.apply(item_seq.long().contiguous(), self.item_embedding.weight, p, _next_seed(), shared)
+        x = EmbedDropoutFn.apply(item_seq.long().contiguous(), self.item_embedding.weight, p, _next_seed(), shared)
         for k in range(self.num_layers):
             w_ih, w_hh = getattr(self.gru_layers, f"weight_ih_l{k}"), getattr(self.gru_layers, f"weight_hh_l{k}")
             train = torch.is_grad_enabled() and (x.requires_grad or w_ih.requires_grad or w_hh.requires_grad)
             x = _GRULayerFn.apply(x, w_ih, w_hh, lens, train)      # (train: keep the gates for the backward)
-        return _GatherDenseFn.apply(x, rows, self.dense.weight, self.dense.bias)
+        return GatherLinearFn.apply(x, rows, self.dense.weight, self.dense.bias, ops.ACTIVATIONS["none"])
 
     def _rows_and_lens(self, item_seq, item_seq_len):
         rows = self._last_rows(item_seq, item_seq_len)
@@ -238,14 +141,11 @@ class GRU4Rec(nn.Module):
     def calculate_loss(self, interaction: dict) -> torch.Tensor:
         item_seq = interaction["inputs"]
         rows, lens = self._rows_and_lens(item_seq, interaction["seq_len"])
-        shared = _SharedGrad() if torch.is_grad_enabled() and self.item_embedding.weight.requires_grad else None
+        shared = self._shared_grad()
         out = self._encode(item_seq, rows, lens, shared)
         target = interaction["target"].to(item_seq.device).long().contiguous()
         all_rows = torch.arange(out.shape[0], device=out.device)
-        return _CatalogCEFn.apply(out, all_rows, self.item_embedding.weight, target, shared)
-
-    # [B, n_items + 1] scores as the reference builds them (-inf outside item_range); small catalogues and tests
-    full_sort_predict = SASRec.full_sort_predict
+        return CatalogCEFn.apply(out, all_rows, self.item_embedding.weight, target, shared)
 
     @torch.no_grad()
     def full_sort_topk(self, interaction: dict, k: int):

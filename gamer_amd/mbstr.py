@@ -20,6 +20,7 @@ else (t_q - 1) b + t_k.  Every step runs as HIP kernels, with no PyTorch fallbac
   head          CGC on the M masked rows only: the shared experts as one GEMM, the specific experts and the gates grouped by type,
                 gamer_mbs_gate_mix_fwd / _bwd, LayerNorm, then gamer_catalog_ce_fwd / _bwd on items [0, n_items]; ranking:
                 gamer_catalog_topk.  behavior_head=False: BERT4Rec's DotProductPredictionHead on the biased catalogue kernels.
+                The cloze task around it is rec_common.ClozeMixin, which BERT4Rec uses too; the types ride along as its ``extra``.
 
 Reference behaviour kept on purpose:
   * ``apply(_init_weights)`` redraws Linear / Embedding weights and ``query`` / ``key`` / ``value`` with normal(0,
@@ -34,23 +35,22 @@ Not the reference's: keys are masked by their TYPE (0 = padding), which is the i
 from __future__ import annotations
 
 import dataclasses
-import json
 import math
-import os
 
 import torch
 from torch import nn
 
 from . import modules, ops
-from .bert4rec import DotProductPredictionHead
-from .sasrec import _CatalogCEFn, _next_seed, _SharedGrad
+from .rec_common import (ClozeMixin, DotProductPredictionHead, DropUnknownConfig, EmbedDropoutFn, GatherLinearFn, _next_seed,
+                         colsum, layernorm_bwd)
 
 _REF_FFN_ERROR = "'FeedForward' object has no attribute 'dropout'"
 
 
 @dataclasses.dataclass(init=False)
-class MBSTRConfig:
-    """The fields and defaults of the reference's MBSTRConfig (ref:SeqRec/models/discriminative/MBSTR/config.py)."""
+class MBSTRConfig(DropUnknownConfig):
+    """The fields and defaults of the reference's MBSTRConfig (ref:SeqRec/models/discriminative/MBSTR/config.py); unknown keys are
+    dropped, as the reference's pydantic model does."""
     n_layers: int = 2
     n_heads: int = 2
     hidden_size: int = 64
@@ -69,26 +69,6 @@ class MBSTRConfig:
     behavior_position_bias: bool = True
     n_shared_experts: int = 3
     n_specific_experts: int = 1
-
-    def __init__(self, **kwargs):
-        # unknown keys are dropped, as the reference's pydantic model does
-        for f in dataclasses.fields(self):
-            setattr(self, f.name, kwargs.get(f.name, f.default))
-
-    @classmethod
-    def from_dict(cls, d: dict) -> "MBSTRConfig":
-        return cls(**d)
-
-    @classmethod
-    def from_pretrained(cls, path: str) -> "MBSTRConfig":
-        f = os.path.join(path, "config.json")
-        if not os.path.exists(f):
-            raise ValueError(f"Can't find a configuration file at {f}.")
-        with open(f, encoding="utf-8") as fh:
-            return cls.from_dict(json.load(fh))
-
-    def to_dict(self) -> dict:
-        return dataclasses.asdict(self)
 
 
 def relative_position_buckets(L: int, num_buckets: int, max_distance: int) -> torch.Tensor:
@@ -170,12 +150,6 @@ class _TypeLists:
         work = torch.empty((B + 1) * (b + 1), dtype=torch.int32, device=dev)
         ops.expert_lists(types, b + 1, perm, slot, self.offsets, work)
         self.perm = perm.long()
-
-
-def _colsum(partial):
-    out = torch.empty(partial.shape[1], dtype=torch.float32, device=partial.device)
-    ops.colsum_reduce(partial, out)
-    return out
 
 
 def _with_ones(x, pad=4):
@@ -276,10 +250,7 @@ class _MBSLayerFn(torch.autograd.Function):
         grp = dict(groups=b, group_offsets=offs[1:])
         g = dout.reshape(T, H).contiguous().float()
         # LayerNorm(y1 + dropout(ffn))
-        dv2 = torch.empty(T, H, **f32)
-        pw, pb = torch.empty(NP, H, **f32), torch.empty(NP, H, **f32)
-        ops.layernorm_bwd(v2, ln2w, mean2, rstd2, g, dv2, pw, pb)
-        dln2w, dln2b = _colsum(pw), _colsum(pb)
+        dv2, dln2w, dln2b = layernorm_bwd(v2, ln2w, mean2, rstd2, g)
         df2 = torch.empty(T, H, **f32)
         ops.residual_dropout_bwd(dv2, p, seeds[2], df2)                           # dv2 stays = d y1 (residual branch)
         df2s = df2.index_select(0, perm)
@@ -295,9 +266,7 @@ class _MBSLayerFn(torch.autograd.Function):
         dy1 = dv2
         dy1.index_add_(0, perm, dy1s)                                             # (perm is a permutation: one addend per row)
         # LayerNorm(x + dropout(context))
-        dv1 = torch.empty(T, H, **f32)
-        ops.layernorm_bwd(v1, ln1w, mean1, rstd1, dy1, dv1, pw, pb)
-        dln1w, dln1b = _colsum(pw), _colsum(pb)
+        dv1, dln1w, dln1b = layernorm_bwd(v1, ln1w, mean1, rstd1, dy1)
         dctx = torch.empty(T, H, **f32)
         ops.residual_dropout_bwd(dv1, p, seeds[1], dctx)                          # dv1 stays = d x (residual branch)
         n = ops.mbs_n_partial(B, h, d, b)
@@ -306,14 +275,14 @@ class _MBSLayerFn(torch.autograd.Function):
         pr = torch.zeros(n, C_, 2 * L - 1, h, **f32) if relt is not None else None
         ops.mbs_attn_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lists.types, w1m, w2m, relt, bucket, B, L, h, d, b, mt["scale"],
                          p, seeds[0], ctxv, dctx, lse, dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:], p1, p2, pr)
-        dw1m, dw2m = _colsum(p1.view(n, -1)).view(C_, h, d, d), _colsum(p2.view(n, -1)).view(C_, h, d, d)
+        dw1m, dw2m = colsum(p1.view(n, -1)).view(C_, h, d, d), colsum(p2.view(n, -1)).view(C_, h, d, d)
         dW1, dal1, dW2, dal2 = torch.empty_like(W1), torch.empty_like(alpha1), torch.empty_like(W2), torch.empty_like(alpha2)
         ops.mbs_mix_bwd(W1.contiguous(), alpha1.contiguous(), dw1m, dW1, dal1)
         ops.mbs_mix_bwd(W2.contiguous(), alpha2.contiguous(), dw2m, dW2, dal2)
         drel = ()
         if relt is not None:
             dr = torch.empty_like(relt)
-            ops.mbs_bias_fold(_colsum(pr.view(n, -1)).view(C_, 2 * L - 1, h), bucket, dr)
+            ops.mbs_bias_fold(colsum(pr.view(n, -1)).view(C_, 2 * L - 1, h), bucket, dr)
             drel = tuple(dr[c] for c in range(C_))
         del p1, p2, pr
         dqkv_s = dqkv.index_select(0, perm)
@@ -425,14 +394,10 @@ class _CGCHeadFn(torch.autograd.Function):
         b, ns, nsp, E4 = mt["b"], mt["ns"], mt["nsp"], mt["E4"]
         E = ns + nsp
         M, H = mix.shape
-        NP = modules._N_PARTIAL
         f32 = dict(dtype=torch.float32, device=mix.device)
         grp = dict(groups=b, group_offsets=offs[1:])
         g = dy.contiguous().float().index_select(0, perm)
-        dmix = torch.empty(M, H, **f32)
-        pw, pb = torch.empty(NP, H, **f32), torch.empty(NP, H, **f32)
-        ops.layernorm_bwd(mix, lnw, mean, rstd, g, dmix, pw, pb)
-        dlnw, dlnb = _colsum(pw), _colsum(pb)
+        dmix, dlnw, dlnb = layernorm_bwd(mix, lnw, mean, rstd, g)
         douts, dlogits = torch.empty(M, E * H, **f32), torch.zeros(M, E4, **f32)
         ops.mbs_gate_mix_bwd(gates, outs.view(M, E, H), dmix, douts.view(M, E, H), dlogits)
         dwsh, dwsp, dwg = torch.zeros_like(wsh), torch.zeros_like(wsp), torch.zeros_like(wg)
@@ -457,79 +422,7 @@ class _CGCHeadFn(torch.autograd.Function):
         return (dx, None, None, None, dwg[:, :, :E], dlnw, dlnb, *dexp)
 
 
-class _DotHeadFn(torch.autograd.Function):
-    """relu(head.out.0(x[rows])) for the rows of x's [B L, H] view (DotProductPredictionHead): [M, H]; dx is zero elsewhere."""
-
-    @staticmethod
-    @ops.scoped_f32_matmul(lambda *a: "f32")
-    def forward(ctx, x, rows, w, bias):
-        H = x.shape[-1]
-        f32 = dict(dtype=torch.float32, device=x.device)
-        xg = x.reshape(-1, H)[rows].contiguous()
-        M = xg.shape[0]
-        pre, out = torch.empty(M, H, **f32), torch.empty(M, H, **f32)
-        ops.linear_fwd(xg, H, w, H, pre, H, M, H, H)
-        ops.bias_act_fwd(pre, bias, ops.ACTIVATIONS["relu"], out)
-        ctx.save_for_backward(xg, rows, w, pre)
-        ctx.x_shape = x.shape
-        return out
-
-    @staticmethod
-    @ops.scoped_f32_matmul(lambda *a: "f32")
-    def backward(ctx, dout):
-        xg, rows, w, pre = ctx.saved_tensors
-        M, H = xg.shape
-        f32 = dict(dtype=torch.float32, device=xg.device)
-        g = dout.contiguous().float().clone()
-        pb = torch.empty(modules._N_PARTIAL, H, **f32)
-        ops.bias_act_bwd(pre, g, ops.ACTIVATIONS["relu"], g, pb)
-        db = _colsum(pb)
-        dw = torch.zeros_like(w)
-        ops.linear_wgrad(g, H, xg, H, dw, H, M, H, H)
-        dxg = torch.empty(M, H, **f32)
-        ops.linear_dgrad(g, H, w, H, dxg, H, M, H, H)
-        dx = torch.zeros(ctx.x_shape, **f32)
-        dx.view(-1, H)[rows] = dxg
-        return dx, None, dw, db
-
-
-class _EmbedDropFn(torch.autograd.Function):
-    """dropout(E[ids]) for ids [B, L]; the table's gradient (padding row 0 skipped) goes into the buffer shared with the head."""
-
-    @staticmethod
-    def forward(ctx, ids, E, p, seed, shared=None):
-        B, L = ids.shape
-        H = E.shape[1]
-        f32 = dict(dtype=torch.float32, device=E.device)
-        x = torch.empty(B * L, H, **f32)
-        ops.embedding_fwd(ids, E, x)
-        if p > 0:
-            ops.residual_dropout_fwd(torch.zeros(B * L, H, **f32), x, p, seed, None, x)
-        ctx.meta = (p, seed, E.shape)
-        ctx.shared = shared
-        ctx.save_for_backward(ids)
-        return x.view(B, L, H)
-
-    @staticmethod
-    def backward(ctx, dy):
-        ids, = ctx.saved_tensors
-        p, seed, e_shape = ctx.meta
-        B, L = ids.shape
-        H = e_shape[1]
-        f32 = dict(dtype=torch.float32, device=dy.device)
-        g = dy.reshape(B * L, H).contiguous().float()
-        if p > 0:
-            gm = torch.empty_like(g)
-            ops.residual_dropout_bwd(g, p, seed, gm)
-            g = gm
-        dE = ctx.shared.dE if ctx.shared is not None and ctx.shared.dE is not None else torch.zeros(e_shape, **f32)
-        if ctx.shared is not None:
-            ctx.shared.dE = None
-        ops.embedding_bwd_large(ids, g, 0, dE)
-        return None, dE, None, None, None
-
-
-class MBSTR(nn.Module):
+class MBSTR(ClozeMixin, nn.Module):
     def __init__(self, config: MBSTRConfig, n_items: int, max_his_len: int, n_behaviors: int, **kwargs):
         super().__init__()
         if config.loss_type != "CE":
@@ -592,8 +485,7 @@ class MBSTR(nn.Module):
 
     # ---- masking ---------------------------------------------------------------------------------------------------------------
     def _cloze(self, item_seq: torch.Tensor, seed=None):
-        if not item_seq.is_cuda:
-            raise RuntimeError("gamer_amd.mbstr runs on the HIP device only (no CPU fallback)")
+        self._require_device(item_seq)
         seed = _next_seed() if seed is None else int(seed)
         ones = torch.ones(item_seq.shape[0], dtype=torch.int64, device=item_seq.device)     # (read by the fine-tuning rows only)
         return ops.cloze_mask(item_seq.long().contiguous(), ones, self.mask_ratio, 0.0, self.mask_token, self.max_seq_length, seed)
@@ -616,8 +508,7 @@ class MBSTR(nn.Module):
 
     def _types(self, item_seq, type_seq, extra=None):
         """int32 [B, L] types after ONE host read that checks their range (and fetches ``extra``, a device scalar, with it)"""
-        if not item_seq.is_cuda:
-            raise RuntimeError("gamer_amd.mbstr runs on the HIP device only (no CPU fallback)")
+        self._require_device(item_seq)
         B, L = item_seq.shape
         if L > self.max_seq_length:
             raise ValueError(f"sequence length {L} > max_his_len {self.max_seq_length}")
@@ -633,7 +524,7 @@ class MBSTR(nn.Module):
 
     def _encode(self, item_seq: torch.Tensor, types: torch.Tensor, shared=None) -> torch.Tensor:
         p = self.dropout_prob if self.training else 0.0
-        x = _EmbedDropFn.apply(item_seq.long().contiguous(), self.item_embedding.weight, p, _next_seed(), shared)
+        x = EmbedDropoutFn.apply(item_seq.long().contiguous(), self.item_embedding.weight, p, _next_seed(), shared)
         lists = _TypeLists(types, self.n_behaviors)
         bucket = self._bucket(item_seq.shape[1], item_seq.device) if self.behavior_position_bias else None
         return self.trm_encoder(x, None, type_seq=lists, bucket=bucket)
@@ -643,7 +534,7 @@ class MBSTR(nn.Module):
         x = self._encode(item_seq, types, shared)
         if not self.behavior_head:
             lin = self.head.out[0]
-            return _DotHeadFn.apply(x, rows, lin.weight, lin.bias)
+            return GatherLinearFn.apply(x, rows, lin.weight, lin.bias, ops.ACTIVATIONS["relu"])
         hd = self.head
         meta = dict(b=self.n_behaviors, ns=self.n_shared_experts, nsp=self.n_specific_experts, eps=self.layer_norm_eps)
         experts = []
@@ -652,88 +543,24 @@ class MBSTR(nn.Module):
         rt = types.flatten().index_select(0, rows).contiguous()
         return _CGCHeadFn.apply(x, rows, rt, meta, hd.w_gates, hd.ln.weight, hd.ln.bias, *experts)
 
-    def _logits(self, y: torch.Tensor) -> torch.Tensor:
-        V, H = self.n_items + 1, self.hidden_size
-        M = y.shape[0]
-        out = torch.empty(M, V, dtype=torch.float32, device=y.device)
-        with ops.f32_matmul("f32"):
-            ops.linear_fwd(y.contiguous(), H, self.item_embedding.weight[:V].detach(), H, out, V, M, V, H)
-        return out if self.behavior_head else out + self.head.bias.detach()
-
+    # ---- the cloze task (ClozeMixin: _loss, calculate_loss, full_sort_predict, full_sort_topk) -----------------------------------
     def forward(self, item_seq: torch.Tensor, type_seq: torch.Tensor, labels: torch.Tensor, candidates=None):
         """(valid_logits [M, n_items + 1], valid_labels [M]) of the positions with labels != 0, the scores materialised (tests and
         small catalogues; no gradient flows through the scores: training goes through calculate_loss)."""
-        if candidates is not None:
-            raise NotImplementedError("MBSTR.forward: candidates (the negative-sampling tasks) are not supported on the HIP path")
-        types, _ = self._types(item_seq, type_seq)
-        flat = labels.to(item_seq.device).flatten()
-        rows = (flat != 0).nonzero()[:, 0]
-        if rows.numel() == 0:
-            return torch.empty(0, self.n_items + 1, device=item_seq.device), flat[rows]
-        with torch.no_grad():
-            return self._logits(self._head_input(item_seq, types, rows)), flat[rows]
+        self._refuse_candidates(candidates)
+        return self._scores_at_labels(item_seq, labels, self._types(item_seq, type_seq)[:1])
 
     def sample_sort_predict(self, interaction: dict):
         raise NotImplementedError("MBSTR.sample_sort_predict: candidates (the negative-sampling tasks) are not supported on the HIP path")
 
-    # ---- training --------------------------------------------------------------------------------------------------------------
-    def _loss(self, masked, types, rows, targets) -> torch.Tensor:
-        if rows.numel() == 0:
-            # what nn.CrossEntropyLoss gives for no rows: NaN, with an all-zero gradient for every parameter of the graph
-            params = [p for n, p in self.named_parameters() if not (".FFN." in n and ".LayerNorm." in n)]
-            return sum((p * 0.0).sum() for p in params) + float("nan")
-        shared = _SharedGrad() if torch.is_grad_enabled() and self.item_embedding.weight.requires_grad else None
-        y = self._head_input(masked, types, rows, shared)
-        all_rows = torch.arange(y.shape[0], device=y.device)
-        if self.behavior_head:
-            return _CatalogCEFn.apply(y, all_rows, self.item_embedding.weight, targets, shared, None, self.n_items + 1)
-        return _CatalogCEFn.apply(y, all_rows, self.item_embedding.weight, targets, shared, self.head.bias, self.n_items + 1)
+    def _extra(self, item_seq, interaction):
+        return self._types(item_seq, interaction["behaviors"])[:1]
 
-    def calculate_loss(self, interaction: dict, masked_labels=None) -> torch.Tensor:
-        """The cloze loss of one batch.  ``masked_labels`` = (masked_item_seq, labels) injects the masking (parity tests); by
-        default gamer_cloze_mask draws it.  One host read per step: the number of masked positions M and the range check of the
-        types.  M = 0: NaN, and backward() leaves every parameter gradient exactly zero, as the reference."""
-        item_seq, type_seq = interaction["inputs"], interaction["behaviors"]
-        if masked_labels is None:
-            masked, _, rows, targets, count = self._cloze(item_seq)
-            types, M = self._types(masked, type_seq, count)
-            rows, targets = rows[:M], targets[:M]
-        else:
-            masked, labels = masked_labels
-            types, _ = self._types(masked, type_seq)
-            flat = labels.to(masked.device).long().flatten()
-            rows = (flat != 0).nonzero()[:, 0]
-            targets = flat[rows]
-        self.last_masked_count = int(rows.numel())
-        return self._loss(masked.long().contiguous(), types, rows.contiguous(), targets.contiguous())
+    def _draw_cloze(self, interaction: dict):
+        masked, _, rows, targets, count = self._cloze(interaction["inputs"])
+        types, M = self._types(masked, interaction["behaviors"], count)          # (the step's host read)
+        return masked, (types,), rows[:M], targets[:M]
 
-    # ---- ranking ---------------------------------------------------------------------------------------------------------------
     @staticmethod
-    def _last_rows(item_seq, item_seq_len):
-        B, S = item_seq.shape
-        n = item_seq_len.to(item_seq.device).long()
-        if n.shape != (B,) or int(n.min()) < 1 or int(n.max()) > S:
-            raise IndexError(f"seq_len must hold {B} values in [1, {S}]")
-        return torch.arange(B, device=item_seq.device) * S + (n - 1)
-
-    @torch.no_grad()
-    def full_sort_predict(self, interaction: dict) -> torch.Tensor:
-        """[B, n_items + 1] scores from position seq_len - 1 of the input as given: the evaluation data already ends with the mask
-        token.  Small catalogues and tests."""
-        item_seq = interaction["inputs"]
-        types, _ = self._types(item_seq, interaction["behaviors"])
-        rows = self._last_rows(item_seq, interaction["seq_len"])
-        return self._logits(self._head_input(item_seq, types, rows))
-
-    @torch.no_grad()
-    def full_sort_topk(self, interaction: dict, k: int):
-        """(indices [B, k], scores [B, k]) of the k best of items [0, n_items + 1), as a stable argsort of full_sort_predict reads
-        them (lower index on ties); the scores are never materialised; <MASK> is never scored."""
-        item_seq = interaction["inputs"]
-        types, _ = self._types(item_seq, interaction["behaviors"])
-        rows = self._last_rows(item_seq, interaction["seq_len"])
-        y = self._head_input(item_seq, types, rows)
-        V = self.n_items + 1
-        if self.behavior_head:
-            return ops.catalog_topk(y, self.item_embedding.weight.detach(), k, 0, V)
-        return ops.catalog_topk_bias(y, self.item_embedding.weight.detach(), self.head.bias.detach().reshape(-1), k, 0, V, V=V)
+    def _in_graph(name: str) -> bool:
+        return not (".FFN." in name and ".LayerNorm." in name)

@@ -1311,123 +1311,94 @@ def _rows(h, row_idx):
     return h2, row_idx, 1 if row_idx.dtype == torch.int64 else 0, row_idx.numel()
 
 
-def catalog_ce_fwd(h, row_idx, E, target, lse, loss, bad):
-    """lse [R], loss (0-d) = mean CE of the rows h[row_idx] against target over the whole table E (gamer_catalog_ce_fwd)."""
+def _head(E, biased, bias, V):
+    """(V, H, the bias argument of the entry point): the head scores the first V rows of E, all of them by default (BERT4Rec's
+    table ends with the <MASK> row); only the _bias entry points take a bias"""
+    V = E.shape[0] if V is None else int(V)
+    if not 0 < V <= E.shape[0]:
+        raise RuntimeError(f"catalogue head: V = {V} outside (0, {E.shape[0]}]")
+    if bias is not None and _dense(bias, torch.float32, "bias").numel() < V:
+        raise RuntimeError(f"catalogue head: bias must hold V = {V} values")
+    return V, E.shape[1], ((ptr(bias),) if biased else ())
+
+
+def _catalog_ce_fwd(biased, h, row_idx, E, bias, target, lse, loss, bad, V):
+    name = "catalog_ce_bias_fwd" if biased else "catalog_ce_fwd"
     h2, idx, idx64, R = _rows(h, row_idx)
     _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
     _dense(loss, torch.float32, "loss"), _dense(bad, torch.int32, "bad")
     if target.numel() != R or lse.numel() != R:
-        raise RuntimeError(f"catalog_ce_fwd: target / lse must hold R = {R} values")
-    V, H = E.shape
-    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
-    ws = _ws("ce", h.device, n)
-    call("gamer_catalog_ce_fwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(target), ptr(lse), ptr(loss), ptr(bad),
-         ptr(ws), ws.numel(), stream_ptr())
+        raise RuntimeError(f"{name}: target / lse must hold R = {R} values")
+    V, H, bias_arg = _head(E, biased, bias, V)
+    ws = _ws("ce", h.device, int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0)))
+    call("gamer_" + name, ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, *bias_arg, ptr(target), ptr(lse), ptr(loss),
+         ptr(bad), ptr(ws), ws.numel(), stream_ptr())
 
 
-def catalog_ce_bwd(h, row_idx, E, target, lse, dloss, scale, dE=None, dh=None):
-    """dE += G^T h, dh rows (at row_idx of dh's row view) <- G E, G = (softmax - onehot) * dloss * scale (gamer_catalog_ce_bwd)."""
+def _catalog_ce_bwd(biased, h, row_idx, E, bias, target, lse, dloss, scale, dE, dh, dbias, V):
+    name = "catalog_ce_bias_bwd" if biased else "catalog_ce_bwd"
     h2, idx, idx64, R = _rows(h, row_idx)
     _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
     if dloss is not None:
         _dense(dloss, torch.float32, "dloss")
     if dE is not None and (_dense(dE, torch.float32, "dE").shape != E.shape):
-        raise RuntimeError("catalog_ce_bwd: dE must have E's shape")
-    V, H = E.shape
+        raise RuntimeError(f"{name}: dE must have E's shape")
+    V, H, bias_arg = _head(E, biased, bias, V)
+    if dbias is not None and _dense(dbias, torch.float32, "dbias").numel() < V:
+        raise RuntimeError(f"{name}: dbias must hold V = {V} values")
     if dh is not None:
         _dense(dh, torch.float32, "dh")                 # (a reshape of a strided dh would be a copy: the writes would be lost)
         if dh.shape[-1] != H or (row_idx is None and dh.numel() // H < R):
-            raise RuntimeError("catalog_ce_bwd: dh must be rows of H values covering the gathered rows")
+            raise RuntimeError(f"{name}: dh must be rows of H values covering the gathered rows")
     dh2 = dh.reshape(-1, dh.shape[-1]) if dh is not None else None
-    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
-    ws = _ws("ce", h.device, n)
-    call("gamer_catalog_ce_bwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(target), ptr(lse), ptr(dloss),
-         float(scale), ptr(dE), ptr(dh2), dh2.stride(0) if dh2 is not None else 0, ptr(ws), ws.numel(), stream_ptr())
+    ws = _ws("ce", h.device, int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0)))
+    call("gamer_" + name, ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, *bias_arg, ptr(target), ptr(lse), ptr(dloss),
+         float(scale), ptr(dE), ptr(dh2), dh2.stride(0) if dh2 is not None else 0, *((ptr(dbias),) if biased else ()), ptr(ws),
+         ws.numel(), stream_ptr())
+
+
+def _catalog_topk(biased, h, E, bias, k, start, end, row_idx, V):
+    h2, idx, idx64, R = _rows(h, row_idx)
+    _dense(E, torch.float32, "E")
+    V, H, bias_arg = _head(E, biased, bias, V)
+    end = V if end is None else int(end)
+    ws = _ws("topk", h.device, int(_lib.load().gamer_catalog_ws_bytes(R, max(end - start, 1), H, k)))
+    out_i = torch.empty(R, k, dtype=torch.int64, device=h.device)
+    out_s = torch.empty(R, k, dtype=torch.float32, device=h.device)
+    call("gamer_catalog_topk_bias" if biased else "gamer_catalog_topk", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H,
+         *bias_arg, int(start), end, int(k), ptr(out_i), ptr(out_s), ptr(ws), ws.numel(), stream_ptr())
+    return out_i, out_s
+
+
+def catalog_ce_fwd(h, row_idx, E, target, lse, loss, bad):
+    """lse [R], loss (0-d) = mean CE of the rows h[row_idx] against target over the whole table E (gamer_catalog_ce_fwd)."""
+    _catalog_ce_fwd(False, h, row_idx, E, None, target, lse, loss, bad, None)
+
+
+def catalog_ce_bwd(h, row_idx, E, target, lse, dloss, scale, dE=None, dh=None):
+    """dE += G^T h, dh rows (at row_idx of dh's row view) <- G E, G = (softmax - onehot) * dloss * scale (gamer_catalog_ce_bwd)."""
+    _catalog_ce_bwd(False, h, row_idx, E, None, target, lse, dloss, scale, dE, dh, None, None)
 
 
 def catalog_topk(h, E, k, start=0, end=None, row_idx=None):
     """(indices int64 [R, k], scores [R, k]): the k best items of [start, end) per row, ties to the lower index, -1 past the range."""
-    h2, idx, idx64, R = _rows(h, row_idx)
-    _dense(E, torch.float32, "E")
-    V, H = E.shape
-    end = V if end is None else int(end)
-    n = int(_lib.load().gamer_catalog_ws_bytes(R, max(end - start, 1), H, k))
-    ws = _ws("topk", h.device, n)
-    out_i = torch.empty(R, k, dtype=torch.int64, device=h.device)
-    out_s = torch.empty(R, k, dtype=torch.float32, device=h.device)
-    call("gamer_catalog_topk", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, int(start), end, int(k), ptr(out_i), ptr(out_s),
-         ptr(ws), ws.numel(), stream_ptr())
-    return out_i, out_s
-
-
-def _bias(bias, V):
-    if bias is not None and _dense(bias, torch.float32, "bias").numel() < V:
-        raise RuntimeError(f"catalogue head: bias must hold V = {V} values")
-    return bias
-
-
-def _head_v(E, V):
-    """the number of table rows the head scores: E's rows, or fewer (BERT4Rec's table ends with the <MASK> row)"""
-    V = E.shape[0] if V is None else int(V)
-    if not 0 < V <= E.shape[0]:
-        raise RuntimeError(f"catalogue head: V = {V} outside (0, {E.shape[0]}]")
-    return V
+    return _catalog_topk(False, h, E, None, k, start, end, row_idx, None)
 
 
 def catalog_ce_bias_fwd(h, row_idx, E, bias, target, lse, loss, bad, V=None):
     """catalog_ce_fwd with score(r, v) = h_r . E_v + bias[v] over the first V rows of E (gamer_catalog_ce_bias_fwd);
     bias None: the same kernels and bits as catalog_ce_fwd."""
-    h2, idx, idx64, R = _rows(h, row_idx)
-    _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
-    _dense(loss, torch.float32, "loss"), _dense(bad, torch.int32, "bad")
-    if target.numel() != R or lse.numel() != R:
-        raise RuntimeError(f"catalog_ce_bias_fwd: target / lse must hold R = {R} values")
-    V, H = _head_v(E, V), E.shape[1]
-    _bias(bias, V)
-    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
-    ws = _ws("ce", h.device, n)
-    call("gamer_catalog_ce_bias_fwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(bias), ptr(target), ptr(lse),
-         ptr(loss), ptr(bad), ptr(ws), ws.numel(), stream_ptr())
+    _catalog_ce_fwd(True, h, row_idx, E, bias, target, lse, loss, bad, V)
 
 
 def catalog_ce_bias_bwd(h, row_idx, E, bias, target, lse, dloss, scale, dE=None, dh=None, dbias=None, V=None):
     """catalog_ce_bwd with the bias in the scores; dE rows [0, V) += G^T h, dh <- G E, dbias [V] <- the column sums of G (written)."""
-    h2, idx, idx64, R = _rows(h, row_idx)
-    _dense(E, torch.float32, "E"), _dense(target, torch.int64, "target"), _dense(lse, torch.float32, "lse")
-    if dloss is not None:
-        _dense(dloss, torch.float32, "dloss")
-    if dE is not None and (_dense(dE, torch.float32, "dE").shape != E.shape):
-        raise RuntimeError("catalog_ce_bias_bwd: dE must have E's shape")
-    V, H = _head_v(E, V), E.shape[1]
-    _bias(bias, V)
-    if dbias is not None and _dense(dbias, torch.float32, "dbias").numel() < V:
-        raise RuntimeError(f"catalog_ce_bias_bwd: dbias must hold V = {V} values")
-    if dh is not None:
-        _dense(dh, torch.float32, "dh")                 # (a reshape of a strided dh would be a copy: the writes would be lost)
-        if dh.shape[-1] != H or (row_idx is None and dh.numel() // H < R):
-            raise RuntimeError("catalog_ce_bias_bwd: dh must be rows of H values covering the gathered rows")
-    dh2 = dh.reshape(-1, dh.shape[-1]) if dh is not None else None
-    n = int(_lib.load().gamer_catalog_ws_bytes(R, V, H, 0))
-    ws = _ws("ce", h.device, n)
-    call("gamer_catalog_ce_bias_bwd", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(bias), ptr(target), ptr(lse),
-         ptr(dloss), float(scale), ptr(dE), ptr(dh2), dh2.stride(0) if dh2 is not None else 0, ptr(dbias), ptr(ws), ws.numel(),
-         stream_ptr())
+    _catalog_ce_bwd(True, h, row_idx, E, bias, target, lse, dloss, scale, dE, dh, dbias, V)
 
 
 def catalog_topk_bias(h, E, bias, k, start=0, end=None, row_idx=None, V=None):
     """catalog_topk with score(r, v) = h_r . E_v + bias[v], over [start, end) of the first V rows of E (gamer_catalog_topk_bias)."""
-    h2, idx, idx64, R = _rows(h, row_idx)
-    _dense(E, torch.float32, "E")
-    V, H = _head_v(E, V), E.shape[1]
-    _bias(bias, V)
-    end = V if end is None else int(end)
-    n = int(_lib.load().gamer_catalog_ws_bytes(R, max(end - start, 1), H, k))
-    ws = _ws("topk", h.device, n)
-    out_i = torch.empty(R, k, dtype=torch.int64, device=h.device)
-    out_s = torch.empty(R, k, dtype=torch.float32, device=h.device)
-    call("gamer_catalog_topk_bias", ptr(h2), h2.stride(0), ptr(idx), idx64, R, ptr(E), V, H, ptr(bias), int(start), end, int(k),
-         ptr(out_i), ptr(out_s), ptr(ws), ws.numel(), stream_ptr())
-    return out_i, out_s
+    return _catalog_topk(True, h, E, bias, k, start, end, row_idx, V)
 
 
 def cloze_threshold(ratio: float) -> int:

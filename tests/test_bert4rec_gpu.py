@@ -399,7 +399,7 @@ def test_training_step_does_not_materialise_logits():
 
 
 def test_bert4rec_dropout_training_is_finite_and_repeatable():
-    from gamer_amd import modules, sasrec
+    from gamer_amd import modules, rec_common
     model, z, m = _model()
     model.dropout_prob = 0.5
     for layer in model.trm_encoder.layer:
@@ -408,7 +408,7 @@ def test_bert4rec_dropout_training_is_finite_and_repeatable():
     inter = dict(inputs=torch.from_numpy(z["inputs"]).to(DEV), seq_len=torch.from_numpy(z["seq_len"]).to(DEV))
     res = []
     for _ in range(2):
-        sasrec._Seeds.value = 77                           # (the cloze masks and the input block's dropout draw from this counter)
+        rec_common._Seeds.value = 77                       # (the cloze masks and the input block's dropout draw from this counter)
         modules._SeedCounter.value = 99
         model.zero_grad()
         loss = model.calculate_loss(inter)

@@ -237,13 +237,13 @@ def test_gru4rec_topk_is_a_stable_argsort_of_full_sort_predict():
 
 
 def test_gru4rec_dropout_is_repeatable_and_equals_fp64_with_its_mask():
-    from gamer_amd import ops, sasrec
+    from gamer_amd import ops, rec_common
     model, z, m, inter, p = _model("b")
     model.dropout_prob = 0.3
     model.train()
     res = []
     for _ in range(2):
-        sasrec._Seeds.value = 77
+        rec_common._Seeds.value = 77
         model.zero_grad()
         loss = model.calculate_loss(inter)
         loss.backward()

@@ -100,7 +100,7 @@ def test_catalog_ce_flags_bad_targets():
 
 
 def test_training_step_does_not_materialise_logits():
-    from gamer_amd import sasrec
+    from gamer_amd import rec_common
     from gamer_amd.sasrec import SASRec, SASRecConfig
     R, V, S = 4096, 200_000, 20
     limit = R * V * 4                               # one [R, V] fp32 logits tensor: 3.3 GB
@@ -132,7 +132,7 @@ def test_training_step_does_not_materialise_logits():
 
     def head():
         E.grad = None
-        sasrec._CatalogCEFn.apply(h, torch.arange(R, device=DEV), E, inter["target"]).backward()
+        rec_common.CatalogCEFn.apply(h, torch.arange(R, device=DEV), E, inter["target"]).backward()
     peak = peak_of(head)
     assert peak < 0.05 * limit, peak                  # the head alone: dE, dh and the workspace
 
@@ -289,7 +289,7 @@ def test_sasrec_full_sort_matches_reference(ranged):
 
 
 def test_sasrec_dropout_training_is_finite_and_repeatable():
-    from gamer_amd import sasrec
+    from gamer_amd import rec_common
     model, z, m, inter = _model()
     model.dropout_prob = 0.5
     for layer in model.trm_encoder.layer:
@@ -297,7 +297,7 @@ def test_sasrec_dropout_training_is_finite_and_repeatable():
     model.train()
     res = []
     for _ in range(2):
-        sasrec._Seeds.value = 77
+        rec_common._Seeds.value = 77
         from gamer_amd import modules
         modules._SeedCounter.value = 99
         model.zero_grad()

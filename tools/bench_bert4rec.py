@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from gamer_amd import bert4rec, ops, sasrec  # noqa: E402
+from gamer_amd import bert4rec, ops, rec_common  # noqa: E402
 from gamer_amd.bert4rec import BERT4Rec, BERT4RecConfig  # noqa: E402
 
 DEV = "cuda:0"
@@ -93,7 +93,7 @@ def bench(B, S, items, a):
 
         def fused():
             drop()
-            sasrec._CatalogCEFn.apply(h, rows, E, target, None, bias, V).backward()
+            rec_common.CatalogCEFn.apply(h, rows, E, target, None, bias, V).backward()
 
         def materialised():
             drop()

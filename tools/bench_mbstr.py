@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from gamer_amd import mbstr, ops  # noqa: E402
+from gamer_amd import mbstr, ops, rec_common  # noqa: E402
 from gamer_amd.mbstr import MBSTR, MBSTRConfig  # noqa: E402
 
 DEV = "cuda:0"
@@ -86,12 +86,12 @@ def attention_pair(B, L, h, d, b, g):
         pr = torch.zeros(n, C, 2 * L - 1, h, device=DEV)
         ops.mbs_attn_bwd(q_, k_, v_, t32, w1m, w2m, rel, bucket, B, L, h, d, b, scale, 0.0, 1, o, d_o, lse, dqkv[:, :H],
                          dqkv[:, H:2 * H], dqkv[:, 2 * H:], p1, p2, pr)
-        dw1m, dw2m = mbstr._colsum(p1.view(n, -1)).view(C, h, d, d), mbstr._colsum(p2.view(n, -1)).view(C, h, d, d)
+        dw1m, dw2m = rec_common.colsum(p1.view(n, -1)).view(C, h, d, d), rec_common.colsum(p2.view(n, -1)).view(C, h, d, d)
         dW1, dW2, da1, da2 = torch.empty_like(W1), torch.empty_like(W2), torch.empty_like(a1), torch.empty_like(a2)
         ops.mbs_mix_bwd(W1, a1, dw1m, dW1, da1)
         ops.mbs_mix_bwd(W2, a2, dw2m, dW2, da2)
         drel = torch.empty_like(rel)
-        ops.mbs_bias_fold(mbstr._colsum(pr.view(n, -1)).view(C, 2 * L - 1, h), bucket, drel)
+        ops.mbs_bias_fold(rec_common.colsum(pr.view(n, -1)).view(C, 2 * L - 1, h), bucket, drel)
         return o
 
     leaves = [t.clone().requires_grad_(True) for t in (qkv, W1, a1, W2, a2, rel)]

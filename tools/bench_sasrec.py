@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from gamer_amd import ops, sasrec  # noqa: E402
+from gamer_amd import ops, rec_common  # noqa: E402
 from gamer_amd.sasrec import SASRec, SASRecConfig  # noqa: E402
 
 DEV = "cuda:0"
@@ -84,7 +84,7 @@ def main():
         def fused():
             E.grad = None
             h.grad = None
-            sasrec._CatalogCEFn.apply(h, rows, E, inter["target"]).backward()
+            rec_common.CatalogCEFn.apply(h, rows, E, inter["target"]).backward()
 
         def drop():
             E.grad = None
