@@ -1298,116 +1298,55 @@ attn_row_order_kernel(const int32_t* __restrict__ row_empty, int S, int32_t* __r
 }
 
 template <int G>
-static int launch_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* kl,
-                      const int32_t* ql, const int32_t* row_empty, int B, int S, int nq, int nkv, float scale,
-                      float p_drop, uint64_t seed, float* o, float* lse, RowOrder ro, int uspan, hipStream_t st) {
+static int launch_fwd(const AttnFwdArgs<float>& a) {
     constexpr int R = (4 / G) * 32;
-    dim3 grid(worklist_grid(B * nkv, (S + R - 1) / R));
-#define GAMER_LAUNCH_FWD(DROPV, ORDV, SPANV)                                                                              \
-    hipLaunchKernelGGL((attn_fwd_kernel<G, DROPV, ORDV, SPANV>), grid, dim3(AT_THREADS), 0, st, q, ldq, k, ldk, v, ldv, \
-                       kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan)
-#define GAMER_LAUNCH_FWD2(DROPV, ORDV) do { if (ro.span) GAMER_LAUNCH_FWD(DROPV, ORDV, true); else GAMER_LAUNCH_FWD(DROPV, ORDV, false); } while (0)
-    if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD2(true, true); else GAMER_LAUNCH_FWD2(true, false); }
-    else { if (ro.perm) GAMER_LAUNCH_FWD2(false, true); else GAMER_LAUNCH_FWD2(false, false); }
-#undef GAMER_LAUNCH_FWD2
-#undef GAMER_LAUNCH_FWD
-    GAMER_CHECK_LAUNCH("gamer_attn_fwd");
-    return 0;
+    const dim3 grid(worklist_grid(a.B * a.nkv, (a.S + R - 1) / R));
+    return with_flags([&](auto drop, auto ord, auto span) {
+        return launch<attn_fwd_kernel<G, drop(), ord(), span()>>("gamer_attn_fwd", grid, dim3(AT_THREADS), 0, a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv,
+                                                                a.kl, a.ql, a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.o,
+                                                                a.lse, a.ro, a.uspan);
+    }, a.p_drop > 0.f, a.ro.perm != nullptr, a.ro.span != nullptr);
 }
 
 template <int G, bool DROP, bool ORD, bool SPAN>
-static int launch_bwd_variant(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                              const float* d_o, const float* lse, float* delta, const int32_t* kl, const int32_t* ql,
-                              const int32_t* row_empty, const int32_t* tile_empty, int B, int S, int nq, int nkv,
-                              float scale, float p_drop, uint64_t seed, float* dq, int lddq, float* dk, int lddk,
-                              float* dv, int lddv, RowOrder ro, float* ds_work, int delta_ready, hipStream_t st) {
+static int launch_bwd_variant(const AttnBwdArgs<float>& a) {
     constexpr int R = (4 / G) * 32;
-    dim3 grid(worklist_grid(B * nkv, (S + R - 1) / R));
-    if (ds_work == nullptr) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<G, DROP, ORD, SPAN>), grid, dim3(AT_THREADS), 0, st, q, ldq, k, ldk, v, ldv, o, d_o,
-                           lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, ro);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd/dq");
-    } else if (!delta_ready) {
-        hipLaunchKernelGGL(attn_delta_kernel, dim3(2048), dim3(AT_THREADS), 0, st, o, d_o, B, S, nq, delta);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd/delta");
-    }
+    const dim3 grid(worklist_grid(a.B * a.nkv, (a.S + R - 1) / R));
+    if (a.ds_work == nullptr)
+        GAMER_TRY(launch<attn_bwd_dq_kernel<G, DROP, ORD, SPAN>>("gamer_attn_bwd/dq", grid, dim3(AT_THREADS), 0, a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv,
+                                                               a.o, a.d_o, a.lse, a.delta, a.kl, a.ql, a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale,
+                                                               a.p_drop, a.seed, a.dq, a.lddq, a.ro));
+    else if (!a.delta_ready)
+        GAMER_TRY(launch<attn_delta_kernel>("gamer_attn_bwd/delta", dim3(2048), dim3(AT_THREADS), 0, a.st, a.o, a.d_o, a.B, a.S, a.nq, a.delta));
     size_t shmem = sizeof(DkvSmem<G>);
     const size_t red_bytes = (size_t)R * 132 * sizeof(float);
     if (shmem < red_bytes) shmem = red_bytes;
-    static bool attr_dev[MAX_DEVICES] = {};   // one set of flags per template instantiation, one flag per device
-    bool& attr_set = attr_dev[current_device()];
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_kernel<G, DROP, ORD, SPAN>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) {
-            set_error("gamer_attn_bwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<G, DROP, ORD, SPAN>), grid, dim3(AT_THREADS), shmem, st, q, ldq, k, ldk, v, ldv, d_o, lse,
-                       delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dk, lddk, dv, lddv, ro,
-                       ds_work);
-    GAMER_CHECK_LAUNCH("gamer_attn_bwd/dkv");
-    if (ds_work != nullptr) {
-        const size_t kall = (size_t)((S + 31) / 32) * 32 * KLD * sizeof(float);
+    GAMER_TRY(launch<attn_bwd_dkv_kernel<G, DROP, ORD, SPAN>>("gamer_attn_bwd/dkv", grid, dim3(AT_THREADS), shmem, a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv,
+                                                            a.d_o, a.lse, a.delta, a.kl, a.ql, a.row_empty, a.tile_empty, a.B, a.S, a.nq, a.nkv,
+                                                            a.scale, a.p_drop, a.seed, a.dk, a.lddk, a.dv, a.lddv, a.ro, a.ds_work));
+    if (a.ds_work != nullptr) {
+        const size_t kall = (size_t)((a.S + 31) / 32) * 32 * KLD * sizeof(float);
         if (kall <= 156 * 1024) {
-            static bool attr3_dev[MAX_DEVICES] = {};
-            bool& attr3 = attr3_dev[current_device()];
-            if (!attr3) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq3_kernel<G, ORD>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-                if (e != hipSuccess) {
-                    set_error("gamer_attn_bwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                    return (int)e;
-                }
-                attr3 = true;
-            }
-            hipLaunchKernelGGL((attn_bwd_dq3_kernel<G, ORD>), dim3(B * nkv), dim3(DQ3_THREADS), kall, st, k, ldk, ds_work,
-                               row_empty, S, nq, nkv, scale, dq, lddq, ro);
+            GAMER_TRY(ensure_dynamic_lds<attn_bwd_dq3_kernel<G, ORD>>("gamer_attn_bwd/dq2", 156 * 1024));
+            GAMER_TRY(launch<attn_bwd_dq3_kernel<G, ORD>>("gamer_attn_bwd/dq2", dim3(a.B * a.nkv), dim3(DQ3_THREADS), kall, a.st, a.k, a.ldk, a.ds_work,
+                                                        a.row_empty, a.S, a.nq, a.nkv, a.scale, a.dq, a.lddq, a.ro));
         } else {
-            hipLaunchKernelGGL((attn_bwd_dq2_kernel<G, ORD>), grid, dim3(AT_THREADS), 0, st, k, ldk, ds_work, row_empty, B, S,
-                               nq, nkv, scale, dq, lddq, ro);
+            GAMER_TRY(launch<attn_bwd_dq2_kernel<G, ORD>>("gamer_attn_bwd/dq2", grid, dim3(AT_THREADS), 0, a.st, a.k, a.ldk, a.ds_work, a.row_empty, a.B,
+                                                        a.S, a.nq, a.nkv, a.scale, a.dq, a.lddq, a.ro));
         }
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd/dq2");
     }
     return 0;
 }
 
 template <int G>
-static int launch_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                      const float* d_o, const float* lse, float* delta, const int32_t* kl, const int32_t* ql,
-                      const int32_t* row_empty, const int32_t* tile_empty, int B, int S, int nq, int nkv, float scale,
-                      float p_drop, uint64_t seed, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
-                      RowOrder ro, float* ds_work, int delta_ready, hipStream_t st) {
-#define GAMER_LAUNCH_BWD(DROPV, ORDV, SPANV)                                                                                \
-    return launch_bwd_variant<G, DROPV, ORDV, SPANV>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, \
-                                              S, nq, nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, ds_work, delta_ready, st)
-#define GAMER_LAUNCH_BWD2(DROPV, ORDV) do { if (ro.span) GAMER_LAUNCH_BWD(DROPV, ORDV, true); else GAMER_LAUNCH_BWD(DROPV, ORDV, false); } while (0)
-    if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_BWD2(true, true); else GAMER_LAUNCH_BWD2(true, false); }
-    else { if (ro.perm) GAMER_LAUNCH_BWD2(false, true); else GAMER_LAUNCH_BWD2(false, false); }
-#undef GAMER_LAUNCH_BWD2
-#undef GAMER_LAUNCH_BWD
-    return -1;      // not reached
+static int launch_bwd(const AttnBwdArgs<float>& a) {
+    return with_flags([&](auto drop, auto ord, auto span) { return launch_bwd_variant<G, drop(), ord(), span()>(a); },
+                      a.p_drop > 0.f, a.ro.perm != nullptr, a.ro.span != nullptr);
 }
 
 }  // namespace gamer
 
 using namespace gamer;
-
-static int check_attn_common(const char* name, const void* q, const void* k, const void* v, const void* kl,
-                             const void* row_empty, int ldq, int ldk, int ldv, int B, int S, int nq, int nkv,
-                             float p_drop) {
-    GAMER_CHECK_ARG(q && k && v && kl && row_empty, "%s: null pointer", name);
-    GAMER_CHECK_ARG(B > 0 && S > 0 && nq > 0 && nkv > 0 && nq % nkv == 0, "%s: bad shape B=%d S=%d nq=%d nkv=%d", name, B, S, nq, nkv);
-    const int G = nq / nkv;
-    GAMER_CHECK_ARG(G == 1 || G == 2, "%s: GQA group %d not built (1 or 2)", name, G);
-    GAMER_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq >= nq * 64 && ldk >= nkv * 64 && ldv >= nkv * 64,
-                    "%s: bad leading dims ldq=%d ldk=%d ldv=%d", name, ldq, ldk, ldv);
-    GAMER_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v), "%s: q/k/v must be 16-byte aligned", name);
-    GAMER_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop=%f", name, p_drop);
-    return 0;
-}
 
 extern "C" int gamer_attn_row_order(const int32_t* row_empty, int B, int S, int32_t* perm, int32_t* tile_kind,
                                     int32_t* tile_maxpos, void* stream) {
@@ -1448,15 +1387,11 @@ extern "C" int gamer_attn_fwd(const float* q, int ldq, const float* k, int ldk, 
     GAMER_CHECK_ARG(!row_perm || (tile_kind && tile_maxpos), "gamer_attn_fwd: row_perm needs tile_kind and tile_maxpos");
     GAMER_CHECK_ARG(!q_span || aligned16(q_span), "gamer_attn_fwd: q_span must be 16-byte aligned");
     const RowOrder ro{row_perm, tile_kind, tile_maxpos, q_span};
-    int rc = check_attn_common("gamer_attn_fwd", q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
+    int rc = check_attn("gamer_attn_fwd", false, q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
     if (rc) return rc;
     GAMER_CHECK_ARG(o && lse && aligned16(o), "gamer_attn_fwd: null/unaligned output");
-    hipStream_t st = (hipStream_t)stream;
-    switch (nq / nkv) {
-        case 1: return launch_fwd<1>(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, st);
-        case 2: return launch_fwd<2>(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, st);
-        default: return launch_fwd<2>(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, st);
-    }
+    const AttnFwdArgs<float> a{q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, (hipStream_t)stream};
+    return with_group(nq, nkv, [&](auto g) { return launch_fwd<g()>(a); });
 }
 
 extern "C" int gamer_attn_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
@@ -1466,7 +1401,7 @@ extern "C" int gamer_attn_bwd(const float* q, int ldq, const float* k, int ldk, 
                               int lddq, float* dk, int lddk, float* dv, int lddv, const int32_t* row_perm,
                               const int32_t* tile_kind, const int32_t* tile_maxpos, float* ds_work,
                               const int32_t* q_span, int delta_ready, void* stream) {
-    int rc = check_attn_common("gamer_attn_bwd", q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
+    int rc = check_attn("gamer_attn_bwd", false, q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
     if (rc) return rc;
     GAMER_CHECK_ARG(o && d_o && lse && tile_empty && delta && dq && dk && dv, "gamer_attn_bwd: null pointer");
     GAMER_CHECK_ARG(!row_perm || (tile_kind && tile_maxpos), "gamer_attn_bwd: row_perm needs tile_kind and tile_maxpos");
@@ -1475,10 +1410,7 @@ extern "C" int gamer_attn_bwd(const float* q, int ldq, const float* k, int ldk, 
     GAMER_CHECK_ARG(lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(dq) && aligned16(dk) && aligned16(dv) &&
                     aligned16(d_o) && aligned16(o),
                     "gamer_attn_bwd: gradient buffers must be 16-byte aligned with leading dims %% 4 == 0");
-    hipStream_t st = (hipStream_t)stream;
-    switch (nq / nkv) {
-        case 1: return launch_bwd<1>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, ds_work, delta_ready, st);
-        case 2: return launch_bwd<2>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, ds_work, delta_ready, st);
-        default: return launch_bwd<2>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, ds_work, delta_ready, st);
-    }
+    const AttnBwdArgs<float> a{q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed,
+                               dq, lddq, dk, lddk, dv, lddv, ro, ds_work, delta_ready, (hipStream_t)stream};
+    return with_group(nq, nkv, [&](auto g) { return launch_bwd<g()>(a); });
 }

@@ -22,7 +22,7 @@
 //   No atomics: dQ has its own kernel (the bf16 products are cheap; the exponentials are recomputed).
 // One LDS image serves row reads and transposing reads without bank conflicts: 128-byte rows, the 16-byte chunk index
 // XOR-ed with a 3-bit permutation of the row's bits 1..3 (lds_off below).
-#include "common.h"
+#include "attention_common.h"      // (host side only: the argument bundles, check_attn and the resident kernels' switches)
 #include <stdlib.h>
 
 namespace gamer {
@@ -453,33 +453,6 @@ struct BrSmem {
     int32_t ctr;
     int32_t pad_[5];
 };
-static inline bool br_enabled() {
-    static EnvSwitch sw("GAMER_ATTN_RES");             // (the switch of the fp32 resident kernels: A/B runs)
-    return sw.get(1) != 0;
-}
-#define GAMER_BR_PART(name) ([]() -> bool { static EnvSwitch sw(name); return sw.get(1) != 0; }())
-static inline int br_grid_cap() {
-    static EnvSwitch grid("GAMER_ATTN_RES_GRID");       // (tests force a few persistent workgroups to walk many units)
-    if (grid.get(0) > 0) return grid.get(0);
-    static int cap[MAX_DEVICES] = {};
-    int& c = cap[current_device()];
-    if (c == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess) n = 256;
-        c = n > 0 ? n : 256;
-    }
-    return c;
-}
-// one query head per workgroup when whole pairs do not fill the CUs evenly (see res_split in attention_split_common.h)
-static inline int br_split(int n_pairs, int ways) {
-    if (ways < 2) return 0;
-    static EnvSwitch sp("GAMER_ATTN_RES_SPLIT");
-    if (sp.is_set()) return sp.get(0) != 0;
-    const int ncu = br_grid_cap();
-    const double whole = (double)((n_pairs + ncu - 1) / ncu), halves = 0.58 * (double)((ways * n_pairs + ncu - 1) / ncu);
-    return halves < whole ? 1 : 0;
-}
-
 template <bool DROP>
 __device__ __forceinline__ void br_stage(BrSmem& sm, const bf16_t* __restrict__ kbase, int ldk, const bf16_t* __restrict__ vbase,
                                          int ldv, const int32_t* __restrict__ klb, int S, int tid, const AttnDropout& rng) {
@@ -1635,176 +1608,98 @@ attn_bwd_dkv_bh_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __re
 }
 
 // ---- launchers ------------------------------------------------------------------------------------
+// (the bundles of attention_common.h with T = bf16_t; of their RowOrder the bf16 kernels take perm, tile_maxpos and span)
+static inline QOrdB ord_b(const RowOrder& ro, const int32_t* row_empty) { return QOrdB{ro.perm, ro.tile_maxpos, row_empty}; }
+// the kernels' template arguments from a call's flags: f(DROP, SPAN, ORD); a row order excludes key spans (the entry points check)
+template <typename F>
+static int with_b_variant(float p_drop, const RowOrder& ro, F&& f) {
+    if (ro.perm) return with_flags([&](auto drop) { return f(drop, std::false_type{}, std::true_type{}); }, p_drop > 0.f);
+    return with_flags([&](auto drop, auto span) { return f(drop, span, std::false_type{}); }, p_drop > 0.f, ro.span != nullptr);
+}
+
 template <int G>
-static int launch_fwd_b(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, const int32_t* kl,
-                        const int32_t* ql, int B, int S, int nq, int nkv, float scale, float p_drop, uint64_t seed,
-                        bf16_t* o, float* lse, const int32_t* span, const QOrdB ord, hipStream_t st) {
+static int launch_fwd_b(const AttnFwdArgs<bf16_t>& a) {
     constexpr int R = (4 / G) * 32;
-    if (S <= BR_MAXKEYS && br_enabled()) {
+    const QOrdB ord = ord_b(a.ro, a.row_empty);
+    if (a.S <= BR_MAXKEYS && res_enabled()) {
         // K / V of a (sequence, kv head) resident in LDS
-        const int split = br_split(B * nkv, G);
-        const int n_units = B * nkv * (split ? G : 1);
-        const dim3 rgrid(n_units < br_grid_cap() ? n_units : br_grid_cap());
-        const size_t shmem = sizeof(BrSmem);
-#define GAMER_LAUNCH_FWD_BR(DROPV, SPANV, ORDV)                                                                             \
-        do {                                                                                                                \
-            static bool attr_dev[MAX_DEVICES] = {};                                                                         \
-            if (!attr_dev[current_device()]) {                                                                              \
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_br_kernel<G, DROPV, SPANV, ORDV>), \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);          \
-                if (e != hipSuccess) { set_error("gamer_attn_fwd_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; } \
-                attr_dev[current_device()] = true;                                                                          \
-            }                                                                                                               \
-            hipLaunchKernelGGL((attn_fwd_br_kernel<G, DROPV, SPANV, ORDV>), rgrid, dim3(BR_THREADS), shmem, st, q, ldq, k, ldk, v, ldv, \
-                               kl, ql, B, S, nq, nkv, scale, p_drop, seed, o, lse, span, ord, split);                       \
-        } while (0)
-        if (ord.perm) { if (p_drop > 0.f) GAMER_LAUNCH_FWD_BR(true, false, true); else GAMER_LAUNCH_FWD_BR(false, false, true); }
-        else if (p_drop > 0.f) { if (span) GAMER_LAUNCH_FWD_BR(true, true, false); else GAMER_LAUNCH_FWD_BR(true, false, false); }
-        else { if (span) GAMER_LAUNCH_FWD_BR(false, true, false); else GAMER_LAUNCH_FWD_BR(false, false, false); }
-#undef GAMER_LAUNCH_FWD_BR
-        GAMER_CHECK_LAUNCH("gamer_attn_fwd_bf16/resident");
-        return 0;
+        const int split = res_split(a.B * a.nkv, G);
+        return with_b_variant(a.p_drop, a.ro, [&](auto drop, auto span, auto ordv) {
+            return launch<attn_fwd_br_kernel<G, drop(), span(), ordv()>>("gamer_attn_fwd_bf16/resident", res_grid(a.B * a.nkv * (split ? G : 1)),
+                                                                         dim3(BR_THREADS), sizeof(BrSmem), a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.kl,
+                                                                         a.ql, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.o, a.lse, a.ro.span,
+                                                                         ord, split);
+        });
     }
-    dim3 grid(worklist_grid_b(B * nkv, (S + R - 1) / R, AB_OCC_FWD));
-#define GAMER_LAUNCH_FWD_B(DROPV, SPANV, ORDV)                                                                              \
-    hipLaunchKernelGGL((attn_fwd_b_kernel<G, DROPV, SPANV, ORDV>), grid, dim3(AB_THREADS), 0, st, q, ldq, k, ldk, v, ldv,   \
-                       kl, ql, B, S, nq, nkv, scale, p_drop, seed, o, lse, span, ord)
-    if (ord.perm) { if (p_drop > 0.f) GAMER_LAUNCH_FWD_B(true, false, true); else GAMER_LAUNCH_FWD_B(false, false, true); }
-    else if (p_drop > 0.f) { if (span) GAMER_LAUNCH_FWD_B(true, true, false); else GAMER_LAUNCH_FWD_B(true, false, false); }
-    else { if (span) GAMER_LAUNCH_FWD_B(false, true, false); else GAMER_LAUNCH_FWD_B(false, false, false); }
-#undef GAMER_LAUNCH_FWD_B
-    GAMER_CHECK_LAUNCH("gamer_attn_fwd_bf16");
-    return 0;
+    const dim3 grid(worklist_grid_b(a.B * a.nkv, (a.S + R - 1) / R, AB_OCC_FWD));
+    return with_b_variant(a.p_drop, a.ro, [&](auto drop, auto span, auto ordv) {
+        return launch<attn_fwd_b_kernel<G, drop(), span(), ordv()>>("gamer_attn_fwd_bf16", grid, dim3(AB_THREADS), 0, a.st, a.q, a.ldq, a.k, a.ldk, a.v,
+                                                                    a.ldv, a.kl, a.ql, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.o, a.lse,
+                                                                    a.ro.span, ord);
+    });
 }
 
 template <int G, bool DROP, bool SPAN, bool ORD>
-static int launch_bwd_b_variant(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv,
-                                const bf16_t* d_o, const float* lse, const float* delta, const int32_t* kl,
-                                const int32_t* ql, int B, int S, int nq, int nkv, float scale, float p_drop, uint64_t seed,
-                                bf16_t* dq, int lddq, bf16_t* dk, int lddk, bf16_t* dv, int lddv, const int32_t* span,
-                                const QOrdB ord, hipStream_t st) {
+static int launch_bwd_b_variant(const AttnBwdArgs<bf16_t>& a) {
     constexpr int R = (4 / G) * 32;
-    dim3 grid(worklist_grid_b(B * nkv, (S + R - 1) / R, 2));
+    const QOrdB ord = ord_b(a.ro, a.row_empty);
+    const dim3 grid(worklist_grid_b(a.B * a.nkv, (a.S + R - 1) / R, 2));
     bool dkv_done = false;
     if constexpr (!SPAN) {
         // dK / dV with a query head's Q / dO resident in LDS: whole (sequence, kv head) pairs on persistent workgroups, one per CU;
         // taken when the pairs fill the CUs' rounds (384 pairs on 256 CUs - per-GPU batch 128 - would leave the second round half empty)
-        const int pairs = B * nkv, cap = br_grid_cap();
+        const int pairs = a.B * a.nkv, cap = res_grid_cap();
         const int rounds = (pairs + cap - 1) / cap;
         const bool fills = (double)pairs >= 0.85 * (double)rounds * (double)cap || pairs <= cap;
-        if (S <= BH_ROWS && br_enabled() && GAMER_BR_PART("GAMER_ATTN_RES_DKV_BF16") && fills) {
-            const size_t hshmem = sizeof(BhSmem);
-            static bool hattr_dev[MAX_DEVICES] = {};
-            if (!hattr_dev[current_device()]) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_bh_kernel<G, DROP, ORD>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hshmem);
-                if (e != hipSuccess) {
-                    set_error("gamer_attn_bwd_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                    return (int)e;
-                }
-                hattr_dev[current_device()] = true;
-            }
-            hipLaunchKernelGGL((attn_bwd_dkv_bh_kernel<G, DROP, ORD>), dim3(pairs < cap ? pairs : cap), dim3(BH_THREADS), hshmem, st, q, ldq,
-                               k, ldk, v, ldv, d_o, lse, delta, kl, ql, B, S, nq, nkv, scale, p_drop, seed, dk, lddk, dv, lddv, ord);
-            GAMER_CHECK_LAUNCH("gamer_attn_bwd_bf16/dkv head-resident");
+        if (a.S <= BH_ROWS && res_enabled() && GAMER_RES_PART("GAMER_ATTN_RES_DKV_BF16") && fills) {
+            GAMER_TRY(launch<attn_bwd_dkv_bh_kernel<G, DROP, ORD>>("gamer_attn_bwd_bf16/dkv head-resident", res_grid(pairs), dim3(BH_THREADS), sizeof(BhSmem),
+                                                                 a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.d_o, a.lse, a.delta, a.kl, a.ql, a.B, a.S,
+                                                                 a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dk, a.lddk, a.dv, a.lddv, ord));
             dkv_done = true;
         }
     }
     if (!dkv_done) {
-    size_t shmem = sizeof(DkvSmemB<G>);
-    const size_t red_bytes = (size_t)R * 132 * sizeof(float);
-    if (shmem < red_bytes) shmem = red_bytes;
-    static bool attr_dev[MAX_DEVICES] = {};   // one set of flags per template instantiation, one flag per device
-    bool& attr_set = attr_dev[current_device()];
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_b_kernel<G, DROP, SPAN, ORD>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) {
-            set_error("gamer_attn_bwd_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_set = true;
+        size_t shmem = sizeof(DkvSmemB<G>);
+        const size_t red_bytes = (size_t)R * 132 * sizeof(float);
+        if (shmem < red_bytes) shmem = red_bytes;
+        GAMER_TRY(launch<attn_bwd_dkv_b_kernel<G, DROP, SPAN, ORD>>("gamer_attn_bwd_bf16/dkv", grid, dim3(AB_THREADS), shmem, a.st, a.q, a.ldq, a.k, a.ldk, a.v,
+                                                                  a.ldv, a.d_o, a.lse, a.delta, a.kl, a.ql, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop,
+                                                                  a.seed, a.dk, a.lddk, a.dv, a.lddv, a.ro.span, ord));
     }
-    hipLaunchKernelGGL((attn_bwd_dkv_b_kernel<G, DROP, SPAN, ORD>), grid, dim3(AB_THREADS), shmem, st, q, ldq, k, ldk, v, ldv, d_o,
-                       lse, delta, kl, ql, B, S, nq, nkv, scale, p_drop, seed, dk, lddk, dv, lddv, span, ord);
-    GAMER_CHECK_LAUNCH("gamer_attn_bwd_bf16/dkv");
-    }
-    if (S <= BR_MAXKEYS && br_enabled() && GAMER_BR_PART("GAMER_ATTN_RES_DQ")) {
+    if (a.S <= BR_MAXKEYS && res_enabled() && GAMER_RES_PART("GAMER_ATTN_RES_DQ")) {
         // dQ with K / V of a (sequence, kv head) resident in LDS
-        const int split = br_split(B * nkv, G);
-        const int n_units = B * nkv * (split ? G : 1);
-        const size_t rshmem = sizeof(BrSmem);
-        static bool rattr_dev[MAX_DEVICES] = {};
-        if (!rattr_dev[current_device()]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_br_kernel<G, DROP, SPAN, ORD>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)rshmem);
-            if (e != hipSuccess) {
-                set_error("gamer_attn_bwd_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-            rattr_dev[current_device()] = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_dq_br_kernel<G, DROP, SPAN, ORD>), dim3(n_units < br_grid_cap() ? n_units : br_grid_cap()),
-                           dim3(BR_THREADS), rshmem, st, q, ldq, k, ldk, v, ldv, d_o, lse, delta, kl, ql, B, S, nq, nkv, scale, p_drop,
-                           seed, dq, lddq, span, ord, split);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_bf16/dq resident");
-        return 0;
+        const int split = res_split(a.B * a.nkv, G);
+        return launch<attn_bwd_dq_br_kernel<G, DROP, SPAN, ORD>>("gamer_attn_bwd_bf16/dq resident", res_grid(a.B * a.nkv * (split ? G : 1)), dim3(BR_THREADS),
+                                                               sizeof(BrSmem), a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.d_o, a.lse, a.delta, a.kl,
+                                                               a.ql, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dq, a.lddq, a.ro.span, ord, split);
     }
-    hipLaunchKernelGGL((attn_bwd_dq_b_kernel<G, DROP, SPAN, ORD>), grid, dim3(AB_THREADS), 0, st, q, ldq, k, ldk, v, ldv, d_o, lse,
-                       delta, kl, ql, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, span, ord);
-    GAMER_CHECK_LAUNCH("gamer_attn_bwd_bf16/dq");
-    return 0;
+    return launch<attn_bwd_dq_b_kernel<G, DROP, SPAN, ORD>>("gamer_attn_bwd_bf16/dq", grid, dim3(AB_THREADS), 0, a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv,
+                                                          a.d_o, a.lse, a.delta, a.kl, a.ql, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dq,
+                                                          a.lddq, a.ro.span, ord);
 }
 
 template <int G>
-static int launch_bwd_b(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, const bf16_t* d_o,
-                        const float* lse, const float* delta, const int32_t* kl, const int32_t* ql, int B, int S, int nq,
-                        int nkv, float scale, float p_drop, uint64_t seed, bf16_t* dq, int lddq, bf16_t* dk, int lddk,
-                        bf16_t* dv, int lddv, const int32_t* span, const QOrdB ord, hipStream_t st) {
-#define GAMER_LAUNCH_BWD_B(DROPV, SPANV, ORDV)                                                                              \
-    return launch_bwd_b_variant<G, DROPV, SPANV, ORDV>(q, ldq, k, ldk, v, ldv, d_o, lse, delta, kl, ql, B, S, nq, nkv, scale, \
-                                                       p_drop, seed, dq, lddq, dk, lddk, dv, lddv, span, ord, st)
-    if (ord.perm) { if (p_drop > 0.f) GAMER_LAUNCH_BWD_B(true, false, true); else GAMER_LAUNCH_BWD_B(false, false, true); }
-    else if (p_drop > 0.f) { if (span) GAMER_LAUNCH_BWD_B(true, true, false); else GAMER_LAUNCH_BWD_B(true, false, false); }
-    else { if (span) GAMER_LAUNCH_BWD_B(false, true, false); else GAMER_LAUNCH_BWD_B(false, false, false); }
-#undef GAMER_LAUNCH_BWD_B
-    return -1;      // not reached
+static int launch_bwd_b(const AttnBwdArgs<bf16_t>& a) {
+    return with_b_variant(a.p_drop, a.ro, [&](auto drop, auto span, auto ordv) { return launch_bwd_b_variant<G, drop(), span(), ordv()>(a); });
 }
 
 }  // namespace gamer
 
 using namespace gamer;
 
-static int check_attn_b(const char* name, const void* q, const void* k, const void* v, const void* kl, int ldq, int ldk,
-                        int ldv, int B, int S, int nq, int nkv, float p_drop) {
-    GAMER_CHECK_ARG(q && k && v && kl, "%s: null pointer", name);
-    GAMER_CHECK_ARG(B > 0 && S > 0 && nq > 0 && nkv > 0 && nq % nkv == 0, "%s: bad shape B=%d S=%d nq=%d nkv=%d", name, B, S, nq, nkv);
-    const int G = nq / nkv;
-    GAMER_CHECK_ARG(G == 1 || G == 2, "%s: GQA group %d not built (1 or 2)", name, G);
-    GAMER_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldq >= nq * 64 && ldk >= nkv * 64 && ldv >= nkv * 64,
-                    "%s: bad leading dims ldq=%d ldk=%d ldv=%d (multiples of 8)", name, ldq, ldk, ldv);
-    GAMER_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v), "%s: q/k/v must be 16-byte aligned", name);
-    GAMER_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop=%f", name, p_drop);
-    return 0;
-}
-
 extern "C" int gamer_attn_fwd_bf16(const gamer_bf16* q, int ldq, const gamer_bf16* k, int ldk, const gamer_bf16* v, int ldv,
                                    const int32_t* kl, const int32_t* ql, int B, int S, int nq, int nkv, float scale,
                                    float p_drop, uint64_t seed, gamer_bf16* o, float* lse, const int32_t* q_span,
                                    const int32_t* perm, const int32_t* tile_maxpos, const int32_t* row_empty, void* stream) {
-    int rc = check_attn_b("gamer_attn_fwd_bf16", q, k, v, kl, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
+    int rc = check_attn("gamer_attn_fwd_bf16", true, q, k, v, kl, nullptr, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
     if (rc) return rc;
     GAMER_CHECK_ARG(o && lse && aligned16(o), "gamer_attn_fwd_bf16: null/unaligned output");
     GAMER_CHECK_ARG(!q_span || aligned16(q_span), "gamer_attn_fwd_bf16: q_span must be 16-byte aligned");
     GAMER_CHECK_ARG(!perm || (tile_maxpos && row_empty && !q_span),
                     "gamer_attn_fwd_bf16: a row order needs perm, tile_maxpos and row_empty, and excludes q_span");
-    const QOrdB ord{perm, tile_maxpos, row_empty};
-    hipStream_t st = (hipStream_t)stream;
-    if (nq / nkv == 1)
-        return launch_fwd_b<1>((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, kl, ql, B, S, nq, nkv,
-                               scale, p_drop, seed, (bf16_t*)o, lse, q_span, ord, st);
-    return launch_fwd_b<2>((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, kl, ql, B, S, nq, nkv, scale,
-                           p_drop, seed, (bf16_t*)o, lse, q_span, ord, st);
+    const AttnFwdArgs<bf16_t> a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed,
+                                (bf16_t*)o, lse, RowOrder{perm, nullptr, tile_maxpos, q_span}, S, (hipStream_t)stream};
+    return with_group(nq, nkv, [&](auto g) { return launch_fwd_b<g()>(a); });
 }
 
 extern "C" int gamer_attn_bwd_bf16(const gamer_bf16* q, int ldq, const gamer_bf16* k, int ldk, const gamer_bf16* v, int ldv,
@@ -1813,7 +1708,7 @@ extern "C" int gamer_attn_bwd_bf16(const gamer_bf16* q, int ldq, const gamer_bf1
                                    uint64_t seed, float* delta, gamer_bf16* dq, int lddq, gamer_bf16* dk, int lddk,
                                    gamer_bf16* dv, int lddv, const int32_t* q_span, int delta_ready, const int32_t* perm,
                                    const int32_t* tile_maxpos, const int32_t* row_empty, void* stream) {
-    int rc = check_attn_b("gamer_attn_bwd_bf16", q, k, v, kl, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
+    int rc = check_attn("gamer_attn_bwd_bf16", true, q, k, v, kl, nullptr, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
     if (rc) return rc;
     GAMER_CHECK_ARG(d_o && lse && delta && dq && dk && dv && (o || delta_ready), "gamer_attn_bwd_bf16: null pointer");
     GAMER_CHECK_ARG(lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(d_o),
@@ -1821,18 +1716,11 @@ extern "C" int gamer_attn_bwd_bf16(const gamer_bf16* q, int ldq, const gamer_bf1
     GAMER_CHECK_ARG(!q_span || aligned16(q_span), "gamer_attn_bwd_bf16: q_span must be 16-byte aligned");
     GAMER_CHECK_ARG(!perm || (tile_maxpos && row_empty && !q_span),
                     "gamer_attn_bwd_bf16: a row order needs perm, tile_maxpos and row_empty, and excludes q_span");
-    const QOrdB ord{perm, tile_maxpos, row_empty};
     hipStream_t st = (hipStream_t)stream;
-    if (!delta_ready) {
-        hipLaunchKernelGGL(attn_delta_b_kernel, dim3(2048), dim3(AB_THREADS), 0, st, (const bf16_t*)o, (const bf16_t*)d_o, B,
-                           S, nq, delta);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_bf16/delta");
-    }
-    if (nq / nkv == 1)
-        return launch_bwd_b<1>((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)d_o, lse,
-                               delta, kl, ql, B, S, nq, nkv, scale, p_drop, seed, (bf16_t*)dq, lddq, (bf16_t*)dk, lddk,
-                               (bf16_t*)dv, lddv, q_span, ord, st);
-    return launch_bwd_b<2>((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)d_o, lse, delta,
-                           kl, ql, B, S, nq, nkv, scale, p_drop, seed, (bf16_t*)dq, lddq, (bf16_t*)dk, lddk, (bf16_t*)dv,
-                           lddv, q_span, ord, st);
+    if (!delta_ready)
+        GAMER_TRY(launch<attn_delta_b_kernel>("gamer_attn_bwd_bf16/delta", dim3(2048), dim3(AB_THREADS), 0, st, (const bf16_t*)o, (const bf16_t*)d_o, B, S, nq, delta));
+    const AttnBwdArgs<bf16_t> a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, (const bf16_t*)o, (const bf16_t*)d_o, lse, delta,
+                                kl, ql, row_empty, nullptr, B, S, nq, nkv, scale, p_drop, seed, (bf16_t*)dq, lddq, (bf16_t*)dk, lddk, (bf16_t*)dv, lddv,
+                                RowOrder{perm, nullptr, tile_maxpos, q_span}, nullptr, delta_ready, st};
+    return with_group(nq, nkv, [&](auto g) { return launch_bwd_b<g()>(a); });
 }

@@ -167,4 +167,88 @@ __device__ __forceinline__ void read_key_quads(const int32_t* __restrict__ base,
 // multiplications + exp2 of the classic scheme disappear from the loop.
 constexpr float RESCALE_TAU = 20.f;
 
+// ---- host side: what an entry point hands to its launchers -----------------------------------------------------------------------
+// The arguments of a forward / backward call (T = float, or bf16_t for attention_bf16.hip), written out once by the extern "C" entry
+// point and once at each kernel launch; the dispatch layers in between pass the bundle.
+template <typename T>
+struct AttnFwdArgs {
+    const T* q; int ldq; const T* k; int ldk; const T* v; int ldv;
+    const int32_t* kl; const int32_t* ql; const int32_t* row_empty;
+    int B, S, nq, nkv; float scale, p_drop; uint64_t seed;
+    T* o; float* lse;
+    RowOrder ro; int uspan;
+    hipStream_t st;
+};
+template <typename T>
+struct AttnBwdArgs {
+    const T* q; int ldq; const T* k; int ldk; const T* v; int ldv;
+    const T* o; const T* d_o; const float* lse; float* delta;
+    const int32_t* kl; const int32_t* ql; const int32_t* row_empty; const int32_t* tile_empty;
+    int B, S, nq, nkv; float scale, p_drop; uint64_t seed;
+    T* dq; int lddq; T* dk; int lddk; T* dv; int lddv;
+    RowOrder ro; float* ds_work; int delta_ready;
+    hipStream_t st;
+};
+// the GQA group nq / nkv (1 or 2: check_attn has refused the rest) as a template argument: f(std::integral_constant<int, G>{})
+template <typename F>
+static inline int with_group(int nq, int nkv, F&& f) {
+    return nq / nkv == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{});
+}
+
+// The argument check every attention entry point starts with.  bf16: 16-byte rows are eight elements, and there is no row_empty.
+static inline int check_attn(const char* name, bool bf16, const void* q, const void* k, const void* v, const void* kl,
+                             const void* row_empty, int ldq, int ldk, int ldv, int B, int S, int nq, int nkv, float p_drop) {
+    GAMER_CHECK_ARG(q && k && v && kl && (bf16 || row_empty), "%s: null pointer", name);
+    GAMER_CHECK_ARG(B > 0 && S > 0 && nq > 0 && nkv > 0 && nq % nkv == 0, "%s: bad shape B=%d S=%d nq=%d nkv=%d", name, B, S, nq, nkv);
+    const int G = nq / nkv, m = bf16 ? 8 : 4;
+    GAMER_CHECK_ARG(G == 1 || G == 2, "%s: GQA group %d not built (1 or 2)", name, G);
+    GAMER_CHECK_ARG(ldq % m == 0 && ldk % m == 0 && ldv % m == 0 && ldq >= nq * 64 && ldk >= nkv * 64 && ldv >= nkv * 64,
+                    "%s: bad leading dims ldq=%d ldk=%d ldv=%d%s", name, ldq, ldk, ldv, bf16 ? " (multiples of 8)" : "");
+    GAMER_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v), "%s: q/k/v must be 16-byte aligned", name);
+    GAMER_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop=%f", name, p_drop);
+    return 0;
+}
+
+// ---- the kernels with one operand of a (sequence, kv head) resident in LDS (attention_res.hip, attention_bf16.hip): switches, grid ------
+// GAMER_ATTN_RES=0 keeps every call on the tiled kernels (A/B runs); default on
+static inline bool res_enabled() {
+    static EnvSwitch sw("GAMER_ATTN_RES");             // (cached: gamer_reload_env() after a change inside the process)
+    return sw.get(1) != 0;
+}
+// GAMER_ATTN_RES_DQ / _DKV / _DKV2 / _SPAN / _DKV_BF16 = 0: that kernel stays tiled (A/B runs)
+#define GAMER_RES_PART(name) ([]() -> bool { static EnvSwitch sw(name); return sw.get(1) != 0; }())
+// persistent workgroups: one per CU (GAMER_ATTN_RES_GRID overrides)
+static inline int res_grid_cap() {
+    static EnvSwitch grid("GAMER_ATTN_RES_GRID");       // (tests force a few persistent workgroups to walk many units)
+    if (grid.get(0) > 0) return grid.get(0);
+    static int cap[MAX_DEVICES] = {};
+    int& c = cap[current_device()];
+    if (c == 0) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess) n = 256;
+        c = n > 0 ? n : 256;
+    }
+    return c;
+}
+// Split a (sequence, kv head) pair's work over `ways` workgroups?  Persistent workgroups take whole units, so the launch lasts
+// ceil(units / CUs) rounds: 384 pairs on 256 CUs (per-GPU batch 128) are two rounds with half the CUs idle in the second, 768 half
+// units three full rounds at ~0.58 of a pair's time each (the split units stage the shared operand once more).  GAMER_ATTN_RES_SPLIT=0/1 forces.
+static inline int res_split(int n_pairs, int ways) {
+    if (ways < 2) return 0;
+    static EnvSwitch sp("GAMER_ATTN_RES_SPLIT");
+    if (sp.is_set()) return sp.get(0) != 0;
+    const int ncu = res_grid_cap();
+    const double whole = (double)((n_pairs + ncu - 1) / ncu), halves = 0.58 * (double)((ways * n_pairs + ncu - 1) / ncu);
+    return halves < whole ? 1 : 0;
+}
+static inline bool res_split_forced() { static EnvSwitch sp("GAMER_ATTN_RES_SPLIT"); return sp.is_set(); }
+// share of the CU-rounds that whole-pair units keep busy
+static inline double res_fill(int n_pairs) {
+    const int ncu = res_grid_cap();
+    if (n_pairs <= ncu) return 1.0;          // (a single round: nothing to balance)
+    return (double)n_pairs / ((double)((n_pairs + ncu - 1) / ncu) * ncu);
+}
+// the grid of a resident kernel: one persistent workgroup per unit, at most one per CU
+static inline dim3 res_grid(int n_units) { return dim3(n_units < res_grid_cap() ? n_units : res_grid_cap()); }
+
 }  // namespace gamer

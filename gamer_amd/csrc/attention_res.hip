@@ -1724,175 +1724,56 @@ attn_bwd_dkv_r2_kernel(const float* __restrict__ q, int ldq, const float* __rest
 #endif
 }
 
-template <int G, bool DROP, bool SPAN, bool ORD>
-static int launch_fwd_r_variant(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* kl,
-                                const int32_t* ql, const int32_t* row_empty, int B, int S, int nq, int nkv, float scale, float p_drop,
-                                uint64_t seed, float* o, float* lse, RowOrder ro, uint32_t* amax_out, AttnAmax am, hipStream_t st) {
-    const size_t shmem = sizeof(ResSmem);
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr_set = attr_dev[current_device()];
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_r_kernel<G, DROP, SPAN, ORD>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) {
-            set_error("gamer_attn_fwd_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_set = true;
-    }
-    const int split = res_split(B * nkv, G);
-    const int n_units = B * nkv * (split ? G : 1);
-    const int grid = n_units < res_grid_cap() ? n_units : res_grid_cap();
-    hipLaunchKernelGGL((attn_fwd_r_kernel<G, DROP, SPAN, ORD>), dim3(grid), dim3(RES_THREADS), shmem, st, q, ldq, k, ldk, v, ldv, kl, ql,
-                       row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, amax_out, am, split);
-    GAMER_CHECK_LAUNCH("gamer_attn_fwd_split/resident");
-    return 0;
+// The template arguments of the resident kernels from a call's flags: f(G, DROP, SPAN, ORD).  Key spans (Qwen3SessionMulti) are built
+// for the GQA group of two only (the caller checks).
+template <typename F>
+static int with_res_variant(int nq, int nkv, float p_drop, const RowOrder& ro, F&& f) {
+    const bool drop = p_drop > 0.f, ord = ro.perm != nullptr;
+    if (ro.span) return with_flags([&](auto d, auto o) { return f(std::integral_constant<int, 2>{}, d, std::true_type{}, o); }, drop, ord);
+    return with_group(nq, nkv, [&](auto g) { return with_flags([&](auto d, auto o) { return f(g, d, std::false_type{}, o); }, drop, ord); });
 }
 
-int launch_fwd_res(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* kl, const int32_t* ql,
-                   const int32_t* row_empty, int B, int S, int nq, int nkv, float scale, float p_drop, uint64_t seed, float* o,
-                   float* lse, RowOrder ro, uint32_t* amax_out, AttnAmax am, hipStream_t st) {
-#define GAMER_LAUNCH_FWD_RS(GV, DROPV, SPANV, ORDV)                                                                           \
-    return launch_fwd_r_variant<GV, DROPV, SPANV, ORDV>(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, \
-                                                        lse, ro, amax_out, am, st)
-#define GAMER_LAUNCH_FWD_R(GV, DROPV, ORDV) GAMER_LAUNCH_FWD_RS(GV, DROPV, false, ORDV)
-    if (ro.span) {                          // per-query key spans (Qwen3SessionMulti): built for the GQA group of two (the caller checks)
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD_RS(2, true, true, true); else GAMER_LAUNCH_FWD_RS(2, true, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_FWD_RS(2, false, true, true); else GAMER_LAUNCH_FWD_RS(2, false, true, false); }
-    }
-    if (nq / nkv == 1) {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD_R(1, true, true); else GAMER_LAUNCH_FWD_R(1, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_FWD_R(1, false, true); else GAMER_LAUNCH_FWD_R(1, false, false); }
-    } else {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD_R(2, true, true); else GAMER_LAUNCH_FWD_R(2, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_FWD_R(2, false, true); else GAMER_LAUNCH_FWD_R(2, false, false); }
-    }
-#undef GAMER_LAUNCH_FWD_R
-#undef GAMER_LAUNCH_FWD_RS
-    return -1;      // not reached
+int launch_fwd_res(const AttnFwdArgs<float>& a, uint32_t* amax_out, AttnAmax am) {
+    return with_res_variant(a.nq, a.nkv, a.p_drop, a.ro, [&](auto g, auto drop, auto span, auto ord) {
+        const int split = res_split(a.B * a.nkv, g());
+        return launch<attn_fwd_r_kernel<g(), drop(), span(), ord()>>("gamer_attn_fwd_split/resident", res_grid(a.B * a.nkv * (split ? g() : 1)),
+                                                                     dim3(RES_THREADS), sizeof(ResSmem), a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.kl,
+                                                                     a.ql, a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.o, a.lse,
+                                                                     a.ro, amax_out, am, split);
+    });
 }
 
-template <int G, bool DROP, bool SPAN, bool ORD>
-static int launch_dq_r_variant(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                               const float* d_o, const float* lse, float* delta, const int32_t* kl, const int32_t* ql,
-                               const int32_t* row_empty, int B, int S, int nq, int nkv, float scale, float p_drop, uint64_t seed,
-                               float* dq, int lddq, RowOrder ro, int delta_ready, AttnAmax am, hipStream_t st) {
-    const size_t shmem = sizeof(ResSmem);
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr_set = attr_dev[current_device()];
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_r_kernel<G, DROP, SPAN, ORD>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) {
-            set_error("gamer_attn_bwd_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_set = true;
-    }
-    const int split = res_split(B * nkv, G);
-    const int n_units = B * nkv * (split ? G : 1);
-    const int grid = n_units < res_grid_cap() ? n_units : res_grid_cap();
-    hipLaunchKernelGGL((attn_bwd_dq_r_kernel<G, DROP, SPAN, ORD>), dim3(grid), dim3(RES_THREADS), shmem, st, q, ldq, k, ldk, v, ldv, o, d_o,
-                       lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, ro, delta_ready, am, split);
-    GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dq resident");
-    return 0;
+int launch_dq_res(const AttnBwdArgs<float>& a, AttnAmax am) {
+    return with_res_variant(a.nq, a.nkv, a.p_drop, a.ro, [&](auto g, auto drop, auto span, auto ord) {
+        const int split = res_split(a.B * a.nkv, g());
+        return launch<attn_bwd_dq_r_kernel<g(), drop(), span(), ord()>>("gamer_attn_bwd_split/dq resident", res_grid(a.B * a.nkv * (split ? g() : 1)),
+                                                                        dim3(RES_THREADS), sizeof(ResSmem), a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv,
+                                                                        a.o, a.d_o, a.lse, a.delta, a.kl, a.ql, a.row_empty, a.B, a.S, a.nq, a.nkv,
+                                                                        a.scale, a.p_drop, a.seed, a.dq, a.lddq, a.ro, a.delta_ready, am, split);
+    });
 }
 
-int launch_dq_res(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, const float* d_o,
-                  const float* lse, float* delta, const int32_t* kl, const int32_t* ql, const int32_t* row_empty, int B, int S,
-                  int nq, int nkv, float scale, float p_drop, uint64_t seed, float* dq, int lddq, RowOrder ro, int delta_ready,
-                  AttnAmax am, hipStream_t st) {
-#define GAMER_LAUNCH_DQ_RS(GV, DROPV, SPANV, ORDV)                                                                            \
-    return launch_dq_r_variant<GV, DROPV, SPANV, ORDV>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, \
-                                                       p_drop, seed, dq, lddq, ro, delta_ready, am, st)
-#define GAMER_LAUNCH_DQ_R(GV, DROPV, ORDV) GAMER_LAUNCH_DQ_RS(GV, DROPV, false, ORDV)
-    if (ro.span) {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_DQ_RS(2, true, true, true); else GAMER_LAUNCH_DQ_RS(2, true, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_DQ_RS(2, false, true, true); else GAMER_LAUNCH_DQ_RS(2, false, true, false); }
-    }
-    if (nq / nkv == 1) {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_DQ_R(1, true, true); else GAMER_LAUNCH_DQ_R(1, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_DQ_R(1, false, true); else GAMER_LAUNCH_DQ_R(1, false, false); }
-    } else {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_DQ_R(2, true, true); else GAMER_LAUNCH_DQ_R(2, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_DQ_R(2, false, true); else GAMER_LAUNCH_DQ_R(2, false, false); }
-    }
-#undef GAMER_LAUNCH_DQ_R
-#undef GAMER_LAUNCH_DQ_RS
-    return -1;      // not reached
-}
-
-template <int G, bool DROP, bool SPAN, bool ORD>
-static int launch_dkv_r_variant(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* d_o,
-                                const float* lse, const float* delta, const int32_t* kl, const int32_t* ql, const int32_t* row_empty,
-                                int B, int S, int nq, int nkv, float scale, float p_drop, uint64_t seed, float* dk, int lddk,
-                                float* dv, int lddv, RowOrder ro, uint32_t* amax_out, AttnAmax am, hipStream_t st) {
-    const size_t shmem = sizeof(DkvRSmem);
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr_set = attr_dev[current_device()];
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_r_kernel<G, DROP, ORD>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) {
-            set_error("gamer_attn_bwd_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
+int launch_dkv_res(const AttnBwdArgs<float>& a, uint32_t* amax_out, AttnAmax am) {
+    return with_res_variant(a.nq, a.nkv, a.p_drop, a.ro, [&](auto g, auto drop, auto span, auto ord) {
+        const int n_pairs = a.B * a.nkv;
+        // (the single-chain kernel is named first in every variant: the kernels keep their order in the code object)
+        GAMER_TRY(ensure_dynamic_lds<attn_bwd_dkv_r_kernel<g(), drop(), ord()>>("gamer_attn_bwd_split/dkv resident", sizeof(DkvRSmem)));
+        if (g() == 2 && (span() || GAMER_RES_PART("GAMER_ATTN_RES_DKV2"))) {
+            // two heads per wave (the element-wise work of one beside the products of the other)
+            const int split = res_split(n_pairs, 2);
+            return launch<attn_bwd_dkv_r2_kernel<drop(), span(), ord()>>("gamer_attn_bwd_split/dkv resident, two heads per wave",
+                                                                         res_grid(n_pairs * (split ? 2 : 1)), dim3(DKV_R_THREADS), sizeof(DkvR2Smem),
+                                                                         a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.d_o, a.lse, a.delta, a.kl, a.ql,
+                                                                         a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dk, a.lddk,
+                                                                         a.dv, a.lddv, a.ro, amax_out, am, split);
         }
-        attr_set = true;
-    }
-    const int n_pairs = B * nkv;
-    const int grid = n_pairs < res_grid_cap() ? n_pairs : res_grid_cap();
-    if (G == 2 && (SPAN || GAMER_RES_PART("GAMER_ATTN_RES_DKV2"))) {
-        // two heads per wave (the element-wise work of one beside the products of the other)
-        const size_t shmem2 = sizeof(DkvR2Smem);
-        static bool attr2_dev[MAX_DEVICES] = {};
-        bool& attr2_set = attr2_dev[current_device()];
-        if (!attr2_set) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_r2_kernel<DROP, SPAN, ORD>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem2);
-            if (e != hipSuccess) {
-                set_error("gamer_attn_bwd_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-            attr2_set = true;
-        }
-        const int split = res_split(n_pairs, 2);
-        const int n_units = n_pairs * (split ? 2 : 1);
-        const int grid2 = n_units < res_grid_cap() ? n_units : res_grid_cap();
-        hipLaunchKernelGGL((attn_bwd_dkv_r2_kernel<DROP, SPAN, ORD>), dim3(grid2), dim3(DKV_R_THREADS), shmem2, st, q, ldq, k, ldk, v, ldv, d_o,
-                           lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, dk, lddk, dv, lddv, ro, amax_out, am, split);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dkv resident, two heads per wave");
+        if constexpr (!span())                  // (the single-chain kernel takes no spans: span calls are G = 2 and ended above)
+            return launch<attn_bwd_dkv_r_kernel<g(), drop(), ord()>>("gamer_attn_bwd_split/dkv resident", res_grid(n_pairs), dim3(DKV_R_THREADS),
+                                                                     sizeof(DkvRSmem), a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.d_o, a.lse, a.delta,
+                                                                     a.kl, a.ql, a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dk,
+                                                                     a.lddk, a.dv, a.lddv, a.ro, amax_out, am);
         return 0;
-    }
-    if constexpr (!SPAN) {                  // (the single-chain kernel takes no spans: SPAN calls are G = 2 and ended above)
-        hipLaunchKernelGGL((attn_bwd_dkv_r_kernel<G, DROP, ORD>), dim3(grid), dim3(DKV_R_THREADS), shmem, st, q, ldq, k, ldk, v, ldv, d_o, lse,
-                           delta, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, dk, lddk, dv, lddv, ro, amax_out, am);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dkv resident");
-    }
-    return 0;
-}
-
-int launch_dkv_res(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* d_o, const float* lse,
-                   const float* delta, const int32_t* kl, const int32_t* ql, const int32_t* row_empty, int B, int S, int nq, int nkv,
-                   float scale, float p_drop, uint64_t seed, float* dk, int lddk, float* dv, int lddv, RowOrder ro, uint32_t* amax_out,
-                   AttnAmax am, hipStream_t st) {
-#define GAMER_LAUNCH_DKV_RS(GV, DROPV, SPANV, ORDV)                                                                           \
-    return launch_dkv_r_variant<GV, DROPV, SPANV, ORDV>(q, ldq, k, ldk, v, ldv, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, \
-                                                        p_drop, seed, dk, lddk, dv, lddv, ro, amax_out, am, st)
-#define GAMER_LAUNCH_DKV_R(GV, DROPV, ORDV) GAMER_LAUNCH_DKV_RS(GV, DROPV, false, ORDV)
-    if (ro.span) {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_DKV_RS(2, true, true, true); else GAMER_LAUNCH_DKV_RS(2, true, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_DKV_RS(2, false, true, true); else GAMER_LAUNCH_DKV_RS(2, false, true, false); }
-    }
-    if (nq / nkv == 1) {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_DKV_R(1, true, true); else GAMER_LAUNCH_DKV_R(1, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_DKV_R(1, false, true); else GAMER_LAUNCH_DKV_R(1, false, false); }
-    } else {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_DKV_R(2, true, true); else GAMER_LAUNCH_DKV_R(2, true, false); }
-        else { if (ro.perm) GAMER_LAUNCH_DKV_R(2, false, true); else GAMER_LAUNCH_DKV_R(2, false, false); }
-    }
-#undef GAMER_LAUNCH_DKV_R
-#undef GAMER_LAUNCH_DKV_RS
-    return -1;      // not reached
+    });
 }
 
 }  // namespace gamer

@@ -1394,155 +1394,93 @@ static thread_local AttnAmax g_attn_amax_armed = {nullptr, nullptr, nullptr, nul
 void disarm_attn_amax() { g_attn_amax_armed = AttnAmax{nullptr, nullptr, nullptr, nullptr}; }
 
 template <int G>
-static int launch_fwd_s(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* kl,
-                        const int32_t* ql, const int32_t* row_empty, int B, int S, int nq, int nkv, float scale,
-                        float p_drop, uint64_t seed, float* o, float* lse, RowOrder ro, int uspan, hipStream_t st) {
+static int launch_fwd_s(const AttnFwdArgs<float>& a) {
     constexpr int R = (4 / G) * 32;
-    dim3 grid(worklist_grid(B * nkv, (S + R - 1) / R));
-#define GAMER_LAUNCH_FWD_SP(DROPV, ORDV, SPANV, H2V)                                                                         \
-    hipLaunchKernelGGL((attn_fwd_s_kernel<G, DROPV, ORDV, SPANV, H2V>), grid, dim3(AT_THREADS), 0, st, q, ldq, k, ldk, v, ldv, \
-                       kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, t_amax_out, t_attn_amax)
-#define GAMER_LAUNCH_FWD_S(DROPV, ORDV, H2V) GAMER_LAUNCH_FWD_SP(DROPV, ORDV, false, H2V)
-    if (ro.span) {
-        // per-query key spans (Qwen3SessionMulti): built for the three-product form (the entry point has checked that it is armed)
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD_SP(true, true, true, true); else GAMER_LAUNCH_FWD_SP(true, false, true, true); }
-        else { if (ro.perm) GAMER_LAUNCH_FWD_SP(false, true, true, true); else GAMER_LAUNCH_FWD_SP(false, false, true, true); }
-    } else if (t_attn_amax.q) {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD_S(true, true, true); else GAMER_LAUNCH_FWD_S(true, false, true); }
-        else { if (ro.perm) GAMER_LAUNCH_FWD_S(false, true, true); else GAMER_LAUNCH_FWD_S(false, false, true); }
-    } else {
-        if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_FWD_S(true, true, false); else GAMER_LAUNCH_FWD_S(true, false, false); }
-        else { if (ro.perm) GAMER_LAUNCH_FWD_S(false, true, false); else GAMER_LAUNCH_FWD_S(false, false, false); }
-    }
-#undef GAMER_LAUNCH_FWD_S
-#undef GAMER_LAUNCH_FWD_SP
-    GAMER_CHECK_LAUNCH("gamer_attn_fwd_split");
-    return 0;
+    const dim3 grid(worklist_grid(a.B * a.nkv, (a.S + R - 1) / R));
+    auto go = [&](auto drop, auto ord, auto span, auto h2) {
+        return launch<attn_fwd_s_kernel<G, drop(), ord(), span(), h2()>>("gamer_attn_fwd_split", grid, dim3(AT_THREADS), 0, a.st, a.q, a.ldq, a.k, a.ldk,
+                                                                         a.v, a.ldv, a.kl, a.ql, a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop,
+                                                                         a.seed, a.o, a.lse, a.ro, a.uspan, t_amax_out, t_attn_amax);
+    };
+    const bool drop = a.p_drop > 0.f, ord = a.ro.perm != nullptr;
+    // per-query key spans (Qwen3SessionMulti): built for the three-product form (the entry point has checked that it is armed)
+    if (a.ro.span) return with_flags([&](auto d, auto o) { return go(d, o, std::true_type{}, std::true_type{}); }, drop, ord);
+    return with_flags([&](auto h2, auto d, auto o) { return go(d, o, std::false_type{}, h2); }, t_attn_amax.q != nullptr, drop, ord);
+}
+
+// Which calls take the kernels of attention_res.hip (h2: the three-product fp16 form is armed - gamer_attn_split_amax).
+// Forward: K / V of a (sequence, kv head) resident in LDS, training semantics; key spans for the GQA group of two.
+static bool takes_res_fwd(const AttnFwdArgs<float>& a, bool h2) {
+    return h2 && (!a.ro.span || (a.nq / a.nkv == 2 && GAMER_RES_PART("GAMER_ATTN_RES_SPAN"))) && a.uspan == a.S && a.S <= 2048 && res_enabled();
+}
+// dQ: K / V of a (sequence, kv head) resident in LDS (the recompute form only)
+static bool takes_res_dq(const AttnBwdArgs<float>& a, bool h2) {
+    return h2 && a.ds_work == nullptr && res_enabled() && a.S <= 2048 && GAMER_RES_PART("GAMER_ATTN_RES_DQ");
+}
+// dK / dV: Q / dO of a (sequence, head, query block) resident in LDS, key tiles from a queue.  (The resident kernel takes whole pairs:
+// when they do not fill the CUs evenly - per-GPU batch 128: 384 pairs on 256 CUs - the tiled kernel is faster than either half-filled
+// rounds or pairs split over two workgroups; measured)
+static bool takes_res_dkv(const AttnBwdArgs<float>& a, bool h2) {
+    return h2 && a.ds_work == nullptr && res_enabled() && a.S <= 2048 && GAMER_RES_PART("GAMER_ATTN_RES_DKV") &&
+           (res_fill(a.B * a.nkv) >= 0.85 || res_split_forced());
+}
+// key spans in the backward: the GQA group of two, and both kernels resident
+static bool takes_res_span_bwd(const AttnBwdArgs<float>& a, bool h2) {
+    return a.ro.span && a.nq / a.nkv == 2 && GAMER_RES_PART("GAMER_ATTN_RES_SPAN") && takes_res_dq(a, h2) && takes_res_dkv(a, h2);
+}
+
+// the tiled backward kernels (SPAN is built with H2 only)
+template <int G, bool DROP, bool ORD, bool SPAN, bool H2>
+static int launch_dq_s(const AttnBwdArgs<float>& a) {
+    constexpr int R = (4 / G) * 32;
+    return launch<attn_bwd_dq_s_kernel<G, DROP, ORD, SPAN, H2>>("gamer_attn_bwd_split/dq", dim3(worklist_grid(a.B * a.nkv, (a.S + R - 1) / R)), dim3(AT_THREADS), 0,
+                                                              a.st, a.q, a.ldq, a.k, a.ldk, a.v, a.ldv, a.o, a.d_o, a.lse, a.delta, a.kl, a.ql, a.row_empty,
+                                                              a.B, a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dq, a.lddq, a.ro, a.delta_ready,
+                                                              t_attn_amax);
+}
+template <int G, bool DROP, bool ORD, bool SPAN, bool H2>
+static int launch_dkv_s(const AttnBwdArgs<float>& a) {
+    const dim3 grid(worklist_grid_1(a.B * a.nkv, (a.S + DKV_S_KEYS - 1) / DKV_S_KEYS));
+    return launch<attn_bwd_dkv_s_kernel<G, DROP, ORD, H2, SPAN>>("gamer_attn_bwd_split/dkv", grid, dim3(256 * G), sizeof(DkvSmemS<G, H2 ? 2 : 3>), a.st, a.q, a.ldq,
+                                                               a.k, a.ldk, a.v, a.ldv, a.d_o, a.lse, a.delta, a.kl, a.ql, a.row_empty, a.tile_empty, a.B,
+                                                               a.S, a.nq, a.nkv, a.scale, a.p_drop, a.seed, a.dk, a.lddk, a.dv, a.lddv, a.ro, a.ds_work,
+                                                               t_amax_out, t_attn_amax);
 }
 
 template <int G, bool DROP, bool ORD>
-static int launch_bwd_s_variant(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                                const float* d_o, const float* lse, float* delta, const int32_t* kl, const int32_t* ql,
-                                const int32_t* row_empty, const int32_t* tile_empty, int B, int S, int nq, int nkv,
-                                float scale, float p_drop, uint64_t seed, float* dq, int lddq, float* dk, int lddk,
-                                float* dv, int lddv, RowOrder ro, int delta_ready, float* ds_work, hipStream_t st) {
+static int launch_bwd_s_variant(const AttnBwdArgs<float>& a) {
     constexpr int R = (4 / G) * 32;
     const bool h2 = t_attn_amax.q != nullptr;       // gamer_attn_split_amax: the three-product fp16 form (recompute form only)
-    // key spans on the resident kernels: the GQA group of two, both kernels resident (the conditions of the two launches below)
-    const bool span_res = ro.span && G == 2 && h2 && ds_work == nullptr && res_enabled() && S <= 2048 &&
-                          GAMER_RES_PART("GAMER_ATTN_RES_SPAN") && GAMER_RES_PART("GAMER_ATTN_RES_DQ") &&
-                          GAMER_RES_PART("GAMER_ATTN_RES_DKV") && (res_fill(B * nkv) >= 0.85 || res_split_forced());
-    if (ro.span && !span_res) {
+    // (a local lambda with a declared return type is instantiated before what the body names itself: the kernels keep their order in
+    // the code object)
+    auto dkv_plain = [&](auto h2v) -> int { return launch_dkv_s<G, DROP, ORD, false, h2v()>(a); };
+    if (a.ro.span && !takes_res_span_bwd(a, h2)) {
         // per-query key spans (Qwen3SessionMulti): the three-product recompute form (checked by the entry point)
-        hipLaunchKernelGGL((attn_bwd_dq_s_kernel<G, DROP, ORD, true, true>), dim3(worklist_grid(B * nkv, (S + R - 1) / R)),
-                           dim3(AT_THREADS), 0, st, q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv,
-                           scale, p_drop, seed, dq, lddq, ro, delta_ready, t_attn_amax);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dq");
-        const size_t shmem = sizeof(DkvSmemS<G, 2>);
-        static bool attr_dev[MAX_DEVICES] = {};
-        bool& attr_set = attr_dev[current_device()];
-        if (!attr_set) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_s_kernel<G, DROP, ORD, true, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            if (e != hipSuccess) {
-                set_error("gamer_attn_bwd_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_dkv_s_kernel<G, DROP, ORD, true, true>), dim3(worklist_grid_1(B * nkv, (S + DKV_S_KEYS - 1) / DKV_S_KEYS)),
-                           dim3(256 * G), shmem, st, q, ldq, k, ldk, v, ldv, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv,
-                           scale, p_drop, seed, dk, lddk, dv, lddv, ro, (float*)nullptr, t_amax_out, t_attn_amax);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dkv");
-        return 0;
+        GAMER_TRY(launch_dq_s<G, DROP, ORD, true, true>(a));
+        return launch_dkv_s<G, DROP, ORD, true, true>(a);
     }
-    if (ds_work == nullptr) {
-        if (h2 && res_enabled() && S <= 2048 && GAMER_RES_PART("GAMER_ATTN_RES_DQ")) {
-            // K / V of a (sequence, kv head) resident in LDS (attention_res.hip)
-            const int rc_dq = launch_dq_res(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop,
-                                            seed, dq, lddq, ro, delta_ready, t_attn_amax, st);
-            if (rc_dq) return rc_dq;
-        } else if (h2)
-            hipLaunchKernelGGL((attn_bwd_dq_s_kernel<G, DROP, ORD, false, true>), dim3(worklist_grid(B * nkv, (S + R - 1) / R)),
-                               dim3(AT_THREADS), 0, st, q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv,
-                               scale, p_drop, seed, dq, lddq, ro, delta_ready, t_attn_amax);
-        else
-            hipLaunchKernelGGL((attn_bwd_dq_s_kernel<G, DROP, ORD, false, false>), dim3(worklist_grid(B * nkv, (S + R - 1) / R)),
-                               dim3(AT_THREADS), 0, st, q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv,
-                               scale, p_drop, seed, dq, lddq, ro, delta_ready, t_attn_amax);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dq");
-    } else if (!delta_ready) {
-        hipLaunchKernelGGL(attn_delta_s_kernel, dim3(2048), dim3(AT_THREADS), 0, st, o, d_o, B, S, nq, delta);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/delta");
+    if (a.ds_work == nullptr) {
+        if (takes_res_dq(a, h2)) GAMER_TRY(launch_dq_res(a, t_attn_amax));
+        else GAMER_TRY(h2 ? launch_dq_s<G, DROP, ORD, false, true>(a) : launch_dq_s<G, DROP, ORD, false, false>(a));
+    } else if (!a.delta_ready) {
+        GAMER_TRY(launch<attn_delta_s_kernel>("gamer_attn_bwd_split/delta", dim3(2048), dim3(AT_THREADS), 0, a.st, a.o, a.d_o, a.B, a.S, a.nq, a.delta));
     }
-    const int n_kt = (S + DKV_S_KEYS - 1) / DKV_S_KEYS;
-    auto launch_dkv = [&]<bool H2V>() -> int {
-        const size_t shmem = sizeof(DkvSmemS<G, H2V ? 2 : 3>);
-        static bool attr_dev[MAX_DEVICES] = {};   // one set of flags per template instantiation, one flag per device
-        bool& attr_set = attr_dev[current_device()];
-        if (!attr_set) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_s_kernel<G, DROP, ORD, H2V>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-            if (e != hipSuccess) {
-                set_error("gamer_attn_bwd_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_dkv_s_kernel<G, DROP, ORD, H2V>), dim3(worklist_grid_1(B * nkv, n_kt)), dim3(256 * G), shmem, st, q, ldq,
-                           k, ldk, v, ldv, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dk,
-                           lddk, dv, lddv, ro, ds_work, t_amax_out, t_attn_amax);
-        return 0;
-    };
-    // (the resident dK/dV kernel takes whole pairs: when they do not fill the CUs evenly - per-GPU batch 128: 384 pairs on 256 CUs -
-    // the tiled kernel below is faster than either half-filled rounds or pairs split over two workgroups; measured)
-    if (h2 && ds_work == nullptr && res_enabled() && S <= 2048 && GAMER_RES_PART("GAMER_ATTN_RES_DKV") &&
-        (res_fill(B * nkv) >= 0.85 || res_split_forced()))
-        // Q / dO of a (sequence, head, query block) resident in LDS, key tiles from a queue (attention_res.hip)
-        return launch_dkv_res(q, ldq, k, ldk, v, ldv, d_o, lse, delta, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, dk, lddk, dv,
-                              lddv, ro, t_amax_out, t_attn_amax, st);
-    const int rc_dkv = h2 ? launch_dkv.template operator()<true>() : launch_dkv.template operator()<false>();
-    if (rc_dkv) return rc_dkv;
-    GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dkv");
-    if (ds_work != nullptr) {
-        hipLaunchKernelGGL((attn_bwd_dq2_s_kernel<G, ORD>), dim3(worklist_grid(B * nkv, (S + R - 1) / R)), dim3(AT_THREADS), 0, st,
-                           k, ldk, ds_work, row_empty, B, S, nq, nkv, scale, dq, lddq, ro);
-        GAMER_CHECK_LAUNCH("gamer_attn_bwd_split/dq2");
-    }
+    if (takes_res_dkv(a, h2)) return launch_dkv_res(a, t_amax_out, t_attn_amax);
+    GAMER_TRY(h2 ? dkv_plain(std::true_type{}) : dkv_plain(std::false_type{}));
+    if (a.ds_work != nullptr)
+        GAMER_TRY(launch<attn_bwd_dq2_s_kernel<G, ORD>>("gamer_attn_bwd_split/dq2", dim3(worklist_grid(a.B * a.nkv, (a.S + R - 1) / R)), dim3(AT_THREADS), 0, a.st,
+                                                      a.k, a.ldk, a.ds_work, a.row_empty, a.B, a.S, a.nq, a.nkv, a.scale, a.dq, a.lddq, a.ro));
     return 0;
 }
 
 template <int G>
-static int launch_bwd_s(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
-                        const float* d_o, const float* lse, float* delta, const int32_t* kl, const int32_t* ql,
-                        const int32_t* row_empty, const int32_t* tile_empty, int B, int S, int nq, int nkv, float scale,
-                        float p_drop, uint64_t seed, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
-                        RowOrder ro, int delta_ready, float* ds_work, hipStream_t st) {
-#define GAMER_LAUNCH_BWD_S(DROPV, ORDV)                                                                                       \
-    return launch_bwd_s_variant<G, DROPV, ORDV>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, \
-                                                nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, delta_ready, ds_work, st)
-    if (p_drop > 0.f) { if (ro.perm) GAMER_LAUNCH_BWD_S(true, true); else GAMER_LAUNCH_BWD_S(true, false); }
-    else { if (ro.perm) GAMER_LAUNCH_BWD_S(false, true); else GAMER_LAUNCH_BWD_S(false, false); }
-#undef GAMER_LAUNCH_BWD_S
-    return -1;      // not reached
+static int launch_bwd_s(const AttnBwdArgs<float>& a) {
+    return with_flags([&](auto drop, auto ord) { return launch_bwd_s_variant<G, drop(), ord()>(a); }, a.p_drop > 0.f, a.ro.perm != nullptr);
 }
 
 }  // namespace gamer
 
 using namespace gamer;
-
-static int check_attn_split(const char* name, const void* q, const void* k, const void* v, const void* kl,
-                            const void* row_empty, int ldq, int ldk, int ldv, int B, int S, int nq, int nkv, float p_drop) {
-    GAMER_CHECK_ARG(q && k && v && kl && row_empty, "%s: null pointer", name);
-    GAMER_CHECK_ARG(B > 0 && S > 0 && nq > 0 && nkv > 0 && nq % nkv == 0, "%s: bad shape B=%d S=%d nq=%d nkv=%d", name, B, S, nq, nkv);
-    const int G = nq / nkv;
-    GAMER_CHECK_ARG(G == 1 || G == 2, "%s: GQA group %d not built (1 or 2)", name, G);
-    GAMER_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq >= nq * 64 && ldk >= nkv * 64 && ldv >= nkv * 64,
-                    "%s: bad leading dims ldq=%d ldk=%d ldv=%d", name, ldq, ldk, ldv);
-    GAMER_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v), "%s: q/k/v must be 16-byte aligned", name);
-    GAMER_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop=%f", name, p_drop);
-    return 0;
-}
 
 extern "C" int gamer_attn_fwd_split(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                                     const int32_t* kl, const int32_t* ql, const int32_t* row_empty, int B, int S, int nq,
@@ -1554,10 +1492,9 @@ extern "C" int gamer_attn_fwd_split(const float* q, int ldq, const float* k, int
     GAMER_CHECK_ARG(!q_span || aligned16(q_span), "gamer_attn_fwd_split: q_span must be 16-byte aligned");
     const int uspan = uniform_len == 0 ? S : uniform_len;
     const RowOrder ro{row_perm, tile_kind, tile_maxpos, q_span};
-    int rc = check_attn_split("gamer_attn_fwd_split", q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
+    int rc = check_attn("gamer_attn_fwd_split", false, q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
     if (rc) return rc;
     GAMER_CHECK_ARG(o && lse && aligned16(o), "gamer_attn_fwd_split: null/unaligned output");
-    hipStream_t st = (hipStream_t)stream;
     t_amax_out = take_amax_sink().out[0];               // gamer_amax_sink: max |o|
     t_attn_amax = g_attn_amax_armed;                    // gamer_attn_split_amax: the three-product fp16 form
     g_attn_amax_armed = AttnAmax{nullptr, nullptr, nullptr, nullptr};
@@ -1565,13 +1502,9 @@ extern "C" int gamer_attn_fwd_split(const float* q, int ldq, const float* k, int
     GAMER_CHECK_ARG(!t_attn_amax.q || p_drop < 0.75f, "gamer_attn_fwd_split: the three-product fp16 form needs p_drop < 0.75 (p_drop=%f): "
                     "its probabilities are cut at a fixed 2^13 scale; do not arm gamer_attn_split_amax for this call", p_drop);
     GAMER_CHECK_ARG(!q_span || t_attn_amax.q, "gamer_attn_fwd_split: q_span is built for the three-product form (arm gamer_attn_split_amax)");
-    if (t_attn_amax.q && (!q_span || (nq / nkv == 2 && GAMER_RES_PART("GAMER_ATTN_RES_SPAN"))) && uspan == S && S <= 2048 && res_enabled())
-        // the three-product form with training semantics: K / V of a (sequence, kv head) resident in LDS (attention_res.hip; key
-        // spans - Qwen3SessionMulti - for the GQA group of two)
-        rc = launch_fwd_res(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, t_amax_out, t_attn_amax, st);
-    else
-    rc = (nq / nkv == 1) ? launch_fwd_s<1>(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, st)
-                         : launch_fwd_s<2>(q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, st);
+    const AttnFwdArgs<float> a{q, ldq, k, ldk, v, ldv, kl, ql, row_empty, B, S, nq, nkv, scale, p_drop, seed, o, lse, ro, uspan, (hipStream_t)stream};
+    rc = takes_res_fwd(a, t_attn_amax.q != nullptr) ? launch_fwd_res(a, t_amax_out, t_attn_amax)
+                                                    : with_group(nq, nkv, [&](auto g) { return launch_fwd_s<g()>(a); });
     t_amax_out = nullptr;
     t_attn_amax = AttnAmax{nullptr, nullptr, nullptr, nullptr};
     return rc;
@@ -1596,7 +1529,7 @@ extern "C" int gamer_attn_bwd_split(const float* q, int ldq, const float* k, int
                                     int lddq, float* dk, int lddk, float* dv, int lddv, const int32_t* row_perm,
                                     const int32_t* tile_kind, const int32_t* tile_maxpos, int delta_ready, float* ds_work,
                                     const int32_t* q_span, void* stream) {
-    int rc = check_attn_split("gamer_attn_bwd_split", q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
+    int rc = check_attn("gamer_attn_bwd_split", false, q, k, v, kl, row_empty, ldq, ldk, ldv, B, S, nq, nkv, p_drop);
     if (rc) return rc;
     GAMER_CHECK_ARG(o && d_o && lse && tile_empty && delta && dq && dk && dv, "gamer_attn_bwd_split: null pointer");
     GAMER_CHECK_ARG(!row_perm || (tile_kind && tile_maxpos), "gamer_attn_bwd_split: row_perm needs tile_kind and tile_maxpos");
@@ -1605,7 +1538,6 @@ extern "C" int gamer_attn_bwd_split(const float* q, int ldq, const float* k, int
     GAMER_CHECK_ARG(lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(dq) && aligned16(dk) && aligned16(dv) &&
                     aligned16(d_o) && aligned16(o),
                     "gamer_attn_bwd_split: gradient buffers must be 16-byte aligned with leading dims %% 4 == 0");
-    hipStream_t st = (hipStream_t)stream;
     t_amax_out = take_amax_sink().out[0];               // gamer_amax_sink: max |dv|
     t_attn_amax = g_attn_amax_armed;
     g_attn_amax_armed = AttnAmax{nullptr, nullptr, nullptr, nullptr};
@@ -1614,9 +1546,9 @@ extern "C" int gamer_attn_bwd_split(const float* q, int ldq, const float* k, int
     GAMER_CHECK_ARG(!t_attn_amax.q || p_drop < 0.75f, "gamer_attn_bwd_split: the three-product fp16 form needs p_drop < 0.75 (p_drop=%f)", p_drop);
     GAMER_CHECK_ARG(!q_span || (t_attn_amax.q && !ds_work), "gamer_attn_bwd_split: q_span is built for the three-product recompute form "
                     "(arm gamer_attn_split_amax, ds_work = NULL)");
-    rc = (nq / nkv == 1)
-        ? launch_bwd_s<1>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, delta_ready, ds_work, st)
-        : launch_bwd_s<2>(q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed, dq, lddq, dk, lddk, dv, lddv, ro, delta_ready, ds_work, st);
+    const AttnBwdArgs<float> a{q, ldq, k, ldk, v, ldv, o, d_o, lse, delta, kl, ql, row_empty, tile_empty, B, S, nq, nkv, scale, p_drop, seed,
+                               dq, lddq, dk, lddk, dv, lddv, ro, ds_work, delta_ready, (hipStream_t)stream};
+    rc = with_group(nq, nkv, [&](auto g) { return launch_bwd_s<g()>(a); });
     t_amax_out = nullptr;
     t_attn_amax = AttnAmax{nullptr, nullptr, nullptr, nullptr};
     return rc;

@@ -217,55 +217,9 @@ struct H2Scales {
 // the maxima of q, k, v (and dO in the backward) of the H2 form: device words (gamer_absmax_f32 / gamer_amax_sink)
 struct AttnAmax { const uint32_t* q; const uint32_t* k; const uint32_t* v; const uint32_t* d_o; };
 
-// ---- attention_res.hip: the H2 kernels with K / V of a (sequence, kv head) resident in LDS ------------------------------------------
-// GAMER_ATTN_RES=0 keeps every call on the tiled kernels of attention_split.hip (A/B runs); default on
-static inline bool res_enabled() {
-    static EnvSwitch sw("GAMER_ATTN_RES");             // (cached: gamer_reload_env() after a change inside the process)
-    return sw.get(1) != 0;
-}
-// GAMER_ATTN_RES_DQ / _DKV / _DKV2 = 0: that kernel stays tiled (A/B runs)
-#define GAMER_RES_PART(name) ([]() -> bool { static EnvSwitch sw(name); return sw.get(1) != 0; }())
-// persistent workgroups: one per CU (GAMER_ATTN_RES_GRID overrides)
-static inline int res_grid_cap() {
-    static EnvSwitch grid("GAMER_ATTN_RES_GRID");       // (tests force a few persistent workgroups to walk many units)
-    if (grid.get(0) > 0) return grid.get(0);
-    static int cap[MAX_DEVICES] = {};
-    int& c = cap[current_device()];
-    if (c == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess) n = 256;
-        c = n > 0 ? n : 256;
-    }
-    return c;
-}
-// Split a (sequence, kv head) pair's work over `ways` workgroups?  Persistent workgroups take whole units, so the launch lasts
-// ceil(units / CUs) rounds: 384 pairs on 256 CUs (per-GPU batch 128) are two rounds with half the CUs idle in the second, 768 half
-// units three full rounds at ~0.58 of a pair's time each (the split units stage the shared operand once more).  GAMER_ATTN_RES_SPLIT=0/1 forces.
-static inline int res_split(int n_pairs, int ways) {
-    if (ways < 2) return 0;
-    static EnvSwitch sp("GAMER_ATTN_RES_SPLIT");
-    if (sp.is_set()) return sp.get(0) != 0;
-    const int ncu = res_grid_cap();
-    const double whole = (double)((n_pairs + ncu - 1) / ncu), halves = 0.58 * (double)((ways * n_pairs + ncu - 1) / ncu);
-    return halves < whole ? 1 : 0;
-}
-static inline bool res_split_forced() { static EnvSwitch sp("GAMER_ATTN_RES_SPLIT"); return sp.is_set(); }
-// share of the CU-rounds that whole-pair units keep busy
-static inline double res_fill(int n_pairs) {
-    const int ncu = res_grid_cap();
-    if (n_pairs <= ncu) return 1.0;          // (a single round: nothing to balance)
-    return (double)n_pairs / ((double)((n_pairs + ncu - 1) / ncu) * ncu);
-}
-int launch_fwd_res(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* kl, const int32_t* ql,
-                   const int32_t* row_empty, int B, int S, int nq, int nkv, float scale, float p_drop, uint64_t seed, float* o,
-                   float* lse, RowOrder ro, uint32_t* amax_out, AttnAmax am, hipStream_t st);
-int launch_dq_res(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, const float* d_o,
-                  const float* lse, float* delta, const int32_t* kl, const int32_t* ql, const int32_t* row_empty, int B, int S,
-                  int nq, int nkv, float scale, float p_drop, uint64_t seed, float* dq, int lddq, RowOrder ro, int delta_ready,
-                  AttnAmax am, hipStream_t st);
-int launch_dkv_res(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* d_o, const float* lse,
-                   const float* delta, const int32_t* kl, const int32_t* ql, const int32_t* row_empty, int B, int S, int nq, int nkv,
-                   float scale, float p_drop, uint64_t seed, float* dk, int lddk, float* dv, int lddv, RowOrder ro, uint32_t* amax_out,
-                   AttnAmax am, hipStream_t st);
+// ---- attention_res.hip: the H2 kernels with K / V of a (sequence, kv head) resident in LDS (switches: attention_common.h) ----------------
+int launch_fwd_res(const AttnFwdArgs<float>& a, uint32_t* amax_out, AttnAmax am);
+int launch_dq_res(const AttnBwdArgs<float>& a, AttnAmax am);
+int launch_dkv_res(const AttnBwdArgs<float>& a, uint32_t* amax_out, AttnAmax am);
 
 }  // namespace gamer

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <atomic>
+#include <type_traits>
 
 #include "../../include/gamer_hip.h"
 
@@ -31,12 +33,55 @@ void set_error(const char* fmt, ...);
         }                                                                               \
     } while (0)
 
-// Per-device "done once" flags (hipFuncSetAttribute and friends are per device; a process may drive several GPUs).
+// Per-device records (function attributes and the like are per device; a process may drive several GPUs).
 constexpr int MAX_DEVICES = 16;
 static inline int current_device() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= MAX_DEVICES) d = 0;
     return d;
+}
+
+// Propagate a non-zero return code (the launch helpers below return 0 or the error they recorded with set_error).
+#define GAMER_TRY(...)                                   \
+    do {                                                 \
+        if (const int rc__ = (__VA_ARGS__)) return rc__; \
+    } while (0)
+
+// ---- kernel launches --------------------------------------------------------------------------------------------------------
+// A kernel that takes more dynamic LDS than the default limit has to raise its limit first, per device.  One record per kernel
+// (the kernel is the template argument) and device: the largest size registered so far; the attribute is set again only when a
+// call needs more.  `who` names the caller in the error text.
+template <auto Kernel>
+static inline int ensure_dynamic_lds(const char* who, size_t bytes) {
+    static std::atomic<int> registered[MAX_DEVICES] = {};
+    std::atomic<int>& r = registered[current_device()];
+    int have = r.load(std::memory_order_relaxed);
+    if ((int)bytes <= have) return 0;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+        return (int)e;
+    }
+    while (have < (int)bytes && !r.compare_exchange_weak(have, (int)bytes, std::memory_order_relaxed)) {}
+    return 0;
+}
+// Every launch: the LDS limit when the kernel takes dynamic LDS, the launch, hipGetLastError.  Returns 0 or the error code.
+template <auto Kernel, typename... Args>
+static inline int launch(const char* who, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args&&... args) {
+    if (lds_bytes > 0) GAMER_TRY(ensure_dynamic_lds<Kernel>(who, lds_bytes));
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, static_cast<Args&&>(args)...);
+    GAMER_CHECK_LAUNCH(who);
+    return 0;
+}
+// Runtime flags as template arguments: with_flags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}) - one generic
+// lambda at the call site instead of an if / else tree per flag.  What gets instantiated is every combination of the flags passed,
+// so a call site passes only the flags whose both values are built (and fixes the others itself).
+template <typename F>
+static inline int with_flags(F&& f) { return f(); }
+template <typename F, typename... Rest>
+static inline int with_flags(F&& f, bool flag, Rest... rest) {
+    if (flag) return with_flags([&](auto... cs) { return f(std::true_type{}, cs...); }, rest...);
+    return with_flags([&](auto... cs) { return f(std::false_type{}, cs...); }, rest...);
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -622,52 +622,17 @@ static int attn_decode_impl(const float* q, int ldq, const float* kp, int ldkp, 
     if (amax_k && amax_v) {
         // the three-piece fp16 form (prompt K / V maxima given); max |o| goes to the slot gamer_amax_sink armed, if any
         uint32_t* sink_o = take_amax_sink().out[0];
-        static bool attr2_dev[MAX_DEVICES] = {};
-        bool& attr2 = attr2_dev[current_device()];
-        if (!attr2) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_h2_kernel<1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, DEC2_LDS_BYTES);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_h2_kernel<2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, DEC2_LDS_BYTES);
-            if (e != hipSuccess) {
-                set_error("gamer_attn_decode_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-            attr2 = true;
-        }
-        if (G == 1)
-            hipLaunchKernelGGL(attn_decode_h2_kernel<1>, grid, dim3(256), DEC2_LDS_BYTES, (hipStream_t)stream, q, ldq, kp, ldkp, vp, ldvp,
-                               key_ok, kg, vg, ldg, tmax, t, gen_ok, uniform, nb, L0, nq, nkv, scale, o, amax_k, amax_v, sink_o);
-        else
-            hipLaunchKernelGGL(attn_decode_h2_kernel<2>, grid, dim3(256), DEC2_LDS_BYTES, (hipStream_t)stream, q, ldq, kp, ldkp, vp, ldvp,
-                               key_ok, kg, vg, ldg, tmax, t, gen_ok, uniform, nb, L0, nq, nkv, scale, o, amax_k, amax_v, sink_o);
-        GAMER_CHECK_LAUNCH("gamer_attn_decode_split");
-        return 0;
+        return with_group(nq, nkv, [&](auto g) {
+            return launch<attn_decode_h2_kernel<g()>>("gamer_attn_decode_split", grid, dim3(256), DEC2_LDS_BYTES, (hipStream_t)stream, q, ldq, kp, ldkp,
+                                                      vp, ldvp, key_ok, kg, vg, ldg, tmax, t, gen_ok, uniform, nb, L0, nq, nkv, scale, o, amax_k,
+                                                      amax_v, sink_o);
+        });
     }
     const size_t shmem = (size_t)DEC_LDS_FLOATS * sizeof(float);
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_kernel<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_decode_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) {
-            set_error("gamer_attn_decode: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr = true;
-    }
-    if (G == 1)
-        hipLaunchKernelGGL(attn_decode_kernel<1>, grid, dim3(256), shmem, (hipStream_t)stream, q, ldq, kp, ldkp, vp, ldvp,
-                           key_ok, kg, vg, ldg, tmax, t, gen_ok, uniform, nb, L0, nq, nkv, scale, o);
-    else
-        hipLaunchKernelGGL(attn_decode_kernel<2>, grid, dim3(256), shmem, (hipStream_t)stream, q, ldq, kp, ldkp, vp, ldvp,
-                           key_ok, kg, vg, ldg, tmax, t, gen_ok, uniform, nb, L0, nq, nkv, scale, o);
-    GAMER_CHECK_LAUNCH("gamer_attn_decode");
-    return 0;
+    return with_group(nq, nkv, [&](auto g) {
+        return launch<attn_decode_kernel<g()>>("gamer_attn_decode", grid, dim3(256), shmem, (hipStream_t)stream, q, ldq, kp, ldkp, vp, ldvp, key_ok,
+                                               kg, vg, ldg, tmax, t, gen_ok, uniform, nb, L0, nq, nkv, scale, o);
+    });
 }
 
 extern "C" int gamer_attn_decode(const float* q, int ldq, const float* kp, int ldkp, const float* vp, int ldvp,

@@ -1284,25 +1284,12 @@ gemm_f32_kernel(const GemmParams p, const int vgrid) {
 
 template <bool A_KC, bool B_KC, int MODE, bool ACCUM, bool STAMP, int NBUF, int EPI = 0, int SPLIT = 0, bool PP = false>
 static int launch_gemm_t(const GemmParams& p, int blocks, hipStream_t st, int lds) {
-    static int attr_lds_dev[MAX_DEVICES] = {};
-    int& attr_lds = attr_lds_dev[current_device()];
-    auto kfn = gemm_f32_kernel<A_KC, B_KC, MODE, ACCUM, STAMP, NBUF, EPI, SPLIT, PP>;
-    if (attr_lds != lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            set_error("gamer_gemm_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        attr_lds = lds;
-    }
     static int persist = -1;
     if (persist < 0) { const char* e = getenv("GAMER_GEMM_PERSIST"); persist = e ? atoi(e) : 0; }
     // GAMER_GEMM_PERSIST=n (n a multiple of 8): at most n workgroups, each walking several tiles (plain split forms only)
     const int grid = (persist > 0 && SPLIT != 0 && !PP && !STAMP && blocks > persist) ? persist : blocks;
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(PP ? 2 * GEMM_THREADS : GEMM_THREADS), lds, st, p, blocks);
-    GAMER_CHECK_LAUNCH("gamer_gemm_f32");
-    return 0;
+    return launch<gemm_f32_kernel<A_KC, B_KC, MODE, ACCUM, STAMP, NBUF, EPI, SPLIT, PP>>("gamer_gemm_f32", dim3(grid), dim3(PP ? 2 * GEMM_THREADS : GEMM_THREADS),
+                                                                                        lds, st, p, blocks);
 }
 
 // the bf16-split forms: one LDS stage; the epilogue's row-major rewrite needs the full 72 KB

@@ -438,6 +438,16 @@ bool gemm_as_eligible(const gamer_gemm_desc* d, bool a_kc, bool b_kc, const uint
     return !d->amax_c || (!d->accumulate && d->amax_c_col0 % AS_SLAB == 0);
 }
 
+// gemm_as_kernel<KP, WRC, EPI, waves>: nw = 4 or 8 waves per workgroup; the SwiGLU epilogue (EPI 5) is built for four only
+template <int KP, bool WRC, int EPI>
+static int launch_as(int nw, dim3 grid, size_t shmem, hipStream_t st, const AsParams& p) {
+    const char* who = "gamer_gemm_f32_split/activation-stationary";
+    if constexpr (EPI == 5) return launch<gemm_as_kernel<KP, WRC, EPI, 4>>(who, grid, dim3(64 * 4), shmem, st, p);
+    else
+        return with_flags([&](auto eight) { return launch<gemm_as_kernel<KP, WRC, EPI, eight() ? 8 : 4>>(who, grid, dim3(eight() ? 512 : 256), shmem, st, p); },
+                          nw == 8);
+}
+
 int launch_gemm_as(const gamer_gemm_desc* d, const uint16_t* b_planes, bool b_kc, hipStream_t st) {
     AsParams p;
     p.A = d->A; p.lda = d->a_rs;
@@ -458,44 +468,29 @@ int launch_gemm_as(const gamer_gemm_desc* d, const uint16_t* b_planes, bool b_kc
     static EnvSwitch wv("GAMER_GEMM_AS_WAVES");
     const int nw = d->sw_hm ? 4 : (wv.is_set() ? (wv.get(4) == 8 ? 8 : 4) : ((b_kc && d->groups == 1 && d->N >= 512 && AS_WAVES == 4) ? 8 : AS_WAVES));
     const dim3 grid((d->M + 32 * nw - 1) / (32 * nw) + (p.group_offsets ? d->groups : 0));
-#define GAMER_LAUNCH_AS_W(KPV, WRCV, EPIV, NWV)                                                                               \
-    do {                                                                                                                      \
-        static bool attr_dev[MAX_DEVICES] = {};                                                                               \
-        if (!attr_dev[current_device()]) {                                                                                    \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_as_kernel<KPV, WRCV, EPIV, NWV>),     \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                 \
-            if (e != hipSuccess) { set_error("gamer_gemm_f32_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; } \
-            attr_dev[current_device()] = true;                                                                                \
-        }                                                                                                                     \
-        hipLaunchKernelGGL((gemm_as_kernel<KPV, WRCV, EPIV, NWV>), grid, dim3(64 * NWV), shmem, st, p);                        \
-    } while (0)
-#define GAMER_LAUNCH_AS(KPV, WRCV, EPIV)                                                                                      \
-    do { if (nw == 8) GAMER_LAUNCH_AS_W(KPV, WRCV, EPIV, 8); else GAMER_LAUNCH_AS_W(KPV, WRCV, EPIV, 4); } while (0)
+    int rc;
     if (b_kc && d->sw_hm) {
-        // (one shared-memory size per instantiation is registered once: always ask for the table's room)
         switch (kp) {
-            case 1: GAMER_LAUNCH_AS_W(1, false, 5, 4); break;
-            case 2: GAMER_LAUNCH_AS_W(2, false, 5, 4); break;
-            case 3: GAMER_LAUNCH_AS_W(3, false, 5, 4); break;
-            default: GAMER_LAUNCH_AS_W(4, false, 5, 4); break;
+            case 1: rc = launch_as<1, false, 5>(nw, grid, shmem, st, p); break;
+            case 2: rc = launch_as<2, false, 5>(nw, grid, shmem, st, p); break;
+            case 3: rc = launch_as<3, false, 5>(nw, grid, shmem, st, p); break;
+            default: rc = launch_as<4, false, 5>(nw, grid, shmem, st, p); break;
         }
     } else if (b_kc) {
         switch (kp) {
-            case 1: GAMER_LAUNCH_AS(1, false, 0); break;
-            case 2: GAMER_LAUNCH_AS(2, false, 0); break;
-            case 3: GAMER_LAUNCH_AS(3, false, 0); break;
-            default: GAMER_LAUNCH_AS(4, false, 0); break;
+            case 1: rc = launch_as<1, false, 0>(nw, grid, shmem, st, p); break;
+            case 2: rc = launch_as<2, false, 0>(nw, grid, shmem, st, p); break;
+            case 3: rc = launch_as<3, false, 0>(nw, grid, shmem, st, p); break;
+            default: rc = launch_as<4, false, 0>(nw, grid, shmem, st, p); break;
         }
     } else if (d->sw_gu) {
-        GAMER_LAUNCH_AS(4, true, 4);
+        rc = launch_as<4, true, 4>(nw, grid, shmem, st, p);
     } else if (d->rowdot_out) {
-        GAMER_LAUNCH_AS(4, true, 2);
+        rc = launch_as<4, true, 2>(nw, grid, shmem, st, p);
     } else {
-        GAMER_LAUNCH_AS(4, true, 0);
+        rc = launch_as<4, true, 0>(nw, grid, shmem, st, p);
     }
-#undef GAMER_LAUNCH_AS
-#undef GAMER_LAUNCH_AS_W
-    GAMER_CHECK_LAUNCH("gamer_gemm_f32_split/activation-stationary");
+    if (rc) return rc;
     g_as_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }

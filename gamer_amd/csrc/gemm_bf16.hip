@@ -1169,57 +1169,24 @@ static const bf16_t* zero_page() {
 
 template <int EPI, bool ACCUM>
 static int launch_hb(const GemmBf16Params& p, int tiles, hipStream_t st) {
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    auto kfn = gemm_bf16_kernel<EPI, ACCUM>;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           HB_LDS_BYTES);
-        if (e != hipSuccess) { set_error("gamer_gemm_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr = true;
-    }
     // HF_WGS workgroups per CU x 256 CUs, in multiples of 8 (one share per XCD); small problems: one workgroup per tile
     int blocks = 256 * HF_WGS;
     if (tiles < blocks) blocks = ((tiles + 7) / 8) * 8;
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(HB_THREADS), HB_LDS_BYTES, st, p, tiles);
-    GAMER_CHECK_LAUNCH("gamer_gemm_bf16");
-    return 0;
+    return launch<gemm_bf16_kernel<EPI, ACCUM>>("gamer_gemm_bf16", dim3(blocks), dim3(HB_THREADS), HB_LDS_BYTES, st, p, tiles);
 }
 
 template <bool ACCUM>
 static int launch_ws(const GemmBf16Params& p, int tiles, hipStream_t st) {
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    auto kfn = gemm_bf16_ws_kernel<ACCUM>;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           WS_LDS_BYTES);
-        if (e != hipSuccess) { set_error("gamer_gemm_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr = true;
-    }
     int blocks = 256;                                   // one workgroup per CU, in multiples of 8 (one share per XCD)
     if (tiles < blocks) blocks = ((tiles + 7) / 8) * 8;
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(WS_THREADS), WS_LDS_BYTES, st, p, tiles);
-    GAMER_CHECK_LAUNCH("gamer_gemm_bf16/ws");
-    return 0;
+    return launch<gemm_bf16_ws_kernel<ACCUM>>("gamer_gemm_bf16/ws", dim3(blocks), dim3(WS_THREADS), WS_LDS_BYTES, st, p, tiles);
 }
 
 template <int EPI, bool ACCUM>
 static int launch_big(const GemmBf16Params& p, int tiles, hipStream_t st) {
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    auto kfn = gemm_bf16_big_kernel<EPI, ACCUM>;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           HG_LDS_BYTES);
-        if (e != hipSuccess) { set_error("gamer_gemm_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr = true;
-    }
     int blocks = 256;                                   // one workgroup per CU, in multiples of 8 (one share per XCD)
     if (tiles < blocks) blocks = ((tiles + 7) / 8) * 8;
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(HG_THREADS), HG_LDS_BYTES, st, p, tiles);
-    GAMER_CHECK_LAUNCH("gamer_gemm_bf16/256");
-    return 0;
+    return launch<gemm_bf16_big_kernel<EPI, ACCUM>>("gamer_gemm_bf16/256", dim3(blocks), dim3(HG_THREADS), HG_LDS_BYTES, st, p, tiles);
 }
 
 extern "C" int gamer_gemm_bf16(const gamer_gemm_bf16_desc* d, void* stream) {
@@ -1337,14 +1304,6 @@ extern "C" int gamer_gemm_bf16(const gamer_gemm_bf16_desc* d, void* stream) {
     const int64_t chunks = (d->K + d->kchunk - 1) / d->kchunk + (d->group_offsets ? d->groups : 0);
     const int64_t blocks = chunks * p.m_tiles * p.n_tiles;
     GAMER_CHECK_ARG(blocks < (1LL << 31), "gamer_gemm_bf16: grid too large");
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_wgrad_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, HW_LDS_BYTES);
-        if (e != hipSuccess) { set_error("gamer_gemm_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr = true;
-    }
     if (d->wgrad_ws) {
         const int64_t need = blocks * (int64_t)(HB_BM * HB_BN);
         GAMER_CHECK_ARG(d->wgrad_ws_floats >= need && aligned16(d->wgrad_ws),
@@ -1352,8 +1311,7 @@ extern "C" int gamer_gemm_bf16(const gamer_gemm_bf16_desc* d, void* stream) {
                         (long long)d->wgrad_ws_floats, (long long)need);
         p.wgrad_ws = d->wgrad_ws;
     }
-    hipLaunchKernelGGL(gemm_bf16_wgrad_kernel, dim3((int)blocks), dim3(HB_THREADS), HW_LDS_BYTES, st, p, zp);
-    GAMER_CHECK_LAUNCH("gamer_gemm_bf16/wgrad");
+    GAMER_TRY(launch<gemm_bf16_wgrad_kernel>("gamer_gemm_bf16/wgrad", dim3((int)blocks), dim3(HB_THREADS), HW_LDS_BYTES, st, p, zp));
     if (p.wgrad_ws) {
         const int e = launch_wgrad_reduce(p.wgrad_ws, reinterpret_cast<float*>(d->C), d->ldc, d->M, d->N, d->groups, d->group_offsets,
                                           d->K, d->kchunk, d->strideC, st);

@@ -337,15 +337,8 @@ int launch_gemm_os(const gamer_gemm_desc* d, const uint16_t* b_planes, int guard
     p.amax_c = d->amax_c; p.amax_c_col0 = d->amax_c_col0;
     p.guard = guard;
     p.groups = d->groups; p.group_offsets = d->groups > 1 ? d->group_offsets : nullptr; p.strideW = d->strideB;
-    static bool attr_dev[MAX_DEVICES] = {};
-    if (!attr_dev[current_device()]) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_os_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, OS_LDS);
-        if (e != hipSuccess) { set_error("gamer_gemm_f32_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr_dev[current_device()] = true;
-    }
     const dim3 grid((d->M + 32 * OS_WAVES - 1) / (32 * OS_WAVES) + (p.group_offsets ? d->groups : 0));
-    hipLaunchKernelGGL(gemm_os_kernel, grid, dim3(OS_THREADS), OS_LDS, st, p);
-    GAMER_CHECK_LAUNCH("gamer_gemm_f32_split/output-stationary input gradient");
+    GAMER_TRY(launch<gemm_os_kernel>("gamer_gemm_f32_split/output-stationary input gradient", grid, dim3(OS_THREADS), OS_LDS, st, p));
     g_os_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }

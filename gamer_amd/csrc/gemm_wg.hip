@@ -356,20 +356,10 @@ int launch_gemm_wg(const gamer_gemm_desc* d, hipStream_t st) {
     const int64_t blocks = chunks * p.mt * p.nt;
     if (blocks >= (1LL << 31)) { set_error("gamer_gemm_f32_split: weight-gradient grid too large"); return 1; }
     const bool full = d->M % WG_T == 0 && d->N % WG_T == 0;
-#define GAMER_LAUNCH_WG(FULLV)                                                                                                \
-    do {                                                                                                                      \
-        static bool attr_dev[MAX_DEVICES] = {};                                                                               \
-        if (!attr_dev[current_device()]) {                                                                                    \
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_wg_kernel<FULLV>),                    \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS);                     \
-            if (e != hipSuccess) { set_error("gamer_gemm_f32_split: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; } \
-            attr_dev[current_device()] = true;                                                                                \
-        }                                                                                                                     \
-        hipLaunchKernelGGL(gemm_wg_kernel<FULLV>, dim3((int)blocks), dim3(WG_THREADS), WG_LDS, st, p);                        \
-    } while (0)
-    if (full) GAMER_LAUNCH_WG(true); else GAMER_LAUNCH_WG(false);
-#undef GAMER_LAUNCH_WG
-    GAMER_CHECK_LAUNCH("gamer_gemm_f32_split/weight gradient, 256 x 256 tiles");
+    GAMER_TRY(with_flags([&](auto full_c) {
+        return launch<gemm_wg_kernel<full_c()>>("gamer_gemm_f32_split/weight gradient, 256 x 256 tiles", dim3((int)blocks), dim3(WG_THREADS),
+                                                WG_LDS, st, p);
+    }, full));
     g_wg_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }

@@ -497,15 +497,6 @@ static int mbs_args(const char* name, MbsArgs& a, const float* q, int ldq, const
     return 0;
 }
 
-template <typename Kern>
-static int mbs_lds_attr(const char* name, Kern kern, bool& done) {
-    if (done) return 0;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MBS_LDS_MAX);
-    if (e != hipSuccess) { set_error("%s: hipFuncSetAttribute failed: %s", name, hipGetErrorString(e)); return (int)e; }
-    done = true;
-    return 0;
-}
-
 extern "C" int gamer_mbs_attn_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* types,
                                   const float* w1m, const float* w2m, const float* rel, const int32_t* bucket, int num_buckets, int B,
                                   int L, int H, int head_dim, int n_behaviors, float scale, float p_drop, uint64_t seed, float* o,
@@ -519,12 +510,8 @@ extern "C" int gamer_mbs_attn_fwd(const float* q, int ldq, const float* k, int l
     const size_t staged = shmem + (size_t)3 * L * (head_dim + 1) * sizeof(float);
     a.stage = staged <= MBS_LDS_MAX ? 1 : 0;
     if (a.stage) shmem = staged;
-    static bool attr_dev[MAX_DEVICES] = {};
-    rc = mbs_lds_attr("gamer_mbs_attn_fwd", mbs_attn_fwd_kernel, attr_dev[current_device()]);
-    if (rc) return rc;
-    hipLaunchKernelGGL(mbs_attn_fwd_kernel, dim3(B * H), dim3(MBS_THREADS), shmem, ST(stream), a, o, ldo, lse);
-    GAMER_CHECK_LAUNCH("gamer_mbs_attn_fwd");
-    return 0;
+    GAMER_TRY(ensure_dynamic_lds<mbs_attn_fwd_kernel>("gamer_mbs_attn_fwd", MBS_LDS_MAX));
+    return launch<mbs_attn_fwd_kernel>("gamer_mbs_attn_fwd", dim3(B * H), dim3(MBS_THREADS), shmem, ST(stream), a, o, ldo, lse);
 }
 
 extern "C" int gamer_mbs_attn_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* types,
@@ -546,13 +533,9 @@ extern "C" int gamer_mbs_attn_bwd(const float* q, int ldq, const float* k, int l
     const size_t staged = shmem + (size_t)4 * L * (head_dim + 1) * sizeof(float);
     a.stage = staged <= MBS_LDS_MAX ? 1 : 0;
     if (a.stage) shmem = staged;
-    static bool attr_dev[MAX_DEVICES] = {};
-    rc = mbs_lds_attr("gamer_mbs_attn_bwd", mbs_attn_bwd_kernel, attr_dev[current_device()]);
-    if (rc) return rc;
-    hipLaunchKernelGGL(mbs_attn_bwd_kernel, dim3(n_partial * H), dim3(MBS_THREADS), shmem, ST(stream), a, o, d_o, ldo, lse, dq, lddq, dk,
-                       lddk, dv, lddv, dw1m_partial, dw2m_partial, drel_partial, n_partial);
-    GAMER_CHECK_LAUNCH("gamer_mbs_attn_bwd");
-    return 0;
+    GAMER_TRY(ensure_dynamic_lds<mbs_attn_bwd_kernel>("gamer_mbs_attn_bwd", MBS_LDS_MAX));
+    return launch<mbs_attn_bwd_kernel>("gamer_mbs_attn_bwd", dim3(n_partial * H), dim3(MBS_THREADS), shmem, ST(stream), a, o, d_o, ldo, lse, dq, lddq,
+                                       dk, lddk, dv, lddv, dw1m_partial, dw2m_partial, drel_partial, n_partial);
 }
 
 extern "C" int gamer_mbs_bias_fold(const float* drel, const int32_t* bucket, int L, int n_pairs, int num_buckets, int H, float* dbias,

@@ -395,17 +395,8 @@ extern "C" int gamer_attn_dense_fwd(const float* q, int ldq, const float* k, int
     const size_t staged = shmem + (size_t)3 * S * (head_dim + 1) * sizeof(float);
     a.stage = staged <= DENSE_LDS_MAX ? 1 : 0;
     if (a.stage) shmem = staged;
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_dense_fwd_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DENSE_LDS_MAX);
-        if (e != hipSuccess) { set_error("gamer_attn_dense_fwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr = true;
-    }
-    hipLaunchKernelGGL(attn_dense_fwd_kernel, dim3(B * H), dim3(MOD_THREADS), shmem, ST(stream), a, o, ldo, lse);
-    GAMER_CHECK_LAUNCH("gamer_attn_dense_fwd");
-    return 0;
+    GAMER_TRY(ensure_dynamic_lds<attn_dense_fwd_kernel>("gamer_attn_dense_fwd", DENSE_LDS_MAX));
+    return launch<attn_dense_fwd_kernel>("gamer_attn_dense_fwd", dim3(B * H), dim3(MOD_THREADS), shmem, ST(stream), a, o, ldo, lse);
 }
 
 extern "C" int gamer_attn_dense_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
@@ -422,16 +413,7 @@ extern "C" int gamer_attn_dense_bwd(const float* q, int ldq, const float* k, int
     const size_t staged = shmem + (size_t)4 * S * (head_dim + 1) * sizeof(float);
     a.stage = staged <= DENSE_LDS_MAX ? 1 : 0;
     if (a.stage) shmem = staged;
-    static bool attr_dev[MAX_DEVICES] = {};
-    bool& attr = attr_dev[current_device()];
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_dense_bwd_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)DENSE_LDS_MAX);
-        if (e != hipSuccess) { set_error("gamer_attn_dense_bwd: hipFuncSetAttribute failed: %s", hipGetErrorString(e)); return (int)e; }
-        attr = true;
-    }
-    hipLaunchKernelGGL(attn_dense_bwd_kernel, dim3(B * H), dim3(MOD_THREADS), shmem, ST(stream), a, o, d_o, ldo, lse, dq,
+    GAMER_TRY(ensure_dynamic_lds<attn_dense_bwd_kernel>("gamer_attn_dense_bwd", DENSE_LDS_MAX));
+    return launch<attn_dense_bwd_kernel>("gamer_attn_dense_bwd", dim3(B * H), dim3(MOD_THREADS), shmem, ST(stream), a, o, d_o, ldo, lse, dq,
                        lddq, dk, lddk, dv, lddv);
-    GAMER_CHECK_LAUNCH("gamer_attn_dense_bwd");
-    return 0;
 }

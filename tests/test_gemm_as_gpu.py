@@ -381,3 +381,59 @@ def test_gemm_as_swiglu_forward_epilogue_equals_the_two_launches(table, p_drop):
         full = ref + (tbl.double().cpu()[row_group.cpu().long()] if table else 0.0)
         want = torch.nn.functional.silu(full[:, :I]) * full[:, I:]
         assert float((hm_f.double().cpu() - want).abs().max()) < 5e-6 * float(want.abs().max())
+
+
+# ---- the dynamic-LDS limit of one kernel instantiation grows with what a later call needs ------------------------------------------------
+_GROWING_LDS_CHILD = r'''
+import ctypes
+import torch
+from gamer_amd import _lib, ops
+DEV = "cuda"
+lib = _lib.load()
+lib.gamer_debug_gemm_as_launches.restype = ctypes.c_longlong
+T, K, G = 300, 256, 2
+offs = torch.tensor([0, 137, T], dtype=torch.int32, device=DEV)          # two groups, ragged boundary
+for I in (32, 64):                                                       # N = 64: 65,792 bytes of LDS; N = 128: 66,048
+    N = 2 * I
+    g = torch.Generator().manual_seed(5 + I)
+    flat = (torch.randn(G * N * K + 8, generator=g) * 0.05).to(DEV)
+    W = flat[:G * N * K].view(G * N, K)
+    x = (torch.randn(T, K, generator=g) * torch.exp(torch.randn(T, 1, generator=g))).to(DEV)
+    grp = dict(strideB=N * K, groups=G, group_offsets=offs)
+    cache = ops.amax_reuse()
+    cache.stable_range(flat.data_ptr(), flat.numel() * 4)
+    cache.planes = torch.zeros(flat.numel(), dtype=torch.float32, device=DEV)
+
+    def run(fused):
+        with ops.env_switches(GAMER_GEMM_AS=1, GAMER_GEMM_AS_MIN_M=1), ops.f32_matmul("split3"), cache:
+            for _ in range(2):                                           # (the packed pieces exist from the second pass on)
+                cache.reset()
+                gu = torch.full((T, N), float("nan"), device=DEV)
+                hm = torch.full((T, I), float("nan"), device=DEV)
+                if fused:
+                    ops.gemm(x, K, 1, W, K, 1, gu, N, T, N, K, swiglu_fwd=(hm, None, None), **grp)
+                else:
+                    ops.gemm(x, K, 1, W, K, 1, gu, N, T, N, K, **grp)
+                    ops.swiglu_fwd_ld(gu, N, T, I, 0.0, 0, hm)
+            torch.cuda.synchronize()
+        return gu, hm
+    n0 = lib.gamer_debug_gemm_as_launches()
+    gu_f, hm_f = run(True)
+    n1 = lib.gamer_debug_gemm_as_launches()
+    print("I", I, "activation-stationary launches", n1 - n0)
+    assert n1 > n0, "the SwiGLU-epilogue call did not reach the activation-stationary kernel"
+    gu_r, hm_r = run(False)
+    assert torch.equal(gu_f, gu_r) and torch.equal(hm_f, hm_r), I
+print("ok")
+'''
+
+
+def test_gemm_as_swiglu_epilogue_lds_grows_with_a_wider_second_call():
+    """Two SwiGLU-epilogue calls in one fresh process (no earlier test has registered an LDS size): K = 256, 300 rows in two ragged groups,
+    first I = 32 (N = 64: 65,536 + 4 N = 65,792 bytes of dynamic LDS), then I = 64 (66,048 bytes) on the same kernel instantiation.  Both
+    return, both reach the activation-stationary kernel, and gate|up and hm of each are the bits of the projection followed by
+    gamer_swiglu_fwd_ld."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _GROWING_LDS_CHILD], cwd=root, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-1000:], r.stderr[-3000:])
