@@ -195,6 +195,9 @@ _SIGNATURES = {
     "gamer_mbs_bias_fold": [P, P, I, I, I, I, P, P],
     "gamer_mbs_gate_mix_fwd": [P, I, P, P, I, I, I, P, P, P],
     "gamer_mbs_gate_mix_bwd": [P, P, P, I, I, I, P, P, I, P],
+    "gamer_rvq_ws_floats": [I],
+    "gamer_rvq_fwd": [P, L, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P],
+    "gamer_rvq_bwd": [P, P, P, P, I, I, I, P, P, F, P, P, P],
 }
 
 
@@ -234,7 +237,7 @@ def load(build_if_missing: bool = False) -> C.CDLL:
     lib.gamer_embedding_bwd_ordered_ws_bytes.restype = c_int64      # (a size, not an error code: call it on the library object)
     lib.gamer_segment_colsum_ws_floats.restype = c_int64
     for name in ("gamer_catalog_ws_bytes", "gamer_embedding_bwd_large_ws_bytes", "gamer_position_bwd_ws_floats",
-                 "gamer_gru_gates_floats", "gamer_cloze_mask_ws_bytes"):
+                 "gamer_gru_gates_floats", "gamer_cloze_mask_ws_bytes", "gamer_rvq_ws_floats"):
         getattr(lib, name).restype = c_int64
     _lib = lib
     return lib

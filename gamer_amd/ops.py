@@ -1631,3 +1631,46 @@ def mbs_gate_mix_bwd(gates, outs, dmix, douts, dlogits):
             or dlogits.stride(1) != 1:
         raise RuntimeError("mbs_gate_mix_bwd: bad shapes")
     call("gamer_mbs_gate_mix_bwd", ptr(gates), ptr(outs), ptr(dmix), M, E, H, ptr(douts), ptr(dlogits), dlogits.stride(0), stream_ptr())
+
+
+# ---- residual quantiser of the RQ-VAE item tokenizer (csrc/rqvae.hip) ------------------------------------------------------------
+RVQ_MAX_LEVELS, RVQ_MAX_D, RVQ_MAX_K = 8, 64, 1024
+
+
+def rvq_check_limits(num_emb_list, e_dim):
+    """The limits of the quantiser kernels as the module reports them (the entry points refuse them too, before any launch)."""
+    if not (1 <= len(num_emb_list) <= RVQ_MAX_LEVELS and all(1 <= k <= RVQ_MAX_K for k in num_emb_list)
+            and 4 <= e_dim <= RVQ_MAX_D and e_dim % 4 == 0):
+        raise NotImplementedError(f"RQ-VAE on the HIP path: at most {RVQ_MAX_LEVELS} levels of at most {RVQ_MAX_K} codes, e_dim a "
+                                  f"multiple of 4 and at most {RVQ_MAX_D} (got num_emb_list={list(num_emb_list)}, e_dim={e_dim})")
+
+
+def _i32_array(values):
+    return (C.c_int32 * len(values))(*[int(v) for v in values])
+
+
+def rvq_ws_floats(B):
+    return int(_lib.load().gamer_rvq_ws_floats(B))
+
+
+def rvq_fwd(r, codebooks, level_offsets, modes, level_begin, level_end, idx, x_q, residual, r_levels=None, dist=None,
+            loss_sums=None):
+    """Levels [level_begin, level_end) of the residual quantiser on r [B, D] (rows may be strided; gamer_rvq_fwd).  level_offsets /
+    modes: Python sequences (n_levels + 1 / n_levels values).  idx int32 [B, n_levels]; x_q, residual [B, D]; r_levels
+    [n_levels, B, D]; dist [B, K of level_end - 1] makes that level distance-only; loss_sums [n_levels]."""
+    n_levels = len(modes)
+    B, D = (r.shape[0], r.shape[1]) if r is not None else (x_q.shape[0], x_q.shape[1])
+    ws = None
+    if loss_sums is not None:
+        ws = _ws("rvq", loss_sums.device, 4 * max(rvq_ws_floats(B), 1))
+    ldr = r.stride(0) if r is not None else D
+    call("gamer_rvq_fwd", ptr(r), ldr, ptr(codebooks), _i32_array(level_offsets), _i32_array(modes), n_levels, level_begin,
+         level_end, B, D, ptr(idx), ptr(x_q), ptr(residual), ptr(r_levels), ptr(dist), ptr(ws), ptr(loss_sums), stream_ptr())
+
+
+def rvq_bwd(idx, r_levels, codebooks, level_offsets, g_xq, g_level, mu, dz, dE):
+    """dz [B, D] and dE [sum K, D] of the quantiser losses (gamer_rvq_bwd): g_xq [B, D] or None, g_level [n_levels] on the device."""
+    n_levels = len(level_offsets) - 1
+    B, D = dz.shape
+    call("gamer_rvq_bwd", ptr(idx), ptr(r_levels), ptr(codebooks), _i32_array(level_offsets), n_levels, B, D, ptr(g_xq),
+         ptr(g_level), float(mu), ptr(dz), ptr(dE), stream_ptr())

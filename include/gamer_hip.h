@@ -946,6 +946,27 @@ int gamer_mbs_gate_mix_fwd(const float* logits, int ldl, const float* outs, cons
 int gamer_mbs_gate_mix_bwd(const float* gates, const float* outs, const float* dmix, int M, int E, int H, float* douts,
                            float* dlogits, int lddl, void* stream);
 
+/* (ABI 9) Residual quantiser of the RQ-VAE item tokenizer (csrc/rqvae.hip; ref:SeqRec/models/tokenizer/RQVAE).  The codebooks of the
+ * n_levels levels are packed as [sum K_l][D]; level_offsets (HOST int32 [n_levels + 1], from 0) and modes (HOST int32 [n_levels]:
+ * 0 = argmin of d = |r|^2 + |e|^2 - 2 r.e with the lowest index on a tie, 1 = the index given in idx) are read on the host.
+ * D % 4 == 0, D <= 64; K_l <= 1024; n_levels <= 8; any B >= 1; beyond that: an error, nothing launched.  fp32 FMA chains, no float
+ * atomics: the same bits on every call, and a row's outputs do not depend on the other rows.  DESIGN.md section 10h. */
+int64_t gamer_rvq_ws_floats(int B);
+/* Runs levels [level_begin, level_end) on r [B][ldr] (the residual entering level_begin): idx [B][n_levels] (written in mode 0,
+ * read in mode 1), x_q [B][D] (read first when level_begin > 0, else started from zero) += x_res_l = r + (e - r), residual [B][D] =
+ * the residual after the last level run; r_levels [n_levels][B][D] (or NULL) keeps the residual ENTERING each level run, for
+ * gamer_rvq_bwd.  dist (or NULL): level_end - 1 only writes its distances d [B][K] and stops (nothing else of that level; residual
+ * is then the one entering it).  loss_sums [n_levels] (or NULL; with loss_partial, gamer_rvq_ws_floats(B) floats): entry l = the sum
+ * over rows of |e - r|^2 of every level run in full. */
+int gamer_rvq_fwd(const float* r, int64_t ldr, const float* codebooks, const int32_t* level_offsets, const int32_t* modes,
+                  int n_levels, int level_begin, int level_end, int B, int D, int32_t* idx, float* x_q, float* residual,
+                  float* r_levels, float* dist, float* loss_partial, float* loss_sums, void* stream);
+/* With s_l = 2 g_level[l] / (B D) (g_level: DEVICE float [n_levels], the upstream gradient of level l's mse):
+ * dE [sum K_l][D]: row k of level l = sum over the rows that chose k, in row order, of s_l (e - r_l) (exact zeros when nobody did);
+ * dz [B][D] = g_xq (or 0 when NULL) + mu s_0 (r_0 - e_0): only level 0's commitment term and x_q's gradient reach z. */
+int gamer_rvq_bwd(const int32_t* idx, const float* r_levels, const float* codebooks, const int32_t* level_offsets, int n_levels,
+                  int B, int D, const float* g_xq, const float* g_level, float mu, float* dz, float* dE, void* stream);
+
 /* misc */
 int gamer_fill_f32(float* p, int64_t n, float value, void* stream);
 
