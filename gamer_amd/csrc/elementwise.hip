@@ -640,9 +640,12 @@ qknorm_rope_fwd_kernel(TA* __restrict__ qkv, int T, int S, int nq, int nkv,
             const int pos = pos_ids ? pos_ids[t] : t % S;        // per-token RoPE position (session model) or the index
             const float4 c4 = reinterpret_cast<const float4*>(cos_t + pos * 64)[g];
             const float4 s4 = reinterpret_cast<const float4*>(sin_t + pos * 64)[g];
+            // fma(sin, sgn * partner, y * cos) spelled out - what the token-major kernel's y * cos + sgn * partner * sin compiles to:
+            // left to the compiler's contraction, this kernel fused y * cos instead and the fp32 outputs of the two forms differed
+            // in the last bit (tests/test_indexed_paths_gpu.py holds them to the same bits)
             float4 o;
-            o.x = y.x * c4.x + sgn * pr.x * s4.x; o.y = y.y * c4.y + sgn * pr.y * s4.y;
-            o.z = y.z * c4.z + sgn * pr.z * s4.z; o.w = y.w * c4.w + sgn * pr.w * s4.w;
+            o.x = __builtin_fmaf(s4.x, sgn * pr.x, y.x * c4.x); o.y = __builtin_fmaf(s4.y, sgn * pr.y, y.y * c4.y);
+            o.z = __builtin_fmaf(s4.z, sgn * pr.z, y.z * c4.z); o.w = __builtin_fmaf(s4.w, sgn * pr.w, y.w * c4.w);
             if (live) {
                 if (isq) { st4(q_rot + (int64_t)t * nq * 64 + hd * 64 + 4 * g, o); amq = amax_f4(amq, o); }
                 else { st4(k_rot + (int64_t)t * nkv * 64 + (hd - nq) * 64 + 4 * g, o); amk = amax_f4(amk, o); }
@@ -2098,7 +2101,8 @@ static int qknorm_rope_fwd_impl(const char* name, TA* qkv, int T, int S, int nq,
     const bool cross = bias_q != nullptr;
     GAMER_CHECK_ARG(!cross || (bias_k && bias_v && act_idx), "%s: cross needs bias_k, bias_v, act_idx", name);
     const int NH = nq + nkv + (cross ? nkv : 0);
-    static const bool row_major = getenv("GAMER_QKNORM_ROW_MAJOR") != nullptr;           // (the round-1 forms, kept for A/B runs)
+    static EnvSwitch row_major_sw("GAMER_QKNORM_ROW_MAJOR");                              // (the round-1 forms, kept for A/B runs and tests)
+    const bool row_major = row_major_sw.is_set();
     if constexpr (sizeof(TA) == 2) {
         if (row_major)
             hipLaunchKernelGGL(qknorm_rope_fwd_b8_kernel, dim3(grid_for_waves(((int64_t)T * NH + 7) / 8)), dim3(EW_THREADS), 0,
@@ -2165,7 +2169,8 @@ static int qknorm_rope_bwd_impl(const char* name, const TA* qkv, const TA* dq_ro
     const int64_t total_waves = (int64_t)NH * waves_per_head;
     const int blocks = (int)((total_waves + EW_WAVES - 1) / EW_WAVES);
     if constexpr (sizeof(TA) == 2) {
-        static const bool row_major16 = getenv("GAMER_QKNORM_ROW_MAJOR") != nullptr;     // (the round-1 form, kept for A/B runs)
+        static EnvSwitch row_major_sw("GAMER_QKNORM_ROW_MAJOR");                         // (the round-1 form, kept for A/B runs and tests)
+        const bool row_major16 = row_major_sw.is_set();
         int n_waves16 = (T + 7) / 8;
         if (n_waves16 > 8192) n_waves16 = 8192;
         if ((int64_t)n_waves16 * 128 > partial_numel) n_waves16 = (int)(partial_numel / 128);
@@ -2188,7 +2193,8 @@ static int qknorm_rope_bwd_impl(const char* name, const TA* qkv, const TA* dq_ro
                                dq_rot, dk_rot, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, cross, bias_q, bias_k, act_idx, nb1,
                                dqkv, partial, waves_per_head, pos_ids);
     } else {
-        static const bool row_major = getenv("GAMER_QKNORM_ROW_MAJOR") != nullptr;       // (the round-1 form, kept for A/B runs)
+        static EnvSwitch row_major_sw("GAMER_QKNORM_ROW_MAJOR");                         // (the round-1 form, kept for A/B runs and tests)
+        const bool row_major = row_major_sw.is_set();
         int n_waves = (T + 3) / 4;
         if (n_waves > 8192) n_waves = 8192;
         if ((int64_t)n_waves * 128 > partial_numel) n_waves = (int)(partial_numel / 128);

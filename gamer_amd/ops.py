@@ -960,7 +960,9 @@ def qknorm_partial_numel(nb1: int = 0) -> int:
 def qknorm_rope_bwd(qkv, dq_rot, dk_rot, S, nq, nkv, wq, wk, eps, cos_t, sin_t, dqkv, dwq, dwk, bias_q=None,
                     bias_k=None, act_idx=None, nb1=0, dbias_q=None, dbias_k=None, dbias_v=None, pos_ids=None,
                     partial=None):
-    """partial: fp32 scratch for the per-wave sums of the weight / bias gradients (allocated here when None)."""
+    """partial: fp32 scratch for the per-wave sums of the weight / bias gradients (allocated here when None).
+    dwq, dwk and dbias_q / _k / _v are ADDED to (`+=`, in a fixed order: the same bits on every call) - zero them for a plain
+    gradient; dqkv[:, :q|k] is overwritten; dqkv[:, v] must hold dV (the cross call sums it into dbias_v) and is left as it is."""
     T = qkv.shape[0]
     if partial is None:
         partial = torch.empty(qknorm_partial_numel(nb1), dtype=torch.float32, device=qkv.device)

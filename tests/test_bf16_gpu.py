@@ -324,6 +324,7 @@ def test_qknorm_rope_bf16(cross):
     act = torch.randint(0, NB1, (T,), generator=g).int()
     bq, bk, bv = (torch.randn(NB1, n * 64, generator=g) * 0.3 for n in (nq, nkv, nkv))
     dq_r, dk_r = _bfr(torch.randn(T, nq * 64, generator=g)), _bfr(torch.randn(T, nkv * 64, generator=g))
+    dv_r = _bfr(torch.randn(T, nkv * 64, generator=g))
 
     def ref(qkv_, wq_, wk_, bq_, bk_, bv_):
         q = qkv_[:, :nq * 64].view(B_, S, nq, 64)
@@ -343,7 +344,8 @@ def test_qknorm_rope_bf16(cross):
     leaves = [t.double().requires_grad_(True) for t in (qkv, wq, wk, bq, bk, bv)]
     q_ref, k_ref, v_ref = ref(*leaves)
     (q_ref.reshape(T, -1) * dq_r.double()).sum().backward(retain_graph=True)
-    (k_ref.reshape(T, -1) * dk_r.double()).sum().backward()
+    (k_ref.reshape(T, -1) * dk_r.double()).sum().backward(retain_graph=True)
+    (v_ref.reshape(T, -1) * dv_r.double()).sum().backward()
     d_qkv = dev(qkv.to(BF))
     q_rot, k_rot = torch.empty(T, nq * 64, dtype=BF, device=DEV), torch.empty(T, nkv * 64, dtype=BF, device=DEV)
     kw = dict(bias_q=dev(bq), bias_k=dev(bk), bias_v=dev(bv), act_idx=dev(act)) if cross else {}
@@ -354,6 +356,7 @@ def test_qknorm_rope_bf16(cross):
         assert _rel(d_qkv[:, (nq + nkv) * 64:], v_ref.reshape(T, -1)) < 1.5 * ulp
         assert torch.equal(d_qkv[:, :(nq + nkv) * 64].cpu(), qkv[:, :(nq + nkv) * 64].to(BF)), "q/k stay un-biased in bf16"
     dqkv = torch.zeros(T, ld, dtype=BF, device=DEV)
+    dqkv[:, (nq + nkv) * 64:] = dev(dv_r.to(BF))            # dV, as the attention backward leaves it: the bias_v gradient sums it
     dwq, dwk = torch.zeros(64, device=DEV), torch.zeros(64, device=DEV)
     dbq, dbk, dbv = (torch.zeros(NB1, n * 64, device=DEV) for n in (nq, nkv, nkv))
     bkw = dict(bias_q=dev(bq), bias_k=dev(bk), act_idx=dev(act), nb1=NB1, dbias_q=dbq, dbias_k=dbk, dbias_v=dbv) if cross else {}
@@ -364,6 +367,8 @@ def test_qknorm_rope_bf16(cross):
     assert _rel(dwq, leaves[1].grad) < 1e-3 and _rel(dwk, leaves[2].grad) < 1e-3
     if cross:
         assert _rel(dbq, leaves[3].grad) < 1e-3 and _rel(dbk, leaves[4].grad) < 1e-3
+        assert _rel(dbv, leaves[5].grad) < 1e-3
+    assert torch.equal(dqkv[:, (nq + nkv) * 64:].cpu(), dv_r.to(BF)), "the v columns of dqkv are read, not written"
 
 
 # ----------------------------------------------------------------------------------------------------------------
