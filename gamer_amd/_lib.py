@@ -198,6 +198,18 @@ _SIGNATURES = {
     "gamer_rvq_ws_floats": [I],
     "gamer_rvq_fwd": [P, L, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P],
     "gamer_rvq_bwd": [P, P, P, P, I, I, I, P, P, F, P, P, P],
+    "gamer_msa_linear_fwd": [P, I, P, I, P, I, P, P, P, P, P, I, I, I, I, I, F, F, U, P, I, P, P],
+    "gamer_msa_linear_bwd": [P, I, P, I, P, I, P, P, P, P, P, I, I, I, I, I, F, F, U, P, I, P, P, I, P, I, P, I, P, I, P],
+    "gamer_seq_mix_fwd": [P, I, P, I, P, I, P, P, I, I, I, P, P],
+    "gamer_seq_mix_bwd": [P, I, P, I, P, I, P, P, I, I, I, P, P, P, P, I, P],
+    "gamer_hg_build_fwd": [P, P, I, I, I, I, I, P, P, P],
+    "gamer_hg_build_bwd": [P, P, P, P, P, I, I, I, I, I, P, P],
+    "gamer_hg_conv_fwd": [P, P, I, I, I, P, P],
+    "gamer_hg_conv_bwd": [P, P, P, I, I, I, P, P, P],
+    "gamer_hg_readout_fwd": [P, P, P, I, I, I, I, I, I, I, P, P],
+    "gamer_hg_readout_bwd": [P, P, P, I, I, I, I, I, I, I, P, P],
+    "gamer_hg_fuse_fwd": [P, P, P, L, I, P, P, P],
+    "gamer_hg_fuse_bwd": [P, P, P, P, P, L, I, P, P, P, I, P],
 }
 
 

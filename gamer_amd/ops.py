@@ -1676,3 +1676,206 @@ def rvq_bwd(idx, r_levels, codebooks, level_offsets, g_xq, g_level, mu, dz, dE):
     B, D = dz.shape
     call("gamer_rvq_bwd", ptr(idx), ptr(r_levels), ptr(codebooks), _i32_array(level_offsets), n_levels, B, D, ptr(g_xq),
          ptr(g_level), float(mu), ptr(dz), ptr(dE), stream_ptr())
+
+
+# ---- MBHT's multi-scale encoder layer (csrc/mbht.hip) ---------------------------------------------------------------------------
+MBHT_MAX_L, MBHT_MAX_D, MBHT_MAX_H, MBHT_MAX_C, MBHT_MAX_HYPER = 128, 64, 256, 16, 8
+
+
+def mbht_check_limits(L, H, d, c=1, hyper_len=1):
+    """The limits of the MBHT kernels, refused on the host before any launch."""
+    if L > MBHT_MAX_L or d > MBHT_MAX_D or H > MBHT_MAX_H or H % 4 or c > MBHT_MAX_C or hyper_len > MBHT_MAX_HYPER or min(L, c, hyper_len) < 1:
+        raise NotImplementedError(f"MBHT on the HIP path: L <= {MBHT_MAX_L}, head size <= {MBHT_MAX_D}, hidden size <= {MBHT_MAX_H} "
+                                  f"and divisible by 4, scales[0] <= {MBHT_MAX_C}, hyper_len <= {MBHT_MAX_HYPER} (got L={L}, head "
+                                  f"size={d}, hidden size={H}, scales[0]={c}, hyper_len={hyper_len})")
+
+
+def _msa_common(q, k, v, keep, Ew, Eb, Fw, Fb, B, L, h, d):
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk(t, torch.float32, n)
+        if t.dim() != 2 or t.shape[0] != B * L or t.shape[1] != h * d or t.stride(1) != 1:
+            raise RuntimeError(f"msa linear attention: {n} must be a [{B * L}, {h * d}] row-strided view")
+    _dense(keep, torch.int32, "keep")
+    for t, n in ((Ew, "Ew"), (Eb, "Eb"), (Fw, "Fw"), (Fb, "Fb")):
+        _dense(t, torch.float32, n)
+    c = Ew.shape[0]
+    mbht_check_limits(L, h * d, d, c)
+    if keep.shape != (B, L) or Ew.shape != (c, L) or Fw.shape != (c, L) or Eb.shape != (c,) or Fb.shape != (c,):
+        raise RuntimeError(f"msa linear attention: keep [{B}, {L}], Ew / Fw [c, {L}], Eb / Fb [c]")
+    return c
+
+
+def msa_linear_fwd(q, k, v, keep, Ew, Eb, Fw, Fb, B, L, h, d, scale, p_drop, seed, o, lse):
+    """gamer_msa_linear_fwd: q / k / v / o [B L, h d] (row-strided views), keep int32 [B, L], Ew / Fw [c, L] (the projections of
+    the values / the keys), lse [B, h, L]."""
+    c = _msa_common(q, k, v, keep, Ew, Eb, Fw, Fb, B, L, h, d)
+    _chk(o, torch.float32, "o"), _dense(lse, torch.float32, "lse")
+    if o.shape != (B * L, h * d) or o.stride(1) != 1 or lse.numel() != B * h * L:
+        raise RuntimeError("msa_linear_fwd: o [B L, h d] and lse [B, h, L]")
+    call("gamer_msa_linear_fwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(keep), ptr(Ew), ptr(Eb), ptr(Fw),
+         ptr(Fb), B, L, h, d, c, float(scale), float(p_drop), int(seed), ptr(o), o.stride(0), ptr(lse), stream_ptr())
+
+
+def msa_n_partial(B, h):
+    """slabs of the linear attention's backward: one workgroup per CU (256) at the most"""
+    return max(1, min(B * h, 256))
+
+
+def msa_linear_bwd(q, k, v, keep, Ew, Eb, Fw, Fb, B, L, h, d, scale, p_drop, seed, d_o, lse, dq, dk, dv, partial):
+    """gamer_msa_linear_bwd: dq / dk / dv are written; partial [n, 2 c L + 2 c] must be zero on entry; its column sums are
+    [dEw | dFw | dEb | dFb]."""
+    c = _msa_common(q, k, v, keep, Ew, Eb, Fw, Fb, B, L, h, d)
+    for t, n in ((d_o, "d_o"), (dq, "dq"), (dk, "dk"), (dv, "dv")):
+        _chk(t, torch.float32, n)
+        if t.shape != (B * L, h * d) or t.stride(1) != 1:
+            raise RuntimeError(f"msa_linear_bwd: {n} must be a [{B * L}, {h * d}] row-strided view")
+    _dense(lse, torch.float32, "lse"), _dense(partial, torch.float32, "partial")
+    n = partial.shape[0]
+    if partial.shape != (n, 2 * c * L + 2 * c) or not 1 <= n <= B * h or lse.numel() != B * h * L:
+        raise RuntimeError(f"msa_linear_bwd: partial [n <= {B * h}, {2 * c * L + 2 * c}], lse [B, h, L]")
+    call("gamer_msa_linear_bwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(keep), ptr(Ew), ptr(Eb), ptr(Fw),
+         ptr(Fb), B, L, h, d, c, float(scale), float(p_drop), int(seed), ptr(d_o), d_o.stride(0), ptr(lse), ptr(dq), dq.stride(0),
+         ptr(dk), dk.stride(0), ptr(dv), dv.stride(0), ptr(partial), n, stream_ptr())
+
+
+def _seq_mix_common(xs, W, B, H, what):
+    if not 1 <= len(xs) <= 3:
+        raise RuntimeError(f"{what}: one to three sources")
+    lens = []
+    for i, x in enumerate(xs):
+        _dense(x, torch.float32, f"x{i}")
+        if x.dim() != 3 or x.shape[0] != B or x.shape[2] != H or x.shape[1] < 1:
+            raise RuntimeError(f"{what}: x{i} must be [{B}, L{i}, {H}]")
+        lens.append(x.shape[1])
+    _dense(W, torch.float32, "W")
+    if W.dim() != 2 or W.shape[1] != sum(lens):
+        raise RuntimeError(f"{what}: W [Lout, {sum(lens)}]")
+    Lout = W.shape[0]
+    if H > MBHT_MAX_H or max(lens + [Lout]) > MBHT_MAX_L:
+        raise NotImplementedError(f"{what}: hidden size <= {MBHT_MAX_H}, every length <= {MBHT_MAX_L}")
+    return lens + [0] * (3 - len(xs)), Lout
+
+
+def seq_mix_fwd(xs, W, bias, y):
+    """y [B, Lout, H] = W [Lout, sum L_i] cat(xs, 1) + bias[:, None] (gamer_seq_mix_fwd); xs: one to three [B, L_i, H]."""
+    B, Lout_, H = y.shape
+    lens, Lout = _seq_mix_common(xs, W, B, H, "seq_mix_fwd")
+    _dense(bias, torch.float32, "bias"), _dense(y, torch.float32, "y")
+    if Lout_ != Lout or bias.shape != (Lout,):
+        raise RuntimeError(f"seq_mix_fwd: y [{B}, {Lout}, {H}] and bias [{Lout}]")
+    px = [ptr(x) for x in xs] + [None] * (3 - len(xs))
+    call("gamer_seq_mix_fwd", px[0], lens[0], px[1], lens[1], px[2], lens[2], ptr(W), ptr(bias), B, H, Lout, ptr(y), stream_ptr())
+
+
+def seq_mix_n_partial(B, Lout, Lin):
+    """slabs of seq_mix_bwd: one workgroup per CU (256) when the slabs stay below 32 MB"""
+    n = max(1, min(B, 256))
+    while n > 1 and n * (Lout * Lin + Lout) * 4 > (32 << 20):
+        n //= 2
+    return n
+
+
+def seq_mix_bwd(xs, W, dy, dxs, partial):
+    """gamer_seq_mix_bwd: dxs (shapes of xs) are written; partial [n, Lout Lin + Lout] must be zero on entry; its column sums are
+    [dW | dbias]."""
+    B, Lout_, H = dy.shape
+    lens, Lout = _seq_mix_common(xs, W, B, H, "seq_mix_bwd")
+    _dense(dy, torch.float32, "dy"), _dense(partial, torch.float32, "partial")
+    if len(dxs) != len(xs) or any(_dense(d, torch.float32, "dx").shape != x.shape for d, x in zip(dxs, xs)) or Lout_ != Lout:
+        raise RuntimeError("seq_mix_bwd: dy [B, Lout, H] and one dx per source, of its shape")
+    n = partial.shape[0]
+    if partial.shape != (n, Lout * sum(lens) + Lout) or not 1 <= n <= B:
+        raise RuntimeError(f"seq_mix_bwd: partial [n <= {B}, {Lout * sum(lens) + Lout}]")
+    px = [ptr(x) for x in xs] + [None] * (3 - len(xs))
+    pd = [ptr(d) for d in dxs] + [None] * (3 - len(xs))
+    call("gamer_seq_mix_bwd", px[0], lens[0], px[1], lens[1], px[2], lens[2], ptr(W), ptr(dy), B, H, Lout, pd[0], pd[1], pd[2],
+         ptr(partial), n, stream_ptr())
+
+
+def _hg_check(x, B, L, H, name):
+    _dense(x, torch.float32, name)
+    if x.shape != (B, L, H):
+        raise RuntimeError(f"{name} must be [{B}, {L}, {H}]")
+
+
+def hg_build_fwd(xm, items, mask_token, hyper_len, G, sel):
+    """gamer_hg_build_fwd: xm [B, L, H], items int32 [B, L] (right-padded with 0) -> G [B, L, L] (zero outside the live block) and
+    sel int32 [B, L, hyper_len] (the selected key positions of every live row that is no <MASK>, best first; -1 unused)."""
+    B, L, H = xm.shape
+    mbht_check_limits(L, H, 1, 1, hyper_len)
+    _hg_check(xm, B, L, H, "xm"), _dense(items, torch.int32, "items"), _dense(G, torch.float32, "G"), _dense(sel, torch.int32, "sel")
+    if items.shape != (B, L) or G.shape != (B, L, L) or sel.shape != (B, L, hyper_len):
+        raise RuntimeError(f"hg_build_fwd: items [{B}, {L}], G [{B}, {L}, {L}], sel [{B}, {L}, {hyper_len}]")
+    call("gamer_hg_build_fwd", ptr(xm), ptr(items), B, L, H, hyper_len, int(mask_token), ptr(G), ptr(sel), stream_ptr())
+
+
+def hg_build_bwd(xm, items, sel, G, dG, mask_token, dxm):
+    """gamer_hg_build_bwd: dxm [B, L, H] from dG [B, L, L] along the selection ``sel`` of the forward."""
+    B, L, H = xm.shape
+    K = sel.shape[-1]
+    mbht_check_limits(L, H, 1, 1, K)
+    _hg_check(xm, B, L, H, "xm"), _hg_check(dxm, B, L, H, "dxm"), _dense(items, torch.int32, "items"), _dense(sel, torch.int32, "sel")
+    _dense(G, torch.float32, "G"), _dense(dG, torch.float32, "dG")
+    if items.shape != (B, L) or G.shape != (B, L, L) or dG.shape != (B, L, L) or sel.shape != (B, L, K):
+        raise RuntimeError(f"hg_build_bwd: items [{B}, {L}], G / dG [{B}, {L}, {L}], sel [{B}, {L}, K]")
+    call("gamer_hg_build_bwd", ptr(xm), ptr(items), ptr(sel), ptr(G), ptr(dG), B, L, H, K, int(mask_token), ptr(dxm), stream_ptr())
+
+
+def hg_conv_fwd(G, x, y):
+    """y [B, L, H] = G [B, L, L] x [B, L, H], row by row of the batch (gamer_hg_conv_fwd)."""
+    B, L, H = x.shape
+    mbht_check_limits(L, H, 1)
+    _hg_check(x, B, L, H, "x"), _hg_check(y, B, L, H, "y"), _hg_check(G, B, L, L, "G")
+    call("gamer_hg_conv_fwd", ptr(G), ptr(x), B, L, H, ptr(y), stream_ptr())
+
+
+def hg_conv_bwd(G, x, dy, dx, dG):
+    """dx = G^T dy and dG = dy x^T (gamer_hg_conv_bwd)."""
+    B, L, H = x.shape
+    mbht_check_limits(L, H, 1)
+    _hg_check(x, B, L, H, "x"), _hg_check(dy, B, L, H, "dy"), _hg_check(dx, B, L, H, "dx"), _hg_check(G, B, L, L, "G"), _hg_check(dG, B, L, L, "dG")
+    call("gamer_hg_conv_bwd", ptr(G), ptr(x), ptr(dy), B, L, H, ptr(dx), ptr(dG), stream_ptr())
+
+
+def _hg_readout(name, a, pos, n_obj, out, before, follow, evaluation):
+    B, L, H = a.shape
+    mbht_check_limits(L, H, 1)
+    _hg_check(a, B, L, H, "x"), _hg_check(out, B, L, H, "out"), _dense(pos, torch.int32, "pos"), _dense(n_obj, torch.int32, "n_obj")
+    if pos.dim() != 2 or pos.shape[0] != B or pos.shape[1] < 1 or n_obj.shape != (B,):
+        raise RuntimeError(f"{name}: pos [{B}, P] and n_obj [{B}]")
+    call(name, ptr(a), ptr(pos), ptr(n_obj), B, L, H, pos.shape[1], int(before), int(follow), 1 if evaluation else 0, ptr(out), stream_ptr())
+
+
+def hg_readout_fwd(x, pos, n_obj, out, before=10, follow=6, evaluation=False):
+    """gamer_hg_readout_fwd: out = x with the rows pos[b] (int32 [B, P], in order; training: entries <= 0 skipped) replaced, one
+    after the other, by the mean of their sliding window; n_obj int32 [B] = the live positions of each row."""
+    _hg_readout("gamer_hg_readout_fwd", x, pos, n_obj, out, before, follow, evaluation)
+
+
+def hg_readout_bwd(dout, pos, n_obj, dx, before=10, follow=6, evaluation=False):
+    _hg_readout("gamer_hg_readout_bwd", dout, pos, n_obj, dx, before, follow, evaluation)
+
+
+def hg_fuse_fwd(x0, x1, w, out, p0):
+    """out [T, H] = p0 x0 + (1 - p0) x1 with p0 [T] = softmax over the two sources of x_s . w (gamer_hg_fuse_fwd)."""
+    T, H = x0.shape
+    for t, n in ((x0, "x0"), (x1, "x1"), (out, "out")):
+        if _dense(t, torch.float32, n).shape != (T, H):
+            raise RuntimeError(f"hg_fuse_fwd: {n} must be [{T}, {H}]")
+    if _dense(w, torch.float32, "w").shape != (H,) or _dense(p0, torch.float32, "p0").shape != (T,) or H > MBHT_MAX_H:
+        raise RuntimeError(f"hg_fuse_fwd: w [{H}], p0 [{T}], H <= {MBHT_MAX_H}")
+    call("gamer_hg_fuse_fwd", ptr(x0), ptr(x1), ptr(w), T, H, ptr(out), ptr(p0), stream_ptr())
+
+
+def hg_fuse_bwd(x0, x1, w, p0, dout, dx0, dx1, partial):
+    """gamer_hg_fuse_bwd: dx0 / dx1 are written; partial [n, H] is written, its column sums are dw."""
+    T, H = x0.shape
+    for t, n in ((x0, "x0"), (x1, "x1"), (dout, "dout"), (dx0, "dx0"), (dx1, "dx1")):
+        if _dense(t, torch.float32, n).shape != (T, H):
+            raise RuntimeError(f"hg_fuse_bwd: {n} must be [{T}, {H}]")
+    _dense(partial, torch.float32, "partial")
+    if _dense(w, torch.float32, "w").shape != (H,) or _dense(p0, torch.float32, "p0").shape != (T,) or partial.dim() != 2 or \
+            partial.shape[1] != H or H > MBHT_MAX_H:
+        raise RuntimeError(f"hg_fuse_bwd: w [{H}], p0 [{T}], partial [n, {H}], H <= {MBHT_MAX_H}")
+    call("gamer_hg_fuse_bwd", ptr(x0), ptr(x1), ptr(w), ptr(p0), ptr(dout), T, H, ptr(dx0), ptr(dx1), ptr(partial), partial.shape[0],
+         stream_ptr())

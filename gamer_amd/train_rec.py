@@ -106,9 +106,12 @@ def evaluate(model, data, batch_size, metrics, dev, collate=smb_dis_data.collate
     return {m: float(np.mean(v)) for m, v in vals.items()}
 
 
-def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="train_rec"):
+def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="train_rec", train_target_only=False,
+        test_target_only=False, pass_target_behavior_id=False):
     """The loop of ``TrainSMBRec.invoke`` for the parsed arguments ``a``: the model and config classes, the data functions
-    (train / valid loader, test loader, collate) and the tag of the printed lines are the command's (train_rec, train_bert4rec)."""
+    (train / valid loader, test loader, collate) and the tag of the printed lines are the command's (train_rec, train_bert4rec).
+    The three flags are what the reference does for MBHT alone: train on the target behaviour's rows only, test the target
+    behaviour only (the merged entry then equals it), and give the model ``target_behavior_id = target_behavior_index + 1``."""
     random.seed(a.seed)
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
@@ -120,9 +123,12 @@ def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="tra
     valid = valid.filter_by_behavior(valid.target_behavior)
     first = trains[0]
     # (n_behaviors: read by the behaviour-aware backbones; the others take it in **kwargs)
-    model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len, n_behaviors=len(first.behaviors)).to(dev)
+    extra = dict(target_behavior_id=first.target_behavior_index + 1) if pass_target_behavior_id else {}
+    model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len, n_behaviors=len(first.behaviors), **extra).to(dev)
     ckpt = os.path.join(a.output_dir, "best_model.pth")
     if not a.only_test:
+        if train_target_only:
+            trains = [t.filter_by_behavior(t.target_behavior) for t in trains]
         train_samples = [s for t in trains for s in t.samples]
         opt = AdamW(model.parameters(), a.learning_rate, a.weight_decay)
         g = torch.Generator().manual_seed(a.seed)
@@ -161,6 +167,8 @@ def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="tra
     model.load_state_dict(torch.load(ckpt, map_location="cpu"))
     results, merged, total = [], {m: 0.0 for m in metrics}, 0
     for b in first.behaviors:
+        if test_target_only and b != first.target_behavior:
+            continue
         part = test.filter_by_behavior(b)
         r = evaluate(model, part, a.batch_size, metrics, dev, collate) if len(part) else {m: float("nan") for m in metrics}
         r["eval_type"] = f"Behavior {b}"

@@ -967,6 +967,64 @@ int gamer_rvq_fwd(const float* r, int64_t ldr, const float* codebooks, const int
 int gamer_rvq_bwd(const int32_t* idx, const float* r_levels, const float* codebooks, const int32_t* level_offsets, int n_levels,
                   int B, int D, const float* g_xq, const float* g_level, float mu, float* dz, float* dE, void* stream);
 
+/* ---- MBHT's multi-scale encoder layer (csrc/mbht.hip) ----
+ * LinearAttention's core, one workgroup per (batch row, head); q / k / v / o as gamer_attn_dense_fwd.  keep int32 [B][L] (non-zero =
+ * a real item); Ew / Fw [c][L] and Eb / Fb [c]: the sequence-axis projections of the values (E) and of the keys (F):
+ *   Kp[j] = sum_l Fw[j][l] keep_l K_l + Fb[j],  Vp[j] = sum_l Ew[j][l] keep_l V_l + Eb[j],  o_i = sum_j dropout(softmax_j(scale Q_i . Kp[j])) Vp[j]
+ * dropout mask of element (b, h, i, j) = counter ((b H + h) L + i) c + j of (p_drop, seed); lse [B][H][L].  L <= 128, head_dim <= 64,
+ * c <= 16.  Nothing of size L x c is written to memory. */
+int gamer_msa_linear_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* keep,
+                         const float* Ew, const float* Eb, const float* Fw, const float* Fb, int B, int L, int H, int head_dim, int c,
+                         float scale, float p_drop, uint64_t seed, float* o, int ldo, float* lse, void* stream);
+/* dq / dk / dv are written (dk / dv: zeros on padding).  partial [n_partial][2 c L + 2 c], ZERO on entry: workgroup g walks the (row,
+ * head) pairs g, g + n_partial, ... in order and ADDS their sums into slab g = [dEw | dFw | dEb | dFb] (no float atomics); the column
+ * sums of the slabs (gamer_colsum_reduce) are the gradients.  1 <= n_partial <= B H. */
+int gamer_msa_linear_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* keep,
+                         const float* Ew, const float* Eb, const float* Fw, const float* Fb, int B, int L, int H, int head_dim, int c,
+                         float scale, float p_drop, uint64_t seed, const float* d_o, int ldo, const float* lse, float* dq, int lddq,
+                         float* dk, int lddk, float* dv, int lddv, float* partial, int n_partial, void* stream);
+/* Y[b] = W X[b] + bias[:, None]: a Linear along the SEQUENCE axis.  X[b] [L0 + L1 + L2][H] is the concatenation of x0[b] [L0][H],
+ * x1[b] [L1][H] and x2[b] [L2][H] (x1 / x2 NULL with length 0: absent), never formed; W [Lout][L0 + L1 + L2], y [B][Lout][H].
+ * H <= 256, every length <= 128. */
+int gamer_seq_mix_fwd(const float* x0, int L0, const float* x1, int L1, const float* x2, int L2, const float* W, const float* bias,
+                      int B, int H, int Lout, float* y, void* stream);
+/* dx0 / dx1 / dx2 (shapes of x0 / x1 / x2) are written.  partial [n_partial][Lout (L0 + L1 + L2) + Lout], ZERO on entry: slab g =
+ * [dW | dbias] of the rows g, g + n_partial, ... added in order.  1 <= n_partial <= B. */
+int gamer_seq_mix_bwd(const float* x0, int L0, const float* x1, int L1, const float* x2, int L2, const float* W, const float* dy,
+                      int B, int H, int Lout, float* dx0, float* dx1, float* dx2, float* partial, int n_partial, void* stream);
+
+/* ---- MBHT's hypergraph branch (csrc/mbht.hip) ----
+ * One workgroup per batch row builds the row's hypergraph from x_m [B][L][H] and items int32 [B][L] (right-padded with 0; n = the
+ * non-zero count): u = x_m with every hidden column divided by its norm over ALL L positions (the reference's F.normalize runs along
+ * the sequence axis), similarities u u^T of the first n rows (negative ones become 0.01), for every row that is no <MASK> the top
+ * k = min(hyper_len, n) of them (the LOWER key position wins among equal values), H as (edge, value) lists in LDS (one edge per
+ * token, <MASK> one of them; one more per non-<MASK> item that occurs more than once; self-loops of 1.0 overwrite similarities; a
+ * selected <MASK> key becomes the row's own item at 1.0), G = Dv^-1 H De^-1 H^T.  G [B][L][L] is zero outside the n x n block; sel
+ * [B][L][hyper_len]: the selected key positions, best first, -1 unused.  L <= 128, H <= 256, hyper_len <= 8. */
+int gamer_hg_build_fwd(const float* xm, const int32_t* items, int B, int L, int H, int hyper_len, int mask_token, float* G,
+                       int32_t* sel, void* stream);
+/* dxm [B][L][H] (written; the rows past n receive the column norms' share) from dG along the forward's selection: through G, both degree vectors, the surviving
+ * similarity entries (every selection of a repeated item receives the entry's full gradient; self-loops, replaced <MASK> keys and
+ * clamped values receive none) and the column scaling. */
+int gamer_hg_build_bwd(const float* xm, const int32_t* items, const int32_t* sel, const float* G, const float* dG, int B, int L, int H,
+                       int hyper_len, int mask_token, float* dxm, void* stream);
+/* y[b] = G[b] x[b] on the padded layout (G [B][L][L], x / y [B][L][H]); backward: dx[b] = G[b]^T dy[b], dG[b] = dy[b] x[b]^T. */
+int gamer_hg_conv_fwd(const float* G, const float* x, int B, int L, int H, float* y, void* stream);
+int gamer_hg_conv_bwd(const float* G, const float* x, const float* dy, int B, int L, int H, float* dx, float* dG, void* stream);
+/* out = x [B][L][H] with the rows pos[b][0 .. P) replaced IN ORDER (a later one sees earlier ones) by the mean of
+ * out[max(pos - before, 0) : pos] ++ out[pos + 1 : end], end = pos + follow if pos + follow < n_obj[b] else n_obj[b] - 1.  Training
+ * (eval = 0): entries <= 0 are skipped.  Evaluation (eval = 1): the window is out[max(pos - before, 0) : pos] only.  An entry >= L is
+ * skipped; an empty window gives NaN.  The backward walks the positions in reverse. */
+int gamer_hg_readout_fwd(const float* x, const int32_t* pos, const int32_t* n_obj, int B, int L, int H, int P, int before, int follow,
+                         int eval, float* out, void* stream);
+int gamer_hg_readout_bwd(const float* dout, const int32_t* pos, const int32_t* n_obj, int B, int L, int H, int P, int before,
+                         int follow, int eval, float* dx, void* stream);
+/* out [T][H] = p0 x0 + (1 - p0) x1, p0 [T] = softmax over the two sources of x_s . w.  Backward: dx0, dx1 and partial [n_partial][H]
+ * (written), whose column sums are dw. */
+int gamer_hg_fuse_fwd(const float* x0, const float* x1, const float* w, int64_t T, int H, float* out, float* p0, void* stream);
+int gamer_hg_fuse_bwd(const float* x0, const float* x1, const float* w, const float* p0, const float* dout, int64_t T, int H,
+                      float* dx0, float* dx1, float* partial, int n_partial, void* stream);
+
 /* misc */
 int gamer_fill_f32(float* p, int64_t n, float value, void* stream);
 
