@@ -195,6 +195,12 @@ _SIGNATURES = {
     "gamer_mbs_bias_fold": [P, P, I, I, I, I, P, P],
     "gamer_mbs_gate_mix_fwd": [P, I, P, P, I, I, I, P, P, P],
     "gamer_mbs_gate_mix_bwd": [P, P, P, I, I, I, P, P, I, P],
+    "gamer_pbat_attn_fwd": [P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, U, P, P, I, P, P, P, P],
+    "gamer_pbat_attn_bwd": [P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, U, P, P, P, P, I, P, P, P, P, P, P, I, P, P, P, P, I, P, P],
+    "gamer_wass_rows_fwd": [P, P, I, I, P, P, P],
+    "gamer_wass_rows_bwd": [P, P, P, P, I, I, P, P, P],
+    "gamer_wass_table_fwd": [P, P, I, I, P, P, P],
+    "gamer_wass_table_bwd": [P, P, P, P, I, I, P, P, P],
     "gamer_rvq_ws_floats": [I],
     "gamer_rvq_fwd": [P, L, P, P, P, I, I, I, I, I, P, P, P, P, P, P, P, P],
     "gamer_rvq_bwd": [P, P, P, P, I, I, I, P, P, F, P, P, P],

@@ -1879,3 +1879,128 @@ def hg_fuse_bwd(x0, x1, w, p0, dout, dx0, dx1, partial):
         raise RuntimeError(f"hg_fuse_bwd: w [{H}], p0 [{T}], partial [n, {H}], H <= {MBHT_MAX_H}")
     call("gamer_hg_fuse_bwd", ptr(x0), ptr(x1), ptr(w), ptr(p0), ptr(dout), T, H, ptr(dx0), ptr(dx1), ptr(partial), partial.shape[0],
          stream_ptr())
+
+
+# ---- PBAT's fused Wasserstein attention and head (csrc/pbat.hip) ------------------------------------------------------------------
+PBAT_MAX_L, PBAT_MAX_D, PBAT_MAX_B, PBAT_MAX_H = 128, 64, 8, 128
+
+
+def pbat_check_limits(L, H, d, b):
+    """The limits of the PBAT kernels, refused on the host before any launch (hidden size: the head runs the biased catalogue
+    kernels at 2 H <= 256)."""
+    if L > PBAT_MAX_L or L < 1 or d > PBAT_MAX_D or d % 4 or H > PBAT_MAX_H or H % 4 or b > PBAT_MAX_B or b < 1:
+        raise NotImplementedError(f"PBAT on the HIP path: L <= {PBAT_MAX_L}, head size <= {PBAT_MAX_D} and a multiple of 4, hidden "
+                                  f"size <= {PBAT_MAX_H} and a multiple of 4, n_behaviors <= {PBAT_MAX_B} (got L={L}, head size={d}, "
+                                  f"hidden size={H}, n_behaviors={b})")
+
+
+def _pbat_common(name, proj, rel_m, rel_c, pos_m, pos_c, weights, types, keep, B, L, h, d, b):
+    pbat_check_limits(L, h * d, d, b)
+    H, NP = h * d, (b + 1) * (b + 1)
+    if len(proj) != 6 or len(weights) != 8:
+        raise RuntimeError(f"{name}: six projections (q1, q2, k1, k2, v1, v2) and (Wq1, bq1, Wq2, bq2, Wk1, bk1, Wk2, bk2)")
+    for t in proj:
+        _chk(t, torch.float32, "projection")
+        if t.shape != (B * L, H) or t.stride(1) != 1 or t.stride(0) != proj[0].stride(0):
+            raise RuntimeError(f"{name}: the projections must be [{B * L}, {H}] row-strided views with one row stride")
+    for t, n, shp in ((rel_m, "rel_m", (B, NP, H)), (rel_c, "rel_c", (B, NP, H)), (pos_m, "pos_m", (L, H)), (pos_c, "pos_c", (L, H))):
+        if _dense(t, torch.float32, n).shape != shp:
+            raise RuntimeError(f"{name}: {n} must be {list(shp)}")
+    for i, w in enumerate(weights):
+        if _dense(w, torch.float32, "weight").shape != ((d,) if i % 2 else (d, d)):
+            raise RuntimeError(f"{name}: Wq1 / Wq2 / Wk1 / Wk2 [{d}, {d}] with biases [{d}]")
+    if _dense(types, torch.int32, "types").shape != (B, L) or _dense(keep, torch.int32, "keep").shape != (B, L):
+        raise RuntimeError(f"{name}: types / keep int32 [{B}, {L}]")
+    ws = _ws("pbat_pos", proj[0].device, 2 * H * L * 4)
+    return ([ptr(t) for t in proj] + [proj[0].stride(0), ptr(rel_m), ptr(rel_c), ptr(pos_m), ptr(pos_c)] + [ptr(w) for w in weights]
+            + [ptr(types), ptr(keep), B, L, h, d, b]), ws
+
+
+def pbat_attn_fwd(proj, rel_m, rel_c, pos_m, pos_c, weights, types, keep, B, L, h, d, b, scale, p_drop, seed, o1, o2, S, lse):
+    """gamer_pbat_attn_fwd: proj = (q1, q2, k1, k2, v1, v2) [B L, h d] row-strided views; rel_m / rel_c [B, (b + 1)^2, h d]; pos_m /
+    pos_c [L, h d]; weights = (Wq1, bq1, Wq2, bq2, Wk1, bk1, Wk2, bk2); types / keep int32 [B, L]; o1 / o2 [B L, h d]; S [B, h, L,
+    b + 1] and lse [B, h, L] are what the backward needs."""
+    args, ws = _pbat_common("pbat_attn_fwd", proj, rel_m, rel_c, pos_m, pos_c, weights, types, keep, B, L, h, d, b)
+    for t in (o1, o2):
+        _chk(t, torch.float32, "o")
+        if t.shape != (B * L, h * d) or t.stride(1) != 1 or t.stride(0) != o1.stride(0):
+            raise RuntimeError("pbat_attn_fwd: o1 / o2 [B L, h d] with one row stride")
+    if _dense(S, torch.float32, "S").shape != (B, h, L, b + 1) or _dense(lse, torch.float32, "lse").shape != (B, h, L):
+        raise RuntimeError("pbat_attn_fwd: S [B, h, L, b + 1] and lse [B, h, L]")
+    call("gamer_pbat_attn_fwd", *args, float(scale), float(p_drop), int(seed), ptr(o1), ptr(o2), o1.stride(0), ptr(S), ptr(lse), ptr(ws),
+         stream_ptr())
+
+
+def pbat_n_partial(B, h):
+    """Slabs of the attention backward's parameter gradients: n h workgroups, about one per CU (256)."""
+    return max(1, min(B, 256 // max(1, h)))
+
+
+def pbat_attn_bwd(proj, rel_m, rel_c, pos_m, pos_c, weights, types, keep, B, L, h, d, b, scale, p_drop, seed, S, lse, do1, do2, dproj,
+                  drel_m, drel_c, w_partial, pos_partial):
+    """gamer_pbat_attn_bwd: dproj = (dq1, dq2, dk1, dk2, dv1, dv2), drel_m / drel_c are written; w_partial [n, h, 4 (d d + d)] and
+    pos_partial [n, h, 4, L, d] must be ZERO on entry (the caller sums them over n)."""
+    args, ws = _pbat_common("pbat_attn_bwd", proj, rel_m, rel_c, pos_m, pos_c, weights, types, keep, B, L, h, d, b)
+    H, NP = h * d, (b + 1) * (b + 1)
+    for t in (do1, do2):
+        _chk(t, torch.float32, "do")
+        if t.shape != (B * L, H) or t.stride(1) != 1 or t.stride(0) != do1.stride(0):
+            raise RuntimeError("pbat_attn_bwd: do1 / do2 [B L, h d] with one row stride")
+    if len(dproj) != 6:
+        raise RuntimeError("pbat_attn_bwd: six projection gradients")
+    for t in dproj:
+        _chk(t, torch.float32, "dproj")
+        if t.shape != (B * L, H) or t.stride(1) != 1 or t.stride(0) != dproj[0].stride(0):
+            raise RuntimeError("pbat_attn_bwd: the projection gradients must be [B L, h d] row-strided views with one row stride")
+    n = w_partial.shape[0]
+    if _dense(S, torch.float32, "S").shape != (B, h, L, b + 1) or _dense(lse, torch.float32, "lse").shape != (B, h, L) or \
+            _dense(drel_m, torch.float32, "drel_m").shape != (B, NP, H) or _dense(drel_c, torch.float32, "drel_c").shape != (B, NP, H) or \
+            _dense(w_partial, torch.float32, "w_partial").shape != (n, h, 4 * (d * d + d)) or \
+            _dense(pos_partial, torch.float32, "pos_partial").shape != (n, h, 4, L, d) or not 0 < n <= B:
+        raise RuntimeError("pbat_attn_bwd: S [B, h, L, b + 1], lse [B, h, L], drel [B, (b + 1)^2, h d], w_partial [n, h, 4 (d d + d)], "
+                           "pos_partial [n, h, 4, L, d], 0 < n <= B")
+    call("gamer_pbat_attn_bwd", *args, float(scale), float(p_drop), int(seed), ptr(S), ptr(lse), ptr(do1), ptr(do2),
+         do1.stride(0), *[ptr(t) for t in dproj], dproj[0].stride(0), ptr(drel_m), ptr(drel_c), ptr(w_partial), ptr(pos_partial), n,
+         ptr(ws), stream_ptr())
+
+
+def _wass_pair(name, a, b, rows=None):
+    R, H = a.shape if rows is None else (rows, a.shape[1])
+    if _dense(a, torch.float32, name).dim() != 2 or _dense(b, torch.float32, name).shape != a.shape or a.shape[0] < R or R < 1:
+        raise RuntimeError(f"{name}: two dense fp32 [rows, H] tensors of one shape")
+    return R, H
+
+
+def wass_rows_fwd(hm, hc, x, a):
+    """x [R, 2 H] = -2 [hm, sqrt(clamp hc)], a [R] = |hm|^2 + sum hc (gamer_wass_rows_fwd)."""
+    R, H = _wass_pair("wass_rows_fwd", hm, hc)
+    if _dense(x, torch.float32, "x").shape != (R, 2 * H) or _dense(a, torch.float32, "a").shape != (R,):
+        raise RuntimeError("wass_rows_fwd: x [R, 2 H], a [R]")
+    call("gamer_wass_rows_fwd", ptr(hm), ptr(hc), R, H, ptr(x), ptr(a), stream_ptr())
+
+
+def wass_rows_bwd(hm, hc, dx, da, dhm, dhc):
+    R, H = _wass_pair("wass_rows_bwd", hm, hc)
+    _wass_pair("wass_rows_bwd", dhm, dhc)
+    if _dense(dx, torch.float32, "dx").shape != (R, 2 * H) or dhm.shape != hm.shape or \
+            (da is not None and _dense(da, torch.float32, "da").shape != (R,)):
+        raise RuntimeError("wass_rows_bwd: dx [R, 2 H], da [R] or None, dhm / dhc [R, H]")
+    call("gamer_wass_rows_bwd", ptr(hm), ptr(hc), ptr(dx), ptr(da), R, H, ptr(dhm), ptr(dhc), stream_ptr())
+
+
+def wass_table_fwd(Em, Ec, V, E2, c):
+    """E2 [V, 2 H] = [Em, sqrt(clamp ec)], c [V] = |Em|^2 + sum ec, ec = ELU(Ec) + 1, over rows [0, V) (gamer_wass_table_fwd)."""
+    V, H = _wass_pair("wass_table_fwd", Em, Ec, int(V))
+    if _dense(E2, torch.float32, "E2").shape != (V, 2 * H) or _dense(c, torch.float32, "c").shape != (V,):
+        raise RuntimeError("wass_table_fwd: E2 [V, 2 H], c [V]")
+    call("gamer_wass_table_fwd", ptr(Em), ptr(Ec), V, H, ptr(E2), ptr(c), stream_ptr())
+
+
+def wass_table_bwd(Em, Ec, V, dE2, dc, dEm, dEc):
+    """rows [0, V) of dEm / dEc are written from dE2 [V, 2 H] and dc [V] (or None)."""
+    V, H = _wass_pair("wass_table_bwd", Em, Ec, int(V))
+    _wass_pair("wass_table_bwd", dEm, dEc, V)
+    if _dense(dE2, torch.float32, "dE2").shape != (V, 2 * H) or dEm.shape[1] != H or \
+            (dc is not None and _dense(dc, torch.float32, "dc").shape != (V,)):
+        raise RuntimeError("wass_table_bwd: dE2 [V, 2 H], dc [V] or None, dEm / dEc [>= V, H]")
+    call("gamer_wass_table_bwd", ptr(Em), ptr(Ec), ptr(dE2), ptr(dc), V, H, ptr(dEm), ptr(dEc), stream_ptr())

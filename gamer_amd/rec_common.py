@@ -295,13 +295,14 @@ class SeqRecMixin:
     def _shared_grad(self):
         return _SharedGrad() if torch.is_grad_enabled() and self.item_embedding.weight.requires_grad else None
 
-    def _item_scores(self, y: torch.Tensor, V: int, bias=None, start: int = 0) -> torch.Tensor:
-        """y @ E[start:V]^T (+ bias), materialised: [R, V - start]"""
+    def _item_scores(self, y: torch.Tensor, V: int, bias=None, start: int = 0, table=None) -> torch.Tensor:
+        """y @ E[start:V]^T (+ bias), materialised: [R, V - start]; E = ``table`` (default: the item table)"""
         R, H = y.shape
         n = V - start
         out = torch.empty(R, n, dtype=torch.float32, device=y.device)
+        E = self.item_embedding.weight if table is None else table
         with ops.f32_matmul("f32"):
-            ops.linear_fwd(y.contiguous(), H, self.item_embedding.weight[start:V].detach(), H, out, n, R, n, H)
+            ops.linear_fwd(y.contiguous(), H, E[start:V].detach(), H, out, n, R, n, H)
         return out if bias is None else out + bias.detach()
 
     def full_sort_predict(self, interaction: dict) -> torch.Tensor:
@@ -322,11 +323,22 @@ class ClozeMixin(SeqRecMixin):
       _extra(item_seq, interaction)                      the device check of item_seq, and ``extra`` from the interaction
       _draw_cloze(interaction)                           (masked, extra, rows, targets) of a fresh masking: ONE host read
       _in_graph(name)                                    whether the loss reaches the parameter of that name
-    and ``head``, whose ``bias`` (when it has one) is added to the scores."""
+    and ``head``, whose ``bias`` (when it has one) is added to the scores.  A model whose head scores against something else than
+    the item table itself (PBAT: a table derived from two) overrides ``_head_table``."""
 
     @property
     def _head_bias(self):
         return getattr(self.head, "bias", None)
+
+    def _head_table(self, shared=None):
+        """(table [>= V, H'], bias or None, V, shared): what the head's hidden state is scored against - rows [0, V) of the table
+        plus the bias - and the gradient buffer the cross entropy hands its table gradient to (None: it returns it to autograd)."""
+        return self.item_embedding.weight, self._head_bias, self.n_items + 1, shared
+
+    def _cloze_scores(self, y: torch.Tensor) -> torch.Tensor:
+        """the materialised scores [R, V] of head inputs y"""
+        E, bias, V, _ = self._head_table()
+        return self._item_scores(y, V, bias, table=E)
 
     def _refuse_candidates(self, candidates):
         if candidates is not None:
@@ -341,8 +353,7 @@ class ClozeMixin(SeqRecMixin):
         if rows.numel() == 0:
             return torch.empty(0, self.n_items + 1, device=item_seq.device), flat[rows]
         with torch.no_grad():
-            y = self._head_input(item_seq, *extra, rows)
-            return self._item_scores(y, self.n_items + 1, self._head_bias), flat[rows]
+            return self._cloze_scores(self._head_input(item_seq, *extra, rows)), flat[rows]
 
     def _loss(self, masked, *rest) -> torch.Tensor:
         *extra, rows, targets = rest
@@ -352,7 +363,8 @@ class ClozeMixin(SeqRecMixin):
         shared = self._shared_grad()
         y = self._head_input(masked, *extra, rows, shared)
         all_rows = torch.arange(y.shape[0], device=y.device)
-        return CatalogCEFn.apply(y, all_rows, self.item_embedding.weight, targets, shared, self._head_bias, self.n_items + 1)
+        E, bias, V, shared = self._head_table(shared)
+        return CatalogCEFn.apply(y, all_rows, E, targets, shared, bias, V)
 
     def calculate_loss(self, interaction: dict, masked_labels=None) -> torch.Tensor:
         """The cloze loss of one batch.  ``masked_labels`` = (masked_item_seq, labels) injects the masking (parity tests); by
@@ -379,14 +391,15 @@ class ClozeMixin(SeqRecMixin):
     def full_sort_predict(self, interaction: dict) -> torch.Tensor:
         """[B, n_items + 1] scores (the head's bias added) from position seq_len - 1 of the input as given: the evaluation data
         already ends with the mask token.  ``item_range`` is ignored, as in the reference.  Small catalogues and tests."""
-        return self._item_scores(self._last_hidden(interaction), self.n_items + 1, self._head_bias)
+        return self._cloze_scores(self._last_hidden(interaction))
 
     @torch.no_grad()
     def full_sort_topk(self, interaction: dict, k: int):
         """(indices [B, k], scores [B, k]) of the k best of items [0, n_items + 1), as a stable argsort of full_sort_predict reads
         them (lower index on ties); the scores are never materialised (gamer_catalog_topk / _topk_bias); <MASK> is never scored."""
         y = self._last_hidden(interaction)
-        V, E, bias = self.n_items + 1, self.item_embedding.weight.detach(), self._head_bias
+        E, bias, V, _ = self._head_table()
+        E = E.detach()
         if bias is None:
             return ops.catalog_topk(y, E, k, 0, V)
         return ops.catalog_topk_bias(y, E, bias.detach().reshape(-1), k, 0, V, V=V)

@@ -36,12 +36,12 @@ def _check_task(task: str) -> bool:
 class SMBDisData:
     """One split (``mode`` in train / valid / test) of ``SMBDisDataset(diff=...)``; ``samples`` is a list of dicts with
     ``inters``, ``inter_behaviors``, ``item`` (an int for train, a list for valid / test), ``behavior`` and optionally
-    ``item_range``."""
+    ``item_range``; with ``add_uid`` (the reference's ``--add_uid``, for PBAT) also ``uid`` = int(user key) + 1 (0 pads)."""
 
-    def __init__(self, data_path: str, dataset: str, max_his_len: int, mode: str, diff: bool = False):
+    def __init__(self, data_path: str, dataset: str, max_his_len: int, mode: str, diff: bool = False, add_uid: bool = False):
         if mode not in ("train", "valid", "test"):
             raise NotImplementedError(mode)
-        self.dataset, self.max_his_len, self.mode, self.diff = dataset, max_his_len, mode, diff
+        self.dataset, self.max_his_len, self.mode, self.diff, self.add_uid = dataset, max_his_len, mode, diff, add_uid
         d = os.path.join(data_path, dataset)
 
         def load(suffix):
@@ -96,9 +96,14 @@ class SMBDisData:
                 inters, ib = self._hist(items[:pos], behs[:pos])
                 if not inters:
                     continue
-                out.append(dict(item=self.item_id(items[i], behs[i]), inters=inters, inter_behaviors=ib,
-                                behavior=self.behaviors.index(behs[i])))
+                out.append(self._with_uid(dict(item=self.item_id(items[i], behs[i]), inters=inters, inter_behaviors=ib,
+                                               behavior=self.behaviors.index(behs[i])), uid))
         return out
+
+    def _with_uid(self, sample: dict, uid) -> dict:
+        if self.add_uid:
+            sample["uid"] = int(uid) + 1
+        return sample
 
     def _session_sample(self, uid, start, end):
         items, behs = self.inters[uid][:end], self.history_behaviors[uid][:end]
@@ -107,7 +112,7 @@ class SMBDisData:
         if not tgt:
             raise ValueError(f"Session for user {uid} is empty after position {start}.")
         inters, ib = self._hist(items[:start], behs[:start])
-        return dict(item=tgt, inters=inters, inter_behaviors=ib, behavior=tb)
+        return self._with_uid(dict(item=tgt, inters=inters, inter_behaviors=ib, behavior=tb), uid)
 
     def _valid(self):
         return [self._session_sample(uid, self.valid_pos[uid], self.test_pos[uid]) for uid in self.inters]
@@ -140,18 +145,19 @@ class SMBDisData:
         return len(self.samples)
 
 
-def load_train_valid(data_path: str, dataset: str, max_his_len: int, tasks: str) -> Tuple[List[SMBDisData], SMBDisData]:
+def load_train_valid(data_path: str, dataset: str, max_his_len: int, tasks: str,
+                     add_uid: bool = False) -> Tuple[List[SMBDisData], SMBDisData]:
     """load_SMBDis_datasets for smb_dis / smb_dis_diff: the training splits of every task and the validation split of the
     last task's kind (unfiltered; the trainer filters it by the target behaviour)."""
     trains, diff = [], False
     for t in tasks.split(","):
         diff = _check_task(t)
-        trains.append(SMBDisData(data_path, dataset, max_his_len, "train", diff))
-    return trains, SMBDisData(data_path, dataset, max_his_len, "valid", diff)
+        trains.append(SMBDisData(data_path, dataset, max_his_len, "train", diff, add_uid))
+    return trains, SMBDisData(data_path, dataset, max_his_len, "valid", diff, add_uid)
 
 
-def load_test(data_path: str, dataset: str, max_his_len: int, test_task: str) -> SMBDisData:
-    return SMBDisData(data_path, dataset, max_his_len, "test", _check_task(test_task))
+def load_test(data_path: str, dataset: str, max_his_len: int, test_task: str, add_uid: bool = False) -> SMBDisData:
+    return SMBDisData(data_path, dataset, max_his_len, "test", _check_task(test_task), add_uid)
 
 
 def collate(samples: list, test: bool = False):
@@ -169,6 +175,8 @@ def collate(samples: list, test: bool = False):
     batch["behavior"] = torch.tensor([s["behavior"] + 1 for s in samples], dtype=torch.long)
     if "item_range" in samples[0]:
         batch["item_range"] = samples[0]["item_range"]
+    if "uid" in samples[0]:
+        batch["uid"] = torch.tensor([s["uid"] for s in samples], dtype=torch.long)
     if test:
         return batch, [s["item"] for s in samples]
     return batch

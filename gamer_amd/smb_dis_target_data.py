@@ -50,18 +50,18 @@ class SMBDisUserLevelData(SMBDisData):
                 begin = random.randint(0, len(items) - self.max_his_len - 1)
                 items, behs = items[begin:begin + self.max_his_len], behs[begin:begin + self.max_his_len]
             inters, ib = self._hist(items, behs)
-            out.append(dict(item=self.item_id(items[-1], behs[-1]), inters=inters, inter_behaviors=ib,
-                            behavior=self.behaviors.index(behs[-1])))
+            out.append(self._with_uid(dict(item=self.item_id(items[-1], behs[-1]), inters=inters, inter_behaviors=ib,
+                                           behavior=self.behaviors.index(behs[-1])), uid))
         return out
 
 
 class SMBDisTargetData(SMBDisData):
     """``SMBDisTargetDataset``'s valid / test splits: history of at most max_his_len - 1 items, then the mask token."""
 
-    def __init__(self, data_path: str, dataset: str, max_his_len: int, mode: str, diff: bool = False):
+    def __init__(self, data_path: str, dataset: str, max_his_len: int, mode: str, diff: bool = False, add_uid: bool = False):
         if mode not in ("valid", "test"):
             raise NotImplementedError(f"SMBDisTargetData: mode {mode!r} (the target tasks' training split is not restated)")
-        super().__init__(data_path, dataset, max_his_len, mode, diff)
+        super().__init__(data_path, dataset, max_his_len, mode, diff, add_uid)
 
     def _session_sample(self, uid, start, end):
         s = super()._session_sample(uid, start, end)
@@ -83,15 +83,16 @@ class SMBDisTargetData(SMBDisData):
         return out
 
 
-def load_train_valid(data_path: str, dataset: str, max_his_len: int, tasks: str) -> Tuple[List[SMBDisData], SMBDisData]:
+def load_train_valid(data_path: str, dataset: str, max_his_len: int, tasks: str,
+                     add_uid: bool = False) -> Tuple[List[SMBDisData], SMBDisData]:
     """load_SMBDis_datasets for smb_dis_decoder / smb_dis_diff_decoder: the user-level training splits of every task and the
     target validation split of the last task's kind (unfiltered; the trainer filters it by the target behaviour)."""
     trains, diff = [], False
     for t in tasks.split(","):
         diff = _diff(t, TRAIN_TASKS)
-        trains.append(SMBDisUserLevelData(data_path, dataset, max_his_len, "train", diff))
-    return trains, SMBDisTargetData(data_path, dataset, max_his_len, "valid", diff)
+        trains.append(SMBDisUserLevelData(data_path, dataset, max_his_len, "train", diff, add_uid))
+    return trains, SMBDisTargetData(data_path, dataset, max_his_len, "valid", diff, add_uid)
 
 
-def load_test(data_path: str, dataset: str, max_his_len: int, test_task: str) -> SMBDisData:
-    return SMBDisTargetData(data_path, dataset, max_his_len, "test", _diff(test_task, TEST_TASKS))
+def load_test(data_path: str, dataset: str, max_his_len: int, test_task: str, add_uid: bool = False) -> SMBDisData:
+    return SMBDisTargetData(data_path, dataset, max_his_len, "test", _diff(test_task, TEST_TASKS), add_uid)

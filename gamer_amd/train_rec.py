@@ -107,11 +107,12 @@ def evaluate(model, data, batch_size, metrics, dev, collate=smb_dis_data.collate
 
 
 def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="train_rec", train_target_only=False,
-        test_target_only=False, pass_target_behavior_id=False):
+        test_target_only=False, pass_target_behavior_id=False, pass_n_users=False):
     """The loop of ``TrainSMBRec.invoke`` for the parsed arguments ``a``: the model and config classes, the data functions
     (train / valid loader, test loader, collate) and the tag of the printed lines are the command's (train_rec, train_bert4rec).
     The three flags are what the reference does for MBHT alone: train on the target behaviour's rows only, test the target
-    behaviour only (the merged entry then equals it), and give the model ``target_behavior_id = target_behavior_index + 1``."""
+    behaviour only (the merged entry then equals it), and give the model ``target_behavior_id = target_behavior_index + 1``.
+    ``pass_n_users`` gives the model ``n_users`` (PBAT, whose data functions put ``uid`` into the batches)."""
     random.seed(a.seed)
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
@@ -124,6 +125,8 @@ def run(a, model_cls, config_cls, load_train_valid, load_test, collate, tag="tra
     first = trains[0]
     # (n_behaviors: read by the behaviour-aware backbones; the others take it in **kwargs)
     extra = dict(target_behavior_id=first.target_behavior_index + 1) if pass_target_behavior_id else {}
+    if pass_n_users:
+        extra["n_users"] = first.num_users
     model = model_cls(config, n_items=first.num_items, max_his_len=a.max_his_len, n_behaviors=len(first.behaviors), **extra).to(dev)
     ckpt = os.path.join(a.output_dir, "best_model.pth")
     if not a.only_test:

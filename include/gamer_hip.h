@@ -1028,6 +1028,44 @@ int gamer_hg_fuse_bwd(const float* x0, const float* x1, const float* w, const fl
 /* misc */
 int gamer_fill_f32(float* p, int64_t n, float value, void* stream);
 
+/* (additions to ABI 9) PBAT's fused behaviour-aware attention (csrc/pbat.hip; ref:SeqRec/modules/layers/pbat.py
+ * FBAMultiHeadAttention).  Two streams per token: q1 / k1 / v1 (means) and q2 / k2 / v2 = ELU(.) + 1 (covariances), all six [B L][ld]
+ * with head h at column h d.  rel_m / rel_c [B][(b + 1)^2][H d]: the row's relation Gaussians at (query type, key type); pos_m / pos_c
+ * [L][H d]; Wq1 / Wk1 act on the relation means, Wq2 / Wk2 on the position means ([d][d] + [d], shared by the heads).  Per query i and
+ * key type t both TriSAGP fusions are built from token i's own projections (as the reference does) and
+ * S[i][t] = -Wasserstein(fused Q, fused K) scale; the softmax over the keys j reads S[i][t_j]; keys with keep == 0 are masked (the
+ * reference's additive finfo.min; a row with no key left attends uniformly).  Dropout of element (b, h, i, j) as
+ * gamer_mbs_attn_fwd.  Saved: S [B][H][L][b + 1] and lse [B][H][L]; nothing of size L^2 is written to memory.  pos_ws: 2 H L d floats
+ * of scratch (Wq2 pos_m + bq2, Wk2 pos_m + bk2).  L <= 128, head_dim <= 64 and a multiple of 4, n_behaviors <= 8. */
+int gamer_pbat_attn_fwd(const float* q1, const float* q2, const float* k1, const float* k2, const float* v1, const float* v2, int ld,
+                        const float* rel_m, const float* rel_c, const float* pos_m, const float* pos_c, const float* wq1,
+                        const float* bq1, const float* wq2, const float* bq2, const float* wk1, const float* bk1, const float* wk2,
+                        const float* bk2, const int32_t* types, const int32_t* keep, int B, int L, int H, int head_dim, int n_behaviors,
+                        float scale, float p_drop, uint64_t seed, float* o1, float* o2, int ldo, float* S, float* lse, float* pos_ws,
+                        void* stream);
+/* From the forward's S and lse and the gradients do1 / do2 [B L][ldo] of its two contexts.  Every output is written: dq1 .. dv2 [B L][ldd], drel_m / drel_c [B][(b + 1)^2][H d].  The parameter gradients leave as slabs, one
+ * per workgroup (slot, head), ZERO on entry: w_partial [n][H][4 (d d + d)] = (Wq1, bq1, Wk1, bk1, Wq2, bq2, Wk2, bk2),
+ * pos_partial [n][H][4][L][d] = (dpos_m, dpos_c, scratch, scratch); the caller sums them over n (and the weights over H) in a
+ * fixed order.  No float atomics: two calls give the same bits.  n_partial <= B. */
+int gamer_pbat_attn_bwd(const float* q1, const float* q2, const float* k1, const float* k2, const float* v1, const float* v2, int ld,
+                        const float* rel_m, const float* rel_c, const float* pos_m, const float* pos_c, const float* wq1,
+                        const float* bq1, const float* wq2, const float* bq2, const float* wk1, const float* bk1, const float* wk2,
+                        const float* bk2, const int32_t* types, const int32_t* keep, int B, int L, int H, int head_dim, int n_behaviors,
+                        float scale, float p_drop, uint64_t seed, const float* S, const float* lse,
+                        const float* do1, const float* do2, int ldo, float* dq1, float* dq2, float* dk1, float* dk2, float* dv1,
+                        float* dv2, int ldd, float* drel_m, float* drel_c, float* w_partial, float* pos_partial, int n_partial,
+                        float* pos_ws, void* stream);
+/* The elementwise halves of PBAT's Wasserstein head (ref:SeqRec/modules/layers/pbat.py WassersteinPredictionHead):
+ * distance(r, v) = a_r + c_v + x'_r . E'_v with x' [R][2 H] = -2 [hm, sqrt(max(hc, 1e-24))], a_r = |hm_r|^2 + sum hc_r, E' [V][2 H] =
+ * [E_m, sqrt(max(ec, 1e-24))], c_v = |E_m v|^2 + sum ec_v, ec = ELU(E_c) + 1, so the biased catalogue entry points serve with
+ * H' = 2 H and bias c.  The backward halves take dx' / dE' and da / dc (NULL = zero) and write dhm, dhc / rows [0, V) of dE_m, dE_c. */
+int gamer_wass_rows_fwd(const float* hm, const float* hc, int R, int H, float* x, float* a, void* stream);
+int gamer_wass_rows_bwd(const float* hm, const float* hc, const float* dx, const float* da, int R, int H, float* dhm, float* dhc,
+                        void* stream);
+int gamer_wass_table_fwd(const float* Em, const float* Ec, int V, int H, float* E2, float* c, void* stream);
+int gamer_wass_table_bwd(const float* Em, const float* Ec, const float* dE2, const float* dc, int V, int H, float* dEm, float* dEc,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
