@@ -216,6 +216,10 @@ _SIGNATURES = {
     "gamer_hg_readout_bwd": [P, P, P, I, I, I, I, I, I, I, P, P],
     "gamer_hg_fuse_fwd": [P, P, P, L, I, P, P, P],
     "gamer_hg_fuse_bwd": [P, P, P, P, P, L, I, P, P, P, I, P],
+    "gamer_t5_attn_fwd": [P, I, P, I, P, I, P, P, P, I, I, I, I, I, I, F, U, P, I, P, P],
+    "gamer_t5_attn_bwd": [P, I, P, I, P, I, P, P, I, I, I, I, I, I, F, U, P, I, P, P, I, P, I, P, I, P, I, P],
+    "gamer_t5_bias_expand": [P, P, I, I, I, P, P],
+    "gamer_t5_bias_fold": [P, I, I, I, I, P, I, P, P],
 }
 
 

@@ -2004,3 +2004,86 @@ def wass_table_bwd(Em, Ec, V, dE2, dc, dEm, dEc):
             (dc is not None and _dense(dc, torch.float32, "dc").shape != (V,)):
         raise RuntimeError("wass_table_bwd: dE2 [V, 2 H], dc [V] or None, dEm / dEc [>= V, H]")
     call("gamer_wass_table_bwd", ptr(Em), ptr(Ec), ptr(dE2), ptr(dc), V, H, ptr(dEm), ptr(dEc), stream_ptr())
+
+
+# ---- T5's attention (TIGER; csrc/t5_attention.hip) ----------------------------------------------------------------------------------
+T5_MAX_S, T5_MAX_H, T5_HEAD_DIMS = 128, 16, (32, 64)
+
+
+def t5_check_limits(Sq, Sk, h, d):
+    """The limits of the T5 attention kernels, refused on the host before any launch."""
+    if Sq < 1 or Sk < 1 or Sq > T5_MAX_S or Sk > T5_MAX_S or h < 1 or h > T5_MAX_H or d not in T5_HEAD_DIMS:
+        raise NotImplementedError(f"T5 attention on the HIP path: Sq, Sk <= {T5_MAX_S}, heads <= {T5_MAX_H}, head size in "
+                                  f"{T5_HEAD_DIMS} (got Sq={Sq}, Sk={Sk}, heads={h}, head size={d})")
+
+
+def _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, Bkv=None):
+    t5_check_limits(Sq, Sk, h, d)
+    Bkv = B if Bkv is None else Bkv
+    for t, n, S, Bt in ((q, "q", Sq, B), (k, "k", Sk, Bkv), (v, "v", Sk, Bkv)):
+        _chk(t, torch.float32, n)
+        if t.dim() != 2 or t.shape != (Bt * S, h * d) or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+            raise RuntimeError(f"t5 attention: {n} must be a [{B * S}, {h * d}] row-strided view (16-byte aligned, row stride % 4 == 0)")
+    if rel is not None and _dense(rel, torch.float32, "rel").shape != (h, Sq + Sk - 1):
+        raise RuntimeError(f"t5 attention: rel [{h}, {Sq + Sk - 1}]")
+    if keep is not None and _dense(keep, torch.uint8, "keep").shape != (Bkv, Sk):
+        raise RuntimeError(f"t5 attention: keep uint8 [{Bkv}, {Sk}]")
+
+
+def t5_attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, o, lse, kv_rows=None, kv_batch=None):
+    """gamer_t5_attn_fwd: q / o [B Sq, h d], k / v [B Sk, h d] (row-strided views), rel [h, Sq + Sk - 1] or None, keep uint8 [B, Sk] or
+    None, lse [B, h, Sq].  No 1 / sqrt(d) scale.  kv_rows int32 [B] with kv_batch: k / v / keep hold kv_batch rows and row b reads
+    row kv_rows[b] of them (values in [0, kv_batch): checked by the caller; decoding only - there is no backward for it)."""
+    if (kv_rows is None) != (kv_batch is None) or (kv_rows is not None and _dense(kv_rows, torch.int32, "kv_rows").shape != (B,)):
+        raise RuntimeError("t5_attn_fwd: kv_rows int32 [B] goes with kv_batch")
+    _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, kv_batch)
+    _chk(o, torch.float32, "o"), _dense(lse, torch.float32, "lse")
+    if o.shape != (B * Sq, h * d) or o.stride(1) != 1 or lse.numel() != B * h * Sq:
+        raise RuntimeError("t5_attn_fwd: o [B Sq, h d] and lse [B, h, Sq]")
+    call("gamer_t5_attn_fwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(keep), ptr(kv_rows), B, Sq, Sk,
+         h, d, int(bool(causal)), float(p_drop), int(seed), ptr(o), o.stride(0), ptr(lse), stream_ptr())
+
+
+def t5_n_slab(B, h):
+    """Workgroup rows of the attention backward: n h workgroups, about two per CU (256 CUs), each walking the rows n apart."""
+    return max(1, min(B, 512 // max(1, h)))
+
+
+def t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial):
+    """gamer_t5_attn_bwd: dq / dk / dv are written in full; drel_partial [n, h, Sq + Sk - 1] (None iff rel is None) is written in
+    full by its n h workgroups (n <= B); without a bias n = t5_n_slab(B, h)."""
+    _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d)
+    for t, n, S in ((d_o, "d_o", Sq), (dq, "dq", Sq), (dk, "dk", Sk), (dv, "dv", Sk)):
+        _chk(t, torch.float32, n)
+        if t.shape != (B * S, h * d) or t.stride(1) != 1:
+            raise RuntimeError(f"t5_attn_bwd: {n} must be a [{B * S}, {h * d}] row-strided view")
+    if _dense(lse, torch.float32, "lse").numel() != B * h * Sq:
+        raise RuntimeError("t5_attn_bwd: lse [B, h, Sq]")
+    if (rel is None) != (drel_partial is None):
+        raise RuntimeError("t5_attn_bwd: drel_partial goes with the bias")
+    n = t5_n_slab(B, h)
+    if drel_partial is not None:
+        n = drel_partial.shape[0]
+        if _dense(drel_partial, torch.float32, "drel_partial").shape != (n, h, Sq + Sk - 1) or not 0 < n <= B:
+            raise RuntimeError(f"t5_attn_bwd: drel_partial [n, {h}, {Sq + Sk - 1}], 0 < n <= B")
+    call("gamer_t5_attn_bwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(keep), B, Sq, Sk, h, d,
+         int(bool(causal)), float(p_drop), int(seed), ptr(d_o), d_o.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk),
+         dk.stride(0), ptr(dv), dv.stride(0), ptr(drel_partial), n, stream_ptr())
+
+
+def t5_bias_expand(table, bucket, rel):
+    """rel [h, R] = table [num_buckets, h] at bucket int32 [R] (values in [0, num_buckets): checked by the caller)."""
+    _dense(table, torch.float32, "table"), _dense(bucket, torch.int32, "bucket"), _dense(rel, torch.float32, "rel")
+    nb, h = table.shape
+    if rel.shape != (h, bucket.numel()) or bucket.dim() != 1:
+        raise RuntimeError("t5_bias_expand: table [num_buckets, h], bucket [R], rel [h, R]")
+    call("gamer_t5_bias_expand", ptr(table), ptr(bucket), nb, h, bucket.numel(), ptr(rel), stream_ptr())
+
+
+def t5_bias_fold(drel_partial, bucket, dtable):
+    """dtable [num_buckets, h] from drel_partial [layers, n, h, R]: slabs, offsets and layers summed in a fixed order."""
+    _dense(drel_partial, torch.float32, "drel_partial"), _dense(bucket, torch.int32, "bucket"), _dense(dtable, torch.float32, "dtable")
+    if drel_partial.dim() != 4 or bucket.shape != (drel_partial.shape[3],) or dtable.dim() != 2 or dtable.shape[1] != drel_partial.shape[2]:
+        raise RuntimeError("t5_bias_fold: drel_partial [layers, n, h, R], bucket [R], dtable [num_buckets, h]")
+    nl, n, h, R = drel_partial.shape
+    call("gamer_t5_bias_fold", ptr(drel_partial), nl, n, h, R, ptr(bucket), dtable.shape[0], ptr(dtable), stream_ptr())

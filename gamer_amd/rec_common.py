@@ -73,10 +73,12 @@ def _next_seed() -> int:
 class _SharedGrad:
     """The item table's gradient buffer of one calculate_loss call: the head's backward (which runs first) writes its dE into
     it and returns no gradient for the table; the input block's backward accumulates the gather's rows into the same buffer
-    and returns it - one [V, H] tensor instead of two plus autograd's sum."""
+    and returns it - one [V, H] tensor instead of two plus autograd's sum.  ``gathers`` > 1 (TIGER: the encoder's and the
+    decoder's inputs): every gather but the last hands the buffer on through ``give`` and returns no gradient itself."""
 
-    def __init__(self):
+    def __init__(self, gathers: int = 1):
         self.dE = None
+        self.gathers = gathers
 
     @staticmethod
     def take(shared, shape, device):
@@ -84,6 +86,17 @@ class _SharedGrad:
         if shared is None or shared.dE is None:
             return torch.zeros(shape, dtype=torch.float32, device=device)
         dE, shared.dE = shared.dE, None
+        return dE
+
+    @staticmethod
+    def give(shared, dE):
+        """after a gather added its rows to ``dE``: None when another gather is still to come (the buffer waits for it), else dE"""
+        if shared is None:
+            return dE
+        shared.gathers -= 1
+        if shared.gathers > 0:
+            shared.dE = dE
+            return None
         return dE
 
 

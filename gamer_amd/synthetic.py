@@ -316,3 +316,37 @@ def write_mb_dataset(root: str, name: str, n_users: int = 30, n_items: int = 50,
         with open(os.path.join(d, name + suffix), "w") as f:
             json.dump(obj, f)
     return d
+
+
+def write_seqrec_dataset(root: str, name: str, n_users: int = 40, n_items: int = 60, codebook: int = 8, seed: int = 0,
+                         min_len: int = 4, max_len: int = 12) -> str:
+    """Write a small single-behaviour dataset in the on-disk format of ``train_decoder`` (seqrec_data.SeqRecData):
+    ``<root>/<name>/<name>.inter.json`` (user -> item ids, at least four so that every user has a training prefix) and
+    ``<name>.index.json`` (item -> 4 semantic-ID tokens, distinct per item).  A user walks the items in steps of 1 or 2 from a random
+    start, so that the next item can be learned.  Returns the dataset directory."""
+    import json
+    import os
+    import random
+    rng = random.Random(seed)
+    d = os.path.join(root, name)
+    os.makedirs(d, exist_ok=True)
+    index, seen = {}, set()
+    for i in range(n_items):
+        while True:
+            toks = tuple(rng.randrange(codebook) for _ in "abcd")
+            if toks not in seen:
+                break
+        seen.add(toks)
+        index[str(i)] = [f"<{c}_{t}>" for c, t in zip("abcd", toks)]
+    inter = {}
+    for u in range(n_users):
+        item = rng.randrange(n_items)
+        items = []
+        for _ in range(rng.randint(min_len, max_len)):
+            items.append(item)
+            item = (item + rng.choice((1, 1, 1, 2))) % n_items
+        inter[str(u)] = items
+    for suffix, obj in ((".inter.json", inter), (".index.json", index)):
+        with open(os.path.join(d, name + suffix), "w") as f:
+            json.dump(obj, f)
+    return d

@@ -1,0 +1,679 @@
+"""TIGER, the T5 encoder-decoder backbone of ``train_decoder``, on the HIP path.
+
+Same nn.Module surface, state-dict names and shapes as the reference (ref:SeqRec/models/generative/TIGER/model.py, a
+``T5ForConditionalGeneration`` with a temperature): ``shared.weight`` = ``encoder.embed_tokens.weight`` =
+``decoder.embed_tokens.weight`` = ``lm_head.weight`` (four keys, one parameter), ``{encoder,decoder}.block.{l}.layer.0.SelfAttention.
+{q,k,v,o}.weight`` with ``relative_attention_bias.weight`` on block 0, ``decoder.block.{l}.layer.1.EncDecAttention.{q,k,v,o}.weight``,
+``layer.{n}.layer_norm.weight``, ``DenseReluDense.{wi,wo}.weight`` and the two ``final_layer_norm.weight``.  A reference checkpoint
+loads here and one saved here loads there.
+
+Every step runs as HIP kernels, with no PyTorch fallback (a CPU tensor raises):
+  input         gamer_embedding_fwd + dropout; backward gamer_embedding_bwd_large into ONE gradient buffer shared by the head and
+                both input gathers (rec_common._SharedGrad with two gathers)
+  a block       one autograd function: T5's RMS norm (gamer_rmsnorm_fwd / _bwd), ONE [q|k|v] GEMM for self attention, one [k|v]
+                GEMM on the encoder output per decoder layer, gamer_t5_attn_fwd / _bwd, the Linear forward / dgrad / wgrad,
+                ReLU through gamer_bias_act (zero bias), residual dropout
+  attention     csrc/t5_attention.hip: no 1 / sqrt(d), the bucketed relative bias of block 0 added in every layer of its stack,
+                key padding mask and causality inside the kernel; nothing of size S x S reaches memory.  The bias table is
+                expanded once per stack per step (gamer_t5_bias_expand) and its gradient folded once per stack, after block 0's
+                backward, from the per-layer slabs in layer order (gamer_t5_bias_fold)
+  loss          rec_common.CatalogCEFn on the rows with label != -100, the decoder rows scaled by d_model ** -0.5 / temperature:
+                the [B T, V] logits are not formed in training.  ``forward(..., labels=None)`` or ``want_logits=True``
+                materialises them (tests, decoding)
+
+Not the reference's: a query row with NO allowed key gives a zero context and zero gradients here; HF's additive finfo.min mask
+gives a softmax over the bias alone in that case.  Real inputs cannot produce it: every row holds at least ``</s>``.  Dropout
+masks come from the project's counter-based hash.
+"""
+from __future__ import annotations
+
+import dataclasses
+import math
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import modules, ops
+from .rec_common import CatalogCEFn, DropUnknownConfig, _SharedGrad, _dropout_bwd, _next_seed, colsum
+
+MAX_ENCODER_LEN, MAX_DECODER_LEN = 128, 8
+
+
+@dataclasses.dataclass(init=False)
+class TigerConfig(DropUnknownConfig):
+    """The keys of ref:config/s2s-models/TIGER/config.json that the model reads, with T5Config's defaults where the file is
+    silent; every other key (``task_specific_params``, ``architectures``, ...) is dropped without a word."""
+    vocab_size: int = 32128
+    d_model: int = 512
+    d_kv: int = 64
+    d_ff: int = 2048
+    num_layers: int = 6
+    num_decoder_layers: Optional[int] = None
+    num_heads: int = 8
+    relative_attention_num_buckets: int = 32
+    relative_attention_max_distance: int = 128
+    dropout_rate: float = 0.1
+    layer_norm_epsilon: float = 1e-6
+    initializer_factor: float = 1.0
+    feed_forward_proj: str = "relu"
+    tie_word_embeddings: bool = True
+    pad_token_id: int = 0
+    eos_token_id: int = 1
+    decoder_start_token_id: int = 0
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        if self.num_decoder_layers is None:
+            self.num_decoder_layers = self.num_layers
+
+
+def relative_position_bucket(relative_position: torch.Tensor, bidirectional: bool, num_buckets: int, max_distance: int) -> torch.Tensor:
+    """HF's ``T5Attention._relative_position_bucket`` expression for expression (torch float32 log, ``.to(long)``, ``min`` with
+    num_buckets - 1), on the host: a kernel-side logf could round differently at a bucket edge."""
+    relative_buckets = 0
+    if bidirectional:
+        num_buckets //= 2
+        relative_buckets += (relative_position > 0).to(torch.long) * num_buckets
+        relative_position = torch.abs(relative_position)
+    else:
+        relative_position = -torch.min(relative_position, torch.zeros_like(relative_position))
+    max_exact = num_buckets // 2
+    is_small = relative_position < max_exact
+    relative_position_if_large = max_exact + (
+        torch.log(relative_position.float() / max_exact) / math.log(max_distance / max_exact) * (num_buckets - max_exact)
+    ).to(torch.long)
+    relative_position_if_large = torch.min(relative_position_if_large, torch.full_like(relative_position_if_large, num_buckets - 1))
+    relative_buckets += torch.where(is_small, relative_position, relative_position_if_large)
+    return relative_buckets
+
+
+def bucket_vector(S: int, bidirectional: bool, num_buckets: int, max_distance: int) -> torch.Tensor:
+    """int32 [2 S - 1] on the CPU: the bucket of the offset j - i (key - query) at index j - i + S - 1."""
+    return relative_position_bucket(torch.arange(-(S - 1), S, dtype=torch.long), bidirectional, num_buckets, max_distance).to(torch.int32)
+
+
+# ---- parameter holders with HF's names ---------------------------------------------------------------------------------------------
+class T5LayerNorm(nn.Module):
+    def __init__(self, hidden_size: int, eps: float):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(hidden_size))
+        self.variance_epsilon = eps
+
+
+class T5Attention(nn.Module):
+    def __init__(self, config: TigerConfig, has_relative_attention_bias: bool):
+        super().__init__()
+        inner = config.num_heads * config.d_kv
+        self.q = nn.Linear(config.d_model, inner, bias=False)
+        self.k = nn.Linear(config.d_model, inner, bias=False)
+        self.v = nn.Linear(config.d_model, inner, bias=False)
+        self.o = nn.Linear(inner, config.d_model, bias=False)
+        if has_relative_attention_bias:
+            self.relative_attention_bias = nn.Embedding(config.relative_attention_num_buckets, config.num_heads)
+
+
+class T5LayerSelfAttention(nn.Module):
+    def __init__(self, config: TigerConfig, has_relative_attention_bias: bool):
+        super().__init__()
+        self.SelfAttention = T5Attention(config, has_relative_attention_bias)
+        self.layer_norm = T5LayerNorm(config.d_model, config.layer_norm_epsilon)
+
+
+class T5LayerCrossAttention(nn.Module):
+    def __init__(self, config: TigerConfig):
+        super().__init__()
+        self.EncDecAttention = T5Attention(config, False)
+        self.layer_norm = T5LayerNorm(config.d_model, config.layer_norm_epsilon)
+
+
+class T5DenseActDense(nn.Module):
+    def __init__(self, config: TigerConfig):
+        super().__init__()
+        self.wi = nn.Linear(config.d_model, config.d_ff, bias=False)
+        self.wo = nn.Linear(config.d_ff, config.d_model, bias=False)
+
+
+class T5LayerFF(nn.Module):
+    def __init__(self, config: TigerConfig):
+        super().__init__()
+        self.DenseReluDense = T5DenseActDense(config)
+        self.layer_norm = T5LayerNorm(config.d_model, config.layer_norm_epsilon)
+
+
+class T5Block(nn.Module):
+    def __init__(self, config: TigerConfig, is_decoder: bool, has_relative_attention_bias: bool):
+        super().__init__()
+        self.layer = nn.ModuleList([T5LayerSelfAttention(config, has_relative_attention_bias)])
+        if is_decoder:
+            self.layer.append(T5LayerCrossAttention(config))
+        self.layer.append(T5LayerFF(config))
+
+
+class T5Stack(nn.Module):
+    def __init__(self, config: TigerConfig, embed_tokens: nn.Embedding, is_decoder: bool):
+        super().__init__()
+        self.is_decoder = is_decoder
+        self.embed_tokens = embed_tokens
+        n = config.num_decoder_layers if is_decoder else config.num_layers
+        self.block = nn.ModuleList([T5Block(config, is_decoder, i == 0) for i in range(n)])
+        self.final_layer_norm = T5LayerNorm(config.d_model, config.layer_norm_epsilon)
+
+
+# ---- backward idioms ---------------------------------------------------------------------------------------------------------------
+def _f32(dev):
+    return dict(dtype=torch.float32, device=dev)
+
+
+def _linear(x, W):
+    """x [M, K] (row-strided) @ W [N, K]^T"""
+    M, (N, K) = x.shape[0], W.shape
+    y = torch.empty(M, N, **_f32(x.device))
+    ops.linear_fwd(x, x.stride(0), W, K, y, N, M, N, K)
+    return y
+
+
+def _linear_bwd(dy, x, W, dx=None, accumulate=False):
+    """(dx [M, K], dW) of y = x W^T from dy [M, N] (row-strided views allowed); ``dx``: written (or added to) in place"""
+    M, (N, K) = x.shape[0], W.shape
+    dW = torch.zeros_like(W)
+    ops.linear_wgrad(dy, dy.stride(0), x, x.stride(0), dW, K, M, N, K)
+    if dx is None:
+        dx = torch.empty(M, K, **_f32(x.device))
+    ops.linear_dgrad(dy, dy.stride(0), W, K, dx, dx.stride(0), M, N, K, accumulate=accumulate)
+    return dx, dW
+
+
+def _rms(x, w, eps):
+    y = torch.empty_like(x)
+    ops.rmsnorm_fwd(x, w, eps, y)
+    return y
+
+
+def _rms_bwd(x, w, eps, dy, dx):
+    """dx += d RMSNorm(x) from dy; returns dw"""
+    part = torch.empty(modules._N_PARTIAL, x.shape[1], **_f32(x.device))
+    ops.rmsnorm_bwd(x, w, dy, dy.stride(0), eps, dx, part, accumulate_dx=True)
+    return colsum(part)
+
+
+def _add_dropout(x, delta, p, seed):
+    out = torch.empty_like(x)
+    ops.residual_dropout_fwd(x, delta, p, seed, None, out)
+    return out
+
+
+def _dropout(x, p, seed):
+    return _add_dropout(torch.zeros_like(x), x, p, seed) if p > 0 else x
+
+
+def _undrop(g, p, seed):
+    if p == 0:
+        return g
+    out = torch.empty_like(g)
+    ops.residual_dropout_bwd(g, p, seed, out)
+    return out
+
+
+class _BiasStack:
+    """The relative bias of one stack for one step: ``rel`` [h, 2 S - 1] expanded once from block 0's table; in the backward every
+    block writes its slabs of the offset gradient into ``slabs`` [layers, n, h, 2 S - 1] and block 0, whose backward runs last,
+    folds them into the table gradient."""
+
+    def __init__(self, table, bucket, S, n_layers):
+        h = table.shape[1]
+        self.bucket, self.n_layers, self.S, self.h = bucket, n_layers, S, h
+        self.rel = torch.empty(h, 2 * S - 1, **_f32(table.device))
+        ops.t5_bias_expand(table.detach().contiguous(), bucket, self.rel)
+        self.slabs = None
+
+    def slab(self, layer, B):
+        if self.slabs is None:
+            self.slabs = torch.empty(self.n_layers, ops.t5_n_slab(B, self.h), self.h, 2 * self.S - 1, **_f32(self.rel.device))
+        return self.slabs[layer]
+
+    def fold(self, num_buckets):
+        dtable = torch.empty(num_buckets, self.h, **_f32(self.rel.device))
+        ops.t5_bias_fold(self.slabs, self.bucket, dtable)
+        self.slabs = None
+        return dtable
+
+
+class _BlockFn(torch.autograd.Function):
+    """One T5Block.  x [B, S, D]; enc [B, Se, D] or None (encoder block).  params: ln0, q, k, v, o, [ln1, cq, ck, cv, co,] lnf, wi,
+    wo, then block 0's bias table (or None: a later block, whose offset gradient block 0 folds)."""
+
+    @staticmethod
+    @ops.scoped_f32_matmul(lambda *a: "f32")
+    def forward(ctx, x, enc, meta, *params):
+        B, S, D = x.shape
+        T = B * S
+        h, d, eps, bias = meta["heads"], meta["d_kv"], meta["eps"], meta["bias"]
+        I = h * d
+        p = meta["dropout"] if meta["training"] else 0.0
+        dec = enc is not None
+        ln0, wq, wk, wv, wo = params[:5]
+        lnf, wi, wff = params[-4:-1]
+        seeds = [modules._SeedCounter.next() for _ in range(6)]
+        xf = x.reshape(T, D).contiguous().float()
+        # self attention: x + dropout(o(attn(norm(x))))
+        n0 = _rms(xf, ln0, eps)
+        wqkv = torch.cat([wq, wk, wv], 0).contiguous()
+        qkv = _linear(n0, wqkv)
+        c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
+        keep = None if dec else meta["keep"]
+        ops.t5_attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0)
+        x1 = _add_dropout(xf, _linear(c0, wo), p, seeds[1])
+        saved = [xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0]
+        if dec:
+            ln1, cq, ck, cv, co = params[5:10]
+            Se = enc.shape[1]
+            ef = enc.reshape(B * Se, D).contiguous().float()
+            n1 = _rms(x1, ln1, eps)
+            q1 = _linear(n1, cq)
+            wkv = torch.cat([ck, cv], 0).contiguous()
+            kv = _linear(ef, wkv)
+            c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
+            ops.t5_attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1)
+            x2 = _add_dropout(x1, _linear(c1, co), p, seeds[3])
+            saved += [ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1, x2]
+        else:
+            x2 = x1
+        # feed forward: x + dropout(wo(dropout(relu(wi(norm(x))))))
+        n2 = _rms(x2, lnf, eps)
+        pre = _linear(n2, wi)
+        act = torch.empty_like(pre)
+        ops.bias_act_fwd(pre, meta["zero_bias"], ops.ACTIVATIONS["relu"], act)
+        actd = _dropout(act, p, seeds[4])
+        x3 = _add_dropout(x2, _linear(actd, wff), p, seeds[5])
+        saved += [lnf, wi, wff, n2, pre, actd]
+        ctx.save_for_backward(*saved, meta["keep"])
+        ctx.meta = dict(meta, p=p, seeds=seeds, shape=(B, S, D), dec=dec, table=params[-1])
+        return x3.view(B, S, D)
+
+    @staticmethod
+    @ops.scoped_f32_matmul(lambda *a: "f32")
+    def backward(ctx, dout):
+        sv = list(ctx.saved_tensors)
+        mt = ctx.meta
+        B, S, D = mt["shape"]
+        T, h, d, eps, p, seeds, dec, bias = B * S, mt["heads"], mt["d_kv"], mt["eps"], mt["p"], mt["seeds"], mt["dec"], mt["bias"]
+        I = h * d
+        keep_mask = sv.pop()
+        xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0 = sv[:9]
+        lnf, wi, wff, n2, pre, actd = sv[-6:]
+        x2 = sv[19] if dec else x1
+        dev = xf.device
+        dx = dout.reshape(T, D).contiguous().float().clone()                      # the gradient of the residual stream, added to in place
+        # feed forward
+        df = _undrop(dx, p, seeds[5])
+        dactd, dwff = _linear_bwd(df, actd, wff)
+        dact = _undrop(dactd, p, seeds[4])
+        ops.bias_act_bwd(pre, dact, ops.ACTIVATIONS["relu"], dact, torch.empty(modules._N_PARTIAL, pre.shape[1], **_f32(dev)))
+        dn2, dwi = _linear_bwd(dact, n2, wi)
+        dlnf = _rms_bwd(x2, lnf, eps, dn2, dx)
+        cross = [None] * 5
+        denc = None
+        if dec:
+            ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1 = sv[9:19]
+            Se = ef.shape[0] // B
+            da = _undrop(dx, p, seeds[3])
+            dc1, dco = _linear_bwd(da, c1, co)
+            dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(B * Se, 2 * I, **_f32(dev))
+            ops.t5_attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
+                            dkv[:, :I], dkv[:, I:], None)
+            dn1, dcq = _linear_bwd(dq1, n1, cq)
+            denc, dwkv = _linear_bwd(dkv, ef, wkv)
+            dln1 = _rms_bwd(x1, ln1, eps, dn1, dx)
+            cross = [dln1, dcq, dwkv[:I], dwkv[I:], dco]
+            denc = denc.view(B, Se, D)
+        # self attention
+        da = _undrop(dx, p, seeds[1])
+        dc0, dwo = _linear_bwd(da, c0, wo)
+        dqkv = torch.empty(T, 3 * I, **_f32(dev))
+        ops.t5_attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
+                        seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B))
+        dn0, dwqkv = _linear_bwd(dqkv, n0, wqkv)
+        dln0 = _rms_bwd(xf, ln0, eps, dn0, dx)
+        dtable = bias.fold(mt["table"].shape[0]) if mt["table"] is not None else None
+        grads = [dln0, dwqkv[:I], dwqkv[I:2 * I], dwqkv[2 * I:], dwo] + (cross if dec else []) + [dlnf, dwi, dwff, dtable]
+        return (dx.view(B, S, D), denc, None, *grads)
+
+
+class _EmbedFn(torch.autograd.Function):
+    """dropout(E[ids]); every row gets its gradient (T5's table has no padding row), into the shared table gradient."""
+
+    @staticmethod
+    def forward(ctx, ids, E, p, seed, shared):
+        B, L = ids.shape
+        x = torch.empty(B * L, E.shape[1], **_f32(E.device))
+        ops.embedding_fwd(ids, E, x)
+        x = _dropout(x, p, seed)
+        ctx.meta = (p, seed, E.shape)
+        ctx.shared = shared
+        ctx.save_for_backward(ids)
+        return x.view(B, L, -1)
+
+    @staticmethod
+    def backward(ctx, dx):
+        ids, = ctx.saved_tensors
+        p, seed, e_shape = ctx.meta
+        g = _dropout_bwd(dx, e_shape[1], p, seed)
+        dE = _SharedGrad.take(ctx.shared, e_shape, g.device)
+        ops.embedding_bwd_large(ids, g, -1, dE)
+        return None, _SharedGrad.give(ctx.shared, dE), None, None, None
+
+
+class _FinalNormFn(torch.autograd.Function):
+    """dropout(RMSNorm(x)) * scale"""
+
+    @staticmethod
+    def forward(ctx, x, w, eps, p, seed, scale):
+        B, S, D = x.shape
+        xf = x.reshape(B * S, D).contiguous().float()
+        y = _dropout(_rms(xf, w, eps), p, seed)
+        ctx.meta = (eps, p, seed, scale, x.shape)
+        ctx.save_for_backward(xf, w)
+        return (y * scale if scale != 1.0 else y).view(B, S, D)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xf, w = ctx.saved_tensors
+        eps, p, seed, scale, shape = ctx.meta
+        g = dy.reshape(xf.shape).contiguous().float()
+        g = _undrop(g * scale if scale != 1.0 else g, p, seed)
+        dx = torch.zeros_like(xf)
+        dw = _rms_bwd(xf, w, eps, g, dx)
+        return dx.view(shape), dw, None, None, None, None
+
+
+class TIGER(nn.Module):
+    def __init__(self, config: TigerConfig):
+        super().__init__()
+        c = config
+        if c.feed_forward_proj != "relu":
+            raise NotImplementedError(f"TIGER on the HIP path: feed_forward_proj 'relu' only (got {c.feed_forward_proj!r})")
+        if not c.tie_word_embeddings:
+            raise NotImplementedError("TIGER on the HIP path: tie_word_embeddings=False is not built (the head is the shared table)")
+        if c.d_kv not in ops.T5_HEAD_DIMS or c.num_heads > ops.T5_MAX_H or c.num_heads < 1:
+            raise NotImplementedError(f"TIGER on the HIP path: d_kv in {ops.T5_HEAD_DIMS}, num_heads <= {ops.T5_MAX_H} "
+                                      f"(got d_kv={c.d_kv}, num_heads={c.num_heads})")
+        if c.d_model % 4 or c.d_model > 256 or c.d_ff % 4:
+            raise NotImplementedError(f"TIGER on the HIP path: d_model <= 256, d_model and d_ff divisible by 4 (got {c.d_model}, {c.d_ff})")
+        self.config = c
+        self.model_dim = c.d_model
+        self.temperature = 1.0
+        self.shared = nn.Embedding(c.vocab_size, c.d_model)
+        self.encoder = T5Stack(c, self.shared, False)
+        self.decoder = T5Stack(c, self.shared, True)
+        self.lm_head = nn.Linear(c.d_model, c.vocab_size, bias=False)
+        self.lm_head.weight = self.shared.weight
+        self.register_buffer("_zero_bias", torch.zeros(c.d_ff), persistent=False)
+        self._buckets = {}
+        self.apply(self._init_weights)
+
+    def _init_weights(self, m: nn.Module):
+        """HF T5PreTrainedModel._init_weights: the per-tensor standard deviations (not its random stream)"""
+        c = self.config
+        f = c.initializer_factor
+        if isinstance(m, T5LayerNorm):
+            m.weight.data.fill_(f * 1.0)
+        elif isinstance(m, TIGER):
+            m.shared.weight.data.normal_(mean=0.0, std=f * 1.0)
+        elif isinstance(m, T5DenseActDense):
+            m.wi.weight.data.normal_(mean=0.0, std=f * c.d_model ** -0.5)
+            m.wo.weight.data.normal_(mean=0.0, std=f * c.d_ff ** -0.5)
+        elif isinstance(m, T5Attention):
+            m.q.weight.data.normal_(mean=0.0, std=f * (c.d_model * c.d_kv) ** -0.5)
+            m.k.weight.data.normal_(mean=0.0, std=f * c.d_model ** -0.5)
+            m.v.weight.data.normal_(mean=0.0, std=f * c.d_model ** -0.5)
+            m.o.weight.data.normal_(mean=0.0, std=f * (c.num_heads * c.d_kv) ** -0.5)
+            if hasattr(m, "relative_attention_bias"):
+                m.relative_attention_bias.weight.data.normal_(mean=0.0, std=f * c.d_model ** -0.5)
+
+    # ---- HF surface ------------------------------------------------------------------------------------------------------------
+    def set_hyper(self, temperature: float):
+        self.temperature = temperature
+
+    def resize_token_embeddings(self, n: int) -> nn.Embedding:
+        """A table of n rows that keeps the first min(n, old) rows; new rows are drawn as HF draws them (normal(0, factor))."""
+        old = self.shared.weight
+        if n != old.shape[0]:
+            new = nn.Embedding(n, old.shape[1]).to(device=old.device, dtype=old.dtype)
+            new.weight.data.normal_(mean=0.0, std=self.config.initializer_factor * 1.0)
+            keep = min(n, old.shape[0])
+            new.weight.data[:keep] = old.data[:keep]
+            self.shared = new
+            self.encoder.embed_tokens = self.decoder.embed_tokens = new
+            self.lm_head = nn.Linear(old.shape[1], n, bias=False)
+            self.lm_head.weight = new.weight
+            self.config.vocab_size = n
+        return self.shared
+
+    def _shift_right(self, labels: torch.Tensor) -> torch.Tensor:
+        c = self.config
+        shifted = labels.new_zeros(labels.shape)
+        shifted[..., 1:] = labels[..., :-1].clone()
+        shifted[..., 0] = c.decoder_start_token_id
+        shifted.masked_fill_(shifted == -100, c.pad_token_id)
+        return shifted
+
+    # ---- the stacks ------------------------------------------------------------------------------------------------------------
+    def _bucket(self, S: int, bidirectional: bool, device) -> torch.Tensor:
+        key = (S, bidirectional, str(device))
+        if key not in self._buckets:
+            c = self.config
+            t = bucket_vector(S, bidirectional, c.relative_attention_num_buckets, c.relative_attention_max_distance)
+            if int(t.min()) < 0 or int(t.max()) >= c.relative_attention_num_buckets:
+                raise IndexError(f"relative position buckets outside [0, {c.relative_attention_num_buckets})")
+            self._buckets[key] = t.to(device)
+        return self._buckets[key]
+
+    def _check(self, ids: torch.Tensor, limit: int, what: str):
+        if not ids.is_cuda:
+            raise RuntimeError("gamer_amd.tiger runs on the HIP device only (no CPU fallback)")
+        if ids.dim() != 2 or ids.shape[1] < 1 or ids.shape[1] > limit:
+            raise NotImplementedError(f"TIGER on the HIP path: {what} length in [1, {limit}] (got {tuple(ids.shape)})")
+
+    def _stack(self, stack: T5Stack, ids, keep, enc=None, shared=None):
+        """keep: uint8 [B, Se] over the ENCODER tokens (the encoder's own keys, the decoder's cross-attention keys)"""
+        c = self.config
+        p = c.dropout_rate if self.training else 0.0
+        B, S = ids.shape
+        x = _EmbedFn.apply(ids.long().contiguous(), stack.embed_tokens.weight, p, _next_seed(), shared)
+        blk0 = stack.block[0].layer[0].SelfAttention
+        table = blk0.relative_attention_bias.weight
+        bias = _BiasStack(table, self._bucket(S, not stack.is_decoder, ids.device), S, len(stack.block))
+        for l, blk in enumerate(stack.block):
+            meta = dict(heads=c.num_heads, d_kv=c.d_kv, eps=c.layer_norm_epsilon, dropout=c.dropout_rate, training=self.training,
+                        bias=bias, keep=keep, layer=l, zero_bias=self._zero_bias)
+            a = blk.layer[0]
+            params = [a.layer_norm.weight, a.SelfAttention.q.weight, a.SelfAttention.k.weight, a.SelfAttention.v.weight,
+                      a.SelfAttention.o.weight]
+            if stack.is_decoder:
+                x_ = blk.layer[1]
+                e = x_.EncDecAttention
+                params += [x_.layer_norm.weight, e.q.weight, e.k.weight, e.v.weight, e.o.weight]
+            ff = blk.layer[-1]
+            params += [ff.layer_norm.weight, ff.DenseReluDense.wi.weight, ff.DenseReluDense.wo.weight, table if l == 0 else None]
+            x = _BlockFn.apply(x, enc, meta, *params)
+        scale = c.d_model ** -0.5 if stack.is_decoder else 1.0
+        return _FinalNormFn.apply(x, stack.final_layer_norm.weight, c.layer_norm_epsilon, p, _next_seed(), scale)
+
+    def encode(self, input_ids, attention_mask=None):
+        """(encoder output [B, Se, D], keep uint8 [B, Se])"""
+        self._check(input_ids, MAX_ENCODER_LEN, "encoder")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        keep = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous()
+        return self._stack(self.encoder, input_ids, keep), keep
+
+    def decode(self, decoder_input_ids, enc, keep, shared=None):
+        """the decoder's output rows, already scaled by d_model ** -0.5: [B, T, D]"""
+        self._check(decoder_input_ids, MAX_DECODER_LEN, "decoder")
+        return self._stack(self.decoder, decoder_input_ids, keep, enc, shared)
+
+    def logits(self, dec_out: torch.Tensor) -> torch.Tensor:
+        """the materialised logits [B, T, V] of decoder rows (no gradient: tests and decoding)"""
+        B, T, D = dec_out.shape
+        V = self.shared.weight.shape[0]
+        out = torch.empty(B * T, V, **_f32(dec_out.device))
+        with ops.f32_matmul("f32"):
+            ops.linear_fwd(dec_out.detach().reshape(B * T, D).contiguous(), D, self.shared.weight.detach(), D, out, V, B * T, V, D)
+        return out.view(B, T, V)
+
+    def forward(self, input_ids, attention_mask=None, labels=None, decoder_input_ids=None, want_logits=None, **kwargs):
+        """(loss, logits).  With labels the loss is the mean over the positions with label != -100 of CE(logits / temperature); the
+        logits are formed only without labels or with ``want_logits=True`` (default: formed when no gradient is recorded)."""
+        for name in ("head_mask", "decoder_head_mask", "cross_attn_head_mask", "inputs_embeds", "decoder_inputs_embeds",
+                     "output_attentions", "output_hidden_states", "past_key_values", "encoder_outputs", "decoder_attention_mask"):
+            if kwargs.pop(name, None) not in (None, False):
+                raise NotImplementedError(f"TIGER on the HIP path: {name} is not supported")
+        kwargs.pop("split", None), kwargs.pop("use_cache", None), kwargs.pop("return_dict", None), kwargs.pop("cache_position", None)
+        if kwargs:
+            raise TypeError(f"TIGER.forward: unexpected arguments {sorted(kwargs)}")
+        if labels is not None and decoder_input_ids is None:
+            decoder_input_ids = self._shift_right(labels.to(input_ids.device))
+        if decoder_input_ids is None:
+            raise ValueError("You have to specify either decoder_input_ids or labels")
+        train = labels is not None and torch.is_grad_enabled()
+        shared = _SharedGrad(gathers=2) if train and self.shared.weight.requires_grad else None
+        # (the encoder's gather is the other user of the table's gradient buffer: it gets the same hand-over object)
+        self._check(input_ids, MAX_ENCODER_LEN, "encoder")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        keep = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous()
+        enc = self._stack(self.encoder, input_ids, keep, shared=shared)
+        out = self.decode(decoder_input_ids.to(input_ids.device), enc, keep, shared)
+        loss = None
+        if labels is not None:
+            flat = labels.to(input_ids.device).long().flatten()
+            rows = (flat != -100).nonzero()[:, 0].contiguous()
+            if rows.numel() == 0:
+                loss = out.sum() * 0.0 + float("nan")                           # CrossEntropyLoss over no rows
+            else:
+                loss = CatalogCEFn.apply(out * (1.0 / self.temperature), rows, self.shared.weight, flat[rows].contiguous(), shared)
+        if want_logits is None:
+            want_logits = not train
+        return loss, (self.logits(out) if want_logits else None)
+
+
+# ---- decoding ----------------------------------------------------------------------------------------------------------------------
+class _DecoderEval:
+    """The decoder without autograd for beam search: the concatenated weights once per search, the cross-attention keys / values
+    once per USER and layer; a beam row reads its user's copy through the attention kernel's row map."""
+
+    def __init__(self, model: "TIGER", enc: torch.Tensor, keep: torch.Tensor):
+        c = model.config
+        self.model, self.keep, self.users, self.Se = model, keep, enc.shape[0], enc.shape[1]
+        ef = enc.reshape(-1, c.d_model).contiguous()
+        self.layers = []
+        with ops.f32_matmul("f32"):
+            for blk in model.decoder.block:
+                a, e, ff = blk.layer[0], blk.layer[1], blk.layer[2]
+                cat = lambda *ws: torch.cat([w.weight.detach() for w in ws], 0).contiguous()
+                self.layers.append(dict(
+                    ln0=a.layer_norm.weight.detach(), wqkv=cat(a.SelfAttention.q, a.SelfAttention.k, a.SelfAttention.v),
+                    wo=a.SelfAttention.o.weight.detach(), ln1=e.layer_norm.weight.detach(), cq=e.EncDecAttention.q.weight.detach(),
+                    kv=_linear(ef, cat(e.EncDecAttention.k, e.EncDecAttention.v)), co=e.EncDecAttention.o.weight.detach(),
+                    lnf=ff.layer_norm.weight.detach(), wi=ff.DenseReluDense.wi.weight.detach(), wff=ff.DenseReluDense.wo.weight.detach()))
+
+    @ops.scoped_f32_matmul(lambda *a: "f32")
+    def last_rows(self, ids: torch.Tensor, kv_rows: torch.Tensor) -> torch.Tensor:
+        """the decoder output at the last position of ids [N, S], scaled for the tied head: [N, D]; kv_rows int32 [N]: the user"""
+        m, c = self.model, self.model.config
+        N, S = ids.shape
+        h, d, eps, dev = c.num_heads, c.d_kv, c.layer_norm_epsilon, ids.device
+        I = h * d
+        x = torch.empty(N * S, c.d_model, **_f32(dev))
+        ops.embedding_fwd(ids.contiguous(), m.shared.weight.detach(), x)
+        table = m.decoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
+        rel = _BiasStack(table, m._bucket(S, False, dev), S, len(self.layers)).rel
+        lse = torch.empty(N, h, S, **_f32(dev))
+        relu = ops.ACTIVATIONS["relu"]
+        for L in self.layers:
+            qkv = _linear(_rms(x, L["ln0"], eps), L["wqkv"])
+            c0 = torch.empty(N * S, I, **_f32(dev))
+            ops.t5_attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], rel, None, N, S, S, h, d, True, 0.0, 0, c0, lse)
+            x = _add_dropout(x, _linear(c0, L["wo"]), 0.0, 0)
+            q1 = _linear(_rms(x, L["ln1"], eps), L["cq"])
+            c1 = torch.empty(N * S, I, **_f32(dev))
+            ops.t5_attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
+                            kv_rows=kv_rows, kv_batch=self.users)
+            x = _add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
+            pre = _linear(_rms(x, L["lnf"], eps), L["wi"])
+            act = torch.empty_like(pre)
+            ops.bias_act_fwd(pre, m._zero_bias, relu, act)
+            x = _add_dropout(x, _linear(act, L["wff"]), 0.0, 0)
+        last = x.view(N, S, -1)[:, -1, :].contiguous()
+        return _rms(last, m.decoder.final_layer_norm.weight.detach(), eps) * (c.d_model ** -0.5)
+
+
+@torch.no_grad()
+def beam_search(model: TIGER, input_ids, attention_mask, trie, num_beams: int, max_new_tokens: int, decoder_prefix=None):
+    """Trie-constrained beam search as ``generate(..., num_beams=k, num_return_sequences=k, prefix_allowed_tokens_fn=...,
+    early_stopping=True)`` runs it for ref:SeqRec/tasks/test_decoder.py and test_SMB_decoder.py.  ``trie``: a decode.ItemTrie over
+    the full decoder sequences ([decoder_start] + ...), every one of them ``len(prefix) + max_new_tokens`` tokens long (so all
+    hypotheses end at the same step, with </s> when the trie holds it).  ``decoder_prefix``: int64 [P] or [B, P], default
+    [decoder_start_token_id].  Returns (sequences [B num_beams, P + max_new_tokens], sequences_scores [B num_beams]), the beams of
+    user b at rows b num_beams .., best first; score = sum of log-probabilities / max_new_tokens (length_penalty 1 over the
+    generated tokens).  The encoder and the cross-attention keys / values run once per user; a beam row reads its user's copy
+    (row -> user map of gamer_t5_attn_fwd).  The decoder re-runs its at most 8 tokens every step: no self-attention cache."""
+    dev = input_ids.device
+    c = model.config
+    B = input_ids.shape[0]
+    nb, K = num_beams, 2 * num_beams
+    N = B * nb
+    V = model.shared.weight.shape[0]
+    if decoder_prefix is None:
+        decoder_prefix = torch.full((B, 1), c.decoder_start_token_id, dtype=torch.int64)
+    prefix = torch.as_tensor(decoder_prefix, dtype=torch.int64).to(dev)
+    if prefix.dim() == 1:
+        prefix = prefix[None, :].expand(B, -1)
+    prefix = prefix.contiguous()
+    P = prefix.shape[1]
+    if P < 1 or P + max_new_tokens - 1 > MAX_DECODER_LEN:
+        raise NotImplementedError(f"tiger.beam_search: 1 <= prefix and prefix + new tokens <= {MAX_DECODER_LEN + 1}")
+    was_training = model.training
+    model.eval()
+    try:
+        enc, keep = model.encode(input_ids, attention_mask)
+        dec = _DecoderEval(model, enc, keep)
+        seqs = prefix[:, None, :].expand(B, nb, P).contiguous()
+        run_scores = torch.zeros(B, nb, device=dev)
+        run_scores[:, 1:] = -1e9                                                  # only beam 0 is live at the first step (HF)
+        node = torch.zeros(N, dtype=torch.int32, device=dev)
+        nxt = torch.empty_like(node)
+        for t in range(P):
+            ops.trie_advance(node, prefix[:, t].repeat_interleave(nb).contiguous(), trie.child_start, trie.child_tok, trie.child_node, nxt)
+            node, nxt = nxt.clone(), nxt
+        scores = torch.empty(N, V, device=dev)
+        users = torch.arange(B, device=dev, dtype=torch.int32)
+        beam_user = users.repeat_interleave(nb).contiguous()
+        E = model.shared.weight.detach()
+        final = None
+        for step in range(max_new_tokens):
+            cur = P + step
+            if step == 0:                                                         # every beam of a user holds the same prefix
+                last, rows = dec.last_rows(prefix, users), beam_user
+            else:
+                last, rows = dec.last_rows(seqs.reshape(N, cur), beam_user), torch.arange(N, device=dev, dtype=torch.int32)
+            logits2d = torch.empty(last.shape[0], V, **_f32(dev))
+            with ops.f32_matmul("f32"):
+                ops.linear_fwd(last, last.shape[1], E, E.shape[1], logits2d, V, last.shape[0], V, E.shape[1])
+            ops.trie_logprobs(logits2d, rows, run_scores.reshape(N).contiguous(), node, trie.child_start, trie.child_tok, V, scores)
+            top_s, top_i = torch.topk(scores.view(B, nb * V), K)
+            beam_i, tok = top_i // V, top_i % V
+            cand = torch.cat([torch.gather(seqs, 1, beam_i[:, :, None].expand(B, K, cur)), tok[:, :, None]], 2)
+            if step == max_new_tokens - 1:
+                final = (cand[:, :nb].reshape(N, cur + 1), (top_s[:, :nb] / max_new_tokens).reshape(N))
+                break
+            seqs = cand[:, :nb].contiguous()
+            run_scores = top_s[:, :nb].contiguous()
+            parent = (beam_i[:, :nb] + torch.arange(B, device=dev)[:, None] * nb).reshape(N)
+            ops.trie_advance(node[parent].contiguous(), tok[:, :nb].reshape(N).contiguous(), trie.child_start, trie.child_tok,
+                             trie.child_node, nxt)
+            node, nxt = nxt.clone(), nxt
+        return final
+    finally:
+        model.train(was_training)

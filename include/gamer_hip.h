@@ -1066,6 +1066,32 @@ int gamer_wass_table_fwd(const float* Em, const float* Ec, int V, int H, float* 
 int gamer_wass_table_bwd(const float* Em, const float* Ec, const float* dE2, const float* dc, int V, int H, float* dEm, float* dEc,
                          void* stream);
 
+/* ---- T5's attention (TIGER; csrc/t5_attention.hip) --------------------------------------------------------------------------------
+ * score[i, j] = q_i . k_j + rel[head][j - i + Sq - 1] (NO 1 / sqrt(d) scale; rel NULL: no bias), softmax over the allowed keys,
+ * dropout (p_drop, seed: the counter hash on element ((b H + head) Sq + i) Sk + j), context.  q [B Sq, ldq], k / v [B Sk, ld*],
+ * o [B Sq, ldo]: head h at column h head_dim (column blocks of one q|k|v GEMM output); bases 16-byte aligned, leading dimensions
+ * multiples of 4.  keep: bytes [B][Sk], non-zero = the key may be attended (NULL: all); causal: key j <= query i.  lse [B][H][Sq]
+ * receives the log-sum-exp of every row.  A row with no allowed key gives a zero context, lse = -inf and zero gradients.
+ * kv_rows (forward only; NULL: row b): int32 [B], row b attends k / v / keep of row kv_rows[b] - the beams of one user share the
+ * user's one copy of the cross-attention keys and values (values in [0, rows of k): checked by the caller).
+ * Limits (refused before any launch): Sq, Sk <= 128, head_dim 32 or 64, H <= 16. */
+int gamer_t5_attn_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel, const uint8_t* keep,
+                      const int32_t* kv_rows, int B, int Sq, int Sk, int H, int head_dim, int causal, float p_drop, uint64_t seed,
+                      float* o, int ldo, float* lse, void* stream);
+/* d_o [B Sq, ldo]; the forward's output is not read (the softmax backward's row term is summed from the probabilities and dP).
+ * dq / dk / dv are written in full.  drel_partial [n_slab][H][Sq + Sk - 1] (NULL iff rel is NULL): workgroup (slab, head) walks the
+ * rows slab, slab + n_slab, ... and writes its slab alone (no float atomics; 1 <= n_slab <= B so that every slab is written). */
+int gamer_t5_attn_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel, const uint8_t* keep,
+                      int B, int Sq, int Sk, int H, int head_dim, int causal, float p_drop, uint64_t seed, const float* d_o,
+                      int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, float* drel_partial,
+                      int n_slab, void* stream);
+/* rel [H][n_offsets] = table [num_buckets][H] at bucket[offset] (the bucket of every relative offset is computed on the host) */
+int gamer_t5_bias_expand(const float* table, const int32_t* bucket, int num_buckets, int H, int n_offsets, float* rel, void* stream);
+/* dtable [num_buckets][H] from drel_partial [n_layers][n_slab][H][n_offsets]: per layer the slabs in order and the offsets of a bucket
+ * in a fixed order, then the layers in order (one table serves every layer of its stack) */
+int gamer_t5_bias_fold(const float* drel_partial, int n_layers, int n_slab, int H, int n_offsets, const int32_t* bucket, int num_buckets,
+                       float* dtable, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

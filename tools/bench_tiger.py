@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""TIGER on one GPU: train step, one layer's attention against a torch composition, and beam search.
+
+  * train step (forward with labels + backward) of the shipped config (d_model 128, 6 heads of 64, 4 + 4 layers, d_ff 1024,
+    dropout 0.1, the T5 vocabulary of 32,128 rows) at batch ``--batch`` x encoder length ``--enc`` with 5 decoder tokens on random
+    ids (full-length rows): time, sequences/s, peak allocated memory;
+  * one layer's self attention at the encoder's shape and one cross attention (5 queries), forward + backward with every gradient
+    (the bias table's included): gamer_t5_attn_fwd / _bwd + gamer_t5_bias_expand / _fold against a torch composition written here,
+    which forms the [B, h, S, S] scores, probabilities and dropout mask and lets autograd differentiate them; time and peak
+    allocated memory of each, and which one is slower;
+  * trie-constrained beam search at ``--users`` users x ``--beams`` beams over ``--items`` random items of 4 tokens: users/s.
+Medians of ``--steps`` device-event timings after ``--warmup``.  Prints one JSON line per (batch, encoder length).
+
+  python tools/bench_tiger.py --batch 256,1024 --enc 81,101 --steps 8 --warmup 3
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from gamer_amd import ops, tiger  # noqa: E402
+from gamer_amd.decode import ItemTrie  # noqa: E402
+
+DEV = "cuda:0"
+SHIPPED = dict(d_model=128, d_kv=64, d_ff=1024, num_layers=4, num_decoder_layers=4, num_heads=6, dropout_rate=0.1, vocab_size=32128)
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def peak(fn):
+    fn()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2**20
+
+
+def attention_pair(B, Sq, Sk, h, d, bias, p, g):
+    """(fused, composition): the same attention both ways, every gradient produced"""
+    I, R = h * d, Sq + Sk - 1
+    rnd = lambda *s: (torch.randn(*s, generator=g) * 0.3).to(DEV)
+    q, k, v, d_o = rnd(B * Sq, I), rnd(B * Sk, I), rnd(B * Sk, I), rnd(B * Sq, I)
+    table = rnd(32, h) if bias else None
+    bucket = tiger.bucket_vector(Sq, True, 32, 128).to(DEV) if bias else None
+    keep = torch.ones(B, Sk, dtype=torch.uint8, device=DEV)
+    keep[:, Sk - 3:] = 0
+    o, lse = torch.empty(B * Sq, I, device=DEV), torch.empty(B, h, Sq, device=DEV)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+
+    def fused():
+        rel = slabs = None
+        if bias:
+            rel = torch.empty(h, R, device=DEV)
+            ops.t5_bias_expand(table, bucket, rel)
+            slabs = torch.empty(1, ops.t5_n_slab(B, h), h, R, device=DEV)
+        ops.t5_attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, False, p, 7, o, lse)
+        ops.t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, False, p, 7, d_o, lse, dq, dk, dv, None if slabs is None else slabs[0])
+        if bias:
+            ops.t5_bias_fold(slabs, bucket, torch.empty(32, h, device=DEV))
+
+    heads = lambda x, S: x.view(B, S, h, d).permute(0, 2, 1, 3)
+    i, j = torch.arange(Sq, device=DEV)[:, None], torch.arange(Sk, device=DEV)[None, :]
+
+    def composition():
+        ql, kl, vl = (t.detach().requires_grad_(True) for t in (q, k, v))
+        s = heads(ql, Sq) @ heads(kl, Sk).transpose(-1, -2)
+        tl = None
+        if bias:
+            tl = table.detach().requires_grad_(True)
+            s = s + tl[bucket.long()].t()[:, j - i + Sq - 1][None]
+        s = s + (1.0 - keep.float())[:, None, None, :] * torch.finfo(torch.float32).min
+        pr = torch.nn.functional.dropout(torch.softmax(s, -1), p, True)
+        out = (pr @ heads(vl, Sk)).permute(0, 2, 1, 3).reshape(B * Sq, I)
+        out.backward(d_o)
+    return fused, composition
+
+
+def bench_attention(B, Sq, Sk, bias, a, g):
+    fused, comp = attention_pair(B, Sq, Sk, 6, 64, bias, 0.1, g)
+    r = dict(fused_ms=timed(fused, a.steps, a.warmup), fused_mib=peak(fused), torch_ms=timed(comp, a.steps, a.warmup), torch_mib=peak(comp))
+    r["fused_slower"] = r["fused_ms"] > r["torch_ms"]
+    return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()}
+
+
+def bench_step(B, S, a, g):
+    torch.manual_seed(0)
+    m = tiger.TIGER(tiger.TigerConfig(**SHIPPED)).to(DEV)
+    m.train()
+    ids = torch.randint(2, SHIPPED["vocab_size"], (B, S), generator=g).to(DEV)
+    labels = torch.randint(2, SHIPPED["vocab_size"], (B, 5), generator=g).to(DEV)
+    am = torch.ones_like(ids)
+
+    def step():
+        for p in m.parameters():
+            p.grad = None
+        loss, _ = m(ids, am, labels=labels)
+        loss.backward()
+    ms = timed(step, a.steps, a.warmup)
+    return dict(step_ms=round(ms, 3), sequences_per_s=round(B / ms * 1e3, 1), peak_mib=round(peak(step), 1))
+
+
+def bench_beams(S, a, g):
+    torch.manual_seed(0)
+    m = tiger.TIGER(tiger.TigerConfig(**SHIPPED)).to(DEV)
+    V = SHIPPED["vocab_size"]
+    items = set()
+    while len(items) < a.items:
+        items.add(tuple(100 + 256 * c + int(torch.randint(0, 256, (1,), generator=g)) for c in range(4)))
+    trie = ItemTrie([[0] + list(it) + [1] for it in sorted(items)], device=DEV, pad_token_id=0)
+    ids = torch.randint(2, V, (a.users, S), generator=g).to(DEV)
+    am = torch.ones_like(ids)
+    ms = timed(lambda: tiger.beam_search(m, ids, am, trie, a.beams, 5), max(2, a.steps // 2), 1)
+    return dict(beam_ms=round(ms, 2), users_per_s=round(a.users / ms * 1e3, 1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", default="256,1024")
+    ap.add_argument("--enc", default="81,101")
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--users", type=int, default=256)
+    ap.add_argument("--beams", type=int, default=20)
+    ap.add_argument("--items", type=int, default=10000)
+    a = ap.parse_args()
+    g = torch.Generator().manual_seed(0)
+    for S in (int(x) for x in a.enc.split(",")):
+        beams = bench_beams(S, a, g)
+        for B in (int(x) for x in a.batch.split(",")):
+            out = dict(batch=B, enc=S, dec=5, **bench_step(B, S, a, g))
+            out["self_attention"] = bench_attention(B, S, S, True, a, g)
+            out["cross_attention"] = bench_attention(B, 5, S, False, a, g)
+            out["beam_search"] = dict(users=a.users, beams=a.beams, items=a.items, **beams)
+            print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
