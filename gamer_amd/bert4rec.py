@@ -40,7 +40,7 @@ from torch import nn
 
 from . import modules, ops
 from .rec_common import (ClozeMixin, DotProductPredictionHead, DropUnknownConfig, InputBlockFn, _next_seed, layernorm_bwd,
-                         linear_act_bwd)
+                         linear_act_bwd, linear_act_fwd)
 
 
 @dataclasses.dataclass(init=False)
@@ -70,15 +70,11 @@ class _OutputChainFn(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=x.device)
         xg = x.reshape(-1, H)[rows].contiguous()
         M = xg.shape[0]
-        pre1, a1 = torch.empty(M, H, **f32), torch.empty(M, H, **f32)
-        ops.linear_fwd(xg, H, w1, H, pre1, H, M, H, H)
-        ops.bias_act_fwd(pre1, b1, ops.ACTIVATIONS["gelu"], a1)
+        pre1, a1 = linear_act_fwd(xg, w1, b1, ops.ACTIVATIONS["gelu"])
         y1 = torch.empty(M, H, **f32)
         mean, rstd = torch.empty(M, **f32), torch.empty(M, **f32)
         ops.layernorm_fwd(a1, None, lnw, lnb, eps, None, y1, mean, rstd)
-        pre2, out = torch.empty(M, H, **f32), torch.empty(M, H, **f32)
-        ops.linear_fwd(y1, H, w2, H, pre2, H, M, H, H)
-        ops.bias_act_fwd(pre2, b2, ops.ACTIVATIONS["relu"], out)
+        pre2, out = linear_act_fwd(y1, w2, b2, ops.ACTIVATIONS["relu"])
         ctx.save_for_backward(xg, rows, w1, pre1, a1, lnw, mean, rstd, y1, w2, pre2)
         ctx.x_shape = x.shape
         return out

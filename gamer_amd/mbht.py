@@ -58,8 +58,9 @@ import torch
 from torch import nn
 
 from . import modules, ops
-from .rec_common import (CatalogCEFn, ClozeMixin, DropUnknownConfig, _SharedGrad, _dropout_bwd, _next_seed, colsum, layernorm_bwd,
-                         linear_act_bwd)
+from .layer_blocks import (_dropout_bwd, attn_block_bwd, attn_block_fwd, colsum, dense_core, dropout_fwd, ffn_bwd, ffn_fwd,
+                           layernorm_bwd, linear_act_bwd, linear_act_fwd)
+from .rec_common import CatalogCEFn, ClozeMixin, DropUnknownConfig, _GatherRowsFn, _SharedGrad, _next_seed
 
 
 @dataclasses.dataclass(init=False)
@@ -137,44 +138,6 @@ class HGNN(nn.Module):
         self.hgc2 = HGNN_conv(n_hid)
 
 
-# ---- one post-LN attention block, y = LayerNorm(x + dropout(dense(core(x Wqkv^T + bqkv)))) ---------------------------------------
-def _attn_block_fwd(xf, wqkv, bqkv, wd, bd, lnw, lnb, eps, p, seed, core):
-    """``core(qkv [T, 3 H], ctx [T, H])`` fills the context and returns what its backward needs.  Returns (y, saved)."""
-    T, H = xf.shape
-    f32 = dict(dtype=torch.float32, device=xf.device)
-    qkv = torch.empty(T, 3 * H, **f32)
-    ops.linear_fwd(xf, H, wqkv, H, qkv, 3 * H, T, 3 * H, H)
-    ops.bias_act_fwd(qkv, bqkv, 0)
-    ctxv = torch.empty(T, H, **f32)
-    kept = core(qkv, ctxv)
-    h = torch.empty(T, H, **f32)
-    ops.linear_fwd(ctxv, H, wd, H, h, H, T, H, H)
-    ops.bias_act_fwd(h, bd, 0)
-    v = torch.empty(T, H, **f32)
-    ops.residual_dropout_fwd(xf, h, p, seed, None, v)
-    y = torch.empty(T, H, **f32)
-    mean, rstd = torch.empty(T, **f32), torch.empty(T, **f32)
-    ops.layernorm_fwd(v, None, lnw, lnb, eps, None, y, mean, rstd)
-    return y, (xf, wqkv, qkv, ctxv, wd, v, mean, rstd, lnw, kept, y)
-
-
-def _attn_block_bwd(dy, saved, p, seed, core_bwd):
-    """``core_bwd(qkv, ctx, dctx, dqkv, kept)`` fills dqkv [T, 3 H] and returns its own parameter gradients.  Returns
-    (dx, dwqkv, dbqkv, dwd, dbd, dlnw, dlnb, core's)."""
-    xf, wqkv, qkv, ctxv, wd, v, mean, rstd, lnw, kept, _ = saved
-    T, H = xf.shape
-    f32 = dict(dtype=torch.float32, device=xf.device)
-    dv, dlnw, dlnb = layernorm_bwd(v, lnw, mean, rstd, dy)
-    dh = torch.empty(T, H, **f32)
-    ops.residual_dropout_bwd(dv, p, seed, dh)                                    # dv stays = d x (residual branch)
-    dctx, dwd, dbd = linear_act_bwd(dh, None, ctxv, wd, 0)
-    dqkv = torch.empty(T, 3 * H, **f32)
-    extra = core_bwd(qkv, ctxv, dctx, dqkv, kept)
-    dxq, dwqkv, dbqkv = linear_act_bwd(dqkv, None, xf, wqkv, 0)
-    dv += dxq
-    return dv, dwqkv, dbqkv, dwd, dbd, dlnw, dlnb, extra
-
-
 class _MSLayerFn(torch.autograd.Function):
     """One MultiScaleTransformerEncoderLayer with multiscale=True.  params: out_fc (w, b); attention1: E (w, b), F (w, b), W_Q, W_K,
     W_V, dense (w, b each), LayerNorm (w, b); attention2: query, key, value, dense (w, b each), LayerNorm (w, b); dense_1, dense_2
@@ -188,7 +151,7 @@ class _MSLayerFn(torch.autograd.Function):
         (wo, bo, Ew, Eb, Fw, Fb, wq1, bq1, wk1, bk1, wv1, bv1, wd1, bd1, l1w, l1b,
          wq2, bq2, wk2, bk2, wv2, bv2, wd2, bd2, l2w, l2b, w1, b1, w2, b2) = params
         B, L, H = x.shape
-        h, dff, act, eps, (s1, s2) = meta["heads"], meta["dff"], meta["act"], meta["eps"], meta["scales"]
+        h, act, eps, (s1, s2) = meta["heads"], meta["act"], meta["eps"], meta["scales"]
         p = meta["dropout"] if meta["training"] else 0.0
         d = H // h
         f32 = dict(dtype=torch.float32, device=x.device)
@@ -201,34 +164,22 @@ class _MSLayerFn(torch.autograd.Function):
             lse = torch.empty(B, h, L, **f32)
             ops.msa_linear_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], keep, Ew, Eb, Fw, Fb, B, L, h, d, scale, p, seeds[0], ctxv, lse)
             return lse
-
-        def dense_core(S, seed):
-            def core(qkv, ctxv):
-                lse = torch.empty(B, h, S, **f32)
-                ops.attn_dense_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], None, B, S, h, d, scale, p, seed, ctxv, lse)
-                return lse
-            return core
         wqkv1, bqkv1 = torch.cat([wq1, wk1, wv1], 0).contiguous(), torch.cat([bq1, bk1, bv1], 0).contiguous()
         wqkv2, bqkv2 = torch.cat([wq2, wk2, wv2], 0).contiguous(), torch.cat([bq2, bk2, bv2], 0).contiguous()
-        y1, sv1 = _attn_block_fwd(xf, wqkv1, bqkv1, wd1.contiguous(), bd1, l1w, l1b, eps, p, seeds[1], linear_core)
+        y1, sv1 = attn_block_fwd(xf, wqkv1, bqkv1, wd1.contiguous(), bd1, l1w, l1b, eps, p, seeds[1], linear_core)
         ys, svs = [y1.view(B, L, H)], [sv1]
         for i, s in enumerate((s1, s2)):
             S = L // s
             xp = x.view(B, s, S, H).mean(1).reshape(B * S, H).contiguous()       # row j averages positions j, j + L / s, ...
-            y, sv = _attn_block_fwd(xp, wqkv2, bqkv2, wd2.contiguous(), bd2, l2w, l2b, eps, p, seeds[3 + 2 * i], dense_core(S, seeds[2 + 2 * i]))
+            core, _ = dense_core(None, B, S, h, d, scale, p, seeds[2 + 2 * i])
+            y, sv = attn_block_fwd(xp, wqkv2, bqkv2, wd2.contiguous(), bd2, l2w, l2b, eps, p, seeds[3 + 2 * i], core)
             ys.append(y.view(B, S, H))
             svs.append(sv)
         wo_ = wo.contiguous()
         m = torch.empty(B, L, H, **f32)
         ops.seq_mix_fwd(ys, wo_, bo, m)
-        T = B * L
-        mf = m.view(T, H)
-        pre1, a1 = torch.empty(T, dff, **f32), torch.empty(T, dff, **f32)
-        ops.linear_fwd(mf, H, w1, H, pre1, dff, T, dff, H)
-        ops.bias_act_fwd(pre1, b1, act, a1)
-        f2 = torch.empty(T, H, **f32)
-        ops.linear_fwd(a1, dff, w2, dff, f2, H, T, H, dff)
-        ops.bias_act_fwd(f2, b2, 0)
+        mf = m.view(B * L, H)
+        f2, (_, pre1, a1) = ffn_fwd(mf, w1, b1, w2, b2, act)
         ctx.meta = dict(meta, p=p, seeds=seeds, scale=scale, shape=(B, L, H))
         flat = []
         for sv in svs:
@@ -249,8 +200,7 @@ class _MSLayerFn(torch.autograd.Function):
         c = Ew.shape[0]
         f32 = dict(dtype=torch.float32, device=mf.device)
         g = dout.reshape(T, H).contiguous().float().clone()
-        da1, dw2, db2 = linear_act_bwd(g, None, a1, w2, 0)
-        dm, dw1, db1 = linear_act_bwd(da1, pre1, mf, w1, act)
+        dm, dw1, db1, dw2, db2 = ffn_bwd(g, (mf, pre1, a1), w1, w2, act)
         # out_fc
         lens = [L, L // s1, L // s2]
         youts = [sv[10].view(B, n, H) for sv, n in zip(svs, lens)]
@@ -269,19 +219,14 @@ class _MSLayerFn(torch.autograd.Function):
             s = colsum(pt)
             return (s[:c * L].view(c, L), s[2 * c * L:2 * c * L + c].clone(), s[c * L:2 * c * L].view(c, L).clone(),
                     s[2 * c * L + c:].clone())
-
-        def dense_core_bwd(S, seed):
-            def core(qkv, ctxv, dctx, dqkv, lse):
-                ops.attn_dense_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], None, B, S, h, d, scale, p, seed, ctxv, dctx, lse,
-                                   dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:])
-            return core
-        dx, dwqkv1, dbqkv1, dwd1, dbd1, dl1w, dl1b, (dEw, dEb, dFw, dFb) = _attn_block_bwd(
+        dx, dwqkv1, dbqkv1, dwd1, dbd1, dl1w, dl1b, (dEw, dEb, dFw, dFb) = attn_block_bwd(
             dys[0].view(T, H), svs[0], p, seeds[1], linear_core_bwd)
         dx = dx.view(B, L, H)
         acc2 = None
         for i, s in enumerate((s1, s2)):
             S = L // s
-            r = _attn_block_bwd(dys[1 + i].view(B * S, H), svs[1 + i], p, seeds[3 + 2 * i], dense_core_bwd(S, seeds[2 + 2 * i]))
+            _, core_bwd = dense_core(None, B, S, h, d, scale, p, seeds[2 + 2 * i])
+            r = attn_block_bwd(dys[1 + i].view(B * S, H), svs[1 + i], p, seeds[3 + 2 * i], core_bwd)
             dx.view(B, s, S, H).add_(r[0].view(B, 1, S, H) / s)                  # the strided mean's backward
             acc2 = list(r[1:7]) if acc2 is None else [a + b for a, b in zip(acc2, r[1:7])]
         dwqkv2, dbqkv2, dwd2, dbd2, dl2w, dl2b = acc2
@@ -302,8 +247,8 @@ class MultiScaleTransformerEncoderLayer(nn.Module):
         """``keep``: int32 [B, L], non-zero where the position holds an item (the reference's 0 / 1 attention mask)."""
         a, f = self.multi_head_attention, self.feed_forward
         a1, a2 = a.attention1, a.attention2
-        meta = dict(heads=a.num_heads, dff=f.dense_1.out_features, act=f.act_code, dropout=self.dropout_p, eps=self.eps,
-                    training=self.training, scales=(a.scale_1, a.scale_2))
+        meta = dict(heads=a.num_heads, act=f.act_code, dropout=self.dropout_p, eps=self.eps, training=self.training,
+                    scales=(a.scale_1, a.scale_2))
         params = [a.out_fc.weight, a.out_fc.bias, a1.E.weight, a1.E.bias, a1.F.weight, a1.F.bias]
         for m in (a1.W_Q, a1.W_K, a1.W_V, a1.dense, a1.LayerNorm, a2.query, a2.key, a2.value, a2.dense, a2.LayerNorm, f.dense_1, f.dense_2):
             params += [m.weight, m.bias]
@@ -326,10 +271,7 @@ class _InputFn(torch.autograd.Function):
         y = torch.empty(B * L, H, **f32)
         mean, rstd = torch.empty(B * L, **f32), torch.empty(B * L, **f32)
         ops.layernorm_fwd(v, None, w, b, eps, None, y, mean, rstd)
-        if p > 0:
-            out = torch.zeros_like(y)
-            ops.residual_dropout_fwd(out, y, p, seed)              # out = 0 + drop(y)
-            y = out
+        y = dropout_fwd(y, p, seed)
         ctx.meta = (p, seed, E.shape, P.shape, T.shape)
         ctx.shared = shared
         ctx.save_for_backward(ids, types, v, w, mean, rstd)
@@ -370,9 +312,7 @@ class _HGFn(torch.autograd.Function):
         sig = ops.ACTIVATIONS["sigmoid"]
         ef = e.reshape(T, H).contiguous().float()
         gwT = gw.t().contiguous()
-        z, sg = torch.empty(T, H, **f32), torch.empty(T, H, **f32)
-        ops.linear_fwd(ef, H, gwT, H, z, H, T, H, H)
-        ops.bias_act_fwd(z, gb.reshape(H).contiguous(), sig, sg)                  # z <- e Wg + bg, sg = sigmoid(z)
+        z, sg = linear_act_fwd(ef, gwT, gb.reshape(H).contiguous(), sig)          # z = e Wg + bg, sg = sigmoid(z)
         x_raw = ef * sg
         ms = (0.5 * (w1 + w2)).reshape(1, H)
         xm = (x_raw * ms).view(B, L, H)
@@ -381,16 +321,10 @@ class _HGFn(torch.autograd.Function):
 
         def layer(x, W, b, seed):
             WT = W.t().contiguous()
-            t = torch.empty(T, H, **f32)
-            ops.linear_fwd(x, H, WT, H, t, H, T, H, H)
-            ops.bias_act_fwd(t, b, 0)
+            _, t = linear_act_fwd(x, WT, b, 0)
             y = torch.empty(B, L, H, **f32)
             ops.hg_conv_fwd(G, t.view(B, L, H), y)
-            if p > 0:
-                out = torch.zeros(T, H, **f32)
-                ops.residual_dropout_fwd(out, y.view(T, H), p, seed)          # out = 0 + drop(y)
-                return WT, t, out
-            return WT, t, y.view(T, H)
+            return WT, t, dropout_fwd(y.view(T, H), p, seed)
         W1T, t1, x1 = layer(x_raw, W1, b1, seeds[0])
         W2T, t2, x2 = layer(x1, W2, b2, seeds[1])
         hg = ((x1 + x2) / 2).view(B, L, H)
@@ -441,29 +375,6 @@ class _HGFn(torch.autograd.Function):
         de += dex
         return (dtrm.view(B, L, H), de.view(B, L, H), None, None, None, None, dgwT.t(), dgb.view(1, H), dms, dms.clone(), dW1, db1,
                 dW2, db2, dA, da)
-
-
-class _GatherRowsFn(torch.autograd.Function):
-    """x.view(-1, H)[rows] for rows that may repeat (the padded slots of masked_index all point at position 0); the backward adds
-    the repeats in slot order (gamer_embedding_bwd_large: no float atomics)."""
-
-    @staticmethod
-    def forward(ctx, x, rows):
-        H = x.shape[-1]
-        xf = x.reshape(-1, H).contiguous().float()
-        y = torch.empty(rows.numel(), H, dtype=torch.float32, device=x.device)
-        ops.embedding_fwd(rows, xf, y)
-        ctx.save_for_backward(rows)
-        ctx.x_shape = x.shape
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        rows, = ctx.saved_tensors
-        H = ctx.x_shape[-1]
-        dx = torch.zeros(ctx.x_shape, dtype=torch.float32, device=dy.device)
-        ops.embedding_bwd_large(rows, dy.contiguous().float(), -1, dx.view(-1, H))
-        return dx, None
 
 
 class MBHT(ClozeMixin, nn.Module):

@@ -41,8 +41,9 @@ import torch
 from torch import nn
 
 from . import modules, ops
-from .rec_common import (ClozeMixin, DotProductPredictionHead, DropUnknownConfig, EmbedDropoutFn, GatherLinearFn, _next_seed,
-                         colsum, layernorm_bwd)
+from .layer_blocks import (_TypeLists, _aug_weights, _with_ones, colsum, grouped_ffn_bwd, grouped_ffn_fwd, layernorm_bwd,
+                           post_ln_bwd, post_ln_fwd, split_aug_grads)
+from .rec_common import ClozeMixin, DotProductPredictionHead, DropUnknownConfig, EmbedDropoutFn, GatherLinearFn, _next_seed
 
 _REF_FFN_ERROR = "'FeedForward' object has no attribute 'dropout'"
 
@@ -136,37 +137,6 @@ class MBSFeedForward(nn.Module):
         self.register_buffer("_zero_bias", torch.zeros(dim_feedforward), persistent=False)
 
 
-class _TypeLists:
-    """The rows of one batch ordered by type: ``perm`` int64 [T] (sorted slot -> flat row), ``offsets`` int32 [b + 2] (type t's
-    slots are offsets[t] .. offsets[t + 1]); shared by every layer of a pass."""
-
-    def __init__(self, types: torch.Tensor, b: int):
-        B, L = types.shape
-        dev = types.device
-        self.types = types
-        perm = torch.empty(B * L, dtype=torch.int32, device=dev)
-        slot = torch.empty(B * L, dtype=torch.int32, device=dev)
-        self.offsets = torch.empty(b + 2, dtype=torch.int32, device=dev)
-        work = torch.empty((B + 1) * (b + 1), dtype=torch.int32, device=dev)
-        ops.expert_lists(types, b + 1, perm, slot, self.offsets, work)
-        self.perm = perm.long()
-
-
-def _with_ones(x, pad=4):
-    """[x | 1 0 0 0]: the bias of a grouped Linear rides as one more input column (the GEMM wants leading dims % 4 == 0)"""
-    T = x.shape[0]
-    tail = torch.zeros(T, pad, dtype=torch.float32, device=x.device)
-    tail[:, 0] = 1.0
-    return torch.cat([x, tail], 1)
-
-
-def _aug_weights(ws, bs, pad=4):
-    """[G, N, K + 4] from G Linear weights [N, K] and biases [N]"""
-    W, b = torch.stack(list(ws)), torch.stack(list(bs))
-    G, N, _ = W.shape
-    return torch.cat([W, b[:, :, None], torch.zeros(G, N, pad - 1, dtype=torch.float32, device=W.device)], 2).contiguous()
-
-
 class _MBSLayerFn(torch.autograd.Function):
     """One MBSTransformerEncoderLayer.  params: W1, alpha1, W2, alpha2, query, key, value, ln1w, ln1b, ln2w, ln2b, then
     (dense_1.weight, dense_1.bias, dense_2.weight, dense_2.bias) of each behaviour's expert, then the b b + 1 bias tables."""
@@ -176,7 +146,7 @@ class _MBSLayerFn(torch.autograd.Function):
     def forward(ctx, x, lists, meta, *params):
         B, L, H = x.shape
         T = B * L
-        h, b, dff, act, eps, bucket = meta["heads"], meta["b"], meta["dff"], meta["act"], meta["eps"], meta["bucket"]
+        h, b, act, eps, bucket = meta["heads"], meta["b"], meta["act"], meta["eps"], meta["bucket"]
         p = meta["dropout"] if meta["training"] else 0.0
         d = H // h
         C_ = b * b + 1
@@ -203,72 +173,35 @@ class _MBSLayerFn(torch.autograd.Function):
         scale = math.sqrt(1.0 / float(d))
         ops.mbs_attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], lists.types, w1m, w2m, relt, bucket, B, L, h, d, b, scale, p,
                          seeds[0], ctxv, lse)
-        v1 = torch.empty(T, H, **f32)
-        ops.residual_dropout_fwd(xf, ctxv, p, seeds[1], None, v1)                  # x + dropout(context): no output projection
-        y1 = torch.empty(T, H, **f32)
-        mean1, rstd1 = torch.empty(T, **f32), torch.empty(T, **f32)
-        ops.layernorm_fwd(v1, None, ln1w, ln1b, eps, None, y1, mean1, rstd1)
+        y1, ln1 = post_ln_fwd(xf, ctxv, ln1w, ln1b, eps, p, seeds[1])            # x + dropout(context): no output projection
         # the behaviour FFN: groups 1 .. b of the sorted rows; padding rows (group 0) stay zero
-        grp = dict(groups=b, group_offsets=offs[1:])
-        y1a = _with_ones(y1.index_select(0, perm))
-        w1a = _aug_weights(ffn[0::4], ffn[1::4])
-        pre1 = torch.zeros(T, dff, **f32)
-        ops.linear_fwd(y1a, H + 4, w1a, H + 4, pre1, dff, T, dff, H + 4, strideB=dff * (H + 4), **grp)
-        a1 = torch.empty(T, dff, **f32)
-        ops.bias_act_fwd(pre1, meta["zero_bias"], act, a1)                       # (the bias rode in the GEMM)
-        a1a = _with_ones(a1)
-        del a1
-        w2a = _aug_weights(ffn[2::4], ffn[3::4])
-        f2s = torch.zeros(T, H, **f32)
-        ops.linear_fwd(a1a, dff + 4, w2a, dff + 4, f2s, H, T, H, dff + 4, strideB=H * (dff + 4), **grp)
-        f2 = torch.empty(T, H, **f32)
-        f2.index_copy_(0, perm, f2s)
-        v2 = torch.empty(T, H, **f32)
-        ops.residual_dropout_fwd(y1, f2, p, seeds[2], None, v2)
-        out = torch.empty(T, H, **f32)
-        mean2, rstd2 = torch.empty(T, **f32), torch.empty(T, **f32)
-        ops.layernorm_fwd(v2, None, ln2w, ln2b, eps, None, out, mean2, rstd2)
+        w1a, w2a = _aug_weights(ffn[0::4], ffn[1::4]), _aug_weights(ffn[2::4], ffn[3::4])
+        f2, fsv = grouped_ffn_fwd(y1, perm, dict(groups=b, group_offsets=offs[1:]), w1a, w2a, act, meta["zero_bias"])
+        out, ln2 = post_ln_fwd(y1, f2, ln2w, ln2b, eps, p, seeds[2])
         ctx.meta = dict(meta, p=p, seeds=seeds, scale=scale, shape=(B, L, H), n_rel=len(rel))
         ctx.lists = lists
-        ctx.save_for_backward(xs, wqkv, qkv, W1, alpha1, W2, alpha2, w1m, w2m, relt, ctxv, lse, v1, mean1, rstd1, ln1w, y1a, w1a,
-                              pre1, a1a, w2a, v2, mean2, rstd2, ln2w)
+        ctx.save_for_backward(xs, wqkv, qkv, W1, alpha1, W2, alpha2, w1m, w2m, relt, ctxv, lse, *ln1, ln1w, *fsv, w1a, w2a, *ln2, ln2w)
         return out.view(B, L, H)
 
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def backward(ctx, dout):
-        (xs, wqkv, qkv, W1, alpha1, W2, alpha2, w1m, w2m, relt, ctxv, lse, v1, mean1, rstd1, ln1w, y1a, w1a, pre1, a1a, w2a, v2,
+        (xs, wqkv, qkv, W1, alpha1, W2, alpha2, w1m, w2m, relt, ctxv, lse, v1, mean1, rstd1, ln1w, y1a, pre1, a1a, w1a, w2a, v2,
          mean2, rstd2, ln2w) = ctx.saved_tensors
         mt, lists = ctx.meta, ctx.lists
         B, L, H = mt["shape"]
-        T, h, b, dff, act, p, seeds, bucket = B * L, mt["heads"], mt["b"], mt["dff"], mt["act"], mt["p"], mt["seeds"], mt["bucket"]
+        T, h, b, act, p, seeds, bucket = B * L, mt["heads"], mt["b"], mt["act"], mt["p"], mt["seeds"], mt["bucket"]
         d = H // h
         C_ = b * b + 1
-        NP = modules._N_PARTIAL
         f32 = dict(dtype=torch.float32, device=xs.device)
         perm, offs = lists.perm, lists.offsets
-        grp = dict(groups=b, group_offsets=offs[1:])
         g = dout.reshape(T, H).contiguous().float()
-        # LayerNorm(y1 + dropout(ffn))
-        dv2, dln2w, dln2b = layernorm_bwd(v2, ln2w, mean2, rstd2, g)
-        df2 = torch.empty(T, H, **f32)
-        ops.residual_dropout_bwd(dv2, p, seeds[2], df2)                           # dv2 stays = d y1 (residual branch)
-        df2s = df2.index_select(0, perm)
-        dw2a = torch.zeros_like(w2a)
-        ops.linear_wgrad(df2s, H, a1a, dff + 4, dw2a, dff + 4, T, H, dff + 4, strideC=H * (dff + 4), **grp)
-        da1 = torch.zeros(T, dff, **f32)
-        ops.gemm(df2s, H, 1, w2a, 1, dff + 4, da1, dff, T, dff, H, strideB=H * (dff + 4), **grp)
-        ops.bias_act_bwd(pre1, da1, act, da1, torch.empty(NP, dff, **f32))
-        dw1a = torch.zeros_like(w1a)
-        ops.linear_wgrad(da1, dff, y1a, H + 4, dw1a, H + 4, T, dff, H + 4, strideC=dff * (H + 4), **grp)
-        dy1s = torch.zeros(T, H, **f32)
-        ops.gemm(da1, dff, 1, w1a, 1, H + 4, dy1s, H, T, H, dff, strideB=dff * (H + 4), **grp)
-        dy1 = dv2
+        # LayerNorm(y1 + dropout(ffn)), the behaviour FFN, LayerNorm(x + dropout(context))
+        dy1, df2, dln2w, dln2b = post_ln_bwd(g, (v2, mean2, rstd2), ln2w, p, seeds[2])
+        dw1a, dw2a = torch.zeros_like(w1a), torch.zeros_like(w2a)
+        dy1s = grouped_ffn_bwd(df2, (y1a, pre1, a1a), perm, dict(groups=b, group_offsets=offs[1:]), w1a, w2a, act, dw1a, dw2a)
         dy1.index_add_(0, perm, dy1s)                                             # (perm is a permutation: one addend per row)
-        # LayerNorm(x + dropout(context))
-        dv1, dln1w, dln1b = layernorm_bwd(v1, ln1w, mean1, rstd1, dy1)
-        dctx = torch.empty(T, H, **f32)
-        ops.residual_dropout_bwd(dv1, p, seeds[1], dctx)                          # dv1 stays = d x (residual branch)
+        dv1, dctx, dln1w, dln1b = post_ln_bwd(dy1, (v1, mean1, rstd1), ln1w, p, seeds[1])
         n = ops.mbs_n_partial(B, h, d, b)
         dqkv = torch.zeros(T, 3 * H, **f32)
         p1, p2 = torch.zeros(n, C_, h, d, d, **f32), torch.zeros(n, C_, h, d, d, **f32)
@@ -293,11 +226,8 @@ class _MBSLayerFn(torch.autograd.Function):
         dx = dv1
         dx.index_add_(0, perm, dxs)
         shp = (b + 1, H, h, d)
-        dffn = []
-        for i in range(b):
-            dffn += [dw1a[i, :, :H], dw1a[i, :, H], dw2a[i, :, :dff], dw2a[i, :, dff]]
         return (dx.view(B, L, H), None, None, dW1, dal1, dW2, dal2, dwqkv[:, :, :H].reshape(shp), dwqkv[:, :, H:2 * H].reshape(shp),
-                dwqkv[:, :, 2 * H:].reshape(shp), dln1w, dln1b, dln2w, dln2b, *dffn, *drel)
+                dwqkv[:, :, 2 * H:].reshape(shp), dln1w, dln1b, dln2w, dln2b, *split_aug_grads(dw1a, dw2a), *drel)
 
 
 class MBSTransformerEncoderLayer(nn.Module):
@@ -313,8 +243,8 @@ class MBSTransformerEncoderLayer(nn.Module):
     def forward(self, hidden_states, attention_mask=None, type_seq=None, bucket=None):
         """``type_seq``: the _TypeLists of the batch; ``bucket``: int32 [2 L - 1] on the device (position bias on)."""
         a, f = self.multi_head_attention, self.feed_forward
-        meta = dict(heads=a.num_attention_heads, b=a.n_behaviors, dff=f.FFN[0].dense_1.out_features, act=f.FFN[0].act_code,
-                    dropout=self.dropout_p, eps=self.eps, training=self.training, bucket=bucket, zero_bias=f._zero_bias)
+        meta = dict(heads=a.num_attention_heads, b=a.n_behaviors, act=f.FFN[0].act_code, dropout=self.dropout_p, eps=self.eps,
+                    training=self.training, bucket=bucket, zero_bias=f._zero_bias)
         params = [a.W1, a.alpha1, a.W2, a.alpha2, a.query, a.key, a.value, a.LayerNorm.weight, a.LayerNorm.bias, f.LayerNorm.weight,
                   f.LayerNorm.bias]
         for e in f.FFN:

@@ -24,8 +24,8 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import ops
+from .layer_blocks import _N_PARTIAL, attn_block_bwd, attn_block_fwd, dense_core, ffn_bwd, ffn_fwd  # noqa: F401
 
-_N_PARTIAL = 256
 _ACT_BY_FN = {F.relu: "relu", F.gelu: "gelu", F.silu: "swish", F.tanh: "tanh", torch.tanh: "tanh",
               F.sigmoid: "sigmoid", torch.sigmoid: "sigmoid", F.elu: "elu"}
 
@@ -50,7 +50,7 @@ class _SeedCounter:
 
 
 class _EncoderLayerFn(torch.autograd.Function):
-    """One TransformerEncoderLayer: forward keeps the activations the hand-written backward needs."""
+    """One TransformerEncoderLayer: layer_blocks' attention block with the dense core, then its dense FFN."""
 
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
@@ -58,105 +58,36 @@ class _EncoderLayerFn(torch.autograd.Function):
         if not x.is_cuda:
             raise RuntimeError("gamer_amd.modules runs on the HIP device only (no CPU fallback)")
         B, S, D = x.shape
-        T = B * S
-        H, dff, act, p, eps, training = (meta["heads"], meta["dff"], meta["act"], meta["dropout"], meta["eps"],
-                                         meta["training"])
-        p = p if training else 0.0
-        dh = D // H
-        f32 = dict(dtype=torch.float32, device=x.device)
-        xf = x.reshape(T, D).contiguous().float()
+        H, act, p, eps = meta["heads"], meta["act"], meta["dropout"], meta["eps"]
+        p = p if meta["training"] else 0.0
+        xf = x.reshape(B * S, D).contiguous().float()
         seeds = [_SeedCounter.next() for _ in range(2)]
         # q, k, v projections as one GEMM on the concatenated weights
         wqkv = torch.cat([wq, wk, wv], 0).contiguous()
         bqkv = torch.cat([bq, bk, bv], 0).contiguous()
-        qkv = torch.empty(T, 3 * D, **f32)
-        ops.linear_fwd(xf, D, wqkv, D, qkv, 3 * D, T, 3 * D, D)
-        ops.bias_act_fwd(qkv, bqkv, 0)
-        ctxv = torch.empty(T, D, **f32)
-        lse = torch.empty(B, H, S, **f32)
-        scale = math.sqrt(1.0 / float(dh))
+        scale = math.sqrt(1.0 / float(D // H))
         m = mask.float().contiguous() if mask is not None else None
-        ops.attn_dense_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], m, B, S, H, dh, scale, p, seeds[0], ctxv, lse)
-        h = torch.empty(T, D, **f32)
-        ops.linear_fwd(ctxv, D, wd, D, h, D, T, D, D)
-        ops.bias_act_fwd(h, bd, 0)
-        v1 = torch.empty(T, D, **f32)
-        ops.residual_dropout_fwd(xf, h, p, seeds[1], None, v1)              # x + dropout(dense(context))
-        y1 = torch.empty(T, D, **f32)
-        mean1, rstd1 = torch.empty(T, **f32), torch.empty(T, **f32)
-        ops.layernorm_fwd(v1, None, ln1w, ln1b, eps, None, y1, mean1, rstd1)
-        # feed forward
-        pre1 = torch.empty(T, dff, **f32)
-        a1 = torch.empty(T, dff, **f32)
-        ops.linear_fwd(y1, D, w1, D, pre1, dff, T, dff, D)
-        ops.bias_act_fwd(pre1, b1, act, a1)
-        f2 = torch.empty(T, D, **f32)
-        ops.linear_fwd(a1, dff, w2, dff, f2, D, T, D, dff)
-        ops.bias_act_fwd(f2, b2, 0)
+        core, _ = dense_core(m, B, S, H, D // H, scale, p, seeds[0])
+        y1, sv = attn_block_fwd(xf, wqkv, bqkv, wd, bd, ln1w, ln1b, eps, p, seeds[1], core)
+        f2, (_, pre1, a1) = ffn_fwd(y1, w1, b1, w2, b2, act)
         ctx.meta = dict(meta, p=p, seeds=seeds, scale=scale, shape=(B, S, D))
         ctx.mask = m
-        ctx.save_for_backward(xf, wqkv, qkv, ctxv, lse, wd, v1, mean1, rstd1, ln1w, y1, w1, pre1, a1, w2)
+        ctx.save_for_backward(*sv, w1, pre1, a1, w2)
         return f2.view(B, S, D)
 
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def backward(ctx, dout):
-        xf, wqkv, qkv, ctxv, lse, wd, v1, mean1, rstd1, ln1w, y1, w1, pre1, a1, w2 = ctx.saved_tensors
+        *sv, w1, pre1, a1, w2 = ctx.saved_tensors
         mt = ctx.meta
         B, S, D = mt["shape"]
-        T, H, dff, act, p, seeds = B * S, mt["heads"], mt["dff"], mt["act"], mt["p"], mt["seeds"]
-        dh = D // H
-        f32 = dict(dtype=torch.float32, device=xf.device)
-        part = torch.empty(_N_PARTIAL, max(3 * D, dff), **f32)
-        part2 = torch.empty(_N_PARTIAL, D, **f32)
-
-        def colsum(partial_view, n):
-            out = torch.empty(n, **f32)
-            ops.colsum_reduce(partial_view, out)
-            return out
-        g = dout.reshape(T, D).contiguous().float().clone()
-        # dense_2
-        pb = part[:, :D].contiguous()
-        ops.bias_act_bwd(None, g, 0, g, pb)
-        db2 = colsum(pb, D)
-        dw2 = torch.zeros_like(w2)
-        ops.linear_wgrad(g, D, a1, dff, dw2, dff, T, D, dff)
-        da1 = torch.empty(T, dff, **f32)
-        ops.linear_dgrad(g, D, w2, dff, da1, dff, T, D, dff)
-        # activation + dense_1
-        pb = part[:, :dff].contiguous()
-        ops.bias_act_bwd(pre1, da1, act, da1, pb)
-        db1 = colsum(pb, dff)
-        dw1 = torch.zeros_like(w1)
-        ops.linear_wgrad(da1, dff, y1, D, dw1, D, T, dff, D)
-        dy1 = torch.empty(T, D, **f32)
-        ops.linear_dgrad(da1, dff, w1, D, dy1, D, T, dff, D)
-        # LayerNorm(x + dropout(h))
-        dv1 = torch.empty(T, D, **f32)
-        pw, pb = part[:, :D].contiguous(), part2
-        ops.layernorm_bwd(v1, ln1w, mean1, rstd1, dy1, dv1, pw, pb)
-        dln1w, dln1b = colsum(pw, D), colsum(pb, D)
-        dh_ = torch.empty(T, D, **f32)
-        ops.residual_dropout_bwd(dv1, p, seeds[1], dh_)                        # dv1 stays = d x (residual branch)
-        pb = part[:, :D].contiguous()
-        ops.bias_act_bwd(None, dh_, 0, dh_, pb)
-        dbd = colsum(pb, D)
-        dwd = torch.zeros_like(wd)
-        ops.linear_wgrad(dh_, D, ctxv, D, dwd, D, T, D, D)
-        dctx = torch.empty(T, D, **f32)
-        ops.linear_dgrad(dh_, D, wd, D, dctx, D, T, D, D)
-        dqkv = torch.empty(T, 3 * D, **f32)
-        ops.attn_dense_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], ctx.mask, B, S, H, dh, mt["scale"], p, seeds[0],
-                           ctxv, dctx, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:])
-        pb = part[:, :3 * D].contiguous()
-        ops.bias_act_bwd(None, dqkv, 0, dqkv, pb)
-        dbqkv = colsum(pb, 3 * D)
-        dwqkv = torch.zeros_like(wqkv)
-        ops.linear_wgrad(dqkv, 3 * D, xf, D, dwqkv, D, T, 3 * D, D)
-        ops.linear_dgrad(dqkv, 3 * D, wqkv, D, dv1, D, T, 3 * D, D, accumulate=True)     # dx = dv1 + dqkv Wqkv
-        dx = dv1.view(B, S, D)
-        return (dx, None, None, dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:], dwd,
-                dbd, dln1w, dln1b, dw1, db1, dw2, db2)
+        H, p, seeds = mt["heads"], mt["p"], mt["seeds"]
+        g = dout.reshape(B * S, D).contiguous().float().clone()
+        dy1, dw1, db1, dw2, db2 = ffn_bwd(g, (sv[-1], pre1, a1), w1, w2, mt["act"])
+        _, core_bwd = dense_core(ctx.mask, B, S, H, D // H, mt["scale"], p, seeds[0])
+        dx, dwqkv, dbqkv, dwd, dbd, dln1w, dln1b, _ = attn_block_bwd(dy1, sv, p, seeds[1], core_bwd)
+        return (dx.view(B, S, D), None, None, dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:],
+                dwd, dbd, dln1w, dln1b, dw1, db1, dw2, db2)
 
 
 class MultiHeadAttention(nn.Module):
@@ -208,8 +139,8 @@ class TransformerEncoderLayer(nn.Module):
         if not f.residual:
             # upstream fails here too: a FeedForward built with residual=False has no LayerNorm / dropout to apply
             raise AttributeError("'FeedForward' object has no attribute 'dropout'")
-        meta = dict(heads=a.num_attention_heads, dff=f.dense_1.out_features, act=f.act_code, dropout=self.dropout_p,
-                    eps=self.eps, training=self.training)
+        meta = dict(heads=a.num_attention_heads, act=f.act_code, dropout=self.dropout_p, eps=self.eps,
+                    training=self.training)
         return _EncoderLayerFn.apply(hidden_states, attention_mask, meta, a.query.weight, a.query.bias, a.key.weight,
                                      a.key.bias, a.value.weight, a.value.bias, a.dense.weight, a.dense.bias,
                                      a.LayerNorm.weight, a.LayerNorm.bias, f.dense_1.weight, f.dense_1.bias,

@@ -40,10 +40,9 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import modules, ops
-from .mbht import _GatherRowsFn
-from .mbstr import _TypeLists, _aug_weights, _with_ones
-from .rec_common import (ClozeMixin, DropUnknownConfig, _dropout_bwd, _next_seed, _SharedGrad, colsum, layernorm_bwd,
-                         linear_act_bwd)
+from .layer_blocks import (_N_PARTIAL, _TypeLists, _aug_weights, _dropout_bwd, colsum, dropout_fwd, grouped_ffn_bwd, grouped_ffn_fwd,
+                           layernorm_bwd, linear_act_bwd, linear_act_fwd, post_ln_bwd, post_ln_fwd, split_aug_grads)
+from .rec_common import ClozeMixin, DropUnknownConfig, _GatherRowsFn, _next_seed, _SharedGrad
 
 _EPS = 1e-24
 _ELU = ops.ACTIVATIONS["elu"]
@@ -108,10 +107,7 @@ class _SimpleEmbedFn(torch.autograd.Function):
         ops.embedding_fwd(ids, E, x)
         y, mean, rstd = torch.empty(T, H, **f32), torch.empty(T, **f32), torch.empty(T, **f32)
         ops.layernorm_fwd(x, None, w, b, eps, None, y, mean, rstd)
-        if p > 0:
-            z = torch.zeros(T, H, **f32)
-            ops.residual_dropout_fwd(z, y, p, seed)                        # z = 0 + drop(y)
-            y = z
+        y = dropout_fwd(y, p, seed)
         out = torch.empty(T, H, **f32)
         ops.bias_act_fwd(y, torch.zeros(H, **f32), _ELU, out)
         ctx.meta = (p, seed, E.shape, tuple(ids.shape))
@@ -126,7 +122,7 @@ class _SimpleEmbedFn(torch.autograd.Function):
         T, H = x.shape
         f32 = dict(dtype=torch.float32, device=x.device)
         g = torch.empty(T, H, **f32)
-        ops.bias_act_bwd(y, dout.reshape(T, H).contiguous().float(), _ELU, g, torch.empty(modules._N_PARTIAL, H, **f32))
+        ops.bias_act_bwd(y, dout.reshape(T, H).contiguous().float(), _ELU, g, torch.empty(_N_PARTIAL, H, **f32))
         dx, dw, db = layernorm_bwd(x, w, mean, rstd, _dropout_bwd(g, H, p, seed))
         dE = _SharedGrad.take(ctx.shared, e_shape, x.device)
         ops.embedding_bwd_large(ids.reshape(-1), dx, 0, dE)
@@ -187,7 +183,7 @@ class _PBATLayerFn(torch.autograd.Function):
     def forward(ctx, xm, xc, tm, tc, rel_m, rel_c, pos_m, pos_c, lists, keep, meta, *params):
         B, L, H = xm.shape
         T = B * L
-        h, b, dff, act, eps = meta["heads"], meta["b"], meta["dff"], meta["act"], meta["eps"]
+        h, b, act, eps = meta["heads"], meta["b"], meta["act"], meta["eps"]
         p = meta["dropout"] if meta["training"] else 0.0
         d = H // h
         f32 = dict(dtype=torch.float32, device=xm.device)
@@ -204,12 +200,8 @@ class _PBATLayerFn(torch.autograd.Function):
         Wc, bc_ = wcat(pxc, pbc)
         Am = torch.cat([xm.reshape(T, H), tm.reshape(T, H)], 1).contiguous().float()
         Ac = torch.cat([xc.reshape(T, H), tc.reshape(T, H)], 1).contiguous().float()
-        pm, pre_c = torch.empty(T, 3 * H, **f32), torch.empty(T, 3 * H, **f32)
-        ops.linear_fwd(Am, 2 * H, Wm, 2 * H, pm, 3 * H, T, 3 * H, 2 * H)
-        ops.bias_act_fwd(pm, bm_, 0)
-        ops.linear_fwd(Ac, 2 * H, Wc, 2 * H, pre_c, 3 * H, T, 3 * H, 2 * H)
-        pc = torch.empty(T, 3 * H, **f32)
-        ops.bias_act_fwd(pre_c, bc_, _ELU, pc)
+        _, pm = linear_act_fwd(Am, Wm, bm_, 0)
+        pre_c, pc = linear_act_fwd(Ac, Wc, bc_, _ELU)
         pc += 1.0
         proj = (pm[:, :H], pc[:, :H], pm[:, H:2 * H], pc[:, H:2 * H], pm[:, 2 * H:], pc[:, 2 * H:])
         rel_m, rel_c = rel_m.reshape(B, -1, H).contiguous().float(), rel_c.reshape(B, -1, H).contiguous().float()
@@ -220,42 +212,21 @@ class _PBATLayerFn(torch.autograd.Function):
         ops.pbat_attn_fwd(proj, rel_m, rel_c, pos_m, pos_c, attw, lists.types, keep, B, L, h, d, b, scale, p, seeds[0], o[0], o[1], S, lse)
 
         def dense_ln(ov, x, W, bias, seed):
-            dn = torch.empty(T, H, **f32)
-            ops.linear_fwd(ov, H, W, H, dn, H, T, H, H)
-            ops.bias_act_fwd(dn, bias, 0)
-            v, y = torch.empty(T, H, **f32), torch.empty(T, H, **f32)
-            ops.residual_dropout_fwd(x, dn, p, seed, None, v)
-            mean, rstd = torch.empty(T, **f32), torch.empty(T, **f32)
-            ops.layernorm_fwd(v, None, lnw, lnb, eps, None, y, mean, rstd)
-            return y, v, mean, rstd
-        ym, vm, mean_m, rstd_m = dense_ln(o[0], Am[:, :H].contiguous(), mdw, mdb, seeds[1])
-        yc, vc, mean_c, rstd_c = dense_ln(o[1], Ac[:, :H].contiguous(), cdw, cdb, seeds[2])
+            return post_ln_fwd(x, linear_act_fwd(ov, W, bias, 0)[1], lnw, lnb, eps, p, seed)
+        ym, ln_m = dense_ln(o[0], Am[:, :H].contiguous(), mdw, mdb, seeds[1])
+        yc, ln_c = dense_ln(o[1], Ac[:, :H].contiguous(), cdw, cdb, seeds[2])
         # the behaviour FFN, once per stream: groups 1 .. b of the sorted rows; padding rows (group 0) stay zero
-        perm, offs = lists.perm, lists.offsets
-        grp = dict(groups=b, group_offsets=offs[1:])
+        perm, grp = lists.perm, dict(groups=b, group_offsets=lists.offsets[1:])
         w1a, w2a = _aug_weights(ffn[0::4], ffn[1::4]), _aug_weights(ffn[2::4], ffn[3::4])
-
-        def ffn_fwd(y):
-            ya = _with_ones(y.index_select(0, perm))
-            pre1 = torch.zeros(T, dff, **f32)
-            ops.linear_fwd(ya, H + 4, w1a, H + 4, pre1, dff, T, dff, H + 4, strideB=dff * (H + 4), **grp)
-            a1 = torch.empty(T, dff, **f32)
-            ops.bias_act_fwd(pre1, meta["zero_ff"], act, a1)
-            a1a = _with_ones(a1)
-            f2s = torch.zeros(T, H, **f32)
-            ops.linear_fwd(a1a, dff + 4, w2a, dff + 4, f2s, H, T, H, dff + 4, strideB=H * (dff + 4), **grp)
-            f2 = torch.empty(T, H, **f32)
-            f2.index_copy_(0, perm, f2s)
-            return f2, ya, pre1, a1a
-        fm, yam, pre1m, a1am = ffn_fwd(ym)
-        fc, yac, pre1c, a1ac = ffn_fwd(yc)
+        fm, ffn_m = grouped_ffn_fwd(ym, perm, grp, w1a, w2a, act, meta["zero_ff"])
+        fc, ffn_c = grouped_ffn_fwd(yc, perm, grp, w1a, w2a, act, meta["zero_ff"])
         out_c = torch.empty(T, H, **f32)
         ops.bias_act_fwd(fc, meta["zero_h"], _ELU, out_c)
         out_c += 1.0
         ctx.meta = dict(meta, p=p, seeds=seeds, scale=scale, shape=(B, L, H))
         ctx.lists, ctx.attw = lists, attw
-        ctx.save_for_backward(Am, Ac, Wm, Wc, pm, pre_c, pc, rel_m, rel_c, pos_m, pos_c, keep, o, S, lse, mdw, cdw, lnw, vm, mean_m,
-                              rstd_m, vc, mean_c, rstd_c, w1a, w2a, yam, pre1m, a1am, yac, pre1c, a1ac, fc)
+        ctx.save_for_backward(Am, Ac, Wm, Wc, pm, pre_c, pc, rel_m, rel_c, pos_m, pos_c, keep, o, S, lse, mdw, cdw, lnw, *ln_m, *ln_c,
+                              w1a, w2a, *ffn_m, *ffn_c, fc)
         return fm.view(B, L, H), out_c.view(B, L, H)
 
     @staticmethod
@@ -265,39 +236,27 @@ class _PBATLayerFn(torch.autograd.Function):
          rstd_c, w1a, w2a, yam, pre1m, a1am, yac, pre1c, a1ac, fc) = ctx.saved_tensors
         mt, lists, attw = ctx.meta, ctx.lists, ctx.attw
         B, L, H = mt["shape"]
-        T, h, b, dff, act, p, seeds = B * L, mt["heads"], mt["b"], mt["dff"], mt["act"], mt["p"], mt["seeds"]
+        T, h, b, act, p, seeds = B * L, mt["heads"], mt["b"], mt["act"], mt["p"], mt["seeds"]
         d = H // h
-        NP = modules._N_PARTIAL
         f32 = dict(dtype=torch.float32, device=Am.device)
-        perm, offs = lists.perm, lists.offsets
-        grp = dict(groups=b, group_offsets=offs[1:])
-        dw1a, dw2a = torch.zeros_like(w1a), torch.zeros_like(w2a)
+        perm, grp = lists.perm, dict(groups=b, group_offsets=lists.offsets[1:])
+        dw1a, dw2a = torch.zeros_like(w1a), torch.zeros_like(w2a)              # both streams' FFN gradients add up here
 
-        def ffn_bwd(df2, ya, pre1, a1a):
-            df2s = df2.index_select(0, perm)
-            ops.linear_wgrad(df2s, H, a1a, dff + 4, dw2a, dff + 4, T, H, dff + 4, strideC=H * (dff + 4), **grp)
-            da1 = torch.zeros(T, dff, **f32)
-            ops.gemm(df2s, H, 1, w2a, 1, dff + 4, da1, dff, T, dff, H, strideB=H * (dff + 4), **grp)
-            ops.bias_act_bwd(pre1, da1, act, da1, torch.empty(NP, dff, **f32))
-            ops.linear_wgrad(da1, dff, ya, H + 4, dw1a, H + 4, T, dff, H + 4, strideC=dff * (H + 4), **grp)
-            dys = torch.zeros(T, H, **f32)
-            ops.gemm(da1, dff, 1, w1a, 1, H + 4, dys, H, T, H, dff, strideB=dff * (H + 4), **grp)
+        def ffn_bwd(df2, saved):
             dy = torch.empty(T, H, **f32)
-            dy.index_copy_(0, perm, dys)
+            dy.index_copy_(0, perm, grouped_ffn_bwd(df2, saved, perm, grp, w1a, w2a, act, dw1a, dw2a))
             return dy
         dfc = torch.empty(T, H, **f32)
-        ops.bias_act_bwd(fc, dout_c.reshape(T, H).contiguous().float(), _ELU, dfc, torch.empty(NP, H, **f32))
-        dym = ffn_bwd(dfm.reshape(T, H).contiguous().float(), yam, pre1m, a1am)
-        dyc = ffn_bwd(dfc, yac, pre1c, a1ac)
+        ops.bias_act_bwd(fc, dout_c.reshape(T, H).contiguous().float(), _ELU, dfc, torch.empty(_N_PARTIAL, H, **f32))
+        dym = ffn_bwd(dfm.reshape(T, H).contiguous().float(), (yam, pre1m, a1am))
+        dyc = ffn_bwd(dfc, (yac, pre1c, a1ac))
 
-        def dense_ln_bwd(dy, v, mean, rstd, ov, W, seed):
-            dv, dlw, dlb = layernorm_bwd(v, lnw, mean, rstd, dy)
-            dd = torch.empty(T, H, **f32)
-            ops.residual_dropout_bwd(dv, p, seed, dd)                         # dv stays = d x (residual branch)
+        def dense_ln_bwd(dy, ln, ov, W, seed):
+            dv, dd, dlw, dlb = post_ln_bwd(dy, ln, lnw, p, seed)
             do, dW, db = linear_act_bwd(dd, None, ov, W, 0)
             return dv, do, dW, db, dlw, dlb
-        dxm_res, do_m, dmdw, dmdb, dlw1, dlb1 = dense_ln_bwd(dym, vm, mean_m, rstd_m, o[0], mdw, seeds[1])
-        dxc_res, do_c, dcdw, dcdb, dlw2, dlb2 = dense_ln_bwd(dyc, vc, mean_c, rstd_c, o[1], cdw, seeds[2])
+        dxm_res, do_m, dmdw, dmdb, dlw1, dlb1 = dense_ln_bwd(dym, (vm, mean_m, rstd_m), o[0], mdw, seeds[1])
+        dxc_res, do_c, dcdw, dcdb, dlw2, dlb2 = dense_ln_bwd(dyc, (vc, mean_c, rstd_c), o[1], cdw, seeds[2])
         proj = (pm[:, :H], pc[:, :H], pm[:, H:2 * H], pc[:, H:2 * H], pm[:, 2 * H:], pc[:, 2 * H:])
         dpm, dpc = torch.empty(T, 3 * H, **f32), torch.empty(T, 3 * H, **f32)
         dproj = (dpm[:, :H], dpc[:, :H], dpm[:, H:2 * H], dpc[:, H:2 * H], dpm[:, 2 * H:], dpc[:, 2 * H:])
@@ -317,13 +276,10 @@ class _PBATLayerFn(torch.autograd.Function):
         dAc, dWc, dbc = linear_act_bwd(dpc, pre_c, Ac, Wc, _ELU)
         dxm, dxc = dAm[:, :H] + dxm_res, dAc[:, :H] + dxc_res
         gm, gc = _split_proj_grads(dWm, dbm, H), _split_proj_grads(dWc, dbc, H)
-        dffn = []
-        for i in range(b):
-            dffn += [dw1a[i, :, :H], dw1a[i, :, H], dw2a[i, :, :dff], dw2a[i, :, dff]]
         NT = b + 1
         return (dxm.view(B, L, H), dxc.view(B, L, H), dAm[:, H:].reshape(B, L, H), dAc[:, H:].reshape(B, L, H),
                 drel_m.view(B, NT, NT, H), drel_c.view(B, NT, NT, H), dpos_m, dpos_c, None, None, None,
-                *gm, *gc, dmdw, dmdb, dcdw, dcdb, dlw1 + dlw2, dlb1 + dlb2, *datt, *dffn)
+                *gm, *gc, dmdw, dmdb, dcdw, dcdb, dlw1 + dlw2, dlb1 + dlb2, *datt, *split_aug_grads(dw1a, dw2a))
 
 
 class PBATLayer(nn.Module):
@@ -340,8 +296,8 @@ class PBATLayer(nn.Module):
         """``hidden_states``: (mean, covariance) [B, L, H]; ``attention_mask``: int32 [B, L], != 0 where a key may be attended;
         ``type_seq``: the _TypeLists of the batch; relations [B, b + 1, b + 1, H] and positions [L, H] as (mean, covariance)."""
         a, f = self.multi_head_attention, self.feed_forward
-        meta = dict(heads=a.num_attention_heads, b=a.n_behaviors, dff=f.FFN[0].dense_1.out_features, act=f.FFN[0].act_code,
-                    dropout=self.dropout_p, eps=self.eps, training=self.training, zero_ff=f._zero_ff, zero_h=f._zero_h)
+        meta = dict(heads=a.num_attention_heads, b=a.n_behaviors, act=f.FFN[0].act_code, dropout=self.dropout_p, eps=self.eps,
+                    training=self.training, zero_ff=f._zero_ff, zero_h=f._zero_h)
         params = []
         for dct in (a.xm, a.bm, a.xc, a.bc):
             for n in ("q", "k", "v"):
@@ -377,9 +333,7 @@ class _WassHeadFn(torch.autograd.Function):
         M, H = om.shape
         f32 = dict(dtype=torch.float32, device=om.device)
         x = torch.cat([om, oc], 0).contiguous().float()
-        pre, hid = torch.empty(2 * M, H, **f32), torch.empty(2 * M, H, **f32)
-        ops.linear_fwd(x, H, W, H, pre, H, 2 * M, H, H)
-        ops.bias_act_fwd(pre, bias, _ELU, hid)
+        pre, hid = linear_act_fwd(x, W, bias, _ELU)
         xp, a = torch.empty(M, 2 * H, **f32), torch.empty(M, **f32)
         ops.wass_rows_fwd(hid[:M], hid[M:], xp, a)
         ctx.save_for_backward(x, W, pre, hid)

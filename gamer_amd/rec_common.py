@@ -4,8 +4,9 @@ Only pieces that at least two models use live here; a model's own layers and hea
   seeds          ``_Seeds`` / ``_next_seed``: the running counter the cloze masks and the input dropout draw from
   ``_SharedGrad``  one item-table gradient buffer per calculate_loss call, written by the head and by the input gather
   functions      ``InputBlockFn`` (dropout(LayerNorm(E[ids] + P[s]))), ``EmbedDropoutFn`` (dropout(E[ids])), ``GatherLinearFn``
-                 (act(x[rows] W^T + b)), ``CatalogCEFn`` (catalogue-wide cross entropy, the scores never written)
-  helpers        ``colsum``, ``linear_act_bwd``, ``layernorm_bwd``: the backward idioms of a Linear + activation and a LayerNorm
+                 (act(x[rows] W^T + b)), ``_GatherRowsFn`` (x[rows], rows may repeat), ``CatalogCEFn`` (catalogue-wide cross
+                 entropy, the scores never written)
+  helpers        ``colsum``, ``linear_act_bwd``, ``layernorm_bwd``: re-exported from layer_blocks, where the layers' blocks live
   ``ConfigBase``   from_dict / from_pretrained / to_dict of the config dataclasses, with the model's rule for unknown keys
   mixins         ``SeqRecMixin`` (all four models) and ``ClozeMixin`` (the cloze models): methods only, no ``__init__`` and no
                  submodules, so every model still creates its parameters in the reference's order
@@ -21,7 +22,9 @@ import warnings
 import torch
 from torch import nn
 
-from . import modules, ops
+from . import ops
+from .layer_blocks import (_dropout_bwd, colsum, dropout_fwd, layernorm_bwd, linear_act_bwd,  # noqa: F401  (re-exported)
+                           linear_act_fwd)
 
 
 class ConfigBase:
@@ -100,50 +103,6 @@ class _SharedGrad:
         return dE
 
 
-# ---- backward idioms -----------------------------------------------------------------------------------------------------------
-def colsum(partial):
-    """the column sums [N] of a [rows, N] table of partial sums (gamer_colsum_reduce)"""
-    out = torch.empty(partial.shape[1], dtype=torch.float32, device=partial.device)
-    ops.colsum_reduce(partial, out)
-    return out
-
-
-def linear_act_bwd(g, pre, x, w, act):
-    """(dx, dw, db) of y = act(x w^T + b) from g = dy [M, N], which is overwritten with d(x w^T + b); ``pre`` = x w^T + b (None
-    for act 0), x [M, K], w [N, K].  Call it under the "f32" matmul mode."""
-    M, K = x.shape
-    N = w.shape[0]
-    f32 = dict(dtype=torch.float32, device=x.device)
-    pb = torch.empty(modules._N_PARTIAL, N, **f32)
-    ops.bias_act_bwd(pre, g, act, g, pb)
-    db = colsum(pb)
-    dw = torch.zeros_like(w)
-    ops.linear_wgrad(g, N, x, K, dw, K, M, N, K)
-    dx = torch.empty(M, K, **f32)
-    ops.linear_dgrad(g, N, w, K, dx, K, M, N, K)
-    return dx, dw, db
-
-
-def layernorm_bwd(v, w, mean, rstd, dy):
-    """(dv, dw, db) of y = LayerNorm(v) [T, H] from the saved mean and rstd"""
-    T, H = v.shape
-    f32 = dict(dtype=torch.float32, device=v.device)
-    dv = torch.empty(T, H, **f32)
-    pw, pb = torch.empty(modules._N_PARTIAL, H, **f32), torch.empty(modules._N_PARTIAL, H, **f32)
-    ops.layernorm_bwd(v, w, mean, rstd, dy, dv, pw, pb)
-    return dv, colsum(pw), colsum(pb)
-
-
-def _dropout_bwd(dy, width, p, seed):
-    """dy as contiguous fp32 rows of ``width`` values, through the dropout mask of (p, seed)"""
-    g = dy.reshape(-1, width).contiguous().float()
-    if p > 0:
-        gm = torch.empty_like(g)
-        ops.residual_dropout_bwd(g, p, seed, gm)
-        g = gm
-    return g
-
-
 # ---- autograd functions --------------------------------------------------------------------------------------------------------
 class InputBlockFn(torch.autograd.Function):
     """dropout(LayerNorm(E[ids] + P[s])) for ids [B, S]; gradients of E (padding row 0 skipped), P, the LayerNorm."""
@@ -176,19 +135,17 @@ class InputBlockFn(torch.autograd.Function):
 
 
 class EmbedDropoutFn(torch.autograd.Function):
-    """dropout(E[ids]) for ids [B, L]; the gradient of E (padding row 0 skipped) into the shared table gradient."""
+    """dropout(E[ids]) for ids [B, L]; the gradient of E (row ``pad_id`` skipped; -1: no padding row) into the shared table
+    gradient, which is returned by the last of its gathers."""
 
     @staticmethod
-    def forward(ctx, ids, E, p, seed, shared=None):
+    def forward(ctx, ids, E, p, seed, shared=None, pad_id=0):
         B, L = ids.shape
         D = E.shape[1]
         x = torch.empty(B * L, D, dtype=torch.float32, device=E.device)
         ops.embedding_fwd(ids, E, x)
-        if p > 0:
-            y = torch.zeros_like(x)
-            ops.residual_dropout_fwd(y, x, p, seed)               # y = 0 + drop(x)
-            x = y
-        ctx.meta = (p, seed, E.shape)
+        x = dropout_fwd(x, p, seed)
+        ctx.meta = (p, seed, E.shape, pad_id)
         ctx.shared = shared
         ctx.save_for_backward(ids)
         return x.view(B, L, D)
@@ -196,11 +153,11 @@ class EmbedDropoutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx):
         ids, = ctx.saved_tensors
-        p, seed, e_shape = ctx.meta
+        p, seed, e_shape, pad_id = ctx.meta
         g = _dropout_bwd(dx, e_shape[1], p, seed)
         dE = _SharedGrad.take(ctx.shared, e_shape, g.device)
-        ops.embedding_bwd_large(ids, g, 0, dE)
-        return None, dE, None, None, None
+        ops.embedding_bwd_large(ids, g, pad_id, dE)
+        return None, _SharedGrad.give(ctx.shared, dE), None, None, None, None
 
 
 class GatherLinearFn(torch.autograd.Function):
@@ -210,14 +167,8 @@ class GatherLinearFn(torch.autograd.Function):
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def forward(ctx, x, rows, w, b, act):
-        H = x.shape[-1]
-        N = w.shape[0]
-        xg = x.reshape(-1, H)[rows].contiguous()
-        R = xg.shape[0]
-        pre = torch.empty(R, N, dtype=torch.float32, device=x.device)
-        ops.linear_fwd(xg, H, w, H, pre, N, R, N, H)
-        out = pre if act == 0 else torch.empty_like(pre)
-        ops.bias_act_fwd(pre, b, act, None if act == 0 else out)          # (pre <- pre + b in place: act 0 needs no more)
+        xg = x.reshape(-1, x.shape[-1])[rows].contiguous()
+        pre, out = linear_act_fwd(xg, w, b, act)
         ctx.save_for_backward(xg, rows, w, None if act == 0 else pre)
         ctx.x_shape, ctx.act = x.shape, act
         return out
@@ -230,6 +181,29 @@ class GatherLinearFn(torch.autograd.Function):
         dx = torch.zeros(ctx.x_shape, dtype=torch.float32, device=xg.device)
         dx.view(-1, xg.shape[1])[rows] = dxg
         return dx, None, dw, db, None
+
+
+class _GatherRowsFn(torch.autograd.Function):
+    """x.view(-1, H)[rows] for rows that may repeat (MBHT: the padded slots of masked_index all point at position 0); the backward
+    adds the repeats in slot order (gamer_embedding_bwd_large: no float atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, rows):
+        H = x.shape[-1]
+        xf = x.reshape(-1, H).contiguous().float()
+        y = torch.empty(rows.numel(), H, dtype=torch.float32, device=x.device)
+        ops.embedding_fwd(rows, xf, y)
+        ctx.save_for_backward(rows)
+        ctx.x_shape = x.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        rows, = ctx.saved_tensors
+        H = ctx.x_shape[-1]
+        dx = torch.zeros(ctx.x_shape, dtype=torch.float32, device=dy.device)
+        ops.embedding_bwd_large(rows, dy.contiguous().float(), -1, dx.view(-1, H))
+        return dx, None
 
 
 class CatalogCEFn(torch.autograd.Function):

@@ -35,7 +35,8 @@ import torch
 from torch import nn
 
 from . import modules, ops
-from .rec_common import CatalogCEFn, DropUnknownConfig, _SharedGrad, _dropout_bwd, _next_seed, colsum
+from .layer_blocks import _N_PARTIAL, _dropout_bwd, add_dropout, colsum, dropout_fwd
+from .rec_common import CatalogCEFn, DropUnknownConfig, EmbedDropoutFn, _SharedGrad, _next_seed
 
 MAX_ENCODER_LEN, MAX_DECODER_LEN = 128, 8
 
@@ -192,27 +193,9 @@ def _rms(x, w, eps):
 
 def _rms_bwd(x, w, eps, dy, dx):
     """dx += d RMSNorm(x) from dy; returns dw"""
-    part = torch.empty(modules._N_PARTIAL, x.shape[1], **_f32(x.device))
+    part = torch.empty(_N_PARTIAL, x.shape[1], **_f32(x.device))
     ops.rmsnorm_bwd(x, w, dy, dy.stride(0), eps, dx, part, accumulate_dx=True)
     return colsum(part)
-
-
-def _add_dropout(x, delta, p, seed):
-    out = torch.empty_like(x)
-    ops.residual_dropout_fwd(x, delta, p, seed, None, out)
-    return out
-
-
-def _dropout(x, p, seed):
-    return _add_dropout(torch.zeros_like(x), x, p, seed) if p > 0 else x
-
-
-def _undrop(g, p, seed):
-    if p == 0:
-        return g
-    out = torch.empty_like(g)
-    ops.residual_dropout_bwd(g, p, seed, out)
-    return out
 
 
 class _BiasStack:
@@ -263,7 +246,7 @@ class _BlockFn(torch.autograd.Function):
         c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
         keep = None if dec else meta["keep"]
         ops.t5_attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0)
-        x1 = _add_dropout(xf, _linear(c0, wo), p, seeds[1])
+        x1 = add_dropout(xf, _linear(c0, wo), p, seeds[1])
         saved = [xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0]
         if dec:
             ln1, cq, ck, cv, co = params[5:10]
@@ -275,7 +258,7 @@ class _BlockFn(torch.autograd.Function):
             kv = _linear(ef, wkv)
             c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
             ops.t5_attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1)
-            x2 = _add_dropout(x1, _linear(c1, co), p, seeds[3])
+            x2 = add_dropout(x1, _linear(c1, co), p, seeds[3])
             saved += [ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1, x2]
         else:
             x2 = x1
@@ -284,8 +267,8 @@ class _BlockFn(torch.autograd.Function):
         pre = _linear(n2, wi)
         act = torch.empty_like(pre)
         ops.bias_act_fwd(pre, meta["zero_bias"], ops.ACTIVATIONS["relu"], act)
-        actd = _dropout(act, p, seeds[4])
-        x3 = _add_dropout(x2, _linear(actd, wff), p, seeds[5])
+        actd = dropout_fwd(act, p, seeds[4])
+        x3 = add_dropout(x2, _linear(actd, wff), p, seeds[5])
         saved += [lnf, wi, wff, n2, pre, actd]
         ctx.save_for_backward(*saved, meta["keep"])
         ctx.meta = dict(meta, p=p, seeds=seeds, shape=(B, S, D), dec=dec, table=params[-1])
@@ -306,10 +289,10 @@ class _BlockFn(torch.autograd.Function):
         dev = xf.device
         dx = dout.reshape(T, D).contiguous().float().clone()                      # the gradient of the residual stream, added to in place
         # feed forward
-        df = _undrop(dx, p, seeds[5])
+        df = _dropout_bwd(dx, D, p, seeds[5])
         dactd, dwff = _linear_bwd(df, actd, wff)
-        dact = _undrop(dactd, p, seeds[4])
-        ops.bias_act_bwd(pre, dact, ops.ACTIVATIONS["relu"], dact, torch.empty(modules._N_PARTIAL, pre.shape[1], **_f32(dev)))
+        dact = _dropout_bwd(dactd, dactd.shape[1], p, seeds[4])
+        ops.bias_act_bwd(pre, dact, ops.ACTIVATIONS["relu"], dact, torch.empty(_N_PARTIAL, pre.shape[1], **_f32(dev)))
         dn2, dwi = _linear_bwd(dact, n2, wi)
         dlnf = _rms_bwd(x2, lnf, eps, dn2, dx)
         cross = [None] * 5
@@ -317,7 +300,7 @@ class _BlockFn(torch.autograd.Function):
         if dec:
             ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1 = sv[9:19]
             Se = ef.shape[0] // B
-            da = _undrop(dx, p, seeds[3])
+            da = _dropout_bwd(dx, D, p, seeds[3])
             dc1, dco = _linear_bwd(da, c1, co)
             dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(B * Se, 2 * I, **_f32(dev))
             ops.t5_attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
@@ -328,7 +311,7 @@ class _BlockFn(torch.autograd.Function):
             cross = [dln1, dcq, dwkv[:I], dwkv[I:], dco]
             denc = denc.view(B, Se, D)
         # self attention
-        da = _undrop(dx, p, seeds[1])
+        da = _dropout_bwd(dx, D, p, seeds[1])
         dc0, dwo = _linear_bwd(da, c0, wo)
         dqkv = torch.empty(T, 3 * I, **_f32(dev))
         ops.t5_attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
@@ -340,30 +323,6 @@ class _BlockFn(torch.autograd.Function):
         return (dx.view(B, S, D), denc, None, *grads)
 
 
-class _EmbedFn(torch.autograd.Function):
-    """dropout(E[ids]); every row gets its gradient (T5's table has no padding row), into the shared table gradient."""
-
-    @staticmethod
-    def forward(ctx, ids, E, p, seed, shared):
-        B, L = ids.shape
-        x = torch.empty(B * L, E.shape[1], **_f32(E.device))
-        ops.embedding_fwd(ids, E, x)
-        x = _dropout(x, p, seed)
-        ctx.meta = (p, seed, E.shape)
-        ctx.shared = shared
-        ctx.save_for_backward(ids)
-        return x.view(B, L, -1)
-
-    @staticmethod
-    def backward(ctx, dx):
-        ids, = ctx.saved_tensors
-        p, seed, e_shape = ctx.meta
-        g = _dropout_bwd(dx, e_shape[1], p, seed)
-        dE = _SharedGrad.take(ctx.shared, e_shape, g.device)
-        ops.embedding_bwd_large(ids, g, -1, dE)
-        return None, _SharedGrad.give(ctx.shared, dE), None, None, None
-
-
 class _FinalNormFn(torch.autograd.Function):
     """dropout(RMSNorm(x)) * scale"""
 
@@ -371,7 +330,7 @@ class _FinalNormFn(torch.autograd.Function):
     def forward(ctx, x, w, eps, p, seed, scale):
         B, S, D = x.shape
         xf = x.reshape(B * S, D).contiguous().float()
-        y = _dropout(_rms(xf, w, eps), p, seed)
+        y = dropout_fwd(_rms(xf, w, eps), p, seed)
         ctx.meta = (eps, p, seed, scale, x.shape)
         ctx.save_for_backward(xf, w)
         return (y * scale if scale != 1.0 else y).view(B, S, D)
@@ -381,7 +340,7 @@ class _FinalNormFn(torch.autograd.Function):
         xf, w = ctx.saved_tensors
         eps, p, seed, scale, shape = ctx.meta
         g = dy.reshape(xf.shape).contiguous().float()
-        g = _undrop(g * scale if scale != 1.0 else g, p, seed)
+        g = _dropout_bwd(g * scale if scale != 1.0 else g, xf.shape[1], p, seed)
         dx = torch.zeros_like(xf)
         dw = _rms_bwd(xf, w, eps, g, dx)
         return dx.view(shape), dw, None, None, None, None
@@ -480,7 +439,7 @@ class TIGER(nn.Module):
         c = self.config
         p = c.dropout_rate if self.training else 0.0
         B, S = ids.shape
-        x = _EmbedFn.apply(ids.long().contiguous(), stack.embed_tokens.weight, p, _next_seed(), shared)
+        x = EmbedDropoutFn.apply(ids.long().contiguous(), stack.embed_tokens.weight, p, _next_seed(), shared, -1)
         blk0 = stack.block[0].layer[0].SelfAttention
         table = blk0.relative_attention_bias.weight
         bias = _BiasStack(table, self._bucket(S, not stack.is_decoder, ids.device), S, len(stack.block))
@@ -595,16 +554,16 @@ class _DecoderEval:
             qkv = _linear(_rms(x, L["ln0"], eps), L["wqkv"])
             c0 = torch.empty(N * S, I, **_f32(dev))
             ops.t5_attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], rel, None, N, S, S, h, d, True, 0.0, 0, c0, lse)
-            x = _add_dropout(x, _linear(c0, L["wo"]), 0.0, 0)
+            x = add_dropout(x, _linear(c0, L["wo"]), 0.0, 0)
             q1 = _linear(_rms(x, L["ln1"], eps), L["cq"])
             c1 = torch.empty(N * S, I, **_f32(dev))
             ops.t5_attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
                             kv_rows=kv_rows, kv_batch=self.users)
-            x = _add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
+            x = add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
             pre = _linear(_rms(x, L["lnf"], eps), L["wi"])
             act = torch.empty_like(pre)
             ops.bias_act_fwd(pre, m._zero_bias, relu, act)
-            x = _add_dropout(x, _linear(act, L["wff"]), 0.0, 0)
+            x = add_dropout(x, _linear(act, L["wff"]), 0.0, 0)
         last = x.view(N, S, -1)[:, -1, :].contiguous()
         return _rms(last, m.decoder.final_layer_norm.weight.detach(), eps) * (c.d_model ** -0.5)
 

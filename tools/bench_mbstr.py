@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from gamer_amd import mbstr, ops, rec_common  # noqa: E402
+from gamer_amd import layer_blocks, mbstr, ops, rec_common  # noqa: E402
 from gamer_amd.mbstr import MBSTR, MBSTRConfig  # noqa: E402
 
 DEV = "cuda:0"
@@ -138,15 +138,15 @@ def ffn_pair(B, L, H, dff, b, g):
 
     def grouped():
         with ops.f32_matmul("f32"):
-            lists = mbstr._TypeLists(types, b)
+            lists = layer_blocks._TypeLists(types, b)
             perm, grp = lists.perm, dict(groups=b, group_offsets=lists.offsets[1:])
-            xa = mbstr._with_ones(x.index_select(0, perm))
-            w1a, w2a = mbstr._aug_weights(w1, b1), mbstr._aug_weights(w2, b2)
+            xa = layer_blocks._with_ones(x.index_select(0, perm))
+            w1a, w2a = layer_blocks._aug_weights(w1, b1), layer_blocks._aug_weights(w2, b2)
             pre = torch.zeros(T, dff, **f32)
             ops.linear_fwd(xa, H + 4, w1a, H + 4, pre, dff, T, dff, H + 4, strideB=dff * (H + 4), **grp)
             a1 = torch.empty(T, dff, **f32)
             ops.bias_act_fwd(pre, torch.zeros(dff, **f32), relu, a1)
-            a1a = mbstr._with_ones(a1)
+            a1a = layer_blocks._with_ones(a1)
             ys = torch.zeros(T, H, **f32)
             ops.linear_fwd(a1a, dff + 4, w2a, dff + 4, ys, H, T, H, dff + 4, strideB=H * (dff + 4), **grp)
             y = torch.empty(T, H, **f32)
