@@ -218,6 +218,8 @@ _SIGNATURES = {
     "gamer_hg_fuse_bwd": [P, P, P, P, P, L, I, P, P, P, I, P],
     "gamer_t5_attn_fwd": [P, I, P, I, P, I, P, P, P, I, I, I, I, I, I, F, U, P, I, P, P],
     "gamer_t5_attn_bwd": [P, I, P, I, P, I, P, P, I, I, I, I, I, I, F, U, P, I, P, P, I, P, I, P, I, P, I, P],
+    "gamer_t5_attn_long_fwd": [P, I, P, I, P, I, P, P, P, I, I, I, I, I, I, F, U, P, I, P, P],
+    "gamer_t5_attn_long_bwd": [P, I, P, I, P, I, P, P, I, I, I, I, I, I, F, U, P, I, P, P, I, P, I, P, I, P, I, P, P],
     "gamer_t5_bias_expand": [P, P, I, I, I, P, P],
     "gamer_t5_bias_fold": [P, I, I, I, I, P, I, P, P],
 }

@@ -2006,7 +2006,7 @@ def wass_table_bwd(Em, Ec, V, dE2, dc, dEm, dEc):
     call("gamer_wass_table_bwd", ptr(Em), ptr(Ec), ptr(dE2), ptr(dc), V, H, ptr(dEm), ptr(dEc), stream_ptr())
 
 
-# ---- T5's attention (TIGER; csrc/t5_attention.hip) ----------------------------------------------------------------------------------
+# ---- T5's attention (TIGER; csrc/t5_attention.hip, csrc/t5_attention_long.hip) --------------------------------------------------------
 T5_MAX_S, T5_MAX_H, T5_HEAD_DIMS = 128, 16, (32, 64)
 
 
@@ -2017,8 +2017,8 @@ def t5_check_limits(Sq, Sk, h, d):
                                   f"{T5_HEAD_DIMS} (got Sq={Sq}, Sk={Sk}, heads={h}, head size={d})")
 
 
-def _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, Bkv=None):
-    t5_check_limits(Sq, Sk, h, d)
+def _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, Bkv=None, check=None):
+    (check or t5_check_limits)(Sq, Sk, h, d)
     Bkv = B if Bkv is None else Bkv
     for t, n, S, Bt in ((q, "q", Sq, B), (k, "k", Sk, Bkv), (v, "v", Sk, Bkv)):
         _chk(t, torch.float32, n)
@@ -2030,17 +2030,17 @@ def _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, Bkv=None):
         raise RuntimeError(f"t5 attention: keep uint8 [{Bkv}, {Sk}]")
 
 
-def t5_attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, o, lse, kv_rows=None, kv_batch=None):
+def t5_attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, o, lse, kv_rows=None, kv_batch=None, _long=False):
     """gamer_t5_attn_fwd: q / o [B Sq, h d], k / v [B Sk, h d] (row-strided views), rel [h, Sq + Sk - 1] or None, keep uint8 [B, Sk] or
     None, lse [B, h, Sq].  No 1 / sqrt(d) scale.  kv_rows int32 [B] with kv_batch: k / v / keep hold kv_batch rows and row b reads
     row kv_rows[b] of them (values in [0, kv_batch): checked by the caller; decoding only - there is no backward for it)."""
     if (kv_rows is None) != (kv_batch is None) or (kv_rows is not None and _dense(kv_rows, torch.int32, "kv_rows").shape != (B,)):
         raise RuntimeError("t5_attn_fwd: kv_rows int32 [B] goes with kv_batch")
-    _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, kv_batch)
+    _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, kv_batch, t5_long_check_limits if _long else None)
     _chk(o, torch.float32, "o"), _dense(lse, torch.float32, "lse")
     if o.shape != (B * Sq, h * d) or o.stride(1) != 1 or lse.numel() != B * h * Sq:
         raise RuntimeError("t5_attn_fwd: o [B Sq, h d] and lse [B, h, Sq]")
-    call("gamer_t5_attn_fwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(keep), ptr(kv_rows), B, Sq, Sk,
+    call("gamer_t5_attn_long_fwd" if _long else "gamer_t5_attn_fwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(keep), ptr(kv_rows), B, Sq, Sk,
          h, d, int(bool(causal)), float(p_drop), int(seed), ptr(o), o.stride(0), ptr(lse), stream_ptr())
 
 
@@ -2049,10 +2049,10 @@ def t5_n_slab(B, h):
     return max(1, min(B, 512 // max(1, h)))
 
 
-def t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial):
+def t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial, _long=False):
     """gamer_t5_attn_bwd: dq / dk / dv are written in full; drel_partial [n, h, Sq + Sk - 1] (None iff rel is None) is written in
     full by its n h workgroups (n <= B); without a bias n = t5_n_slab(B, h)."""
-    _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d)
+    _t5_common(q, k, v, rel, keep, B, Sq, Sk, h, d, check=t5_long_check_limits if _long else None)
     for t, n, S in ((d_o, "d_o", Sq), (dq, "dq", Sq), (dk, "dk", Sk), (dv, "dv", Sk)):
         _chk(t, torch.float32, n)
         if t.shape != (B * S, h * d) or t.stride(1) != 1:
@@ -2066,9 +2066,35 @@ def t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, d_o, 
         n = drel_partial.shape[0]
         if _dense(drel_partial, torch.float32, "drel_partial").shape != (n, h, Sq + Sk - 1) or not 0 < n <= B:
             raise RuntimeError(f"t5_attn_bwd: drel_partial [n, {h}, {Sq + Sk - 1}], 0 < n <= B")
-    call("gamer_t5_attn_bwd", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(keep), B, Sq, Sk, h, d,
-         int(bool(causal)), float(p_drop), int(seed), ptr(d_o), d_o.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk),
-         dk.stride(0), ptr(dv), dv.stride(0), ptr(drel_partial), n, stream_ptr())
+    args = (ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(keep), B, Sq, Sk, h, d, int(bool(causal)),
+            float(p_drop), int(seed), ptr(d_o), d_o.stride(0), ptr(lse), ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv),
+            dv.stride(0), ptr(drel_partial), n)
+    if _long:
+        row_ws = torch.empty(2, B, h, Sq, dtype=torch.float32, device=q.device)  # the softmax backward's row terms
+        call("gamer_t5_attn_long_bwd", *args, ptr(row_ws), stream_ptr())
+    else:
+        call("gamer_t5_attn_bwd", *args, stream_ptr())
+
+
+# the key-streaming family (csrc/t5_attention_long.hip): the same semantics for Sq, Sk <= 512, no buffer sized by the sequence
+T5_LONG_MAX_S = 512
+
+
+def t5_long_check_limits(Sq, Sk, h, d):
+    """The limits of the key-streaming T5 attention kernels, refused on the host before any launch."""
+    if Sq < 1 or Sk < 1 or Sq > T5_LONG_MAX_S or Sk > T5_LONG_MAX_S or h < 1 or h > T5_MAX_H or d not in T5_HEAD_DIMS:
+        raise NotImplementedError(f"T5 attention on the HIP path (key-streaming kernels): Sq, Sk <= {T5_LONG_MAX_S}, heads <= {T5_MAX_H}, "
+                                  f"head size in {T5_HEAD_DIMS} (got Sq={Sq}, Sk={Sk}, heads={h}, head size={d})")
+
+
+def t5_attn_long_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, o, lse, kv_rows=None, kv_batch=None):
+    """gamer_t5_attn_long_fwd: the arguments of t5_attn_fwd, Sq, Sk <= 512."""
+    t5_attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, o, lse, kv_rows, kv_batch, _long=True)
+
+
+def t5_attn_long_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial):
+    """gamer_t5_attn_long_bwd: the arguments of t5_attn_bwd, Sq, Sk <= 512; allocates the row-term workspace [2, B, h, Sq]."""
+    t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial, _long=True)
 
 
 def t5_bias_expand(table, bucket, rel):

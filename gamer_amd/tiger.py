@@ -13,7 +13,8 @@ Every step runs as HIP kernels, with no PyTorch fallback (a CPU tensor raises):
   a block       one autograd function: T5's RMS norm (gamer_rmsnorm_fwd / _bwd), ONE [q|k|v] GEMM for self attention, one [k|v]
                 GEMM on the encoder output per decoder layer, gamer_t5_attn_fwd / _bwd, the Linear forward / dgrad / wgrad,
                 ReLU through gamer_bias_act (zero bias), residual dropout
-  attention     csrc/t5_attention.hip: no 1 / sqrt(d), the bucketed relative bias of block 0 added in every layer of its stack,
+  attention     csrc/t5_attention.hip up to 128 tokens, csrc/t5_attention_long.hip (K / V streamed in key blocks) up to 512, picked
+                per call by the shape: no 1 / sqrt(d), the bucketed relative bias of block 0 added in every layer of its stack,
                 key padding mask and causality inside the kernel; nothing of size S x S reaches memory.  The bias table is
                 expanded once per stack per step (gamer_t5_bias_expand) and its gradient folded once per stack, after block 0's
                 backward, from the per-layer slabs in layer order (gamer_t5_bias_fold)
@@ -38,7 +39,10 @@ from . import modules, ops
 from .layer_blocks import _N_PARTIAL, _dropout_bwd, add_dropout, colsum, dropout_fwd
 from .rec_common import CatalogCEFn, DropUnknownConfig, EmbedDropoutFn, _SharedGrad, _next_seed
 
+# MAX_ENCODER_LEN: the bound of the resident attention kernels (K / V of a head in LDS); longer encoders, up to
+# MAX_LONG_ENCODER_LEN, run on the key-streaming kernels.  The decoder's self attention always runs resident.
 MAX_ENCODER_LEN, MAX_DECODER_LEN = 128, 8
+MAX_LONG_ENCODER_LEN = 512
 
 
 @dataclasses.dataclass(init=False)
@@ -198,6 +202,15 @@ def _rms_bwd(x, w, eps, dy, dx):
     return colsum(part)
 
 
+def _attn_fwd(q, k, v, rel, keep, B, Sq, Sk, *rest, **kw):
+    """t5_attn_fwd on the kernel family that the shape needs: resident up to ops.T5_MAX_S, key-streaming above"""
+    (ops.t5_attn_long_fwd if max(Sq, Sk) > ops.T5_MAX_S else ops.t5_attn_fwd)(q, k, v, rel, keep, B, Sq, Sk, *rest, **kw)
+
+
+def _attn_bwd(q, k, v, rel, keep, B, Sq, Sk, *rest):
+    (ops.t5_attn_long_bwd if max(Sq, Sk) > ops.T5_MAX_S else ops.t5_attn_bwd)(q, k, v, rel, keep, B, Sq, Sk, *rest)
+
+
 class _BiasStack:
     """The relative bias of one stack for one step: ``rel`` [h, 2 S - 1] expanded once from block 0's table; in the backward every
     block writes its slabs of the offset gradient into ``slabs`` [layers, n, h, 2 S - 1] and block 0, whose backward runs last,
@@ -245,7 +258,7 @@ class _BlockFn(torch.autograd.Function):
         qkv = _linear(n0, wqkv)
         c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
         keep = None if dec else meta["keep"]
-        ops.t5_attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0)
+        _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0)
         x1 = add_dropout(xf, _linear(c0, wo), p, seeds[1])
         saved = [xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0]
         if dec:
@@ -257,7 +270,7 @@ class _BlockFn(torch.autograd.Function):
             wkv = torch.cat([ck, cv], 0).contiguous()
             kv = _linear(ef, wkv)
             c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
-            ops.t5_attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1)
+            _attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1)
             x2 = add_dropout(x1, _linear(c1, co), p, seeds[3])
             saved += [ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1, x2]
         else:
@@ -303,8 +316,8 @@ class _BlockFn(torch.autograd.Function):
             da = _dropout_bwd(dx, D, p, seeds[3])
             dc1, dco = _linear_bwd(da, c1, co)
             dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(B * Se, 2 * I, **_f32(dev))
-            ops.t5_attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
-                            dkv[:, :I], dkv[:, I:], None)
+            _attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
+                      dkv[:, :I], dkv[:, I:], None)
             dn1, dcq = _linear_bwd(dq1, n1, cq)
             denc, dwkv = _linear_bwd(dkv, ef, wkv)
             dln1 = _rms_bwd(x1, ln1, eps, dn1, dx)
@@ -314,8 +327,8 @@ class _BlockFn(torch.autograd.Function):
         da = _dropout_bwd(dx, D, p, seeds[1])
         dc0, dwo = _linear_bwd(da, c0, wo)
         dqkv = torch.empty(T, 3 * I, **_f32(dev))
-        ops.t5_attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
-                        seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B))
+        _attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
+                  seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B))
         dn0, dwqkv = _linear_bwd(dqkv, n0, wqkv)
         dln0 = _rms_bwd(xf, ln0, eps, dn0, dx)
         dtable = bias.fold(mt["table"].shape[0]) if mt["table"] is not None else None
@@ -461,7 +474,7 @@ class TIGER(nn.Module):
 
     def encode(self, input_ids, attention_mask=None):
         """(encoder output [B, Se, D], keep uint8 [B, Se])"""
-        self._check(input_ids, MAX_ENCODER_LEN, "encoder")
+        self._check(input_ids, MAX_LONG_ENCODER_LEN, "encoder")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         keep = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous()
@@ -498,7 +511,7 @@ class TIGER(nn.Module):
         train = labels is not None and torch.is_grad_enabled()
         shared = _SharedGrad(gathers=2) if train and self.shared.weight.requires_grad else None
         # (the encoder's gather is the other user of the table's gradient buffer: it gets the same hand-over object)
-        self._check(input_ids, MAX_ENCODER_LEN, "encoder")
+        self._check(input_ids, MAX_LONG_ENCODER_LEN, "encoder")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         keep = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous()
@@ -553,12 +566,12 @@ class _DecoderEval:
         for L in self.layers:
             qkv = _linear(_rms(x, L["ln0"], eps), L["wqkv"])
             c0 = torch.empty(N * S, I, **_f32(dev))
-            ops.t5_attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], rel, None, N, S, S, h, d, True, 0.0, 0, c0, lse)
+            _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], rel, None, N, S, S, h, d, True, 0.0, 0, c0, lse)
             x = add_dropout(x, _linear(c0, L["wo"]), 0.0, 0)
             q1 = _linear(_rms(x, L["ln1"], eps), L["cq"])
             c1 = torch.empty(N * S, I, **_f32(dev))
-            ops.t5_attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
-                            kv_rows=kv_rows, kv_batch=self.users)
+            _attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
+                      kv_rows=kv_rows, kv_batch=self.users)
             x = add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
             pre = _linear(_rms(x, L["lnf"], eps), L["wi"])
             act = torch.empty_like(pre)

@@ -73,6 +73,9 @@ def parse_args(argv=None):
         raise NotImplementedError(f"--lr_scheduler_type {a.lr_scheduler_type}: only cosine (gamer_amd/schedule.py)")
     if a.optim not in ("adamw_torch", "adamw"):
         raise NotImplementedError(f"--optim {a.optim}: only AdamW (gamer_adamw)")
+    if not 1 <= a.model_max_length <= tiger.MAX_LONG_ENCODER_LEN:
+        raise NotImplementedError(f"--model_max_length {a.model_max_length}: the encoder runs at most {tiger.MAX_LONG_ENCODER_LEN} tokens "
+                                  f"on the HIP path (tiger.MAX_LONG_ENCODER_LEN)")
     return a
 
 

@@ -1085,6 +1085,21 @@ int gamer_t5_attn_bwd(const float* q, int ldq, const float* k, int ldk, const fl
                       int B, int Sq, int Sk, int H, int head_dim, int causal, float p_drop, uint64_t seed, const float* d_o,
                       int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv, float* drel_partial,
                       int n_slab, void* stream);
+/* The key-streaming family (csrc/t5_attention_long.hip): the same semantics, arguments and outputs as gamer_t5_attn_fwd / _bwd for
+ * 1 <= Sq, Sk <= 512 (H <= 16, head_dim 32 or 64, the same leading-dimension and alignment rules; refused before any launch).  K / V
+ * pass through LDS in blocks of 64 keys, so no buffer is sized by the sequence and nothing of size Sq x Sk reaches memory.  Both
+ * families accept every shape within their limits; the results agree to rounding, not bit for bit.  No float atomics: two calls give
+ * the same bits. */
+int gamer_t5_attn_long_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                           const uint8_t* keep, const int32_t* kv_rows, int B, int Sq, int Sk, int H, int head_dim, int causal,
+                           float p_drop, uint64_t seed, float* o, int ldo, float* lse, void* stream);
+/* row_ws: workspace of 2 B H Sq floats for the softmax backward's two row terms (written, then read, by this call's launches): the
+ * normaliser 1 / sum_j exp(s_ij - lse_i) of the recomputed probabilities and delta_i, summed from dropout(p) dP as in
+ * gamer_t5_attn_bwd.  drel_partial and n_slab as in gamer_t5_attn_bwd. */
+int gamer_t5_attn_long_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                           const uint8_t* keep, int B, int Sq, int Sk, int H, int head_dim, int causal, float p_drop, uint64_t seed,
+                           const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
+                           float* drel_partial, int n_slab, float* row_ws, void* stream);
 /* rel [H][n_offsets] = table [num_buckets][H] at bucket[offset] (the bucket of every relative offset is computed on the host) */
 int gamer_t5_bias_expand(const float* table, const int32_t* bucket, int num_buckets, int H, int n_offsets, float* rel, void* stream);
 /* dtable [num_buckets][H] from drel_partial [n_layers][n_slab][H][n_offsets]: per layer the slabs in order and the offsets of a bucket

@@ -5,13 +5,15 @@
     dropout 0.1, the T5 vocabulary of 32,128 rows) at batch ``--batch`` x encoder length ``--enc`` with 5 decoder tokens on random
     ids (full-length rows): time, sequences/s, peak allocated memory;
   * one layer's self attention at the encoder's shape and one cross attention (5 queries), forward + backward with every gradient
-    (the bias table's included): gamer_t5_attn_fwd / _bwd + gamer_t5_bias_expand / _fold against a torch composition written here,
-    which forms the [B, h, S, S] scores, probabilities and dropout mask and lets autograd differentiate them; time and peak
-    allocated memory of each, and which one is slower;
+    (the bias table's included): the model's attention dispatch (tiger._attn_fwd / _attn_bwd: the resident kernels up to 128
+    tokens, the key-streaming ones above) + gamer_t5_bias_expand / _fold against a torch composition written here, which forms
+    the [B, h, S, S] scores, probabilities and dropout mask and lets autograd differentiate them; time and peak allocated memory
+    of each, which one is slower, and whether the fused temporaries stay below a tenth of the composition's;
   * trie-constrained beam search at ``--users`` users x ``--beams`` beams over ``--items`` random items of 4 tokens: users/s.
 Medians of ``--steps`` device-event timings after ``--warmup``.  Prints one JSON line per (batch, encoder length).
 
-  python tools/bench_tiger.py --batch 256,1024 --enc 81,101 --steps 8 --warmup 3
+  python tools/bench_tiger.py --batch 256,1024 --enc 81,101,401,506 --steps 8 --warmup 3
+(81 / 101: 20 items of train_decoder / of the behaviour layouts; 401: 100 items of train_decoder; 506: the longest generative row)
 """
 import argparse
 import json
@@ -72,8 +74,8 @@ def attention_pair(B, Sq, Sk, h, d, bias, p, g):
             rel = torch.empty(h, R, device=DEV)
             ops.t5_bias_expand(table, bucket, rel)
             slabs = torch.empty(1, ops.t5_n_slab(B, h), h, R, device=DEV)
-        ops.t5_attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, False, p, 7, o, lse)
-        ops.t5_attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, False, p, 7, d_o, lse, dq, dk, dv, None if slabs is None else slabs[0])
+        tiger._attn_fwd(q, k, v, rel, keep, B, Sq, Sk, h, d, False, p, 7, o, lse)
+        tiger._attn_bwd(q, k, v, rel, keep, B, Sq, Sk, h, d, False, p, 7, d_o, lse, dq, dk, dv, None if slabs is None else slabs[0])
         if bias:
             ops.t5_bias_fold(slabs, bucket, torch.empty(32, h, device=DEV))
 
@@ -98,6 +100,7 @@ def bench_attention(B, Sq, Sk, bias, a, g):
     fused, comp = attention_pair(B, Sq, Sk, 6, 64, bias, 0.1, g)
     r = dict(fused_ms=timed(fused, a.steps, a.warmup), fused_mib=peak(fused), torch_ms=timed(comp, a.steps, a.warmup), torch_mib=peak(comp))
     r["fused_slower"] = r["fused_ms"] > r["torch_ms"]
+    r["fused_temporaries_below_a_tenth"] = r["fused_mib"] < 0.1 * r["torch_mib"]
     return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()}
 
 
@@ -135,7 +138,7 @@ def bench_beams(S, a, g):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="256,1024")
-    ap.add_argument("--enc", default="81,101")
+    ap.add_argument("--enc", default="81,101,401,506")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--users", type=int, default=256)
