@@ -60,6 +60,10 @@ class GemmDesc(C.Structure):
         ("sw_gu", c_void_p), ("sw_ld", c_int64),
         ("group_div", c_int), ("sw_tbl", c_void_p), ("b_planes_t", c_void_p),
         ("sw_hm", c_void_p), ("sw_row_group", c_void_p),
+        ("norm_x", c_void_p), ("norm_w", c_void_p), ("norm_eps", c_float),
+        ("norm_dst_rows", c_void_p), ("norm_src_rows", c_void_p),
+        ("bias_idx", c_void_p), ("bias_q", c_void_p), ("bias_k", c_void_p), ("bias_v", c_void_p),
+        ("bias_rows", c_int), ("bias_nq", c_int), ("bias_nkv", c_int),
     ]
 
 

@@ -1550,7 +1550,33 @@ static int gemm_entry(const gamer_gemm_desc* d, void* stream, int split) {
                     "gamer_gemm_f32: the SwiGLU-forward epilogue (sw_hm) needs a Linear-forward layout with N = 2 I (N=%d), alpha = 1, no other "
                     "epilogue, and sw_row_group with sw_tbl", d->N);
     // short-contraction Linear forward from packed weight pieces: the activation-stationary kernel (csrc/gemm_as.hip)
+    GAMER_CHECK_ARG(!d->norm_x || (d->norm_w && d->group_mode == 0 && a_kc && b_kc && d->norm_eps > 0.f && d->K % 4 == 0 && d->K <= 1024 &&
+                                   aligned16(d->norm_x) && aligned16(d->norm_w) &&
+                                   (d->norm_dst_rows != nullptr) == (d->norm_src_rows != nullptr)),
+                    "gamer_gemm_f32: the RMSNorm prologue (norm_x) needs a Linear-forward layout, norm_w, norm_eps > 0, K %% 4 == 0 (K=%d) "
+                    "and norm_dst_rows / norm_src_rows both or neither", d->K);
+    GAMER_CHECK_ARG(!d->bias_idx || (d->bias_q && d->bias_k && d->bias_v && d->group_mode == 0 && d->groups == 1 && a_kc && b_kc &&
+                                     !d->accumulate && !d->resid && !d->rowdot_out && !d->qk_q_rot && !d->sw_gu && !d->sw_hm &&
+                                     d->bias_rows >= 1 && d->bias_nq > 0 && d->bias_nkv > 0 && d->bias_nq % 4 == 0 && d->bias_nkv % 4 == 0 &&
+                                     d->N == d->bias_nq + 2 * d->bias_nkv && d->ldc % 4 == 0 && aligned16(d->C) && aligned16(d->bias_q) &&
+                                     aligned16(d->bias_k) && aligned16(d->bias_v)),
+                    "gamer_gemm_f32: the bias-row epilogue (bias_idx) needs a plain Linear-forward GEMM with one group, three tables and "
+                    "N = bias_nq + 2 bias_nkv in multiples of 4 (N=%d)", d->N);
     if (split == 3 && gemm_as_eligible(d, a_kc, b_kc, p.b_planes)) return launch_gemm_as(d, p.b_planes, b_kc, (hipStream_t)stream);
+    if (d->norm_x || d->bias_idx) {
+        // a norm prologue / bias epilogue that kernel did not take (few rows, no packed pieces yet, another product form or K, a switch
+        // off): the separate launches they stand for - gamer_rmsnorm_fwd into A, the product, the pass that adds the bias rows
+        gamer_gemm_desc d2 = *d;
+        if (d->norm_x) {
+            if (d->amax_a) gamer_amax_sink(const_cast<uint32_t*>(d->amax_a), nullptr);
+            GAMER_TRY(gamer_rmsnorm_fwd(d->norm_x, d->norm_w, d->M, d->K, d->norm_eps, d->norm_dst_rows, const_cast<float*>(d->A), (int)d->a_rs,
+                                        stream));
+            d2.norm_x = nullptr; d2.norm_w = nullptr; d2.norm_dst_rows = nullptr; d2.norm_src_rows = nullptr;
+        }
+        if (d->bias_idx) { d2.bias_idx = nullptr; d2.amax_c = nullptr; }
+        GAMER_TRY(gemm_entry(&d2, stream, split));
+        return d->bias_idx ? launch_gemm_bias_rows(d, (hipStream_t)stream) : 0;
+    }
     if (d->sw_hm) {
         // sw_hm not taken by that kernel (few rows, no packed pieces yet, another product form): the projection as it would run without
         // it, then gamer_swiglu_fwd_ld(_tbl) on its output - the same results by definition

@@ -16,6 +16,9 @@
 //     the other is multiplied - one barrier per slab of 48 MFMAs per wave (K = 256), no vector work in the loop but the epilogue's scale;
 //   * C^T = W A^T puts the output row on the lane: the tile leaves as 16-byte stores per lane.
 // A is read once, C written once, W (<= 1 MB) comes from the L2 once per 128 rows.
+// Because the lane holds its whole (half) row before the cut, the RMSNorm in front of these projections is a prologue here (NORM: the
+// launch reads the residual stream, stores the normalised rows once for the weight gradient and never reads them back), and because the
+// lane owns an output row, the cross block's per-row behaviour biases are an epilogue (BIAS: the table waits in LDS).
 //
 // Measured (batch 1024 x 505 tokens, tools/dev_gemm_as_time.py): q|k|v [517120 x 256] x [768 x 256]^T 0.94 ms (tile kernel) -> 0.70,
 // tied head (N = 1041) 1.36 -> 0.95, the experts' gate|up (N = 1024, grouped) 1.37 -> 0.97; the forward GEMMs of a step 39.0 -> 33.4 ms
@@ -70,6 +73,14 @@ struct AsParams {
     // The slabs are walked gate 0, up 0, gate 1, up 1, ...; tbl (optional): [groups][N] added to the values hm is computed from (not to
     // C); group_div: that many consecutive row groups share one W.
     float* hm; const float* tbl; int group_div;
+    // NORM (W k-contiguous, K == the hidden size): A holds the rows BEFORE the RMSNorm.  The lane normalises its half row in registers
+    // - norm_w * (x * rstd), rstd = rsqrtf(sum x^2 / K + eps): rmsnorm_fwd_kernel's arithmetic per element -, stores it to h [.][ldh]
+    // (the weight gradient reads it) and cuts its pieces from those values.  src_rows (optional): row m of the launch reads row
+    // src_rows[m] of A (the experts' sorted order: slot -> token); h is written at row m.  amax_h: slot of max |h|.
+    const float* norm_w; float norm_eps; float* h; int64_t ldh; const int32_t* src_rows; uint32_t* amax_h;
+    // BIAS (EPI 0): C[m][n] = (alpha * acc) + table[act_idx[m]][n], the table's columns [0, c1) from bias_q [nb1][c1], [c1, c2) from
+    // bias_k [nb1][c2 - c1], [c2, N) from bias_v [nb1][N - c2] (the cross block's behaviour biases); amax_c sees the biased values
+    const int32_t* act_idx; const float* bias_q; const float* bias_k; const float* bias_v; int bias_c1, bias_c2, nb1;
 };
 
 // KP = K / 64 panels.  WRC = false: W [N][K] (k-contiguous, the Linear-forward layout): piece images [n][64 k] per panel, fragments by
@@ -78,9 +89,13 @@ struct AsParams {
 // accumulate), 2 row-dot, 4 SwiGLU backward (the epilogues of csrc/gemm.hip, same definitions).
 // NW = waves per workgroup (32 rows each): 4 (two workgroups per CU, out of step) or 8 (one; W is fetched once per 256 rows - faster for
 // the wide ungrouped launches, q|k|v 0.73 -> 0.68 ms, head 0.97 -> 0.93; slower for the grouped gate|up, 0.97 -> 1.15, and the 256-column gate)
-template <int KP, bool WRC, int EPI, int NW>
+// NORM / BIAS: the RMSNorm prologue and the bias-row epilogue of AsParams (W k-contiguous forms only); launches without them run the
+// instantiations with both flags off.
+template <int KP, bool WRC, int EPI, int NW, bool NORM = false, bool BIAS = false>
 __global__ void __launch_bounds__(64 * NW, AS_DEPTH == 2 ? 1 : 8 / NW)
 gemm_as_kernel(const AsParams p) {
+    static_assert(!(NORM || BIAS) || !WRC, "the norm prologue and the bias epilogue are built for W k-contiguous");
+    static_assert(!BIAS || EPI == 0, "the bias epilogue belongs to the plain store");
     constexpr int AS_WAVES_K = NW, AS_THREADS_K = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char as_raw[];
     bf16_t* const wimg = reinterpret_cast<bf16_t*>(as_raw);                // [buffer 2][piece 2][panel KP][AS_PANEL]
@@ -110,12 +125,35 @@ gemm_as_kernel(const AsParams p) {
     bf16x8 af[2][KP * 4];
     float row_inv;
     {
-        const float* arow = p.A + (int64_t)(valid_m ? m : row_end - 1) * p.lda + 8 * h;
+        int64_t src_row = valid_m ? m : row_end - 1;
+        if (NORM && p.src_rows) src_row = p.src_rows[src_row];
+        const float* arow = p.A + src_row * p.lda + 8 * h;
         float4 raw[KP * 8];
 #pragma unroll
         for (int s = 0; s < KP * 4; ++s) {
             raw[2 * s] = *reinterpret_cast<const float4*>(arow + 16 * s);
             raw[2 * s + 1] = *reinterpret_cast<const float4*>(arow + 16 * s + 4);
+        }
+        if constexpr (NORM) {
+            // the row's sum of squares: this lane's half, then the other's (the exchange the row maximum below uses)
+            float ss = 0.f;
+#pragma unroll
+            for (int i = 0; i < KP * 8; ++i) ss += raw[i].x * raw[i].x + raw[i].y * raw[i].y + raw[i].z * raw[i].z + raw[i].w * raw[i].w;
+            ss = xor32_sum(ss);
+            const float rstd = rsqrtf(ss * (1.f / (float)(KP * 64)) + p.norm_eps);
+            float* hrow = p.h + (int64_t)m * p.ldh + 8 * h;
+            const float* wrow = p.norm_w + 8 * h;
+#pragma unroll
+            for (int s = 0; s < KP * 4; ++s) {                           // (the weight per k-step: nothing of it is held)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const float4 w4 = *reinterpret_cast<const float4*>(wrow + 16 * s + 4 * j);
+                    float4 x = raw[2 * s + j];
+                    x.x = w4.x * (x.x * rstd); x.y = w4.y * (x.y * rstd); x.z = w4.z * (x.z * rstd); x.w = w4.w * (x.w * rstd);
+                    raw[2 * s + j] = x;
+                    if (valid_m) *reinterpret_cast<float4*>(hrow + 16 * s + 4 * j) = x;
+                }
+            }
         }
         float mx = 0.f;
 #pragma unroll
@@ -124,6 +162,15 @@ gemm_as_kernel(const AsParams p) {
             mx = fmaxf(fmaxf(fmaxf(mx, fabsf(raw[i].x)), fabsf(raw[i].y)), fmaxf(fabsf(raw[i].z), fabsf(raw[i].w)));
         }
         mx = xor32_max(mx);                                              // the row's other half
+        if constexpr (NORM) {
+            // max |h| of the wave's rows (rows past the end are zeros) into the slot the GEMMs that read h take; one atomic per wave
+            if (p.amax_h) {
+                uint32_t hm = __float_as_uint(mx);
+#pragma unroll
+                for (int o2 = 16; o2 > 0; o2 >>= 1) hm = max(hm, (uint32_t)__shfl_xor((int)hm, o2, 64));
+                if (lane == 0 && hm) amax_publish(hm, p.amax_h, blockIdx.x * AS_WAVES_K + w);
+            }
+        }
         float s_row = 1.f;
         row_inv = 1.f;
         if (mx > 0.f) scale_from_amax(__float_as_uint(mx), s_row, row_inv);
@@ -215,6 +262,20 @@ gemm_as_kernel(const AsParams p) {
         const float4* src = reinterpret_cast<const float4*>(p.tbl + (int64_t)grp * p.N);
         for (int i = tid; i < p.N / 4; i += AS_THREADS_K) reinterpret_cast<float4*>(tbl_lds)[i] = src[i];
     }
+    // BIAS: the whole [nb1][N] table waits in the same place (a load from memory inside the slab epilogue is waited for on the spot);
+    // the lane's row of it is fixed for the launch
+    int bias_row = 0;
+    if constexpr (BIAS) {
+        const int n4 = p.N >> 2;
+        for (int i = tid; i < p.nb1 * n4; i += AS_THREADS_K) {
+            const int a = i / n4, c = 4 * (i - a * n4);
+            const float* src = c < p.bias_c1 ? p.bias_q + (int64_t)a * p.bias_c1 + c
+                             : c < p.bias_c2 ? p.bias_k + (int64_t)a * (p.bias_c2 - p.bias_c1) + (c - p.bias_c1)
+                                             : p.bias_v + (int64_t)a * (p.N - p.bias_c2) + (c - p.bias_c2);
+            reinterpret_cast<float4*>(tbl_lds)[i] = *reinterpret_cast<const float4*>(src);
+        }
+        if (valid_m) bias_row = min(max(p.act_idx[m], 0), p.nb1 - 1) * p.N;
+    }
 
     float cmax = 0.f;
     float* crow = p.C + (int64_t)m * p.ldc;
@@ -260,6 +321,13 @@ gemm_as_kernel(const AsParams p) {
                             float4 t4 = make_float4(acc[nt][4 * g4] * out_scale, acc[nt][4 * g4 + 1] * out_scale,
                                                     acc[nt][4 * g4 + 2] * out_scale, acc[nt][4 * g4 + 3] * out_scale);
                             if (AS_ABLATE & 1) { asm volatile("" :: "v"(t4.x), "v"(t4.y), "v"(t4.z), "v"(t4.w)); continue; }
+                            if constexpr (BIAS) {
+                                // (alpha * acc) + bias as TWO rounded operations - the bits of the store followed by the add of
+                                // qknorm_rope_fwd; the empty asm keeps the compiler from contracting them into one fma.  N % 4 == 0.
+                                asm volatile("" : "+v"(t4.x), "+v"(t4.y), "+v"(t4.z), "+v"(t4.w));
+                                const float4 b4 = *reinterpret_cast<const float4*>(tbl_lds + bias_row + col);
+                                t4.x += b4.x; t4.y += b4.y; t4.z += b4.z; t4.w += b4.w;
+                            }
                             if (EPI == 4) {
                                 // C = d(hm) is not stored: with mult = the dropout multiplier of flat element m N + col, the gate | up values
                                 // a, b stored at sw_gu[m][col], sw_gu[m][N + col] become mult C b silu'(a), mult C silu(a)  (gemm.hip, EPI == 4)
@@ -385,6 +453,7 @@ gemm_as_kernel(const AsParams p) {
 }
 
 static std::atomic<long long> g_as_launches{0};
+static std::atomic<long long> g_as_fused_launches{0};          // ... of them with the norm prologue and / or the bias epilogue
 
 static inline bool gemm_as_enabled() {
     static EnvSwitch sw("GAMER_GEMM_AS");                // (cached: gamer_reload_env() after a change inside the process)
@@ -398,6 +467,20 @@ bool gemm_as_eligible(const gamer_gemm_desc* d, bool a_kc, bool b_kc, const uint
     if (!gemm_as_enabled() || !a_kc || !b_planes || !d->amax_b) return false;
     if (d->group_mode != 0 || d->resid || d->qk_q_rot) return false;
     if ((d->group_div > 1 || d->sw_tbl) && !d->sw_hm) return false;      // (row groups that share a W / the row table: the fused SwiGLU forward only)
+    if (d->norm_x) {
+        // the RMSNorm prologue: W k-contiguous, the row of A is the whole hidden state (the kernel sums K squares), 16-byte rows
+        static EnvSwitch swn("GAMER_GEMM_AS_NORM");          // (0: gamer_rmsnorm_fwd and the product as two launches - A/B runs)
+        if (swn.get(1) == 0 || !b_kc || !d->norm_w || !aligned16(d->norm_x) || !aligned16(d->norm_w) || !aligned16(d->A) ||
+            (d->norm_dst_rows != nullptr) != (d->norm_src_rows != nullptr))
+            return false;
+    }
+    if (d->bias_idx) {
+        // the bias rows in the epilogue: plain store, one group, the table (bias_rows x N floats) beside the W buffers in LDS
+        static EnvSwitch swb("GAMER_GEMM_AS_BIAS");          // (0: the product, then the pass that adds the rows)
+        if (swb.get(1) == 0 || !b_kc || d->sw_hm || d->groups != 1 || d->accumulate || d->bias_rows < 1 ||
+            (int64_t)d->bias_rows * d->N * (int64_t)sizeof(float) > 16384)
+            return false;
+    }
     if (d->sw_hm) {
         // the experts' gate|up projection with the SwiGLU forward in its epilogue: W k-contiguous, N = 2 I in whole slab pairs, no other epilogue
         static EnvSwitch sw5("GAMER_GEMM_AS_SWIGLU");        // (0: the projection and gamer_swiglu_fwd_ld(_tbl) as two launches - A/B runs)
@@ -442,10 +525,17 @@ bool gemm_as_eligible(const gamer_gemm_desc* d, bool a_kc, bool b_kc, const uint
 template <int KP, bool WRC, int EPI>
 static int launch_as(int nw, dim3 grid, size_t shmem, hipStream_t st, const AsParams& p) {
     const char* who = "gamer_gemm_f32_split/activation-stationary";
-    if constexpr (EPI == 5) return launch<gemm_as_kernel<KP, WRC, EPI, 4>>(who, grid, dim3(64 * 4), shmem, st, p);
-    else
+    [[maybe_unused]] const bool norm = p.norm_w != nullptr, bias = p.act_idx != nullptr;
+    if constexpr (WRC) {
         return with_flags([&](auto eight) { return launch<gemm_as_kernel<KP, WRC, EPI, eight() ? 8 : 4>>(who, grid, dim3(eight() ? 512 : 256), shmem, st, p); },
                           nw == 8);
+    } else if constexpr (EPI == 5) {
+        return with_flags([&](auto nm) { return launch<gemm_as_kernel<KP, WRC, EPI, 4, nm()>>(who, grid, dim3(64 * 4), shmem, st, p); }, norm);
+    } else {
+        return with_flags([&](auto eight, auto nm, auto bs) {
+            return launch<gemm_as_kernel<KP, WRC, EPI, eight() ? 8 : 4, nm(), bs()>>(who, grid, dim3(eight() ? 512 : 256), shmem, st, p); },
+                          nw == 8, norm, bias);
+    }
 }
 
 int launch_gemm_as(const gamer_gemm_desc* d, const uint16_t* b_planes, bool b_kc, hipStream_t st) {
@@ -462,8 +552,15 @@ int launch_gemm_as(const gamer_gemm_desc* d, const uint16_t* b_planes, bool b_kc
     p.rowdot_other = d->rowdot_other; p.rowdot_out = d->rowdot_out; p.rowdot_S = d->rowdot_S;
     p.sw_gu = d->sw_gu; p.sw_ld = d->sw_ld; p.p_drop = d->p_drop; p.seed = d->seed;
     p.hm = d->sw_hm; p.tbl = d->sw_hm ? d->sw_tbl : nullptr; p.group_div = d->group_div > 1 ? d->group_div : 1;
+    const bool norm = b_kc && d->norm_x, bias = b_kc && d->bias_idx;
+    p.norm_w = norm ? d->norm_w : nullptr; p.norm_eps = d->norm_eps; p.src_rows = norm ? d->norm_src_rows : nullptr;
+    p.h = const_cast<float*>(d->A); p.ldh = d->a_rs; p.amax_h = norm ? const_cast<uint32_t*>(d->amax_a) : nullptr;
+    if (norm) { p.A = d->norm_x; p.lda = d->K; }         // (the rows before the norm, dense; d->A receives the normalised rows)
+    p.act_idx = bias ? d->bias_idx : nullptr; p.bias_q = d->bias_q; p.bias_k = d->bias_k; p.bias_v = d->bias_v;
+    p.bias_c1 = d->bias_nq; p.bias_c2 = d->bias_nq + d->bias_nkv; p.nb1 = d->bias_rows;
     const int kp = d->K / 64;
-    const size_t shmem = (size_t)(AS_DEPTH == 2 ? 3 : 2) * 2 * kp * AS_PANEL * sizeof(bf16_t) + (d->sw_hm ? (size_t)d->N * sizeof(float) : 0);
+    const size_t shmem = (size_t)(AS_DEPTH == 2 ? 3 : 2) * 2 * kp * AS_PANEL * sizeof(bf16_t) + (d->sw_hm ? (size_t)d->N * sizeof(float) : 0) +
+                         (bias ? (size_t)d->bias_rows * d->N * sizeof(float) : 0);
     // eight waves per workgroup for the wide ungrouped Linear forwards (q|k|v, head), four otherwise (see the kernel)
     static EnvSwitch wv("GAMER_GEMM_AS_WAVES");
     const int nw = d->sw_hm ? 4 : (wv.is_set() ? (wv.get(4) == 8 ? 8 : 4) : ((b_kc && d->groups == 1 && d->N >= 512 && AS_WAVES == 4) ? 8 : AS_WAVES));
@@ -492,7 +589,41 @@ int launch_gemm_as(const gamer_gemm_desc* d, const uint16_t* b_planes, bool b_kc
     }
     if (rc) return rc;
     g_as_launches.fetch_add(1, std::memory_order_relaxed);
+    if (norm || bias) g_as_fused_launches.fetch_add(1, std::memory_order_relaxed);
     return 0;
+}
+
+// The bias rows of a descriptor the kernel above did not take: C[m][.] += row bias_idx[m] of bias_q | bias_k | bias_v after the plain
+// product - the add gamer_qknorm_rope_fwd made in place (same operands, same single rounding); the maximum of the columns from
+// amax_c_col0 on goes to amax_c.
+__global__ void __launch_bounds__(256)
+gemm_bias_rows_kernel(float* __restrict__ Cm, int64_t ldc, int M, int N, const int32_t* __restrict__ idx, const float* __restrict__ bq,
+                      const float* __restrict__ bk, const float* __restrict__ bv, int c1, int c2, int nb1, uint32_t* __restrict__ amax_c,
+                      int col0) {
+    __shared__ uint32_t amax_lds[4];
+    uint32_t am = 0;
+    const int n4 = N >> 2;
+    const int64_t total = (int64_t)M * n4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int m = (int)(i / n4), c = 4 * (int)(i - (int64_t)m * n4);
+        const int a = min(max(idx[m], 0), nb1 - 1);
+        const float* src = c < c1 ? bq + (int64_t)a * c1 + c : c < c2 ? bk + (int64_t)a * (c2 - c1) + (c - c1) : bv + (int64_t)a * (N - c2) + (c - c2);
+        const float4 b4 = *reinterpret_cast<const float4*>(src);
+        float4* dst = reinterpret_cast<float4*>(Cm + (int64_t)m * ldc + c);
+        float4 x = *dst;
+        x.x += b4.x; x.y += b4.y; x.z += b4.z; x.w += b4.w;
+        *dst = x;
+        if (c >= col0) am = amax_f4(am, x);
+    }
+    amax_block_commit(am, amax_c, amax_lds);
+}
+
+int launch_gemm_bias_rows(const gamer_gemm_desc* d, hipStream_t st) {
+    const int64_t total = (int64_t)d->M * (d->N >> 2);
+    const int blocks = total > 8192 * 256 ? 8192 : (int)((total + 255) / 256);
+    return launch<gemm_bias_rows_kernel>("gamer_gemm_f32/bias rows", dim3(blocks), dim3(256), 0, st, d->C, d->ldc, d->M, d->N, d->bias_idx,
+                                         d->bias_q, d->bias_k, d->bias_v, d->bias_nq, d->bias_nq + d->bias_nkv, d->bias_rows, d->amax_c,
+                                         d->amax_c_col0);
 }
 
 }  // namespace gamer
@@ -501,3 +632,6 @@ int launch_gemm_as(const gamer_gemm_desc* d, const uint16_t* b_planes, bool b_kc
 // the kernel returns the BITS of the tile kernel (a power-of-two scale does not change an fp16 rounding), so a test cannot tell from
 // the results which of the two ran.
 extern "C" long long gamer_debug_gemm_as_launches(void) { return gamer::g_as_launches.load(std::memory_order_relaxed); }
+// ... and those among them that carried the RMSNorm prologue and / or the bias epilogue (a call with norm_x / bias_idx that is not
+// counted here ran as the separate launches)
+extern "C" long long gamer_debug_gemm_as_fused_launches(void) { return gamer::g_as_fused_launches.load(std::memory_order_relaxed); }

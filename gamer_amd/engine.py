@@ -758,7 +758,13 @@ class Engine:
             # ---- behaviour-level "cross" attention (model.py:220-235) ----
             if W.cross:
                 C, Cm = W.cross_attn, Wm.cross_attn
-                ops.rmsnorm_fwd(xs[1], W.ln2, eps, A["h2"])
+                # split3, plain projection: the norm is the q|k|v GEMM's prologue and the behaviour biases its epilogue (gamer_gemm_desc
+                # .norm_x / .bias_idx) - A["h2"] is written by that call (the gate projection below reads it), and q/k-norm + RoPE
+                # run without the biases (their in-place write of the biased q|k|v included)
+                nrm = dict(norm=dict(x=xs[1], w=W.ln2, eps=eps)) if (c.fuse_norm and not fuse_qkv) else {}
+                fuse_bias = c.fuse_bias and not fuse_qkv
+                if not nrm:
+                    ops.rmsnorm_fwd(xs[1], W.ln2, eps, A["h2"])
                 qkv_x, k_x = kv_dest(l, "cross") if kv_dest is not None else (A["qkv_c"], A["k_c"])
                 # (evaluation: no workspace tensor is declared unchanging - the layers share the buffers - but h2 is read by two GEMMs
                 # of this block, the q|k|v projection and the gate: its maximum is kept between them instead of measured twice)
@@ -770,8 +776,13 @@ class Engine:
                              qknorm=dict(wq=C["qn"], wk=C["kn"], eps=eps, cos=cos, sin=sin, q_rot=A["q_c"], k_rot=k_x,
                                          bias_q=C["bq"], bias_k=C["bk"], bias_v=C["bv"], act_idx=r["act_idx"],
                                          pos_ids=pos_ids, S=S, nq=nq, nkv=nkv))
+                elif fuse_bias:
+                    ops.linear_fwd(A["h2"], H, Cm["qkv"], H, qkv_x, QKV, T, QKV, H,
+                                   bias=dict(idx=r["act_idx"], q=C["bq"], k=C["bk"], v=C["bv"]),
+                                   c_amax=(qkv_x[:, NQ + NKV:], NQ + NKV), **nrm)
+                    ops.qknorm_rope_fwd(qkv_x, S, nq, nkv, C["qn"], C["kn"], eps, cos, sin, A["q_c"], k_x, pos_ids=pos_ids)
                 else:
-                    ops.linear_fwd(A["h2"], H, Cm["qkv"], H, qkv_x, QKV, T, QKV, H)
+                    ops.linear_fwd(A["h2"], H, Cm["qkv"], H, qkv_x, QKV, T, QKV, H, **nrm)
                     ops.qknorm_rope_fwd(qkv_x, S, nq, nkv, C["qn"], C["kn"], eps, cos, sin, A["q_c"], k_x,
                                         bias_q=C["bq"], bias_k=C["bk"], bias_v=C["bv"], act_idx=r["act_idx"],
                                         pos_ids=pos_ids)
@@ -826,31 +837,38 @@ class Engine:
                 self._ffn_fwd_plain(c, l, xcur, xnext)
                 continue
             grp = dict(groups=E, group_offsets=ws.offsets)
+            # split3, K = the hidden size: the post-attention norm is the gate|up GEMM's prologue (gamer_gemm_desc.norm_x) - the call reads
+            # the residual stream in token order through perm (sorted row -> token) and writes hin in sorted order
+            nrm = dict(norm=dict(x=xcur, w=W.ln3, eps=eps, dst_rows=ws.slot, src_rows=ws.perm)) if c.fuse_norm else {}
             if W.inject and self.split_inject:
                 # K = 256 of the 320 input columns; the embedding columns' share comes from the (expert, behaviour) table
                 hin = A["hin"].view(-1)[:T * H].view(T, H)
-                ops.rmsnorm_fwd(xcur, W.ln3, eps, hin, H, ws.slot)
+                if not nrm:
+                    ops.rmsnorm_fwd(xcur, W.ln3, eps, hin, H, ws.slot)
                 tb = ws._buf((f"l{l}_" if train else "l_") + "inject_tbl", (E * NB1, 2 * I))
                 ops.inject_table_fwd(W.beh, W.gu, din, H, E, 2 * I, tb)
                 if c.fuse_swiglu_fwd:
                     # one call: gate|up AND hm (the SwiGLU forward as the projection's epilogue; rows grouped by (expert, behaviour))
                     ops.gemm(hin, H, 1, Wm.gu, din, 1, A["gu"], 2 * I, T, 2 * I, H, strideB=2 * I * din, groups=E * NB1,
                              group_offsets=ws.grp_offsets, group_div=NB1, p_drop=p_res, seed=self._seed(l, 4),
-                             swiglu_fwd=(A["hm"], tb, ws.row_group))
+                             swiglu_fwd=(A["hm"], tb, ws.row_group), **nrm)
                 else:
-                    ops.linear_fwd(hin, H, Wm.gu, din, A["gu"], 2 * I, T, 2 * I, H, strideB=2 * I * din, **grp)
+                    ops.linear_fwd(hin, H, Wm.gu, din, A["gu"], 2 * I, T, 2 * I, H, strideB=2 * I * din, **grp, **nrm)
                     ops.swiglu_fwd_ld_tbl(A["gu"], 2 * I, T, I, p_res, self._seed(l, 4), A["hm"], tb, ws.row_group)
             else:
-                ops.rmsnorm_fwd(xcur, W.ln3, eps, A["hin"], din, ws.slot)
+                if din != H:
+                    nrm = {}                     # (the behaviour-embedding columns join the normalised rows before the product)
+                if not nrm:
+                    ops.rmsnorm_fwd(xcur, W.ln3, eps, A["hin"], din, ws.slot)
                 if W.inject:
                     ops.rowtable_fwd(W.beh, r["beh_idx"], A["hin"], din, H, ws.slot)
                 # gate_proj and up_proj of the position's expert in ONE grouped GEMM against the stacked [2 I, din] weight (FFN.py:25-27:
                 # both read the same input): A["gu"][:, :I] = gate, [:, I:] = up
                 if c.fuse_swiglu_fwd and din == H:
                     ops.gemm(A["hin"], din, 1, Wm.gu, din, 1, A["gu"], 2 * I, T, 2 * I, din, strideB=2 * I * din, p_drop=p_res,
-                             seed=self._seed(l, 4), swiglu_fwd=(A["hm"], None, None), **grp)
+                             seed=self._seed(l, 4), swiglu_fwd=(A["hm"], None, None), **grp, **nrm)
                 else:
-                    ops.linear_fwd(A["hin"], din, Wm.gu, din, A["gu"], 2 * I, T, 2 * I, din, strideB=2 * I * din, **grp)
+                    ops.linear_fwd(A["hin"], din, Wm.gu, din, A["gu"], 2 * I, T, 2 * I, din, strideB=2 * I * din, **grp, **nrm)
                     ops.swiglu_fwd_ld(A["gu"], 2 * I, T, I, p_res, self._seed(l, 4), A["hm"])
             # down projection: rows are in expert-sorted order, the epilogue scatters them back to token
             # order through perm while adding the residual and applying dropout (FFN.py:25-27, model.py:241)
@@ -988,6 +1006,11 @@ class Engine:
         # (three-product form) the SwiGLU forward as the epilogue of the gate|up projection (gamer_gemm_desc.sw_hm); A/B switch
         c.fuse_swiglu_fwd = not c.bf16 and self.matmul == "split3" and os.environ.get("GAMER_FUSE_SWIGLU_FWD", "1") != "0"
         c.fuse_swiglu_bwd = (c.bf16 or self.matmul == "split3") and self.fuse_swiglu_bwd
+        # (three-product form) RMSNorm as the prologue and the cross block's behaviour biases as the epilogue of the projections that follow
+        # them (gamer_gemm_desc.norm_x / .bias_idx).  The engine asks for each half only while the library's switch for it is on: with a
+        # switch off the pass makes the separate launches itself (A/B runs of one half alone)
+        c.fuse_norm = not c.bf16 and self.matmul == "split3" and os.environ.get("GAMER_GEMM_AS_NORM", "1") != "0"
+        c.fuse_bias = not c.bf16 and self.matmul == "split3" and os.environ.get("GAMER_GEMM_AS_BIAS", "1") != "0"
         return c
 
     def _prologue(self, input_ids, attention_mask, labels, train, dropout, dropout_rate, kv_dest, hidden_sink,
@@ -1055,7 +1078,10 @@ class Engine:
         ``pos_ids``: per-query key spans and RoPE positions (None: causal, 0..S-1)."""
         W, Wm, A, xs = self.W[l], self.Wm[l], c.ws.layers[l], c.ws.x[l]
         T, H, NQ, NKV, QKV, eps = c.T, c.H, c.NQ, c.NKV, c.QKV, c.eps
-        ops.rmsnorm_fwd(xs[0], W.ln1, eps, A["h1"])
+        # split3, plain projection: the input norm is the q|k|v GEMM's prologue (gamer_gemm_desc.norm_x) - A["h1"] is written by that call
+        nrm = dict(norm=dict(x=xs[0], w=W.ln1, eps=eps)) if (c.fuse_norm and not fuse_qkv) else {}
+        if not nrm:
+            ops.rmsnorm_fwd(xs[0], W.ln1, eps, A["h1"])
         # (kv_dest: the q|k|v projection and the rotated keys of this layer are written where the caller keeps them - a
         # generation's prompt caches - instead of the workspace's buffers and a copy)
         qkv_s, k_s = kv_dest(l, "self") if kv_dest is not None else (A["qkv"], A["k"])
@@ -1066,7 +1092,7 @@ class Engine:
                                  k_rot=k_s, pos_ids=pos_ids, S=c.S, nq=c.nq, nkv=c.nkv))
         else:
             v_amax = dict(c_amax=(qkv_s[:, NQ + NKV:], NQ + NKV)) if (c.h2 and self.gemm_c_amax) else {}
-            ops.linear_fwd(A["h1"], H, Wm.self_attn["qkv"], H, qkv_s, QKV, T, QKV, H, **v_amax)
+            ops.linear_fwd(A["h1"], H, Wm.self_attn["qkv"], H, qkv_s, QKV, T, QKV, H, **v_amax, **nrm)
             ops.qknorm_rope_fwd(qkv_s, c.S, c.nq, c.nkv, W.self_attn["qn"], W.self_attn["kn"], eps, c.cos, c.sin, A["q"], k_s,
                                 pos_ids=pos_ids)
         if kv_sink is not None:
@@ -1091,15 +1117,18 @@ class Engine:
             self._saved = None
             self.last_logits_buf = small               # [B, ldl] (columns >= V are padding), what DecodeSession scores
             return None, small.view(B, 1, ws.ldl)[:, :, :V]
-        ops.rmsnorm_fwd(ws.x_final, self.params["model.norm.weight"], eps, ws.xn)
-        if hidden_sink is not None:
-            hidden_sink.append(ws.xn.view(B, S, H).clone())
+        # split3: the final norm is the head GEMM's prologue (gamer_gemm_desc.norm_x) - ws.xn is written by that call
+        nrm = dict(norm=dict(x=ws.x_final, w=self.params["model.norm.weight"], eps=eps)) if c.fuse_norm else {}
+        if not nrm:
+            ops.rmsnorm_fwd(ws.x_final, self.params["model.norm.weight"], eps, ws.xn)
         emb_m = self.shadow.params16["model.embed_tokens.weight"] if c.bf16 else self.params["model.embed_tokens.weight"]
         # with labels the logits leave the head GEMM already divided by the temperature (its alpha; model.py:913 divides them in place):
         # the loss kernel then only reads them (fp32 engine; the bf16 head rounds to bf16 first, as the reference's autocast does)
         lab = c.lab
         head_alpha = (1.0 / self.temperature) if (lab is not None and ws.logits.dtype == torch.float32) else 1.0
-        ops.linear_fwd(ws.xn, H, emb_m, H, ws.logits, ws.ldl, c.T, V, H, alpha=head_alpha)
+        ops.linear_fwd(ws.xn, H, emb_m, H, ws.logits, ws.ldl, c.T, V, H, alpha=head_alpha, **nrm)
+        if hidden_sink is not None:
+            hidden_sink.append(ws.xn.view(B, S, H).clone())
         loss = None
         if lab is not None:
             ops.ce_fwd(ws.logits, ws.ldl, lab, V, 1.0 if head_alpha != 1.0 else self.temperature, IGNORE_INDEX, ws.lse_ce,

@@ -527,9 +527,12 @@ def scoped_amax(get_cache):
     return deco
 
 
-def absmax_slot(x, batch, stride, rows, cols, ld):
-    """Device pointer of a word holding the bits of max |x| over `batch` matrices [rows, cols] (leading dimension ld)."""
+def absmax_slot(x, batch, stride, rows, cols, ld, produced=False):
+    """Device pointer of a word holding the bits of max |x| over `batch` matrices [rows, cols] (leading dimension ld).
+    produced: x is about to be written by the kernel that gets the slot (it fills a zeroed word) - nothing is measured."""
     if _AMAX_REUSE is not None:
+        if produced:
+            _AMAX_REUSE.preset(x, (batch, stride, rows, cols, ld))
         return _AMAX_REUSE.slot(x, (batch, stride, rows, cols, ld))
     key = (x.device.index, stream_ptr())
     ring = _AMAX_RING.get(key)
@@ -540,7 +543,8 @@ def absmax_slot(x, batch, stride, rows, cols, ld):
         ring[1] = 0
     slot = ring[0].data_ptr() + 4 * AMAX_WORDS * ring[1]
     ring[1] += 1
-    call("gamer_absmax_f32", ptr(x), batch, stride, rows, cols, ld, slot, stream_ptr())
+    if not produced:
+        call("gamer_absmax_f32", ptr(x), batch, stride, rows, cols, ld, slot, stream_ptr())
     return slot
 
 
@@ -621,12 +625,14 @@ def set_f32_matmul(mode) -> int:
 
 def gemm(A, a_rs, a_ks, Bm, b_rs, b_ks, Cm, ldc, M, N, K, alpha=1.0, accumulate=False, groups=1, group_mode=0,
          group_offsets=None, strideB=0, strideC=0, kchunk=0, resid=None, row_map=None, p_drop=0.0, seed=0,
-         rowdot=None, qknorm=None, c_amax=None, swiglu_bwd=None, group_div=0, sw_tbl=None, swiglu_fwd=None):
+         rowdot=None, qknorm=None, c_amax=None, swiglu_bwd=None, group_div=0, sw_tbl=None, swiglu_fwd=None, norm=None, bias=None):
     """C[m][n] (=|+=) alpha * sum_k A(m,k) B(n,k); see gamer_gemm_desc in include/gamer_hip.h.  bf16 operands go to
-    gamer_gemm_bf16 (k-contiguous x k-contiguous, or the token-major wgrad form; see gamer_gemm_bf16_desc)."""
+    gamer_gemm_bf16 (k-contiguous x k-contiguous, or the token-major wgrad form; see gamer_gemm_bf16_desc).
+    norm: dict(x, w, eps[, dst_rows, src_rows]) - A is first WRITTEN as the RMSNorm of x's rows (gamer_gemm_desc.norm_x);
+    bias: dict(idx, q, k, v) - the row idx[m] of the tables q | k | v is added to C[m] (gamer_gemm_desc.bias_idx)."""
     if A.dtype == torch.bfloat16:
-        if group_div > 1 or sw_tbl is not None or swiglu_fwd is not None:
-            raise RuntimeError("group_div / sw_tbl / swiglu_fwd are options of the fp32 GEMM")
+        if group_div > 1 or sw_tbl is not None or swiglu_fwd is not None or norm is not None or bias is not None:
+            raise RuntimeError("group_div / sw_tbl / swiglu_fwd / norm / bias are options of the fp32 GEMM")
         return _gemm_bf16(A, a_rs, a_ks, Bm, b_rs, b_ks, Cm, ldc, M, N, K, alpha, accumulate, groups, group_mode,
                           group_offsets, strideB, strideC, kchunk, resid, row_map, p_drop, seed, rowdot, qknorm, swiglu_bwd)
     d = GemmDesc()
@@ -670,6 +676,15 @@ def gemm(A, a_rs, a_ks, Bm, b_rs, b_ks, Cm, ldc, M, N, K, alpha=1.0, accumulate=
         if _AMAX_REUSE is not None and F32_MATMUL_TERMS == 3 and ld_gu == 2 * N:
             d.amax_c, d.amax_c_col0 = _AMAX_REUSE.preset(gu, (1, 0, 1, M * ld_gu, M * ld_gu)), 0
     d.group_div = int(group_div)
+    if norm is not None:
+        nx = norm["x"]
+        if group_mode != 0 or a_ks != 1 or b_ks != 1 or nx.dim() != 2 or nx.shape[0] < M or nx.shape[1] != K or not nx.is_contiguous():
+            raise RuntimeError("gemm(norm=...): a Linear-forward GEMM whose rows are the RMSNorm of a dense [M, K] tensor")
+        d.norm_x, d.norm_w, d.norm_eps = ptr(norm["x"]), ptr(norm["w"]), float(norm["eps"])
+        d.norm_dst_rows, d.norm_src_rows = ptr(norm.get("dst_rows")), ptr(norm.get("src_rows"))
+    if bias is not None:
+        d.bias_idx, d.bias_q, d.bias_k, d.bias_v = ptr(bias["idx"]), ptr(bias["q"]), ptr(bias["k"]), ptr(bias["v"])
+        d.bias_rows, d.bias_nq, d.bias_nkv = int(bias["q"].shape[0]), int(bias["q"].shape[1]), int(bias["k"].shape[1])
     if swiglu_fwd is not None:
         # (hm, tbl or None, row_group or None): C = gate | up AND hm = dropout(silu(gate + tg) * (up + tu)) from one call
         # (gamer_gemm_desc.sw_hm); the maximum of hm goes to the slot its consumer GEMM will take
@@ -687,7 +702,8 @@ def gemm(A, a_rs, a_ks, Bm, b_rs, b_ks, Cm, ldc, M, N, K, alpha=1.0, accumulate=
         ga = (M, K, a_rs) if a_ks == 1 else (K, M, a_ks)
         gb = (N, K, b_rs) if b_ks == 1 else (K, N, b_ks)
         nb = (groups // max(1, int(group_div))) if (group_mode == 0 and groups > 1) else 1
-        d.amax_a = absmax_slot(A, 1, 0, *ga)
+        # (norm: A is produced by this call - its maximum too, into a fresh slot that the GEMMs reading A later take)
+        d.amax_a = absmax_slot(A, 1, 0, *ga, produced=norm is not None)
         geom_b = (nb, strideB if nb > 1 else 0) + gb
         c = _AMAX_REUSE
         parent = c.plane_parent(Bm.data_ptr(), geom_b) if (c is not None and c.planes is not None and group_mode == 0) else None

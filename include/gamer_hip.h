@@ -332,6 +332,29 @@ typedef struct {
      * [groups][N] with the row groups of group_offsets (group_div groups per B); sw_row_group: int32 [M], the group of every row.  */
     float* sw_hm;
     const int32_t* sw_row_group;
+    /* (ABI 9, appended) RMSNorm in front of the product (Linear-forward layout, group_mode 0, K = the hidden size): A is then an OUTPUT as well -
+     * the call first leaves A[r][.] = norm_w * (x * rsqrt(mean(x^2) + norm_eps)) for the rows x of norm_x ([M][K], dense), exactly
+     * what gamer_rmsnorm_fwd(norm_x, norm_w, M, K, norm_eps, norm_dst_rows, A, a_rs) computes (ref:SeqRec/models/generative/
+     * Qwen3Multi/model.py:204,220,238,869), and multiplies those rows.  Row order: norm_dst_rows (token -> row of A, what
+     * gamer_rmsnorm_fwd takes) and norm_src_rows (row of A -> token, its inverse) describe the same permutation - give both or neither
+     * (the experts' sorted order; NULL = identity).  amax_a, when given, RECEIVES max |A| before it is read (as gamer_amax_sink does for
+     * gamer_rmsnorm_fwd).  The activation-stationary kernel normalises in registers - norm_x is read once, A written once and not read
+     * back; a call it does not take (see "kernel choice", GAMER_GEMM_AS_NORM=0) runs gamer_rmsnorm_fwd and then the plain product.
+     * NULL = off. */
+    const float* norm_x;
+    const float* norm_w;
+    float norm_eps;
+    const int32_t* norm_dst_rows;
+    const int32_t* norm_src_rows;
+    /* (ABI 9, appended) bias rows in the epilogue (Linear-forward layout, one group, N = bias_nq + 2 bias_nkv, all multiples of 4, no accumulate /
+     * residual / other epilogue): C[m][n] = (alpha * acc[m][n]) + row bias_idx[m] of the table bias_q [bias_rows][bias_nq] |
+     * bias_k [bias_rows][bias_nkv] | bias_v [bias_rows][bias_nkv] - two rounded operations, the bits of the plain product followed by
+     * the in-place bias add of gamer_qknorm_rope_fwd (the cross block's behaviour biases, model.py:93-99), which then runs without
+     * them.  amax_c sees the biased values.  Not taken by the activation-stationary kernel (GAMER_GEMM_AS_BIAS=0 included): the plain
+     * product, then one pass that adds the rows.  bias_idx == NULL: off. */
+    const int32_t* bias_idx;
+    const float* bias_q; const float* bias_k; const float* bias_v;
+    int bias_rows, bias_nq, bias_nkv;
 } gamer_gemm_desc;
 
 int gamer_gemm_f32(const gamer_gemm_desc* d, void* stream);

@@ -30,14 +30,14 @@ def counters():
 
 def hooked(A, a_rs, a_ks, Bm, b_rs, b_ks, Cm, ldc, M, N, K, *a, **kw):
     names = ["alpha", "accumulate", "groups", "group_mode", "group_offsets", "strideB", "strideC", "kchunk", "resid", "row_map", "p_drop",
-             "seed", "rowdot", "qknorm", "c_amax", "swiglu_bwd", "group_div", "sw_tbl", "swiglu_fwd"]
+             "seed", "rowdot", "qknorm", "c_amax", "swiglu_bwd", "group_div", "sw_tbl", "swiglu_fwd", "norm", "bias"]
     k2 = dict(zip(names, a)); k2.update(kw)
     c0 = counters()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record(); r = orig(A, a_rs, a_ks, Bm, b_rs, b_ks, Cm, ldc, M, N, K, *a, **kw); e.record()
     c1 = counters()
     kern = "as" if c1[0] > c0[0] else "os" if c1[1] > c0[1] else "wg" if c1[2] > c0[2] else "tile"
-    epi = "+".join(n for n in ("resid", "row_map", "rowdot", "qknorm", "swiglu_bwd", "swiglu_fwd", "sw_tbl") if k2.get(n) is not None) or "-"
+    epi = "+".join(n for n in ("resid", "row_map", "rowdot", "qknorm", "swiglu_bwd", "swiglu_fwd", "sw_tbl", "norm", "bias") if k2.get(n) is not None) or "-"
     rec.append((s, e, M, N, K, a_ks, b_ks, k2.get("groups", 1), k2.get("group_mode", 0), bool(k2.get("accumulate", False)), epi, kern,
                 str(A.dtype).replace("torch.", "")))
     return r
