@@ -48,14 +48,15 @@ TIME_PAD = -1.0             # collator.py:105
 class TokenTable:
     """token string -> id, exactly what ``Qwen2Tokenizer.from_pretrained(base) + add_tokens(sorted(new_tokens))``
     assigns: the base vocabulary keeps its ids, every new token not already present gets the next free id in
-    list order (train_SMB_decoder.py:251)."""
+    list order (train_SMB_decoder.py:251).  ``pad_token`` names the base vocabulary's pad token: Qwen's by default, ``<pad>``
+    (id 0) for the T5 vocabulary of gamer_amd/t5_mb_data.py."""
 
-    def __init__(self, new_tokens: Sequence[str], base_vocab: Optional[Dict[str, int]] = None):
+    def __init__(self, new_tokens: Sequence[str], base_vocab: Optional[Dict[str, int]] = None, pad_token: str = PAD_TOKEN):
         self.vocab: Dict[str, int] = dict(QWEN3MULTI_BASE_VOCAB if base_vocab is None else base_vocab)
         for t in new_tokens:
             if t not in self.vocab:
                 self.vocab[t] = len(self.vocab)
-        self.pad_id = self.vocab[PAD_TOKEN]
+        self.pad_id = self.vocab[pad_token]
 
     def __len__(self) -> int:
         return len(self.vocab)
@@ -116,7 +117,7 @@ class SMBData:
     """One dataset directory in the reference's format, split by session (BaseSMBDataset._load_data)."""
 
     def __init__(self, data_path: str, dataset: str, index_file: str = ".index.json",
-                 base_vocab: Optional[Dict[str, int]] = None):
+                 base_vocab: Optional[Dict[str, int]] = None, pad_token: str = PAD_TOKEN):
         d = os.path.join(data_path, dataset)
 
         def load(suffix):
@@ -143,7 +144,7 @@ class SMBData:
         new = {t for idx in indices.values() for t in idx}
         new.update(f"<behavior_{b}>" for b in self.behaviors)
         self.new_tokens = sorted(new)
-        self.tokens = TokenTable(self.new_tokens, base_vocab)
+        self.tokens = TokenTable(self.new_tokens, base_vocab, pad_token)
         self.behavior_token_ids = {b: self.tokens[f"<behavior_{b}>"] for b in self.behaviors}
         # item id -> row of token ids (this replaces the per-batch string tokenisation)
         self.item_keys = list(indices.keys())

@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .data import IGNORE_INDEX, TokenTable, _pad_batch
+from .data import IGNORE_INDEX, PAD_TOKEN, TokenTable, _pad_batch
 
 TASKS = ("mb", "mb_explicit", "mb_explicit_filter", "mb_explicit_decoder", "mb_explicit_back")
 
@@ -76,7 +76,7 @@ class MBData:
     """One dataset directory in the reference's MB format, read for one task (``load_MB_datasets`` with one task)."""
 
     def __init__(self, data_path: str, dataset: str, task: str, index_file: str = ".index.json",
-                 base_vocab: Optional[Dict[str, int]] = None):
+                 base_vocab: Optional[Dict[str, int]] = None, pad_token: str = PAD_TOKEN):
         d = os.path.join(data_path, dataset)
 
         def load(suffix):
@@ -101,7 +101,7 @@ class MBData:
         if self.kind == "explicit":
             new |= {self.behavior_token(b) for b in self.behaviors}
         self.new_tokens = sorted(new)
-        self.tokens = TokenTable(self.new_tokens, base_vocab)
+        self.tokens = TokenTable(self.new_tokens, base_vocab, pad_token)
         self.item_ids = {k: np.array([self.tokens[t] for t in v], dtype=np.int64) for k, v in self.indices.items()}
         self.behavior_token_ids = ({b: self.tokens[self.behavior_token(b)] for b in self.behaviors}
                                    if self.kind == "explicit" else {})

@@ -156,58 +156,76 @@ def test(model, data, collator, a, dev):
     return {m: totals[m] / max(n, 1) for m in metrics}
 
 
-def main(argv=None):
-    a = parse_args(argv)
+def run(a, tag, data, collator, test_fn):
+    """The train-and-test loop of the TIGER commands (train_tiger, train_tiger_smb, train_tiger_mb).  ``data``: ``vocab_size`` and
+    ``samples(mode, max_his_len)``; ``collator(samples, index)`` -> input_ids / attention_mask / labels; ``test_fn(model, data,
+    collator, a, dev)`` -> (what goes to ``--results_file``, its one-line summary).  ``a.gradient_accumulation_steps`` (where the
+    command has the flag) micro-batches share one update, each weighing 1 / steps as HF's Trainer scales them; the last group of an
+    epoch may be shorter."""
     random.seed(a.seed)
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
     dev = torch.device("cuda")
     os.makedirs(a.output_dir, exist_ok=True)
     config = tiger.TigerConfig.from_pretrained(a.base_model)
-    data = SeqRecData(a.data_path, a.dataset, a.index_file)
-    collator = EncoderDecoderCollator(data, a.model_max_length)
     model = tiger.TIGER(config)
     model.set_hyper(a.temperature)
     model.resize_token_embeddings(data.vocab_size)
     model.to(dev)
     ckpt = os.path.join(a.output_dir, "best_model.pth")
+    accum = getattr(a, "gradient_accumulation_steps", 1)
     if not a.only_test:
         train, valid = data.samples("train", a.max_his_len), data.samples("valid", a.max_his_len)
-        steps_per_epoch = (len(train) + a.per_device_batch_size - 1) // a.per_device_batch_size
+        batches_per_epoch = (len(train) + a.per_device_batch_size - 1) // a.per_device_batch_size
+        steps_per_epoch = (batches_per_epoch + accum - 1) // accum
         total = steps_per_epoch * a.epochs
         warmup = schedule.warmup_steps_for(total, a.warmup_ratio)
         opt = FlatAdamW(model, a.weight_decay)
         g = torch.Generator().manual_seed(a.seed)
         best, patience, step = float("inf"), 0, 0
-        print(f"[train_tiger] {len(train)} training samples, {len(valid)} validation samples, vocabulary {data.vocab_size}", flush=True)
+        print(f"[{tag}] {len(train)} training samples, {len(valid)} validation samples, vocabulary {data.vocab_size}", flush=True)
         for epoch in range(a.epochs):
             model.train()
             losses = []
-            for b in _batches(train, collator, a.per_device_batch_size, torch.randperm(len(train), generator=g).tolist()):
-                for p in model.parameters():
-                    p.grad = None
+            order = torch.randperm(len(train), generator=g).tolist()
+            for n, b in enumerate(_batches(train, collator, a.per_device_batch_size, order)):
+                if n % accum == 0:
+                    for p in model.parameters():
+                        p.grad = None
                 loss, _ = model(b["input_ids"].to(dev), b["attention_mask"].to(dev), labels=b["labels"].to(dev))
-                loss.backward()
-                opt.step(schedule.cosine_with_warmup(step, a.learning_rate, warmup, total))
-                step += 1
+                (loss if accum == 1 else loss / accum).backward()
                 losses.append(loss.detach())
+                if (n + 1) % accum == 0 or n + 1 == batches_per_epoch:
+                    opt.step(schedule.cosine_with_warmup(step, a.learning_rate, warmup, total))
+                    step += 1
             ev = eval_loss(model, valid, collator, a.per_device_batch_size, dev)
-            print(f"[train_tiger] epoch {epoch + 1}/{a.epochs} loss {float(torch.stack(losses).mean()):.4f} eval_loss {ev:.4f}", flush=True)
+            print(f"[{tag}] epoch {epoch + 1}/{a.epochs} loss {float(torch.stack(losses).mean()):.4f} eval_loss {ev:.4f}", flush=True)
             if ev < best:
                 best, patience = ev, 0
                 torch.save(model.state_dict(), ckpt)
             else:
                 patience += 1
                 if patience >= a.patience:
-                    print(f"[train_tiger] early stopping on epoch {epoch + 1}", flush=True)
+                    print(f"[{tag}] early stopping on epoch {epoch + 1}", flush=True)
                     break
     model.load_state_dict(torch.load(ckpt, map_location="cpu"))
-    results = test(model, data, collator, a, dev)
+    results, line = test_fn(model, data, collator, a, dev)
     os.makedirs(os.path.dirname(os.path.abspath(a.results_file)), exist_ok=True)
     with open(a.results_file, "w") as f:
         json.dump(results, f, indent=4)
-    print("[train_tiger] " + " ".join(f"{m} {v:.4f}" for m, v in results.items()) + f"; results saved to {a.results_file}", flush=True)
+    print(f"[{tag}] {line}; results saved to {a.results_file}", flush=True)
     return results
+
+
+def _test_and_line(model, data, collator, a, dev):
+    results = test(model, data, collator, a, dev)
+    return results, " ".join(f"{m} {v:.4f}" for m, v in results.items())
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    data = SeqRecData(a.data_path, a.dataset, a.index_file)
+    return run(a, "train_tiger", data, EncoderDecoderCollator(data, a.model_max_length), _test_and_line)
 
 
 if __name__ == "__main__":
