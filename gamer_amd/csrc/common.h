@@ -112,6 +112,25 @@ struct EnvSwitch {
 // ---- device helpers -----------------------------------------------------------------------
 constexpr int WAVE = 64;
 
+// the HBM-bound kernels (elementwise.hip, qknorm_rope.hip): workgroup size, and the grid of a kernel whose waves stride over their work
+constexpr int EW_THREADS = 256;
+constexpr int EW_WAVES = EW_THREADS / WAVE;
+#ifndef EW_MAX_BLOCKS_W
+#define EW_MAX_BLOCKS_W 8192
+#endif
+static inline int grid_for_waves(int64_t n_waves, int max_blocks = EW_MAX_BLOCKS_W) {
+    int64_t blocks = (n_waves + EW_WAVES - 1) / EW_WAVES;
+    if (blocks < 1) blocks = 1;
+    if (blocks > max_blocks) blocks = max_blocks;
+    return (int)blocks;
+}
+
+// rows of a behaviour table (the table-row kernels of elementwise.hip, the bias rows of qknorm_rope.hip): num_behavior + 1 <= 8
+constexpr int TBL_MAXROWS = 8;
+
+// the void* stream of the C ABI as a HIP stream
+#define ST(s) ((hipStream_t)(s))
+
 // bf16 activations (the AMP variant): raw storage type of the C ABI is uint16_t (gamer_bf16), device code uses the
 // compiler's __bf16 so that conversions are v_cvt_pk_bf16_f32 (round to nearest even, NaN stays NaN).
 typedef __bf16 bf16_t;
@@ -124,7 +143,7 @@ typedef float f32x8v __attribute__((ext_vector_type(8)));
 
 // four consecutive elements as a float4 (p aligned to 4 elements): 16-byte access for fp32, 8-byte for bf16
 template <typename T> __device__ __forceinline__ float4 ld4(const T* p);
-// EW_NT=1 (elementwise.hip only): nontemporal 16-byte loads / stores.  Measured (round 3, docs/DESIGN_rounds1-4.md section 5): in isolation SwiGLU
+// EW_NT=1 (elementwise.hip and qknorm_rope.hip only): nontemporal 16-byte loads / stores.  Measured (round 3, docs/DESIGN_rounds1-4.md section 5): in isolation SwiGLU
 // forward / backward gain 5-11 % (6.3 TB/s), in the train step the GEMMs that read those tensors next lose what was gained.
 #ifndef EW_NT
 #define EW_NT 0

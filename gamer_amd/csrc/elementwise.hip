@@ -1,25 +1,13 @@
 // HBM-bound pieces of the Qwen3Multi decoder layer: embedding, RMSNorm, behaviour tables,
-// q/k norm + RoPE, residual/dropout, SwiGLU, output gate, temperature cross-entropy.
+// residual/dropout, SwiGLU, output gate, temperature cross-entropy (the per-head q/k norm + RoPE has a file of its own).
 // Every kernel moves 16 B per lane and reduces with wave shuffles (wave = 64).
 #include "common.h"
 
 namespace gamer {
 
-constexpr int EW_THREADS = 256;
-constexpr int EW_WAVES = EW_THREADS / WAVE;
-
-#ifndef EW_MAX_BLOCKS_W
-#define EW_MAX_BLOCKS_W 8192
-#endif
 #ifndef EW_MAX_BLOCKS_T
 #define EW_MAX_BLOCKS_T 16384
 #endif
-static inline int grid_for_waves(int64_t n_waves, int max_blocks = EW_MAX_BLOCKS_W) {
-    int64_t blocks = (n_waves + EW_WAVES - 1) / EW_WAVES;
-    if (blocks < 1) blocks = 1;
-    if (blocks > max_blocks) blocks = max_blocks;
-    return (int)blocks;
-}
 static inline int grid_for_threads(int64_t n, int max_blocks = EW_MAX_BLOCKS_T) {
     int64_t blocks = (n + EW_THREADS - 1) / EW_THREADS;
     if (blocks < 1) blocks = 1;
@@ -509,7 +497,6 @@ rowtable_fwd_kernel(const float4* __restrict__ table, const int32_t* __restrict_
     amax_block_commit(am, amax_out, amax_lds);
 }
 
-constexpr int TBL_MAXROWS = 8;   // num_behavior + 1 <= 8
 
 // dtable[idx[t]][c] += dy[src(t)][col0+c]; per-thread predicated accumulators, LDS combine, one
 // atomic per workgroup per table element.
@@ -566,816 +553,6 @@ rowtable_bwd_kernel(const TG* __restrict__ dy, int lddy, int col0, const int32_t
         }
     } else {
         for (int i = threadIdx.x; i < nrows * E; i += EW_THREADS) atomicAdd(&dtable[i], lds_tbl[i]);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// q/k per-head RMSNorm + RoPE (+ behaviour bias), head_dim = 64: one wave per (token, head)
-// ---------------------------------------------------------------------------------------------
-// 16 lanes x float4 per (token, head) row, four rows per wave: 16-byte accesses, the 64-wide reductions
-// are four xor-shuffles inside the 16-lane group, the RoPE partner (d +- 32) is lane +- 8 of the group.
-__device__ __forceinline__ float group16_sum(float v) {
-    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
-    return v;
-}
-
-// TA = activation type of qkv / q_rot / k_rot.  With bf16 activations the arithmetic mirrors what the reference does
-// under autocast (ref:SeqRec/tasks/train_SMB_decoder.py:114-118): the projection output is bf16; for the self attention
-// Qwen3MoeRMSNorm sees a bf16 input and rounds the normalised value to bf16 before the fp32 weight multiply; for the
-// cross attention the fp32 behaviour bias is added first, so the norm runs in fp32; RoPE is fp32; SDPA's inputs
-// (q_rot, k_rot, v) are rounded to bf16.  The biased pre-norm values are NOT written back in bf16 (the backward adds
-// the bias again, exactly); the fp32 kernels keep writing them back as in round 1.
-template <typename TA>
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_fwd_kernel(TA* __restrict__ qkv, int T, int S, int nq, int nkv,
-                       const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                       const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                       const float* __restrict__ bias_q, const float* __restrict__ bias_k,
-                       const float* __restrict__ bias_v, const int32_t* __restrict__ act_idx,
-                       TA* __restrict__ q_rot, TA* __restrict__ k_rot, const int32_t* __restrict__ pos_ids,
-                       uint32_t* __restrict__ amax_q, uint32_t* __restrict__ amax_k, uint32_t* __restrict__ amax_v) {
-    constexpr bool F32 = sizeof(TA) == 4;
-    __shared__ uint32_t amax_lds[3][4];
-    uint32_t amq = 0, amk = 0, amv = 0;                 // gamer_amax_sink(3): max |q_rot|, max |k_rot|, max |v + bias_v|
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 15, sub = lane >> 4;
-    const int64_t wave = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * EW_THREADS) >> 6;
-    const bool cross = bias_q != nullptr;
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    const float4 wq4 = reinterpret_cast<const float4*>(wq)[g], wk4 = reinterpret_cast<const float4*>(wk)[g];
-    const float sgn = g < 8 ? -1.f : 1.f;
-    const int64_t total = (int64_t)T * NH;
-    for (int64_t i0 = wave * 4; i0 < total; i0 += nwaves * 4) {
-        const int64_t i = i0 + sub;
-        const bool live = i < total;
-        const int64_t ic = live ? i : total - 1;
-        const int t = (int)(ic / NH);
-        const int hd = (int)(ic % NH);
-        const int a = cross ? act_idx[t] : 0;
-        TA* row = qkv + (int64_t)t * ldqkv;
-        if (hd < nq + nkv) {
-            const bool isq = hd < nq;
-            TA* src = row + hd * 64 + 4 * g;   // q heads then k heads are contiguous
-            float4 x = ld4(src);
-            if (cross) {
-                const float4 b4 = isq ? reinterpret_cast<const float4*>(bias_q + (int64_t)a * nq * 64 + hd * 64)[g]
-                                      : reinterpret_cast<const float4*>(bias_k + (int64_t)a * nkv * 64 + (hd - nq) * 64)[g];
-                x.x += b4.x; x.y += b4.y; x.z += b4.z; x.w += b4.w;
-                if (F32 && live) st4(src, x);             // fp32: keep the pre-norm (biased) value for the backward
-            }
-            const float ss = group16_sum(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-            const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-            const float4 w4 = isq ? wq4 : wk4;
-            float4 xn;
-            xn.x = x.x * rstd; xn.y = x.y * rstd; xn.z = x.z * rstd; xn.w = x.w * rstd;
-            if (!F32 && !cross) {                         // Qwen3MoeRMSNorm on a bf16 tensor: .to(input_dtype) before * weight
-                xn.x = round_as<TA>(xn.x); xn.y = round_as<TA>(xn.y); xn.z = round_as<TA>(xn.z); xn.w = round_as<TA>(xn.w);
-            }
-            float4 y;
-            y.x = w4.x * xn.x; y.y = w4.y * xn.y; y.z = w4.z * xn.z; y.w = w4.w * xn.w;
-            float4 pr;
-            pr.x = __shfl_xor(y.x, 8, 64); pr.y = __shfl_xor(y.y, 8, 64); pr.z = __shfl_xor(y.z, 8, 64); pr.w = __shfl_xor(y.w, 8, 64);
-            const int pos = pos_ids ? pos_ids[t] : t % S;        // per-token RoPE position (session model) or the index
-            const float4 c4 = reinterpret_cast<const float4*>(cos_t + pos * 64)[g];
-            const float4 s4 = reinterpret_cast<const float4*>(sin_t + pos * 64)[g];
-            // fma(sin, sgn * partner, y * cos) spelled out - what the token-major kernel's y * cos + sgn * partner * sin compiles to:
-            // left to the compiler's contraction, this kernel fused y * cos instead and the fp32 outputs of the two forms differed
-            // in the last bit (tests/test_indexed_paths_gpu.py holds them to the same bits)
-            float4 o;
-            o.x = __builtin_fmaf(s4.x, sgn * pr.x, y.x * c4.x); o.y = __builtin_fmaf(s4.y, sgn * pr.y, y.y * c4.y);
-            o.z = __builtin_fmaf(s4.z, sgn * pr.z, y.z * c4.z); o.w = __builtin_fmaf(s4.w, sgn * pr.w, y.w * c4.w);
-            if (live) {
-                if (isq) { st4(q_rot + (int64_t)t * nq * 64 + hd * 64 + 4 * g, o); amq = amax_f4(amq, o); }
-                else { st4(k_rot + (int64_t)t * nkv * 64 + (hd - nq) * 64 + 4 * g, o); amk = amax_f4(amk, o); }
-            }
-        } else {
-            // (only reached when cross) v += bias_v; the shuffles above are skipped by the whole 16-lane group
-            const int hv = hd - nq - nkv;
-            TA* dst = row + (nq + nkv + hv) * 64 + 4 * g;
-            const float4 b4 = reinterpret_cast<const float4*>(bias_v + (int64_t)a * nkv * 64 + hv * 64)[g];
-            float4 x = ld4(dst);
-            x.x += b4.x; x.y += b4.y; x.z += b4.z; x.w += b4.w;
-            if (live) { st4(dst, x); amv = amax_f4(amv, x); }
-        }
-    }
-    amax_block_commit(amq, amax_q, amax_lds[0]);
-    amax_block_commit(amk, amax_k, amax_lds[1]);
-    amax_block_commit(amv, amax_v, amax_lds[2]);
-}
-
-// fp32, token-major: one 16-lane group per TOKEN, walking its q and k heads three at a time (three 16-byte loads in flight
-// per lane, the token's cos / sin rows and behaviour index loaded once instead of once per head, no 64-bit division per row).
-// Same arithmetic per element as the kernel above (bit-identical outputs).  The row-major form above reached 3.5 TB/s of
-// 5.6 achievable: one dependent load -> reduce -> store chain per lane and per iteration, behind ~100 integer instructions.
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_fwd_tok_kernel(float* __restrict__ qkv, int T, int S, int nq, int nkv,
-                           const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                           const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                           const float* __restrict__ bias_q, const float* __restrict__ bias_k,
-                           const float* __restrict__ bias_v, const int32_t* __restrict__ act_idx,
-                           float* __restrict__ q_rot, float* __restrict__ k_rot, const int32_t* __restrict__ pos_ids,
-                           uint32_t* __restrict__ amax_q, uint32_t* __restrict__ amax_k, uint32_t* __restrict__ amax_v) {
-    __shared__ uint32_t amax_lds[3][4];
-    uint32_t amq = 0, amk = 0, amv = 0;
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 15, sub = lane >> 4;
-    const int64_t wave = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * EW_THREADS) >> 6;
-    const bool cross = bias_q != nullptr;
-    const int nqk = nq + nkv;
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    const float4 wq4 = reinterpret_cast<const float4*>(wq)[g], wk4 = reinterpret_cast<const float4*>(wk)[g];
-    const float sgn = g < 8 ? -1.f : 1.f;
-    for (int64_t t0 = wave * 4; t0 < T; t0 += nwaves * 4) {
-        const int64_t tt = t0 + sub;
-        const bool live = tt < T;
-        const int t = (int)(live ? tt : T - 1);
-        const int a = cross ? act_idx[t] : 0;
-        const int pos = pos_ids ? pos_ids[t] : t % S;
-        const float4 c4 = reinterpret_cast<const float4*>(cos_t + pos * 64)[g];
-        const float4 s4 = reinterpret_cast<const float4*>(sin_t + pos * 64)[g];
-        float* row = qkv + (int64_t)t * ldqkv + 4 * g;
-        const float* bq = cross ? bias_q + (int64_t)a * nq * 64 + 4 * g : nullptr;
-        const float* bk = cross ? bias_k + (int64_t)a * nkv * 64 + 4 * g : nullptr;
-        for (int h0 = 0; h0 < nqk; h0 += 3) {
-            float4 x[3];
-#pragma unroll
-            for (int u = 0; u < 3; ++u) x[u] = ld4(row + min(h0 + u, nqk - 1) * 64);
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int hd = h0 + u;
-                if (hd >= nqk) break;                       // (uniform over the wave)
-                const bool isq = hd < nq;
-                float4 xx = x[u];
-                if (cross) {
-                    const float4 b4 = *reinterpret_cast<const float4*>(isq ? bq + hd * 64 : bk + (hd - nq) * 64);
-                    xx.x += b4.x; xx.y += b4.y; xx.z += b4.z; xx.w += b4.w;
-                    if (live) st4(row + hd * 64, xx);       // keep the pre-norm (biased) value for the backward
-                }
-                const float ss = group16_sum(xx.x * xx.x + xx.y * xx.y + xx.z * xx.z + xx.w * xx.w);
-                const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-                const float4 w4 = isq ? wq4 : wk4;
-                float4 xn;
-                xn.x = xx.x * rstd; xn.y = xx.y * rstd; xn.z = xx.z * rstd; xn.w = xx.w * rstd;
-                float4 y;
-                y.x = w4.x * xn.x; y.y = w4.y * xn.y; y.z = w4.z * xn.z; y.w = w4.w * xn.w;
-                float4 pr;
-                pr.x = __shfl_xor(y.x, 8, 64); pr.y = __shfl_xor(y.y, 8, 64); pr.z = __shfl_xor(y.z, 8, 64); pr.w = __shfl_xor(y.w, 8, 64);
-                float4 o;
-                o.x = y.x * c4.x + sgn * pr.x * s4.x; o.y = y.y * c4.y + sgn * pr.y * s4.y;
-                o.z = y.z * c4.z + sgn * pr.z * s4.z; o.w = y.w * c4.w + sgn * pr.w * s4.w;
-                if (live) {
-                    if (isq) { st4(q_rot + (int64_t)t * nq * 64 + hd * 64 + 4 * g, o); amq = amax_f4(amq, o); }
-                    else { st4(k_rot + (int64_t)t * nkv * 64 + (hd - nq) * 64 + 4 * g, o); amk = amax_f4(amk, o); }
-                }
-            }
-        }
-        if (cross) {                                        // v += bias_v
-            for (int hv = 0; hv < nkv; ++hv) {
-                float* dst = row + (nqk + hv) * 64;
-                const float4 b4 = *reinterpret_cast<const float4*>(bias_v + (int64_t)a * nkv * 64 + hv * 64 + 4 * g);
-                float4 xv = ld4(dst);
-                xv.x += b4.x; xv.y += b4.y; xv.z += b4.z; xv.w += b4.w;
-                if (live) { st4(dst, xv); amv = amax_f4(amv, xv); }
-            }
-        }
-    }
-    amax_block_commit(amq, amax_q, amax_lds[0]);
-    amax_block_commit(amk, amax_k, amax_lds[1]);
-    amax_block_commit(amv, amax_v, amax_lds[2]);
-}
-
-// Each wave keeps one head for its whole life so that the norm-weight and bias gradients accumulate in
-// registers (four tokens per iteration, one per 16-lane group).  At the end every wave writes its sums as one row of
-// `partial` [waves_per_head][NH][1 + nb1][64] (slot 0: norm weight, slots 1..: bias rows) and
-// qknorm_partial_reduce_kernel folds the rows in a fixed order.  (Round 1 finished with same-address float atomics
-// from ~8000 waves into 64 + nb1*64 addresses per head: a 0.4 ms floor per call at every batch size.)
-template <typename TA>
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_bwd_kernel(const TA* __restrict__ qkv, const TA* __restrict__ dq_rot,
-                       const TA* __restrict__ dk_rot, int T, int S, int nq, int nkv,
-                       const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                       const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                       int cross, const float* __restrict__ bias_q, const float* __restrict__ bias_k,
-                       const int32_t* __restrict__ act_idx, int nb1,
-                       TA* __restrict__ dqkv, float* __restrict__ partial,
-                       int waves_per_head, const int32_t* __restrict__ pos_ids, uint32_t* __restrict__ amax_out) {
-    constexpr bool F32 = sizeof(TA) == 4;
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 15, sub = lane >> 4;
-    const int64_t wave = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6;
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    if (wave >= (int64_t)NH * waves_per_head) return;
-    float am = 0.f;                                    // gamer_amax_sink: max |dq|, |dk| written here (one atomic per wave)
-    const int hd = (int)(wave % NH);
-    const int w0 = (int)(wave / NH);
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    float4 dwacc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 dbacc[TBL_MAXROWS];
-#pragma unroll
-    for (int a = 0; a < TBL_MAXROWS; ++a) dbacc[a] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float sgn = g < 8 ? 1.f : -1.f;             // transpose of the rotation
-    if (hd < nq + nkv) {
-        const bool isq = hd < nq;
-        const float4 w4 = isq ? reinterpret_cast<const float4*>(wq)[g] : reinterpret_cast<const float4*>(wk)[g];
-        for (int tb = w0 * 4; tb < T; tb += waves_per_head * 4) {
-            const int t = tb + sub;
-            const bool live = t < T;
-            const int tc = live ? t : T - 1;
-            float4 x = ld4(qkv + (int64_t)tc * ldqkv + hd * 64 + 4 * g);   // pre-norm (fp32: bias included)
-            const int a_t = cross ? act_idx[tc] : 0;
-            if (!F32 && cross) {
-                const float4 b4 = isq ? reinterpret_cast<const float4*>(bias_q + (int64_t)a_t * nq * 64 + hd * 64)[g]
-                                      : reinterpret_cast<const float4*>(bias_k + (int64_t)a_t * nkv * 64 + (hd - nq) * 64)[g];
-                x.x += b4.x; x.y += b4.y; x.z += b4.z; x.w += b4.w;
-            }
-            const float4 d = isq ? ld4(dq_rot + (int64_t)tc * nq * 64 + hd * 64 + 4 * g)
-                                 : ld4(dk_rot + (int64_t)tc * nkv * 64 + (hd - nq) * 64 + 4 * g);
-            const int pos = pos_ids ? pos_ids[tc] : tc % S;
-            const float4 c4 = reinterpret_cast<const float4*>(cos_t + pos * 64)[g];
-            const float4 s4 = reinterpret_cast<const float4*>(sin_t + pos * 64)[g];
-            float4 dp;
-            dp.x = __shfl_xor(d.x, 8, 64); dp.y = __shfl_xor(d.y, 8, 64); dp.z = __shfl_xor(d.z, 8, 64); dp.w = __shfl_xor(d.w, 8, 64);
-            // dy_j = dout_j cos_j + (j<32 ? +1 : -1) * dout_partner * sin_j
-            float4 dy;
-            dy.x = d.x * c4.x + sgn * dp.x * s4.x; dy.y = d.y * c4.y + sgn * dp.y * s4.y;
-            dy.z = d.z * c4.z + sgn * dp.z * s4.z; dy.w = d.w * c4.w + sgn * dp.w * s4.w;
-            const float ss = group16_sum(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-            const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-            float4 xh;
-            xh.x = x.x * rstd; xh.y = x.y * rstd; xh.z = x.z * rstd; xh.w = x.w * rstd;
-            const float lv = live ? 1.f : 0.f;
-            if (!F32 && !cross) {
-                // the weight multiplied the bf16-rounded normalised value in the forward (the cast's gradient is identity)
-                dwacc.x += lv * dy.x * round_as<TA>(xh.x); dwacc.y += lv * dy.y * round_as<TA>(xh.y);
-                dwacc.z += lv * dy.z * round_as<TA>(xh.z); dwacc.w += lv * dy.w * round_as<TA>(xh.w);
-            } else {
-                dwacc.x += lv * dy.x * xh.x; dwacc.y += lv * dy.y * xh.y; dwacc.z += lv * dy.z * xh.z; dwacc.w += lv * dy.w * xh.w;
-            }
-            float4 gg;
-            gg.x = dy.x * w4.x; gg.y = dy.y * w4.y; gg.z = dy.z * w4.z; gg.w = dy.w * w4.w;
-            const float dot = group16_sum(gg.x * xh.x + gg.y * xh.y + gg.z * xh.z + gg.w * xh.w) * (1.f / 64.f);
-            float4 dx;
-            dx.x = rstd * (gg.x - xh.x * dot); dx.y = rstd * (gg.y - xh.y * dot);
-            dx.z = rstd * (gg.z - xh.z * dot); dx.w = rstd * (gg.w - xh.w * dot);
-            if (live) {
-                st4(dqkv + (int64_t)t * ldqkv + hd * 64 + 4 * g, dx);
-                am = fmaxf(fmaxf(fmaxf(am, fabsf(dx.x)), fabsf(dx.y)), fmaxf(fabsf(dx.z), fabsf(dx.w)));
-            }
-            if (cross) {
-                const int a_l = live ? a_t : -1;
-#pragma unroll
-                for (int a = 0; a < TBL_MAXROWS; ++a) {
-                    const float m = (a_l == a) ? 1.f : 0.f;
-                    dbacc[a].x += m * dx.x; dbacc[a].y += m * dx.y; dbacc[a].z += m * dx.z; dbacc[a].w += m * dx.w;
-                }
-            }
-        }
-    } else {
-        const int hv = hd - nq - nkv;
-        for (int tb = w0 * 4; tb < T; tb += waves_per_head * 4) {
-            const int t = tb + sub;
-            const bool live = t < T;
-            const int tc = live ? t : T - 1;
-            const float4 dv = ld4(dqkv + (int64_t)tc * ldqkv + (nq + nkv + hv) * 64 + 4 * g);
-            const int a_t = live ? act_idx[t] : -1;
-#pragma unroll
-            for (int a = 0; a < TBL_MAXROWS; ++a) {
-                const float m = (a_t == a) ? 1.f : 0.f;
-                dbacc[a].x += m * dv.x; dbacc[a].y += m * dv.y; dbacc[a].z += m * dv.z; dbacc[a].w += m * dv.w;
-            }
-        }
-    }
-    if (amax_out) {
-        uint32_t m = __float_as_uint(am);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-        if (lane == 0 && m) amax_publish(m, amax_out, (uint32_t)wave);
-    }
-    // fold the four 16-lane groups, then group 0 writes this wave's row of partial sums
-    auto fold = [&](float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; };
-    const int SL = 1 + (cross ? nb1 : 0);
-    float* prow = partial + ((int64_t)w0 * NH + hd) * SL * 64;
-    {
-        const float a0 = fold(dwacc.x), a1 = fold(dwacc.y), a2 = fold(dwacc.z), a3 = fold(dwacc.w);
-        if (sub == 0) reinterpret_cast<float4*>(prow)[g] = make_float4(a0, a1, a2, a3);      // zeros for the v heads
-    }
-    if (cross) {
-#pragma unroll
-        for (int a = 0; a < TBL_MAXROWS; ++a) {
-            const float b0 = fold(dbacc[a].x), b1 = fold(dbacc[a].y), b2 = fold(dbacc[a].z), b3 = fold(dbacc[a].w);
-            if (a < nb1 && sub == 0) reinterpret_cast<float4*>(prow + (1 + a) * 64)[g] = make_float4(b0, b1, b2, b3);
-        }
-    }
-}
-
-// fp32, self attention (no behaviour biases): token-major like qknorm_rope_fwd_tok_kernel - one 16-lane group per token walks its
-// q and k heads three at a time (six 16-byte loads in flight per lane), cos / sin once per token; the two norm-weight gradients
-// accumulate in registers over all the heads of all the tokens of the wave and leave as ONE partial row [dwq | dwk] per wave
-// (qknorm_partial_reduce_kernel with nq = nkv = 1 folds them).  Same arithmetic per element as qknorm_rope_bwd_kernel.
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_bwd_tok_kernel(const float* __restrict__ qkv, const float* __restrict__ dq_rot, const float* __restrict__ dk_rot,
-                           int T, int S, int nq, int nkv, const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                           const float* __restrict__ cos_t, const float* __restrict__ sin_t, float* __restrict__ dqkv,
-                           float* __restrict__ partial, int n_waves, const int32_t* __restrict__ pos_ids,
-                           uint32_t* __restrict__ amax_out) {
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 15, sub = lane >> 4;
-    const int wave = (int)(((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6);
-    if (wave >= n_waves) return;
-    float am = 0.f;
-    const int nqk = nq + nkv;
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    const float4 wq4 = reinterpret_cast<const float4*>(wq)[g], wk4 = reinterpret_cast<const float4*>(wk)[g];
-    float4 dwq = make_float4(0.f, 0.f, 0.f, 0.f), dwk = dwq;
-    const float sgn = g < 8 ? 1.f : -1.f;             // transpose of the rotation
-    for (int tb = wave * 4; tb < T; tb += n_waves * 4) {
-        const int t = tb + sub;
-        const bool live = t < T;
-        const int tc = live ? t : T - 1;
-        const int pos = pos_ids ? pos_ids[tc] : tc % S;
-        const float4 c4 = reinterpret_cast<const float4*>(cos_t + pos * 64)[g];
-        const float4 s4 = reinterpret_cast<const float4*>(sin_t + pos * 64)[g];
-        const float* xrow = qkv + (int64_t)tc * ldqkv + 4 * g;
-        const float* dqrow = dq_rot + (int64_t)tc * nq * 64 + 4 * g;
-        const float* dkrow = dk_rot + (int64_t)tc * nkv * 64 + 4 * g;
-        const float lv = live ? 1.f : 0.f;
-        for (int h0 = 0; h0 < nqk; h0 += 3) {
-            float4 xs[3], ds[3];
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int hd = min(h0 + u, nqk - 1);
-                xs[u] = ld4(xrow + hd * 64);
-                ds[u] = hd < nq ? ld4(dqrow + hd * 64) : ld4(dkrow + (hd - nq) * 64);
-            }
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int hd = h0 + u;
-                if (hd >= nqk) break;                       // (uniform over the wave)
-                const bool isq = hd < nq;
-                const float4 x = xs[u], d = ds[u];
-                const float4 w4 = isq ? wq4 : wk4;
-                float4 dp;
-                dp.x = __shfl_xor(d.x, 8, 64); dp.y = __shfl_xor(d.y, 8, 64); dp.z = __shfl_xor(d.z, 8, 64); dp.w = __shfl_xor(d.w, 8, 64);
-                float4 dy;
-                dy.x = d.x * c4.x + sgn * dp.x * s4.x; dy.y = d.y * c4.y + sgn * dp.y * s4.y;
-                dy.z = d.z * c4.z + sgn * dp.z * s4.z; dy.w = d.w * c4.w + sgn * dp.w * s4.w;
-                const float ss = group16_sum(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-                const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-                float4 xh;
-                xh.x = x.x * rstd; xh.y = x.y * rstd; xh.z = x.z * rstd; xh.w = x.w * rstd;
-                if (isq) { dwq.x += lv * dy.x * xh.x; dwq.y += lv * dy.y * xh.y; dwq.z += lv * dy.z * xh.z; dwq.w += lv * dy.w * xh.w; }
-                else { dwk.x += lv * dy.x * xh.x; dwk.y += lv * dy.y * xh.y; dwk.z += lv * dy.z * xh.z; dwk.w += lv * dy.w * xh.w; }
-                float4 gg;
-                gg.x = dy.x * w4.x; gg.y = dy.y * w4.y; gg.z = dy.z * w4.z; gg.w = dy.w * w4.w;
-                const float dot = group16_sum(gg.x * xh.x + gg.y * xh.y + gg.z * xh.z + gg.w * xh.w) * (1.f / 64.f);
-                float4 dx;
-                dx.x = rstd * (gg.x - xh.x * dot); dx.y = rstd * (gg.y - xh.y * dot);
-                dx.z = rstd * (gg.z - xh.z * dot); dx.w = rstd * (gg.w - xh.w * dot);
-                if (live) {
-                    st4(dqkv + (int64_t)t * ldqkv + hd * 64 + 4 * g, dx);
-                    am = fmaxf(fmaxf(fmaxf(am, fabsf(dx.x)), fabsf(dx.y)), fmaxf(fabsf(dx.z), fabsf(dx.w)));
-                }
-            }
-        }
-    }
-    if (amax_out) {
-        uint32_t m = __float_as_uint(am);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-        if (lane == 0 && m) amax_publish(m, amax_out, (uint32_t)wave);
-    }
-    auto fold = [&](float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; };
-    float* prow = partial + (int64_t)wave * 128;
-    const float a0 = fold(dwq.x), a1 = fold(dwq.y), a2 = fold(dwq.z), a3 = fold(dwq.w);
-    const float b0 = fold(dwk.x), b1 = fold(dwk.y), b2 = fold(dwk.z), b3 = fold(dwk.w);
-    if (sub == 0) {
-        reinterpret_cast<float4*>(prow)[g] = make_float4(a0, a1, a2, a3);
-        reinterpret_cast<float4*>(prow + 64)[g] = make_float4(b0, b1, b2, b3);
-    }
-}
-
-// ---- bf16 activations: 8 lanes x 8 elements (16 bytes) per (token, head) row, 8 rows per wave --------------------
-// Same arithmetic as the <bf16_t> instantiations of the kernels above (which move 8 bytes per lane and ran at
-// 2.4 TB/s); the RoPE partner (d +- 32) is lane +- 4 of the 8-lane group.
-__device__ __forceinline__ float group8_sum(float v) {
-    v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-    return v;
-}
-__device__ __forceinline__ void ld8(const bf16_t* p, float (&f)[8]) {
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-}
-__device__ __forceinline__ void ld8(const float* p, float (&f)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-__device__ __forceinline__ void st8(bf16_t* p, const float (&f)[8]) {
-    f32x8v v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = f[e];
-    *reinterpret_cast<bf16x8*>(p) = __builtin_convertvector(v, bf16x8);
-}
-
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_fwd_b8_kernel(bf16_t* __restrict__ qkv, int T, int S, int nq, int nkv,
-                          const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                          const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                          const float* __restrict__ bias_q, const float* __restrict__ bias_k,
-                          const float* __restrict__ bias_v, const int32_t* __restrict__ act_idx,
-                          bf16_t* __restrict__ q_rot, bf16_t* __restrict__ k_rot, const int32_t* __restrict__ pos_ids) {
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 7, sub = lane >> 3;
-    const int64_t wave = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * EW_THREADS) >> 6;
-    const bool cross = bias_q != nullptr;
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    float wqv[8], wkv[8];
-    ld8(wq + 8 * g, wqv);
-    ld8(wk + 8 * g, wkv);
-    const float sgn = g < 4 ? -1.f : 1.f;
-    const int64_t total = (int64_t)T * NH;
-    for (int64_t i0 = wave * 8; i0 < total; i0 += nwaves * 8) {
-        const int64_t i = i0 + sub;
-        const bool live = i < total;
-        const int64_t ic = live ? i : total - 1;
-        const int t = (int)(ic / NH);
-        const int hd = (int)(ic % NH);
-        const int a = cross ? act_idx[t] : 0;
-        bf16_t* row = qkv + (int64_t)t * ldqkv;
-        if (hd < nq + nkv) {
-            const bool isq = hd < nq;
-            float x[8];
-            ld8(row + hd * 64 + 8 * g, x);
-            if (cross) {
-                float b[8];
-                ld8(isq ? bias_q + (int64_t)a * nq * 64 + hd * 64 + 8 * g : bias_k + (int64_t)a * nkv * 64 + (hd - nq) * 64 + 8 * g, b);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] += b[e];
-            }
-            float ss = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss += x[e] * x[e];
-            ss = group8_sum(ss);
-            const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-            float y[8], pr[8], c[8], sn[8], o[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float xn = x[e] * rstd;
-                if (!cross) xn = round_as<bf16_t>(xn);        // Qwen3MoeRMSNorm on a bf16 tensor: .to(input_dtype) before * weight
-                y[e] = (isq ? wqv[e] : wkv[e]) * xn;
-                pr[e] = __shfl_xor(y[e], 4, 64);
-            }
-            const int pos = pos_ids ? pos_ids[t] : t % S;
-            ld8(cos_t + pos * 64 + 8 * g, c);
-            ld8(sin_t + pos * 64 + 8 * g, sn);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = y[e] * c[e] + sgn * pr[e] * sn[e];
-            if (live) {
-                if (isq) st8(q_rot + (int64_t)t * nq * 64 + hd * 64 + 8 * g, o);
-                else st8(k_rot + (int64_t)t * nkv * 64 + (hd - nq) * 64 + 8 * g, o);
-            }
-        } else {
-            const int hv = hd - nq - nkv;
-            bf16_t* dst = row + (nq + nkv + hv) * 64 + 8 * g;
-            float x[8], b[8];
-            ld8(dst, x);
-            ld8(bias_v + (int64_t)a * nkv * 64 + hv * 64 + 8 * g, b);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] += b[e];
-            if (live) st8(dst, x);
-        }
-    }
-}
-
-// token-major form of the kernel above (see qknorm_rope_fwd_tok_kernel): one 8-lane group per token, its heads three at a
-// time, cos / sin / behaviour index once per token; same arithmetic per element
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_fwd_b8_tok_kernel(bf16_t* __restrict__ qkv, int T, int S, int nq, int nkv,
-                              const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                              const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                              const float* __restrict__ bias_q, const float* __restrict__ bias_k,
-                              const float* __restrict__ bias_v, const int32_t* __restrict__ act_idx,
-                              bf16_t* __restrict__ q_rot, bf16_t* __restrict__ k_rot, const int32_t* __restrict__ pos_ids) {
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 7, sub = lane >> 3;
-    const int64_t wave = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6;
-    const int64_t nwaves = ((int64_t)gridDim.x * EW_THREADS) >> 6;
-    const bool cross = bias_q != nullptr;
-    const int nqk = nq + nkv;
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    float wqv[8], wkv[8];
-    ld8(wq + 8 * g, wqv);
-    ld8(wk + 8 * g, wkv);
-    const float sgn = g < 4 ? -1.f : 1.f;
-    for (int64_t t0 = wave * 8; t0 < T; t0 += nwaves * 8) {
-        const int64_t tt = t0 + sub;
-        const bool live = tt < T;
-        const int t = (int)(live ? tt : T - 1);
-        const int a = cross ? act_idx[t] : 0;
-        const int pos = pos_ids ? pos_ids[t] : t % S;
-        float c[8], sn[8];
-        ld8(cos_t + pos * 64 + 8 * g, c);
-        ld8(sin_t + pos * 64 + 8 * g, sn);
-        bf16_t* row = qkv + (int64_t)t * ldqkv + 8 * g;
-        for (int h0 = 0; h0 < nqk; h0 += 3) {
-            float x[3][8];
-#pragma unroll
-            for (int u = 0; u < 3; ++u) ld8(row + min(h0 + u, nqk - 1) * 64, x[u]);
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int hd = h0 + u;
-                if (hd >= nqk) break;                       // (uniform over the wave)
-                const bool isq = hd < nq;
-                if (cross) {
-                    float b[8];
-                    ld8(isq ? bias_q + (int64_t)a * nq * 64 + hd * 64 + 8 * g : bias_k + (int64_t)a * nkv * 64 + (hd - nq) * 64 + 8 * g, b);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) x[u][e] += b[e];
-                }
-                float ss = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ss += x[u][e] * x[u][e];
-                ss = group8_sum(ss);
-                const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-                float y[8], pr[8], o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float xn = x[u][e] * rstd;
-                    if (!cross) xn = round_as<bf16_t>(xn);    // Qwen3MoeRMSNorm on a bf16 tensor: .to(input_dtype) before * weight
-                    y[e] = (isq ? wqv[e] : wkv[e]) * xn;
-                    pr[e] = __shfl_xor(y[e], 4, 64);
-                }
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = y[e] * c[e] + sgn * pr[e] * sn[e];
-                if (live) {
-                    if (isq) st8(q_rot + (int64_t)t * nq * 64 + hd * 64 + 8 * g, o);
-                    else st8(k_rot + (int64_t)t * nkv * 64 + (hd - nq) * 64 + 8 * g, o);
-                }
-            }
-        }
-        if (cross) {
-            for (int hv = 0; hv < nkv; ++hv) {
-                bf16_t* dst = row + (nqk + hv) * 64;
-                float xv[8], b[8];
-                ld8(dst, xv);
-                ld8(bias_v + (int64_t)a * nkv * 64 + hv * 64 + 8 * g, b);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) xv[e] += b[e];
-                if (live) st8(dst, xv);
-            }
-        }
-    }
-}
-
-// token-major form for the self-attention calls (see qknorm_rope_bwd_tok_kernel): one 8-lane group per token walks its heads three
-// at a time, cos / sin once per token, the two norm-weight gradients accumulate over all heads and leave as one partial row
-// [dwq | dwk] per wave; same arithmetic per element as the kernel below with cross = 0
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_bwd_b8_tok_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dq_rot, const bf16_t* __restrict__ dk_rot,
-                              int T, int S, int nq, int nkv, const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                              const float* __restrict__ cos_t, const float* __restrict__ sin_t, bf16_t* __restrict__ dqkv,
-                              float* __restrict__ partial, int n_waves, const int32_t* __restrict__ pos_ids) {
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 7, sub = lane >> 3;
-    const int wave = (int)(((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6);
-    if (wave >= n_waves) return;
-    const int nqk = nq + nkv;
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    float wq8[8], wk8[8], dwq[8], dwk[8];
-    ld8(wq + 8 * g, wq8);
-    ld8(wk + 8 * g, wk8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { dwq[e] = 0.f; dwk[e] = 0.f; }
-    const float sgn = g < 4 ? 1.f : -1.f;             // transpose of the rotation
-    for (int tb = wave * 8; tb < T; tb += n_waves * 8) {
-        const int t = tb + sub;
-        const bool live = t < T;
-        const int tc = live ? t : T - 1;
-        const int pos = pos_ids ? pos_ids[tc] : tc % S;
-        float c[8], sn[8];
-        ld8(cos_t + pos * 64 + 8 * g, c);
-        ld8(sin_t + pos * 64 + 8 * g, sn);
-        const bf16_t* xrow = qkv + (int64_t)tc * ldqkv + 8 * g;
-        const bf16_t* dqrow = dq_rot + (int64_t)tc * nq * 64 + 8 * g;
-        const bf16_t* dkrow = dk_rot + (int64_t)tc * nkv * 64 + 8 * g;
-        const float lv = live ? 1.f : 0.f;
-        for (int h0 = 0; h0 < nqk; h0 += 3) {
-            float xs[3][8], ds[3][8];
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int hd = min(h0 + u, nqk - 1);
-                ld8(xrow + hd * 64, xs[u]);
-                ld8(hd < nq ? dqrow + hd * 64 : dkrow + (hd - nq) * 64, ds[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int hd = h0 + u;
-                if (hd >= nqk) break;                       // (uniform over the wave)
-                const bool isq = hd < nq;
-                float ss = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ss += xs[u][e] * xs[u][e];
-                ss = group8_sum(ss);
-                const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-                float gg[8], xh[8], dot = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float dp = __shfl_xor(ds[u][e], 4, 64);
-                    const float dy = ds[u][e] * c[e] + sgn * dp * sn[e];
-                    xh[e] = xs[u][e] * rstd;
-                    const float contrib = lv * dy * round_as<bf16_t>(xh[e]);
-                    if (isq) dwq[e] += contrib; else dwk[e] += contrib;
-                    gg[e] = dy * (isq ? wq8[e] : wk8[e]);
-                    dot += gg[e] * xh[e];
-                }
-                dot = group8_sum(dot) * (1.f / 64.f);
-                float dx[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dx[e] = rstd * (gg[e] - xh[e] * dot);
-                if (live) st8(dqkv + (int64_t)t * ldqkv + hd * 64 + 8 * g, dx);
-            }
-        }
-    }
-    auto fold = [&](float v) { v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; };
-    float* prow = partial + (int64_t)wave * 128;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float a = fold(dwq[e]), b = fold(dwk[e]);
-        if (sub == 0) { prow[8 * g + e] = a; prow[64 + 8 * g + e] = b; }
-    }
-}
-
-// NBR = compile-time bound of the bias-table rows (4 for the shipped three behaviours, 8 otherwise)
-template <int NBR>
-__global__ void __launch_bounds__(EW_THREADS)
-qknorm_rope_bwd_b8_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dq_rot,
-                          const bf16_t* __restrict__ dk_rot, int T, int S, int nq, int nkv,
-                          const float* __restrict__ wq, const float* __restrict__ wk, float eps,
-                          const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                          int cross, const float* __restrict__ bias_q, const float* __restrict__ bias_k,
-                          const int32_t* __restrict__ act_idx, int nb1,
-                          bf16_t* __restrict__ dqkv, float* __restrict__ partial,
-                          int waves_per_head, const int32_t* __restrict__ pos_ids) {
-    const int lane = threadIdx.x & 63;
-    const int g = lane & 7, sub = lane >> 3;
-    const int64_t wave = ((int64_t)blockIdx.x * EW_THREADS + threadIdx.x) >> 6;
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    if (wave >= (int64_t)NH * waves_per_head) return;
-    const int hd = (int)(wave % NH);
-    const int w0 = (int)(wave / NH);
-    const int ldqkv = (nq + 2 * nkv) * 64;
-    float dwacc[8], dbacc[NBR][8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dwacc[e] = 0.f;
-#pragma unroll
-    for (int a = 0; a < NBR; ++a)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) dbacc[a][e] = 0.f;
-    const float sgn = g < 4 ? 1.f : -1.f;             // transpose of the rotation
-    if (hd < nq + nkv) {
-        const bool isq = hd < nq;
-        float w8[8];
-        ld8((isq ? wq : wk) + 8 * g, w8);
-        for (int tb = w0 * 8; tb < T; tb += waves_per_head * 8) {
-            const int t = tb + sub;
-            const bool live = t < T;
-            const int tc = live ? t : T - 1;
-            float x[8], d[8], c[8], sn[8];
-            ld8(qkv + (int64_t)tc * ldqkv + hd * 64 + 8 * g, x);
-            const int a_t = cross ? act_idx[tc] : 0;
-            if (cross) {
-                float b[8];
-                ld8(isq ? bias_q + (int64_t)a_t * nq * 64 + hd * 64 + 8 * g : bias_k + (int64_t)a_t * nkv * 64 + (hd - nq) * 64 + 8 * g, b);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) x[e] += b[e];
-            }
-            ld8(isq ? dq_rot + (int64_t)tc * nq * 64 + hd * 64 + 8 * g : dk_rot + (int64_t)tc * nkv * 64 + (hd - nq) * 64 + 8 * g, d);
-            const int pos = pos_ids ? pos_ids[tc] : tc % S;
-            ld8(cos_t + pos * 64 + 8 * g, c);
-            ld8(sin_t + pos * 64 + 8 * g, sn);
-            float ss = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) ss += x[e] * x[e];
-            ss = group8_sum(ss);
-            const float rstd = rsqrtf(ss * (1.f / 64.f) + eps);
-            const float lv = live ? 1.f : 0.f;
-            float gg[8], xh[8], dot = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float dp = __shfl_xor(d[e], 4, 64);
-                const float dy = d[e] * c[e] + sgn * dp * sn[e];
-                xh[e] = x[e] * rstd;
-                dwacc[e] += lv * dy * (cross ? xh[e] : round_as<bf16_t>(xh[e]));
-                gg[e] = dy * w8[e];
-                dot += gg[e] * xh[e];
-            }
-            dot = group8_sum(dot) * (1.f / 64.f);
-            float dx[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dx[e] = rstd * (gg[e] - xh[e] * dot);
-            if (live) st8(dqkv + (int64_t)t * ldqkv + hd * 64 + 8 * g, dx);
-            if (cross) {
-                const int a_l = live ? a_t : -1;
-#pragma unroll
-                for (int a = 0; a < NBR; ++a) {
-                    const float m = (a_l == a) ? 1.f : 0.f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) dbacc[a][e] += m * dx[e];
-                }
-            }
-        }
-    } else {
-        const int hv = hd - nq - nkv;
-        for (int tb = w0 * 8; tb < T; tb += waves_per_head * 8) {
-            const int t = tb + sub;
-            const bool live = t < T;
-            const int tc = live ? t : T - 1;
-            float dv[8];
-            ld8(dqkv + (int64_t)tc * ldqkv + (nq + nkv + hv) * 64 + 8 * g, dv);
-            const int a_t = live ? act_idx[t] : -1;
-#pragma unroll
-            for (int a = 0; a < NBR; ++a) {
-                const float m = (a_t == a) ? 1.f : 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dbacc[a][e] += m * dv[e];
-            }
-        }
-    }
-    // fold the eight 8-lane groups, then group 0 writes this wave's row of partial sums (same layout as above)
-    auto fold = [&](float v) { v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; };
-    const int SL = 1 + (cross ? nb1 : 0);
-    float* prow = partial + ((int64_t)w0 * NH + hd) * SL * 64;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float s0 = fold(dwacc[e]);
-        if (sub == 0) prow[8 * g + e] = s0;
-    }
-    if (cross) {
-#pragma unroll
-        for (int a = 0; a < NBR; ++a)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float s0 = fold(dbacc[a][e]);
-                if (a < nb1 && sub == 0) prow[(1 + a) * 64 + 8 * g + e] = s0;
-            }
-    }
-}
-
-// dwq[c] += sum over (row, q head) of slot 0; dwk likewise over the k heads; dbias_x[a][head*64 + c] += sum over rows of
-// slot 1 + a.  One workgroup per 32 output columns, 32 row groups, fixed summation order (deterministic).
-// QKR_CW output columns per workgroup, 1024 / QKR_CW row groups: with 32 columns per workgroup the self-attention call
-// (128 output columns) ran on FOUR workgroups, every thread walking ~170 dependent-latency loads: 54 us per call at every
-// batch size, 0.65 ms per step.  8 columns per workgroup = 16 (self) / 400 (cross) workgroups, ~43 / 7 loads per thread;
-// 32-byte row segments out of a 2-MB, L2-resident buffer.  Fixed summation order (deterministic).
-constexpr int QKR_CW = 8;
-constexpr int QKR_RG = 1024 / QKR_CW;
-__global__ void __launch_bounds__(1024)
-qknorm_partial_reduce_kernel(const float* __restrict__ partial, int n_rows, int nq, int nkv, int cross, int nb1,
-                             float* __restrict__ dwq, float* __restrict__ dwk, float* __restrict__ dbias_q,
-                             float* __restrict__ dbias_k, float* __restrict__ dbias_v) {
-    __shared__ float sh[16][QKR_CW];
-    const int cl = threadIdx.x & (QKR_CW - 1), rg = threadIdx.x / QKR_CW;
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    const int SL = 1 + (cross ? nb1 : 0);
-    const int64_t row_stride = (int64_t)NH * SL * 64;
-    const int col = blockIdx.x * QKR_CW + cl;        // [0,64): dwq, [64,128): dwk, then bias columns (head, a, c)
-    int h0, h1, slot, c;
-    float* dst;
-    if (col < 64) { h0 = 0; h1 = nq; slot = 0; c = col; dst = dwq + c; }
-    else if (col < 128) { h0 = nq; h1 = nq + nkv; slot = 0; c = col - 64; dst = dwk + c; }
-    else {
-        const int b = col - 128;
-        const int hd = b / (nb1 * 64), a = (b / 64) % nb1;
-        c = b % 64; h0 = hd; h1 = hd + 1; slot = 1 + a;
-        if (hd < nq) dst = dbias_q + (int64_t)a * nq * 64 + hd * 64 + c;
-        else if (hd < nq + nkv) dst = dbias_k + (int64_t)a * nkv * 64 + (hd - nq) * 64 + c;
-        else dst = dbias_v + (int64_t)a * nkv * 64 + (hd - nq - nkv) * 64 + c;
-    }
-    const int nh = h1 - h0;
-    const int64_t n_items = (int64_t)n_rows * nh;     // (row, head) pairs to add up
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    auto at = [&](int64_t it) { return partial[(it / nh) * row_stride + ((int64_t)(h0 + it % nh) * SL + slot) * 64 + c]; };
-    int64_t it = rg;
-    for (; it + 3 * QKR_RG < n_items; it += 4 * QKR_RG) {
-        s0 += at(it); s1 += at(it + QKR_RG); s2 += at(it + 2 * QKR_RG); s3 += at(it + 3 * QKR_RG);
-    }
-    for (; it < n_items; it += QKR_RG) s0 += at(it);
-    // a wave holds 8 row groups of the same 8 columns: fold them with three shuffles, then the 16 waves through LDS
-    float t = (s0 + s1) + (s2 + s3);
-    t += __shfl_xor(t, 8, 64); t += __shfl_xor(t, 16, 64); t += __shfl_xor(t, 32, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane < QKR_CW) sh[w][lane] = t;
-    __syncthreads();
-    if (threadIdx.x < QKR_CW) {
-        float tot = 0.f;
-#pragma unroll
-        for (int gi = 0; gi < 16; ++gi) tot += sh[gi][threadIdx.x];
-        *dst += tot;
     }
 }
 
@@ -1859,8 +1036,6 @@ AmaxSink take_amax_sink() {
 
 using namespace gamer;
 
-#define ST(s) ((hipStream_t)(s))
-
 extern "C" int gamer_amax_sink(uint32_t* out0, uint32_t* out1) {
     g_amax_sink.out[0] = out0;
     g_amax_sink.out[1] = out1;
@@ -2089,157 +1264,6 @@ extern "C" int gamer_rowtable_bwd_bf16(const gamer_bf16* dy, int lddy, int col0,
                                        float* partial, int64_t partial_numel, void* stream) {
     return rowtable_bwd_impl<bf16_t>("gamer_rowtable_bwd_bf16", (const bf16_t*)dy, lddy, col0, idx, dy_rows, T, E,
                                      n_rows_table, dtable, partial, partial_numel, stream);
-}
-
-template <typename TA>
-static int qknorm_rope_fwd_impl(const char* name, TA* qkv, int T, int S, int nq, int nkv, const float* wq,
-                                const float* wk, float eps, const float* cos_t, const float* sin_t, const float* bias_q,
-                                const float* bias_k, const float* bias_v, const int32_t* act_idx, TA* q_rot, TA* k_rot,
-                                const int32_t* pos_ids, void* stream) {
-    GAMER_CHECK_ARG(qkv && wq && wk && cos_t && sin_t && q_rot && k_rot, "%s: null pointer", name);
-    GAMER_CHECK_ARG(T > 0 && S > 0 && nq > 0 && nkv > 0 && T % S == 0, "%s: bad shape T=%d S=%d nq=%d nkv=%d", name, T, S, nq, nkv);
-    const bool cross = bias_q != nullptr;
-    GAMER_CHECK_ARG(!cross || (bias_k && bias_v && act_idx), "%s: cross needs bias_k, bias_v, act_idx", name);
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    static EnvSwitch row_major_sw("GAMER_QKNORM_ROW_MAJOR");                              // (the round-1 forms, kept for A/B runs and tests)
-    const bool row_major = row_major_sw.is_set();
-    if constexpr (sizeof(TA) == 2) {
-        if (row_major)
-            hipLaunchKernelGGL(qknorm_rope_fwd_b8_kernel, dim3(grid_for_waves(((int64_t)T * NH + 7) / 8)), dim3(EW_THREADS), 0,
-                               ST(stream), qkv, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, bias_q, bias_k, bias_v, act_idx, q_rot,
-                               k_rot, pos_ids);
-        else
-            hipLaunchKernelGGL(qknorm_rope_fwd_b8_tok_kernel, dim3(grid_for_waves(((int64_t)T + 7) / 8)), dim3(EW_THREADS), 0,
-                               ST(stream), qkv, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, bias_q, bias_k, bias_v, act_idx, q_rot,
-                               k_rot, pos_ids);
-    } else {
-        const AmaxSink sink = take_amax_sink();
-        if (row_major)
-            hipLaunchKernelGGL(qknorm_rope_fwd_kernel<TA>, dim3(grid_for_waves(((int64_t)T * NH + 3) / 4)), dim3(EW_THREADS), 0,
-                               ST(stream), qkv, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, bias_q, bias_k, bias_v, act_idx, q_rot,
-                               k_rot, pos_ids, sink.out[0], sink.out[1], sink.out[2]);
-        else
-            hipLaunchKernelGGL(qknorm_rope_fwd_tok_kernel, dim3(grid_for_waves(((int64_t)T + 3) / 4)), dim3(EW_THREADS), 0,
-                               ST(stream), qkv, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, bias_q, bias_k, bias_v, act_idx, q_rot,
-                               k_rot, pos_ids, sink.out[0], sink.out[1], sink.out[2]);
-    }
-    GAMER_CHECK_LAUNCH(name);
-    return 0;
-}
-extern "C" int gamer_qknorm_rope_fwd(float* qkv, int T, int S, int nq, int nkv, const float* wq, const float* wk,
-                                     float eps, const float* cos_t, const float* sin_t, const float* bias_q,
-                                     const float* bias_k, const float* bias_v, const int32_t* act_idx, float* q_rot,
-                                     float* k_rot, const int32_t* pos_ids, void* stream) {
-    return qknorm_rope_fwd_impl<float>("gamer_qknorm_rope_fwd", qkv, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, bias_q,
-                                       bias_k, bias_v, act_idx, q_rot, k_rot, pos_ids, stream);
-}
-extern "C" int gamer_qknorm_rope_fwd_bf16(gamer_bf16* qkv, int T, int S, int nq, int nkv, const float* wq,
-                                          const float* wk, float eps, const float* cos_t, const float* sin_t,
-                                          const float* bias_q, const float* bias_k, const float* bias_v,
-                                          const int32_t* act_idx, gamer_bf16* q_rot, gamer_bf16* k_rot,
-                                          const int32_t* pos_ids, void* stream) {
-    return qknorm_rope_fwd_impl<bf16_t>("gamer_qknorm_rope_fwd_bf16", (bf16_t*)qkv, T, S, nq, nkv, wq, wk, eps, cos_t,
-                                        sin_t, bias_q, bias_k, bias_v, act_idx, (bf16_t*)q_rot, (bf16_t*)k_rot, pos_ids,
-                                        stream);
-}
-
-template <typename TA>
-static int qknorm_rope_bwd_impl(const char* name, const TA* qkv, const TA* dq_rot, const TA* dk_rot, int T, int S,
-                                int nq, int nkv, const float* wq, const float* wk, float eps, const float* cos_t,
-                                const float* sin_t, const float* bias_q, const float* bias_k, const int32_t* act_idx,
-                                int nb1, TA* dqkv, float* dwq, float* dwk, float* dbias_q, float* dbias_k,
-                                float* dbias_v, const int32_t* pos_ids, float* partial, int64_t partial_numel,
-                                void* stream) {
-    GAMER_CHECK_ARG(qkv && dq_rot && dk_rot && wq && wk && cos_t && sin_t && dqkv && dwq && dwk && partial,
-                    "%s: null pointer", name);
-    GAMER_CHECK_ARG(T > 0 && S > 0 && nq > 0 && nkv > 0 && T % S == 0, "%s: bad shape", name);
-    const int cross = bias_q != nullptr ? 1 : 0;
-    GAMER_CHECK_ARG(!cross || (bias_k && act_idx && dbias_q && dbias_k && dbias_v && nb1 > 0 && nb1 <= TBL_MAXROWS),
-                    "%s: cross needs bias_k, act_idx, dbias_*, 0<nb1<=8 (nb1=%d)", name, nb1);
-    const int NH = nq + nkv + (cross ? nkv : 0);
-    const int SL = 1 + (cross ? nb1 : 0);
-    constexpr int RPW = sizeof(TA) == 2 ? 8 : 4;        // token rows per wave iteration
-    int waves_per_head = 8192 / NH;
-    if (waves_per_head > (T + RPW - 1) / RPW) waves_per_head = (T + RPW - 1) / RPW;
-    const int64_t cap = partial_numel / ((int64_t)NH * SL * 64);
-    if (waves_per_head > cap) waves_per_head = (int)cap;
-    GAMER_CHECK_ARG(waves_per_head >= 1 && aligned16(partial),
-                    "%s: partial needs at least %d floats, 16-byte aligned (got %lld)", name, NH * SL * 64,
-                    (long long)partial_numel);
-    const int64_t total_waves = (int64_t)NH * waves_per_head;
-    const int blocks = (int)((total_waves + EW_WAVES - 1) / EW_WAVES);
-    if constexpr (sizeof(TA) == 2) {
-        static EnvSwitch row_major_sw("GAMER_QKNORM_ROW_MAJOR");                         // (the round-1 form, kept for A/B runs and tests)
-        const bool row_major16 = row_major_sw.is_set();
-        int n_waves16 = (T + 7) / 8;
-        if (n_waves16 > 8192) n_waves16 = 8192;
-        if ((int64_t)n_waves16 * 128 > partial_numel) n_waves16 = (int)(partial_numel / 128);
-        if (!cross && !row_major16 && n_waves16 >= 1) {
-            hipLaunchKernelGGL(qknorm_rope_bwd_b8_tok_kernel, dim3((n_waves16 + EW_WAVES - 1) / EW_WAVES), dim3(EW_THREADS), 0,
-                               ST(stream), qkv, dq_rot, dk_rot, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, dqkv, partial, n_waves16,
-                               pos_ids);
-            GAMER_CHECK_LAUNCH(name);
-            hipLaunchKernelGGL(qknorm_partial_reduce_kernel, dim3(128 / QKR_CW), dim3(1024), 0, ST(stream), partial, n_waves16, 1, 1, 0,
-                               0, dwq, dwk, dbias_q, dbias_k, dbias_v);
-            GAMER_CHECK_LAUNCH(name);
-            return 0;
-        }
-        if (!cross || nb1 <= 4)
-            hipLaunchKernelGGL(qknorm_rope_bwd_b8_kernel<4>, dim3(blocks), dim3(EW_THREADS), 0, ST(stream), qkv, dq_rot, dk_rot,
-                               T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, cross, bias_q, bias_k, act_idx, nb1, dqkv, partial,
-                               waves_per_head, pos_ids);
-        else
-            hipLaunchKernelGGL(qknorm_rope_bwd_b8_kernel<TBL_MAXROWS>, dim3(blocks), dim3(EW_THREADS), 0, ST(stream), qkv,
-                               dq_rot, dk_rot, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, cross, bias_q, bias_k, act_idx, nb1,
-                               dqkv, partial, waves_per_head, pos_ids);
-    } else {
-        static EnvSwitch row_major_sw("GAMER_QKNORM_ROW_MAJOR");                         // (the round-1 form, kept for A/B runs and tests)
-        const bool row_major = row_major_sw.is_set();
-        int n_waves = (T + 3) / 4;
-        if (n_waves > 8192) n_waves = 8192;
-        if ((int64_t)n_waves * 128 > partial_numel) n_waves = (int)(partial_numel / 128);
-        if (!cross && !row_major && n_waves >= 1) {
-            // self attention: token-major (one partial row [dwq | dwk] per wave; the reduce sees one q and one k "head")
-            hipLaunchKernelGGL(qknorm_rope_bwd_tok_kernel, dim3((n_waves + EW_WAVES - 1) / EW_WAVES), dim3(EW_THREADS), 0, ST(stream),
-                               qkv, dq_rot, dk_rot, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, dqkv, partial, n_waves, pos_ids,
-                               take_amax_sink().out[0]);
-            GAMER_CHECK_LAUNCH(name);
-            hipLaunchKernelGGL(qknorm_partial_reduce_kernel, dim3(128 / QKR_CW), dim3(1024), 0, ST(stream), partial, n_waves, 1, 1, 0,
-                               0, dwq, dwk, dbias_q, dbias_k, dbias_v);
-            GAMER_CHECK_LAUNCH(name);
-            return 0;
-        }
-        hipLaunchKernelGGL(qknorm_rope_bwd_kernel<TA>, dim3(blocks), dim3(EW_THREADS), 0, ST(stream), qkv, dq_rot, dk_rot, T,
-                           S, nq, nkv, wq, wk, eps, cos_t, sin_t, cross, bias_q, bias_k, act_idx, nb1, dqkv, partial,
-                           waves_per_head, pos_ids, take_amax_sink().out[0]);
-    }
-    GAMER_CHECK_LAUNCH(name);
-    const int cols = 128 + (cross ? NH * nb1 * 64 : 0);
-    hipLaunchKernelGGL(qknorm_partial_reduce_kernel, dim3(cols / QKR_CW), dim3(1024), 0, ST(stream), partial,
-                       waves_per_head, nq, nkv, cross, nb1, dwq, dwk, dbias_q, dbias_k, dbias_v);
-    GAMER_CHECK_LAUNCH(name);
-    return 0;
-}
-extern "C" int gamer_qknorm_rope_bwd(const float* qkv, const float* dq_rot, const float* dk_rot, int T, int S, int nq,
-                                     int nkv, const float* wq, const float* wk, float eps, const float* cos_t,
-                                     const float* sin_t, const float* bias_q, const float* bias_k,
-                                     const int32_t* act_idx, int nb1, float* dqkv, float* dwq, float* dwk,
-                                     float* dbias_q, float* dbias_k, float* dbias_v, const int32_t* pos_ids,
-                                     float* partial, int64_t partial_numel, void* stream) {
-    return qknorm_rope_bwd_impl<float>("gamer_qknorm_rope_bwd", qkv, dq_rot, dk_rot, T, S, nq, nkv, wq, wk, eps, cos_t,
-                                       sin_t, bias_q, bias_k, act_idx, nb1, dqkv, dwq, dwk, dbias_q, dbias_k, dbias_v,
-                                       pos_ids, partial, partial_numel, stream);
-}
-extern "C" int gamer_qknorm_rope_bwd_bf16(const gamer_bf16* qkv, const gamer_bf16* dq_rot, const gamer_bf16* dk_rot,
-                                          int T, int S, int nq, int nkv, const float* wq, const float* wk, float eps,
-                                          const float* cos_t, const float* sin_t, const float* bias_q,
-                                          const float* bias_k, const int32_t* act_idx, int nb1, gamer_bf16* dqkv,
-                                          float* dwq, float* dwk, float* dbias_q, float* dbias_k, float* dbias_v,
-                                          const int32_t* pos_ids, float* partial, int64_t partial_numel, void* stream) {
-    return qknorm_rope_bwd_impl<bf16_t>("gamer_qknorm_rope_bwd_bf16", (const bf16_t*)qkv, (const bf16_t*)dq_rot,
-                                        (const bf16_t*)dk_rot, T, S, nq, nkv, wq, wk, eps, cos_t, sin_t, bias_q, bias_k,
-                                        act_idx, nb1, (bf16_t*)dqkv, dwq, dwk, dbias_q, dbias_k, dbias_v, pos_ids,
-                                        partial, partial_numel, stream);
 }
 
 extern "C" int gamer_residual_dropout_fwd(const float* x_in, const float* delta, const int32_t* src_rows, int T, int H,

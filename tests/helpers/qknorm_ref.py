@@ -19,13 +19,14 @@ NB1S = (1, 4, 5, 8)
 GUARD = 8                                                        # sentinel rows behind every output buffer
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# host dispatch, restated (csrc/elementwise.hip: grid_for_waves, qknorm_rope_fwd_impl, qknorm_rope_bwd_impl, gamer_embedding_bwd)
+# host dispatch, restated (csrc/common.h: grid_for_waves; csrc/qknorm_rope.hip: qknorm_rope_fwd_impl, qknorm_rope_bwd_impl;
+# csrc/elementwise.hip: gamer_embedding_bwd)
 # ---------------------------------------------------------------------------------------------------------------------------
 EW_WAVES = 4                     # waves per workgroup
 FWD_MAX_BLOCKS = 8192            # grid_for_waves' cap: 32768 waves
 BWD_MAX_WAVES = 8192
 QKR_RG = 128                     # row groups of qknorm_partial_reduce_kernel: its four-way loop needs more than 3 * QKR_RG items
-TOK = {F32: "qknorm_rope_bwd_tok_kernel", BF: "qknorm_rope_bwd_b8_tok_kernel"}
+TOK = {F32: "qknorm_rope_bwd_tok_kernel<float>", BF: "qknorm_rope_bwd_tok_kernel<bf16_t>"}
 
 
 def rpw(dtype):
@@ -52,16 +53,15 @@ def min_scratch(cross, nb1, nq, nkv):
 
 def head_major(dtype, cross, nb1):
     if dtype == F32:
-        return "qknorm_rope_bwd_kernel<float>"
-    return "qknorm_rope_bwd_b8_kernel<4>" if (not cross or nb1 <= 4) else "qknorm_rope_bwd_b8_kernel<8>"
+        return "qknorm_rope_bwd_head_kernel<float, 8>"
+    return "qknorm_rope_bwd_head_kernel<bf16_t, 4>" if (not cross or nb1 <= 4) else "qknorm_rope_bwd_head_kernel<bf16_t, 8>"
 
 
 def fwd_dispatch(dtype, cross, T, nq, nkv, row_major=False):
     r, NH = rpw(dtype), n_heads(cross, nq, nkv)
     rows = T * NH if row_major else T                    # row-major: one group of lanes per (token, head); else per token
     waves = EW_WAVES * min(max(cdiv(cdiv(rows, r), EW_WAVES), 1), FWD_MAX_BLOCKS)
-    stem = "qknorm_rope_fwd" + ("_b8" if dtype == BF else "")
-    kernel = (stem + "_kernel" + ("<float>" if dtype == F32 else "")) if row_major else stem + "_tok_kernel"
+    kernel = f"qknorm_rope_fwd_{'row' if row_major else 'tok'}_kernel<{'float' if dtype == F32 else 'bf16_t'}>"
     return dict(kernel=kernel, waves=waves, iters=cdiv(rows, waves * r))
 
 

@@ -1,22 +1,22 @@
-"""Every dispatch path of the indexed kernels in the second half of csrc/elementwise.hip - per-head q/k RMSNorm + RoPE (+ behaviour
-bias), behaviour-table rows, embedding - against fp64 torch on the CPU, through the C ABI (gamer_amd.ops), at the smallest
+"""Every dispatch path of the indexed kernels of csrc/qknorm_rope.hip - per-head q/k RMSNorm + RoPE (+ behaviour bias) - and of
+csrc/elementwise.hip - behaviour-table rows, embedding - against fp64 torch on the CPU, through the C ABI (gamer_amd.ops), at the smallest
 shapes that reach each regime.  tests/helpers/qknorm_ref.py holds the cases, the references and a restatement of the host
 dispatch; every case asserts with it that it runs the kernel, the iteration count and the reduce loop its name claims.
 
 q/k norm + RoPE paths (rows per wave iteration: 4 fp32, 8 bf16; NH = nq + nkv (+ nkv cross); nqk = nq + nkv):
-  forward   token-major (default): qknorm_rope_fwd_tok_kernel / _b8_tok_kernel, heads in groups of three - nqk = 2, 3, 4, 5, 8, 9
-            fill the last group with 2, 3, 1, 2, 2, 3 heads; row-major (GAMER_QKNORM_ROW_MAJOR): qknorm_rope_fwd_kernel<float> /
-            _b8_kernel, bit-identical outputs; grid capped at 32768 waves: T = 131075 (fp32) / 262150 (bf16) take two passes
-  backward  self, token-major  qknorm_rope_bwd_tok_kernel / _b8_tok_kernel: n_waves = min(ceil(T / rows), 8192, scratch / 128)
+  forward   token-major (default): qknorm_rope_fwd_tok_kernel<float> / <bf16_t>, heads in groups of three - nqk = 2, 3, 4, 5, 8, 9
+            fill the last group with 2, 3, 1, 2, 2, 3 heads; row-major (GAMER_QKNORM_ROW_MAJOR): qknorm_rope_fwd_row_kernel<float> /
+            <bf16_t>, bit-identical outputs; grid capped at 32768 waves: T = 131075 (fp32) / 262150 (bf16) take two passes
+  backward  self, token-major  qknorm_rope_bwd_tok_kernel<float> / <bf16_t>: n_waves = min(ceil(T / rows), 8192, scratch / 128)
               T = 301: one iteration per wave; scratch 3 * 128 (or 9 * 64 with (6, 3) heads: 4 waves), T = 101: 9 / 5 iterations,
               the last one partly filled; n_waves = 384 / 385 / 386 / 700: qknorm_partial_reduce_kernel's four-way loop (needs
               more than 384 items) off / on for one row group / on / on with a tail everywhere; T = 32773 / 65541: 4096 waves x 3
               iterations with ops' default scratch, 8192 waves x 2 iterations (the cap) with 8192 * 128 floats
             self, smallest accepted scratch (NH * 64 floats): still token-major, ONE wave; anything smaller is refused, so the
               head-major fallback of a self call is reached through the row-major switch only
-            self, head-major (row-major switch): qknorm_rope_bwd_kernel<float> / _b8_kernel<4> with cross = 0, waves_per_head =
+            self, head-major (row-major switch): qknorm_rope_bwd_head_kernel<float, 8> / <bf16_t, 4> with cross = 0, waves_per_head =
               min(8192 / NH, ceil(T / rows), scratch / (NH * 64))
-            cross, head-major  qknorm_rope_bwd_kernel<float>, _b8_kernel<4> (nb1 <= 4), _b8_kernel<8> (nb1 5 .. 8): nb1 = 1, 4, 5, 8;
+            cross, head-major  qknorm_rope_bwd_head_kernel<float, 8>, <bf16_t, 4> (nb1 <= 4), <bf16_t, 8> (nb1 5 .. 8): nb1 = 1, 4, 5, 8;
               (6, 3) heads at T = 2737 / 5467: 682 waves per head (the natural cap 8192 / 12) x 2 iterations, 4092 / 2046 / 682
               items per reduce column; scratch for waves_per_head = 1 and 2 at T = 101
 Every case: T no multiple of the rows per wave; 8 sentinel rows behind q_rot, k_rot, dqkv (and 64 sentinel floats behind the
@@ -130,8 +130,8 @@ def test_every_case_is_in_the_regime_its_name_claims():
         d = c.check_regime()
         kinds.setdefault(d["kernel"], []).append(d)
     # all five backward kernels, each with one and with several iterations per wave
-    assert set(kinds) == {"qknorm_rope_bwd_tok_kernel", "qknorm_rope_bwd_b8_tok_kernel", "qknorm_rope_bwd_kernel<float>",
-                          "qknorm_rope_bwd_b8_kernel<4>", "qknorm_rope_bwd_b8_kernel<8>"}
+    assert set(kinds) == {"qknorm_rope_bwd_tok_kernel<float>", "qknorm_rope_bwd_tok_kernel<bf16_t>", "qknorm_rope_bwd_head_kernel<float, 8>",
+                          "qknorm_rope_bwd_head_kernel<bf16_t, 4>", "qknorm_rope_bwd_head_kernel<bf16_t, 8>"}
     for name, ds in kinds.items():
         assert min(d["iters"] for d in ds) == 1 and max(d["iters"] for d in ds) >= 2, name
         assert any(qr.reduce_four_way(max(d["items"].values())) for d in ds), name
@@ -188,7 +188,7 @@ def _check_fwd_layout(c, inp, out):
 def test_qknorm_rope_fwd_every_head_count(dtype, cross, nq, nkv):
     for c in qr.fwd_cases(dtype, cross, nq, nkv):
         d = qr.fwd_dispatch(dtype, cross, c.T, nq, nkv)
-        assert d["kernel"].endswith("_tok_kernel") and d["iters"] == 1, (c.id, d)
+        assert d["kernel"].startswith("qknorm_rope_fwd_tok_kernel<") and d["iters"] == 1, (c.id, d)
         inp = qr.make_inputs(c, backward=False)
         out = _run_fwd(c, inp)
         _check_fwd_layout(c, inp, out)

@@ -66,6 +66,9 @@ def main():
     trees = [os.path.abspath(args.a), os.path.abspath(args.b)]
     build = _load_build(trees[1])
     sources = [s for s in build.SOURCES if not args.only or s in args.only]
+    for s in [s for s in sources if not os.path.exists(os.path.join(trees[0], "gamer_amd", "csrc", s))]:
+        print(f"{s:22s} not in {args.a}: a new source, nothing to compare")
+        sources.remove(s)
     readelf, objcopy = _llvm(build._hipcc(), "llvm-readelf"), _llvm(build._hipcc(), "llvm-objcopy")
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
         jobs = {(src, i): ex.submit(_parts, trees[i], build, src, os.path.join(tmp, f"{i}_{src}.co"), readelf, objcopy)

@@ -3,7 +3,7 @@
 
   python tools/kbench.py attn --B 256          attention fwd + bwd, self and cross, dropout 0.2
   python tools/kbench.py gemm --B 256          the GEMM shapes of one decoder layer (fwd/dgrad/wgrad)
-  python tools/kbench.py elem --B 256          the HBM-bound kernels
+  python tools/kbench.py elem --B 256          the HBM-bound kernels (--only qknorm: the q/k norm + RoPE calls alone)
 """
 import argparse
 import os
@@ -155,6 +155,8 @@ def bench_elem(args):
     B, S, H, I = args.B, args.items * 5, 256, 512
     T = B * S
     dev = "cuda"
+    if args.only == "qknorm":                        # (elem --only qknorm: the q/k norm + RoPE lines alone)
+        return bench_qknorm(args, T, S)
     x, y = torch.randn(T, H, device=dev), torch.empty(T, H, device=dev)
     w = torch.ones(H, device=dev)
     t = timeit(lambda: ops.rmsnorm_fwd(x, w, 1e-6, y), args.iters)
@@ -170,17 +172,35 @@ def bench_elem(args):
     print(f"swiglu_fwd {t:.3f} ms  {3 * T * I * 4 / t / 1e6:.0f} GB/s")
     t = timeit(lambda: ops.swiglu_bwd(g, u, hm, T * I, 0.2, 3), args.iters)
     print(f"swiglu_bwd {t:.3f} ms  {5 * T * I * 4 / t / 1e6:.0f} GB/s")
-    nq, nkv = 6, 3
-    qkv = torch.randn(T, 768, device=dev)
-    q_rot, k_rot = torch.empty(T, 384, device=dev), torch.empty(T, 192, device=dev)
+    bench_qknorm(args, T, S)
+
+
+def bench_qknorm(args, T, S, nq=6, nkv=3, nb1=4):
+    """q/k norm + RoPE, forward and backward, self and cross (behaviour biases), fp32 and bf16 (GB/s: the q | k columns read and
+    written; the cross calls also move the v columns and the bias rows)"""
+    dev = "cuda"
     cos, sin = torch.randn(S, 64, device=dev), torch.randn(S, 64, device=dev)
     w64 = torch.ones(64, device=dev)
-    t = timeit(lambda: ops.qknorm_rope_fwd(qkv, S, nq, nkv, w64, w64, 1e-6, cos, sin, q_rot, k_rot), args.iters)
-    print(f"qknorm_rope_fwd {t:.3f} ms  {2 * T * 576 * 4 / t / 1e6:.0f} GB/s")
-    dqkv = torch.empty_like(qkv)
+    act = torch.randint(0, nb1, (T,), device=dev, dtype=torch.int32)
+    bq, bk, bv = (0.5 * torch.randn(nb1, n * 64, device=dev) for n in (nq, nkv, nkv))
+    dbq, dbk, dbv = torch.zeros_like(bq), torch.zeros_like(bk), torch.zeros_like(bv)
     dw1, dw2 = torch.zeros(64, device=dev), torch.zeros(64, device=dev)
-    t = timeit(lambda: ops.qknorm_rope_bwd(qkv, q_rot, k_rot, S, nq, nkv, w64, w64, 1e-6, cos, sin, dqkv, dw1, dw2), args.iters)
-    print(f"qknorm_rope_bwd {t:.3f} ms  {3 * T * 576 * 4 / t / 1e6:.0f} GB/s")
+    for dt, sfx in ((torch.float32, ""), (torch.bfloat16, "_bf16")):
+        qkv0 = torch.randn(T, (nq + 2 * nkv) * 64, device=dev).to(dt)
+        qkv = qkv0.clone()
+        q_rot, k_rot = torch.empty(T, nq * 64, device=dev, dtype=dt), torch.empty(T, nkv * 64, device=dev, dtype=dt)
+        dqkv = torch.randn(T, (nq + 2 * nkv) * 64, device=dev).to(dt)
+        dq, dk = torch.randn_like(q_rot), torch.randn_like(k_rot)
+        nbytes = T * (nq + nkv) * 64 * qkv.element_size()
+        for name, cross in (("", {}), ("_cross", dict(bias_q=bq, bias_k=bk, act_idx=act))):
+            fwd_kw = dict(cross, bias_v=bv) if cross else {}
+            bwd_kw = dict(cross, nb1=nb1, dbias_q=dbq, dbias_k=dbk, dbias_v=dbv, partial=torch.empty(ops.qknorm_partial_numel(nb1), device=dev)) \
+                if cross else dict(partial=torch.empty(ops.qknorm_partial_numel(), device=dev))
+            t = timeit(lambda: ops.qknorm_rope_fwd(qkv, S, nq, nkv, w64, w64, 1e-6, cos, sin, q_rot, k_rot, **fwd_kw), args.iters)
+            print(f"qknorm_rope_fwd{name}{sfx} {t:.3f} ms  {2 * nbytes / t / 1e6:.0f} GB/s")
+            qkv.copy_(qkv0)                              # (the fp32 cross forward adds the biases in place, call after call)
+            t = timeit(lambda: ops.qknorm_rope_bwd(qkv, dq, dk, S, nq, nkv, w64, w64, 1e-6, cos, sin, dqkv, dw1, dw2, **bwd_kw), args.iters)
+            print(f"qknorm_rope_bwd{name}{sfx} {t:.3f} ms  {3 * nbytes / t / 1e6:.0f} GB/s")
 
 
 if __name__ == "__main__":
