@@ -16,6 +16,10 @@
 // sums dS along the diagonals for the bias gradient by relative offset.  A workgroup walks the rows slot, slot + n_slab, ...
 // and owns slab `slot` of the offset gradient: written by that workgroup alone (no float atomics), reduced in slab order by
 // gamer_t5_bias_fold.
+// The packed forms (gamer_t5_attn_packed_fwd / _bwd; PK = true): the rows lie one behind the other without padding tokens and a workgroup
+// looks its row up in the offset arrays (t5_row<PK> of t5_attention_common.h).  a.Sq, a.Sk are then the shape of the dense run that the
+// call replaces: the bias offset j - i + a.Sq - 1 and the dropout counter ((b H + head) a.Sq + i) a.Sk + j are that run's, there is no
+// keep, and the LDS arrays are laid out by the row's own lengths inside what the host sized by (a.Sq, a.Sk).
 //   gamer_t5_bias_expand   table [num_buckets][h] -> rel [h][R] through the host's bucket-per-offset vector
 //   gamer_t5_bias_fold     slabs [layers][n_slab][h][R] -> table gradient [num_buckets][h]: slabs in order, offsets in order,
 //                          then the layers in order (the table of layer 0 serves every layer of its stack)
@@ -31,31 +35,32 @@ __device__ __forceinline__ void t5_stage_keep(int* __restrict__ kp, const uint8_
     for (int j = threadIdx.x; j < Sk16; j += T5_THREADS) kp[j] = j < Sk && (!keep || keep[(int64_t)b * Sk + j]) ? 1 : 0;
 }
 
-template <int D>
+template <int D, bool PK>
 __global__ void __launch_bounds__(T5_THREADS)
 t5_attn_fwd_kernel(const T5Args a, float* __restrict__ o, int ldo, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int LD = D + 4;
-    const int Sq = a.Sq, Sk = a.Sk, Sk16 = (Sk + 15) & ~15, nkt = Sk16 / 16, nqt = (Sq + 15) / 16;
+    const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
+    const int bk = a.kv_rows ? a.kv_rows[b] : b;
+    const T5Row row = t5_row<PK>(a, b, bk, hh);
+    const int Sq = row.Sq, Sk = row.Sk, Sk16 = (Sk + 15) & ~15, nkt = Sk16 / 16, nqt = (Sq + 15) / 16;
     float* Ks = lds;                          // [Sk16][LD]
     float* Vs = Ks + Sk16 * LD;               // [Sk16][LD]
     int* kp = (int*)(Vs + Sk16 * LD);         // [Sk16]
-    const int b = blockIdx.x / a.H, hh = blockIdx.x % a.H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int bk = a.kv_rows ? a.kv_rows[b] : b;
-    t5_stage<D>(Ks, a.k + (int64_t)bk * Sk * a.ldk + hh * D, a.ldk, Sk, Sk16);
-    t5_stage<D>(Vs, a.v + (int64_t)bk * Sk * a.ldv + hh * D, a.ldv, Sk, Sk16);
+    t5_stage<D>(Ks, a.k + row.k0 * a.ldk + hh * D, a.ldk, Sk, Sk16);
+    t5_stage<D>(Vs, a.v + row.k0 * a.ldv + hh * D, a.ldv, Sk, Sk16);
     t5_stage_keep(kp, a.keep, bk, Sk, Sk16);
     __syncthreads();
     const DropoutRng rng(a.p_drop, a.seed);
-    const float* qb = a.q + (int64_t)b * Sq * a.ldq + hh * D;
-    float* ob = o + (int64_t)b * Sq * ldo + hh * D;
+    const float* qb = a.q + row.q0 * a.ldq + hh * D;
+    float* ob = o + row.q0 * ldo + hh * D;
     for (int qt = wave; qt < nqt; qt += T5_WAVES) {
         const int i = qt * 16 + (lane & 15);
         const bool iv = i < Sq;
         float qr[D / 4];
         t5_row_operand<D>(qr, iv ? qb + (int64_t)i * a.ldq : nullptr, lane);
-        const float* relrow = a.rel ? a.rel + (int64_t)hh * (Sq + Sk - 1) + (Sq - 1 - i) : nullptr;      // read at [j] for allowed (i, j) only
+        const float* relrow = a.rel ? a.rel + (int64_t)hh * (a.Sq + a.Sk - 1) + (a.Sq - 1 - i) : nullptr;      // read at [j] for allowed (i, j) only
         f32x4v s[T5_MAX_KT];
         float m = -INFINITY;
 #pragma unroll
@@ -83,7 +88,7 @@ t5_attn_fwd_kernel(const T5Args a, float* __restrict__ o, int ldo, float* __rest
         sum = t5_xor_sum(sum);
         const float l = m + logf(sum);                          // (no allowed key: -inf + -inf)
         const float ls = m == -INFINITY ? 0.f : l;
-        if (iv && lane < 16) lse[((int64_t)b * a.H + hh) * Sq + i] = l;
+        if (iv && lane < 16) lse[row.l0 + i] = l;
         f32x4v acc[D / 16];
 #pragma unroll
         for (int n = 0; n < D / 16; ++n) acc[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -94,7 +99,7 @@ t5_attn_fwd_kernel(const T5Args a, float* __restrict__ o, int ldo, float* __rest
                 for (int reg = 0; reg < 4; ++reg) {
                     const int j = nt * 16 + 4 * (lane >> 4) + reg;
                     float p = expf(s[nt][reg] - ls);            // (a key that is not allowed: exp(-inf) = 0)
-                    if (rng.on && iv && j < Sk) p *= rng.mult((((uint64_t)b * a.H + hh) * Sq + i) * Sk + j);
+                    if (rng.on && iv && j < Sk) p *= rng.mult((((uint64_t)b * a.H + hh) * a.Sq + i) * a.Sk + j);
                     s[nt][reg] = p;
                 }
                 t5_tile_out<D>(acc, s[nt], Vs + nt * 16 * LD, lane);
@@ -122,30 +127,33 @@ __device__ __forceinline__ void t5_key_tile(f32x4v (&acc)[D / 16], const float* 
     }
 }
 
-template <int D>
+template <int D, bool PK>
 __global__ void __launch_bounds__(T5_THREADS)
 t5_attn_bwd_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const float* __restrict__ lse,
                    float* __restrict__ dq, int lddq, float* __restrict__ dk, int lddk, float* __restrict__ dv, int lddv,
                    float* __restrict__ drel_part, int n_slab) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int LD = D + 4;
-    const int Sq = a.Sq, Sk = a.Sk, Sk16 = (Sk + 15) & ~15, Sq16 = (Sq + 15) & ~15, nkt = Sk16 / 16, nqt = Sq16 / 16;
-    const int ldp = t5_ldp(Sk16), R = Sq + Sk - 1;
-    float* Ks = lds;                          // [Sk16][LD]
-    float* Vs = Ks + Sk16 * LD;               // [Sk16][LD]
-    float* P = Vs + Sk16 * LD;                // [Sq16][ldp]
-    int* kp = (int*)(P + Sq16 * ldp);         // [Sk16]
+    const int R = a.Sq + a.Sk - 1;
     const int hh = blockIdx.x % a.H, slot = blockIdx.x / a.H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const DropoutRng rng(a.p_drop, a.seed);
     const float keep_scale = rng.scale;
     float* slab = drel_part ? drel_part + ((int64_t)slot * a.H + hh) * R : nullptr;
     for (int b = slot; b < a.B; b += n_slab) {
-        const float* qb = a.q + (int64_t)b * Sq * a.ldq + hh * D;
-        const float* gb = d_o + (int64_t)b * Sq * ldo + hh * D;
+        // (the LDS arrays are laid out by this row's lengths: within what the host sized by a.Sq, a.Sk)
+        const T5Row row = t5_row<PK>(a, b, b, hh);
+        const int Sq = row.Sq, Sk = row.Sk, Sk16 = (Sk + 15) & ~15, Sq16 = (Sq + 15) & ~15, nkt = Sk16 / 16, nqt = Sq16 / 16;
+        const int ldp = t5_ldp(Sk16);
+        float* Ks = lds;                          // [Sk16][LD]
+        float* Vs = Ks + Sk16 * LD;               // [Sk16][LD]
+        float* P = Vs + Sk16 * LD;                // [Sq16][ldp]
+        int* kp = (int*)(P + Sq16 * ldp);         // [Sk16]
+        const float* qb = a.q + row.q0 * a.ldq + hh * D;
+        const float* gb = d_o + row.q0 * ldo + hh * D;
         __syncthreads();                                                         // (the row before is done with the LDS)
-        t5_stage<D>(Ks, a.k + (int64_t)b * Sk * a.ldk + hh * D, a.ldk, Sk, Sk16);
-        t5_stage<D>(Vs, a.v + (int64_t)b * Sk * a.ldv + hh * D, a.ldv, Sk, Sk16);
+        t5_stage<D>(Ks, a.k + row.k0 * a.ldk + hh * D, a.ldk, Sk, Sk16);
+        t5_stage<D>(Vs, a.v + row.k0 * a.ldv + hh * D, a.ldv, Sk, Sk16);
         t5_stage_keep(kp, a.keep, b, Sk, Sk16);
         __syncthreads();
         // ---- p from the saved log-sum-exp (query tiles) ----------------------------------------------------------------------
@@ -154,8 +162,8 @@ t5_attn_bwd_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const
             const bool iv = i < Sq;
             float qr[D / 4];
             t5_row_operand<D>(qr, iv ? qb + (int64_t)i * a.ldq : nullptr, lane);
-            const float* relrow = a.rel ? a.rel + (int64_t)hh * R + (Sq - 1 - i) : nullptr;
-            const float l = iv ? lse[((int64_t)b * a.H + hh) * Sq + i] : 0.f;
+            const float* relrow = a.rel ? a.rel + (int64_t)hh * R + (a.Sq - 1 - i) : nullptr;
+            const float l = iv ? lse[row.l0 + i] : 0.f;
             for (int nt = 0; nt < nkt; ++nt) {
                 const f32x4v s = t5_tile<D>(Ks + nt * 16 * LD, qr, lane);
                 float4 pv;
@@ -167,7 +175,7 @@ t5_attn_bwd_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const
                     float p = 0.f;
                     if (ok) {
                         p = expf(s[reg] + (relrow ? relrow[j] : 0.f) - l);
-                        if (rng.on && rng.mult((((uint64_t)b * a.H + hh) * Sq + i) * Sk + j) == 0.f) p = -p;
+                        if (rng.on && rng.mult((((uint64_t)b * a.H + hh) * a.Sq + i) * a.Sk + j) == 0.f) p = -p;
                     }
                     pp[reg] = p;
                 }
@@ -179,7 +187,7 @@ t5_attn_bwd_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const
         for (int kt = wave; kt < nkt; kt += T5_WAVES) {
             f32x4v acc[D / 16];
             t5_key_tile<D, true>(acc, P + kt * 16, ldp, gb, ldo, Sq, Sq16, keep_scale, lane);
-            t5_store_rows<D>(dv + (int64_t)b * Sk * lddv + hh * D, lddv, kt * 16, Sk, acc, lane);
+            t5_store_rows<D>(dv + row.k0 * lddv + hh * D, lddv, kt * 16, Sk, acc, lane);
         }
         __syncthreads();
         // ---- dS in place, dQ = dS K (query tiles).  delta_i = sum_j dropout(p)[i, j] dP[i, j] from the very products it is subtracted
@@ -216,19 +224,19 @@ t5_attn_bwd_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const
                     *pp = make_float4(ds[0], ds[1], ds[2], ds[3]);
                     t5_tile_out<D>(acc, ds, Ks + nt * 16 * LD, lane);
                 }
-            t5_store_rows<D>(dq + (int64_t)b * Sq * lddq + hh * D, lddq, qt * 16, Sq, acc, lane);
+            t5_store_rows<D>(dq + row.q0 * lddq + hh * D, lddq, qt * 16, Sq, acc, lane);
         }
         __syncthreads();
         // ---- dK = dS^T Q (key tiles) -----------------------------------------------------------------------------------------------
         for (int kt = wave; kt < nkt; kt += T5_WAVES) {
             f32x4v acc[D / 16];
             t5_key_tile<D, false>(acc, P + kt * 16, ldp, qb, a.ldq, Sq, Sq16, 1.f, lane);
-            t5_store_rows<D>(dk + (int64_t)b * Sk * lddk + hh * D, lddk, kt * 16, Sk, acc, lane);
+            t5_store_rows<D>(dk + row.k0 * lddk + hh * D, lddk, kt * 16, Sk, acc, lane);
         }
         // ---- the bias gradient by relative offset: sums of dS along the diagonals j - i = r - (Sq - 1), queries in order -----------
         if (slab)
             for (int r = threadIdx.x; r < R; r += T5_THREADS) {
-                const int off = r - (Sq - 1);
+                const int off = r - (a.Sq - 1);
                 float acc = 0.f;
                 for (int i = max(0, -off); i < Sq && i + off < Sk; ++i) acc += P[i * ldp + i + off];
                 slab[r] = b == slot ? acc : slab[r] + acc;
@@ -280,8 +288,8 @@ extern "C" int gamer_t5_attn_fwd(const float* q, int ldq, const float* k, int ld
     GAMER_CHECK_ARG(o && lse && ldo >= H * head_dim, "gamer_t5_attn_fwd: bad output");
     const int Sk16 = (Sk + 15) & ~15;
     const size_t shmem = ((size_t)2 * Sk16 * (head_dim + 4) + Sk16) * sizeof(float);
-    if (head_dim == 64) return launch<t5_attn_fwd_kernel<64>>("gamer_t5_attn_fwd", dim3(B * H), dim3(T5_THREADS), shmem, ST(stream), a, o, ldo, lse);
-    return launch<t5_attn_fwd_kernel<32>>("gamer_t5_attn_fwd", dim3(B * H), dim3(T5_THREADS), shmem, ST(stream), a, o, ldo, lse);
+    if (head_dim == 64) return launch<t5_attn_fwd_kernel<64, false>>("gamer_t5_attn_fwd", dim3(B * H), dim3(T5_THREADS), shmem, ST(stream), a, o, ldo, lse);
+    return launch<t5_attn_fwd_kernel<32, false>>("gamer_t5_attn_fwd", dim3(B * H), dim3(T5_THREADS), shmem, ST(stream), a, o, ldo, lse);
 }
 
 extern "C" int gamer_t5_attn_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
@@ -300,10 +308,51 @@ extern "C" int gamer_t5_attn_bwd(const float* q, int ldq, const float* k, int ld
     const size_t shmem = ((size_t)2 * Sk16 * (head_dim + 4) + (size_t)Sq16 * t5_ldp(Sk16) + Sk16) * sizeof(float);
     GAMER_CHECK_ARG(shmem <= T5_LDS_MAX, "gamer_t5_attn_bwd: %zu bytes of LDS", shmem);
     if (head_dim == 64)
-        return launch<t5_attn_bwd_kernel<64>>("gamer_t5_attn_bwd", dim3(n_slab * H), dim3(T5_THREADS), shmem, ST(stream), a, d_o, ldo, lse, dq,
+        return launch<t5_attn_bwd_kernel<64, false>>("gamer_t5_attn_bwd", dim3(n_slab * H), dim3(T5_THREADS), shmem, ST(stream), a, d_o, ldo, lse, dq,
                                               lddq, dk, lddk, dv, lddv, drel_partial, n_slab);
-    return launch<t5_attn_bwd_kernel<32>>("gamer_t5_attn_bwd", dim3(n_slab * H), dim3(T5_THREADS), shmem, ST(stream), a, d_o, ldo, lse, dq, lddq,
+    return launch<t5_attn_bwd_kernel<32, false>>("gamer_t5_attn_bwd", dim3(n_slab * H), dim3(T5_THREADS), shmem, ST(stream), a, d_o, ldo, lse, dq, lddq,
                                           dk, lddk, dv, lddv, drel_partial, n_slab);
+}
+
+// ---- the packed forms: rows of q_start[b + 1] - q_start[b] queries and k_start[b + 1] - k_start[b] keys, no padding tokens ----------------
+extern "C" int gamer_t5_attn_packed_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                                        const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                        const int32_t* k_start_host, const int32_t* kv_rows, int B, int kv_batch, int max_sq, int max_sk,
+                                        int H, int head_dim, int causal, float p_drop, uint64_t seed, float* o, int ldo, float* lse,
+                                        void* stream) {
+    const char* name = "gamer_t5_attn_packed_fwd";
+    T5Args a;
+    GAMER_TRY(t5_packed_args(name, a, q, ldq, k, ldk, v, ldv, rel, q_start, k_start, q_start_host, k_start_host, B, kv_rows ? kv_batch : B,
+                             max_sq, max_sk, H, head_dim, causal, p_drop, seed, T5_MAX_S));
+    a.kv_rows = kv_rows;
+    GAMER_CHECK_ARG(o && lse && ldo >= H * head_dim, "%s: bad output", name);
+    const int Sk16 = (max_sk + 15) & ~15;
+    const size_t shmem = ((size_t)2 * Sk16 * (head_dim + 4) + Sk16) * sizeof(float);
+    if (head_dim == 64) return launch<t5_attn_fwd_kernel<64, true>>(name, dim3(B * H), dim3(T5_THREADS), shmem, ST(stream), a, o, ldo, lse);
+    return launch<t5_attn_fwd_kernel<32, true>>(name, dim3(B * H), dim3(T5_THREADS), shmem, ST(stream), a, o, ldo, lse);
+}
+
+extern "C" int gamer_t5_attn_packed_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                                        const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                        const int32_t* k_start_host, int B, int max_sq, int max_sk, int H, int head_dim, int causal,
+                                        float p_drop, uint64_t seed, const float* d_o, int ldo, const float* lse, float* dq, int lddq,
+                                        float* dk, int lddk, float* dv, int lddv, float* drel_partial, int n_slab, void* stream) {
+    const char* name = "gamer_t5_attn_packed_bwd";
+    T5Args a;
+    GAMER_TRY(t5_packed_args(name, a, q, ldq, k, ldk, v, ldv, rel, q_start, k_start, q_start_host, k_start_host, B, B, max_sq, max_sk, H,
+                             head_dim, causal, p_drop, seed, T5_MAX_S));
+    GAMER_CHECK_ARG(d_o && lse && dq && dk && dv, "%s: null pointer", name);
+    GAMER_CHECK_ARG(ldo >= H * head_dim && lddq >= H * head_dim && lddk >= H * head_dim && lddv >= H * head_dim, "%s: bad leading dims", name);
+    GAMER_CHECK_ARG(n_slab > 0 && n_slab <= B, "%s: n_slab=%d (1 .. B: every slab is written by its workgroup)", name, n_slab);
+    GAMER_CHECK_ARG(!rel == !drel_partial, "%s: drel_partial goes with the bias", name);
+    const int Sk16 = (max_sk + 15) & ~15, Sq16 = (max_sq + 15) & ~15;
+    const size_t shmem = ((size_t)2 * Sk16 * (head_dim + 4) + (size_t)Sq16 * t5_ldp(Sk16) + Sk16) * sizeof(float);
+    GAMER_CHECK_ARG(shmem <= T5_LDS_MAX, "%s: %zu bytes of LDS", name, shmem);
+    if (head_dim == 64)
+        return launch<t5_attn_bwd_kernel<64, true>>(name, dim3(n_slab * H), dim3(T5_THREADS), shmem, ST(stream), a, d_o, ldo, lse, dq, lddq, dk,
+                                                    lddk, dv, lddv, drel_partial, n_slab);
+    return launch<t5_attn_bwd_kernel<32, true>>(name, dim3(n_slab * H), dim3(T5_THREADS), shmem, ST(stream), a, d_o, ldo, lse, dq, lddq, dk, lddk,
+                                                dv, lddv, drel_partial, n_slab);
 }
 
 extern "C" int gamer_t5_bias_expand(const float* table, const int32_t* bucket, int num_buckets, int H, int R, float* rel, void* stream) {

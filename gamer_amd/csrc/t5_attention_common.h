@@ -17,10 +17,28 @@ struct T5Args {
     const float* rel;              // [H][Sq + Sk - 1] or nullptr
     const uint8_t* keep;           // [B][Sk] or nullptr
     const int32_t* kv_rows;        // forward only: row b reads k / v / keep of row kv_rows[b] (beams of one user), nullptr: b
-    int B, Sq, Sk, H, causal;
+    int B, Sq, Sk, H, causal;      // packed: Sq / Sk are max_sq / max_sk, the shape of the dense run (bias offsets, dropout counters)
     float p_drop;
     uint64_t seed;
+    const int32_t *q_start, *k_start;      // packed entry points only: the rows' first query / key row, B + 1 (kv_batch + 1) entries
+    int Tq;                                // packed: q_start[B]; lse is [H][Tq]
 };
+
+// One batch row as its workgroup sees it: its own lengths, the first row of its queries and of its keys in q / k / v, and the index
+// of its query 0 in lse (and the long backward's row terms).  Dense: the fixed pitch.  Packed: the offset arrays.  The bias offset
+// j - i + a.Sq - 1 and the dropout counter ((b H + head) a.Sq + i) a.Sk + j keep the dense geometry in both forms.
+struct T5Row {
+    int Sq, Sk;
+    int64_t q0, k0, l0;
+};
+template <bool PK>
+__device__ __forceinline__ T5Row t5_row(const T5Args& a, int b, int bk, int hh) {
+    if (PK) {
+        const int q0 = a.q_start[b], k0 = a.k_start[bk];
+        return T5Row{a.q_start[b + 1] - q0, a.k_start[bk + 1] - k0, q0, k0, (int64_t)hh * a.Tq + q0};
+    }
+    return T5Row{a.Sq, a.Sk, (int64_t)b * a.Sq, (int64_t)bk * a.Sk, ((int64_t)b * a.H + hh) * a.Sq};
+}
 
 // rows [0, rows) of a head's [rows, D] block -> LDS [rows16][D + 4], zero rows behind
 template <int D>
@@ -96,6 +114,33 @@ static inline int t5_args(const char* name, T5Args& a, const float* q, int ldq, 
     GAMER_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop=%f", name, p_drop);
     a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.rel = rel; a.keep = keep; a.kv_rows = nullptr;
     a.B = B; a.Sq = Sq; a.Sk = Sk; a.H = H; a.causal = causal != 0; a.p_drop = p_drop; a.seed = seed;
+    a.q_start = a.k_start = nullptr; a.Tq = 0;
+    return 0;
+}
+
+// one offset array of a packed call, read from its host copy: starts at 0, never decreases, no row longer than max_len
+static inline int t5_offsets(const char* name, const char* what, const int32_t* host, int n, int max_len) {
+    GAMER_CHECK_ARG(host[0] == 0, "%s: %s[0] = %d (offsets start at 0)", name, what, host[0]);
+    for (int b = 0; b < n; ++b) {
+        GAMER_CHECK_ARG(host[b + 1] >= host[b], "%s: %s decreases at row %d (%d -> %d)", name, what, b, host[b], host[b + 1]);
+        GAMER_CHECK_ARG(host[b + 1] - host[b] <= max_len, "%s: row %d of %s holds %d tokens, more than max %d", name, b, what,
+                        host[b + 1] - host[b], max_len);
+    }
+    GAMER_CHECK_ARG(host[n] > 0, "%s: %s holds no token", name, what);
+    return 0;
+}
+// the packed entry points: the dense check on the geometry (max_sq, max_sk), then the offsets.  q_start / k_start are device arrays of
+// B + 1 / kv_rows_n + 1 entries and *_host their host copies, which is what this check reads (no device-to-host copy in a call).
+static inline int t5_packed_args(const char* name, T5Args& a, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                 const float* rel, const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                 const int32_t* k_start_host, int B, int kv_batch, int max_sq, int max_sk, int H, int dh, int causal,
+                                 float p_drop, uint64_t seed, int max_s) {
+    GAMER_TRY(t5_args(name, a, q, ldq, k, ldk, v, ldv, rel, nullptr, B, max_sq, max_sk, H, dh, causal, p_drop, seed, max_s));
+    GAMER_CHECK_ARG(q_start && k_start && q_start_host && k_start_host && kv_batch > 0, "%s: null offsets", name);
+    GAMER_TRY(t5_offsets(name, "q_start", q_start_host, B, max_sq));
+    GAMER_TRY(t5_offsets(name, "k_start", k_start_host, kv_batch, max_sk));
+    GAMER_CHECK_ARG((int64_t)H * q_start_host[B] < (1LL << 31), "%s: H Tq >= 2^31", name);
+    a.q_start = q_start; a.k_start = k_start; a.Tq = q_start_host[B];
     return 0;
 }
 

@@ -20,6 +20,9 @@
 //                       ... and their query blocks, puts each 64 x 64 tile of dS into LDS and adds its diagonals, queries in order,
 //                       to an LDS accumulator of Sq + Sk - 1 offsets that it writes to its slab at the end; without a bias one
 //                       workgroup per (row, head, query block)
+// The packed forms (PK = true, semantics at the top of t5_attention.hip): the grids keep the dense geometry (a.Sq, a.Sk); a workgroup whose
+// query block (forward, row terms, dQ) or key block (dK, dV) lies past its row's end returns before it touches memory, and the key / query
+// loops run to the row's own lengths.  The row terms are [2][H][Tq].
 // Causal: key blocks wholly above the diagonal of a query block are skipped (every score there is masked).
 #include "t5_attention_common.h"
 
@@ -35,27 +38,30 @@ __device__ __forceinline__ void t5l_stage_keep(int* __restrict__ kp, const uint8
 // the value of query (lane & 15)'s lane for the accumulator row 4 (lane >> 4) + reg
 __device__ __forceinline__ float t5l_row_value(float v, int reg, int lane) { return __shfl(v, 4 * (lane >> 4) + reg, 64); }
 
-template <int D>
+template <int D, bool PK>
 __global__ void __launch_bounds__(T5_THREADS)
 t5l_attn_fwd_kernel(const T5Args a, float* __restrict__ o, int ldo, float* __restrict__ lse) {
     constexpr int LD = D + 4;
     __shared__ __attribute__((aligned(16))) float Ks[T5L_KB * LD];
     __shared__ __attribute__((aligned(16))) float Vs[T5L_KB * LD];
     __shared__ int kp[T5L_KB];
-    const int Sq = a.Sq, Sk = a.Sk, nqb = (Sq + T5L_QB - 1) / T5L_QB;
+    const int nqb = (a.Sq + T5L_QB - 1) / T5L_QB;                           // (the grid: query blocks of the dense geometry)
     const int qb = blockIdx.x % nqb, bh = blockIdx.x / nqb, b = bh / a.H, hh = bh % a.H;
+    const int bk = a.kv_rows ? a.kv_rows[b] : b;
+    const T5Row row = t5_row<PK>(a, b, bk, hh);
+    const int Sq = row.Sq, Sk = row.Sk;
+    if (PK && qb * T5L_QB >= Sq) return;                                    // a query block past the row's end
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool split = Sq <= 16;                                            // one query tile: the waves share its key tiles
+    const bool split = a.Sq <= 16;                                          // one query tile: the waves share its key tiles
     const int q0 = qb * T5L_QB + (split ? 0 : wave * 16);
     const bool active = q0 < Sq;
     const int i = q0 + (lane & 15);
     const bool iv = i < Sq;
     const int q_last = min(Sq, (qb + 1) * T5L_QB) - 1;
-    const int bk = a.kv_rows ? a.kv_rows[b] : b;
     const DropoutRng rng(a.p_drop, a.seed);
     float qr[D / 4];
-    t5_row_operand<D>(qr, iv ? a.q + ((int64_t)b * Sq + i) * a.ldq + hh * D : nullptr, lane);
-    const float* relrow = a.rel ? a.rel + (int64_t)hh * (Sq + Sk - 1) + (Sq - 1 - i) : nullptr;      // read at [j] for allowed (i, j) only
+    t5_row_operand<D>(qr, iv ? a.q + (row.q0 + i) * a.ldq + hh * D : nullptr, lane);
+    const float* relrow = a.rel ? a.rel + (int64_t)hh * (a.Sq + a.Sk - 1) + (a.Sq - 1 - i) : nullptr;      // read at [j] for allowed (i, j) only
     float m = -INFINITY, l = 0.f;                                           // l: this lane's keys only until the end
     f32x4v acc[D / 16];
 #pragma unroll
@@ -64,8 +70,8 @@ t5l_attn_fwd_kernel(const T5Args a, float* __restrict__ o, int ldo, float* __res
         if (a.causal && k0 > q_last) break;
         const int rows = min(T5L_KB, Sk - k0), nt = (rows + 15) / 16;
         __syncthreads();                                                    // (the block before is consumed)
-        t5_stage<D>(Ks, a.k + ((int64_t)bk * Sk + k0) * a.ldk + hh * D, a.ldk, rows, nt * 16);
-        t5_stage<D>(Vs, a.v + ((int64_t)bk * Sk + k0) * a.ldv + hh * D, a.ldv, rows, nt * 16);
+        t5_stage<D>(Ks, a.k + (row.k0 + k0) * a.ldk + hh * D, a.ldk, rows, nt * 16);
+        t5_stage<D>(Vs, a.v + (row.k0 + k0) * a.ldv + hh * D, a.ldv, rows, nt * 16);
         t5l_stage_keep(kp, a.keep, bk, Sk, k0);
         __syncthreads();
         const int mine = !active ? 0 : split ? (wave < nt ? 1 : 0) : nt;      // key tiles of this wave in this block
@@ -104,15 +110,15 @@ t5l_attn_fwd_kernel(const T5Args a, float* __restrict__ o, int ldo, float* __res
                     const int j = k0 + kt * 16 + 4 * (lane >> 4) + reg;
                     float p = expf(s[t][reg] - ms);                         // (a key that is not allowed: exp(-inf) = 0)
                     l += p;
-                    if (rng.on && iv && j < Sk) p *= rng.mult((((uint64_t)b * a.H + hh) * Sq + i) * Sk + j);
+                    if (rng.on && iv && j < Sk) p *= rng.mult((((uint64_t)b * a.H + hh) * a.Sq + i) * a.Sk + j);
                     s[t][reg] = p;
                 }
                 t5_tile_out<D>(acc, s[t], Vs + kt * 16 * LD, lane);
             }
     }
     l = t5_xor_sum(l);
-    float* ob = o + (int64_t)b * Sq * ldo + hh * D;
-    float* lb = lse + ((int64_t)b * a.H + hh) * Sq;
+    float* ob = o + row.q0 * ldo + hh * D;
+    float* lb = lse + row.l0;
     if (!split) {
         if (!active) return;
         if (iv && lane < 16) lb[i] = m + logf(l);                           // (no allowed key: -inf + -inf)
@@ -175,7 +181,7 @@ __device__ __forceinline__ T5lProb t5l_prob(const T5Args& a, const DropoutRng& r
 
 // Query-side walk of the backward.  DQ = false: the row terms alone (grid B H nqb; row_ws = [delta | c], each [B][H][Sq]).  DQ = true: dQ and, with `drel_part`, the offset
 // gradient (grid n_slab H, the workgroup walks its rows and their query blocks); without it grid B H nqb.
-template <int D, bool DQ, bool BIAS>
+template <int D, bool DQ, bool BIAS, bool PK>
 __global__ void __launch_bounds__(T5_THREADS)
 t5l_attn_bwd_q_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const float* __restrict__ lse, float* __restrict__ row_ws,
                       float* __restrict__ dq, int lddq, float* __restrict__ drel_part, int n_slab) {
@@ -185,11 +191,11 @@ t5l_attn_bwd_q_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, co
     __shared__ __attribute__((aligned(16))) float dSs[BIAS ? T5L_QB * LDS_ : 4];      // one tile of dS [query][key]
     __shared__ float dacc[BIAS ? 2 * T5L_MAX_S : 1];                                    // the offset gradient of this workgroup
     __shared__ int kp[T5L_KB];
-    const int Sq = a.Sq, Sk = a.Sk, nqb = (Sq + T5L_QB - 1) / T5L_QB, R = Sq + Sk - 1;
+    const int nqb = (a.Sq + T5L_QB - 1) / T5L_QB, R = a.Sq + a.Sk - 1;      // (the dense geometry: the grid and the offsets)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const DropoutRng rng(a.p_drop, a.seed);
     float* delta = row_ws;
-    float* norm = row_ws + (int64_t)a.B * a.H * Sq;
+    float* norm = row_ws + (PK ? (int64_t)a.H * a.Tq : (int64_t)a.B * a.H * a.Sq);
     int hh, b_first, b_step, b_end, qb_first, qb_end;
     if (BIAS) {
         hh = blockIdx.x % a.H;
@@ -200,20 +206,22 @@ t5l_attn_bwd_q_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, co
         hh = bh % a.H;
         b_first = bh / a.H, b_step = 1, b_end = b_first + 1, qb_first = blockIdx.x % nqb, qb_end = qb_first + 1;
     }
-    for (int b = b_first; b < b_end; b += b_step)
-        for (int qb = qb_first; qb < qb_end; ++qb) {
+    for (int b = b_first; b < b_end; b += b_step) {
+        const T5Row row = t5_row<PK>(a, b, b, hh);
+        const int Sq = row.Sq, Sk = row.Sk;
+        for (int qb = qb_first; qb < qb_end && qb * T5L_QB < Sq; ++qb) {     // (packed: query blocks past the row's end have nothing to do)
             const int q0 = qb * T5L_QB + wave * 16;
             const bool active = q0 < Sq;
             const int i = q0 + (lane & 15);
             const bool iv = i < Sq;
             const int q_rows = min(T5L_QB, Sq - qb * T5L_QB), q_last = qb * T5L_QB + q_rows - 1;
             float qr[D / 4], gr[D / 4];
-            t5_row_operand<D>(qr, iv ? a.q + ((int64_t)b * Sq + i) * a.ldq + hh * D : nullptr, lane);
-            t5_row_operand<D>(gr, iv ? d_o + ((int64_t)b * Sq + i) * ldo + hh * D : nullptr, lane);
-            const float* relrow = a.rel ? a.rel + (int64_t)hh * R + (Sq - 1 - i) : nullptr;
-            const float l = iv ? lse[((int64_t)b * a.H + hh) * Sq + i] : 0.f;
-            float dl = DQ && iv ? delta[((int64_t)b * a.H + hh) * Sq + i] : 0.f;
-            const float cn = DQ && iv ? norm[((int64_t)b * a.H + hh) * Sq + i] : 1.f;
+            t5_row_operand<D>(qr, iv ? a.q + (row.q0 + i) * a.ldq + hh * D : nullptr, lane);
+            t5_row_operand<D>(gr, iv ? d_o + (row.q0 + i) * ldo + hh * D : nullptr, lane);
+            const float* relrow = a.rel ? a.rel + (int64_t)hh * R + (a.Sq - 1 - i) : nullptr;
+            const float l = iv ? lse[row.l0 + i] : 0.f;
+            float dl = DQ && iv ? delta[row.l0 + i] : 0.f;
+            const float cn = DQ && iv ? norm[row.l0 + i] : 1.f;
             double zs = 0.0, dls = 0.0;                                     // the row sums of 512 terms: fp64, a few adds per element
             f32x4v acc[D / 16];
 #pragma unroll
@@ -222,8 +230,8 @@ t5l_attn_bwd_q_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, co
                 if (a.causal && k0 > q_last) break;
                 const int rows = min(T5L_KB, Sk - k0), nt = (rows + 15) / 16;
                 __syncthreads();                                            // (the block before is consumed, dS tile included)
-                t5_stage<D>(Ks, a.k + ((int64_t)b * Sk + k0) * a.ldk + hh * D, a.ldk, rows, nt * 16);
-                t5_stage<D>(Vs, a.v + ((int64_t)b * Sk + k0) * a.ldv + hh * D, a.ldv, rows, nt * 16);
+                t5_stage<D>(Ks, a.k + (row.k0 + k0) * a.ldk + hh * D, a.ldk, rows, nt * 16);
+                t5_stage<D>(Vs, a.v + (row.k0 + k0) * a.ldv + hh * D, a.ldv, rows, nt * 16);
                 t5l_stage_keep(kp, a.keep, b, Sk, k0);
                 __syncthreads();
                 if (active)
@@ -257,23 +265,24 @@ t5l_attn_bwd_q_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, co
                     if (off < T5L_KB) {
                         float sum = 0.f;
                         for (int il = max(0, -off); il < q_rows && il + off < rows; ++il) sum += dSs[il * LDS_ + il + off];
-                        const int r = k0 - qb * T5L_QB + off + Sq - 1;
+                        const int r = k0 - qb * T5L_QB + off + a.Sq - 1;
                         if (r >= 0 && r < R) dacc[r] += sum;
                     }
                 }
             }
             if (!active) continue;
             if (DQ) {
-                t5_store_rows<D>(dq + (int64_t)b * Sq * lddq + hh * D, lddq, q0, Sq, acc, lane);
+                t5_store_rows<D>(dq + row.q0 * lddq + hh * D, lddq, q0, Sq, acc, lane);
             } else {
                 zs = t5l_xor_sum(zs);
                 dls = t5l_xor_sum(dls);
                 if (iv && lane < 16) {                                      // (no allowed key: every p is 0 anyway)
-                    delta[((int64_t)b * a.H + hh) * Sq + i] = zs > 0.0 ? (float)(dls / zs) : 0.f;
-                    norm[((int64_t)b * a.H + hh) * Sq + i] = zs > 0.0 ? (float)(1.0 / zs) : 0.f;
+                    delta[row.l0 + i] = zs > 0.0 ? (float)(dls / zs) : 0.f;
+                    norm[row.l0 + i] = zs > 0.0 ? (float)(1.0 / zs) : 0.f;
                 }
             }
         }
+    }
     if (BIAS) {
         __syncthreads();
         float* slab = drel_part + ((int64_t)(blockIdx.x / a.H) * a.H + hh) * R;
@@ -282,7 +291,7 @@ t5l_attn_bwd_q_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, co
 }
 
 // dK and dV of 64 keys: a wave per 16 keys, the queries and dO stream through LDS
-template <int D>
+template <int D, bool PK>
 __global__ void __launch_bounds__(T5_THREADS)
 t5l_attn_bwd_kv_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, const float* __restrict__ lse, const float* __restrict__ row_ws,
                        float* __restrict__ dk, int lddk, float* __restrict__ dv, int lddv) {
@@ -290,19 +299,22 @@ t5l_attn_bwd_kv_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, c
     __shared__ __attribute__((aligned(16))) float Qs[T5L_QB * LD];
     __shared__ __attribute__((aligned(16))) float Gs[T5L_QB * LD];
     __shared__ float ls[T5L_QB], dls[T5L_QB], cs[T5L_QB];
-    const int Sq = a.Sq, Sk = a.Sk, nkb = (Sk + T5L_KB - 1) / T5L_KB, R = Sq + Sk - 1;
+    const int nkb = (a.Sk + T5L_KB - 1) / T5L_KB, R = a.Sq + a.Sk - 1;      // (the dense geometry: the grid and the offsets)
     const int kb = blockIdx.x % nkb, bh = blockIdx.x / nkb, b = bh / a.H, hh = bh % a.H;
+    const T5Row row = t5_row<PK>(a, b, b, hh);
+    const int Sq = row.Sq, Sk = row.Sk;
+    if (PK && kb * T5L_KB >= Sk) return;                                    // a key block past the row's end
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j0 = kb * T5L_KB + wave * 16, j = j0 + (lane & 15);
     const bool active = j0 < Sk, jv = j < Sk;
     const bool kept = jv && (!a.keep || a.keep[(int64_t)b * Sk + j]);
     const float* delta = row_ws;
-    const float* norm = row_ws + (int64_t)a.B * a.H * Sq;
+    const float* norm = row_ws + (PK ? (int64_t)a.H * a.Tq : (int64_t)a.B * a.H * a.Sq);
     const DropoutRng rng(a.p_drop, a.seed);
     float kr[D / 4], vr[D / 4];
-    t5_row_operand<D>(kr, jv ? a.k + ((int64_t)b * Sk + j) * a.ldk + hh * D : nullptr, lane);
-    t5_row_operand<D>(vr, jv ? a.v + ((int64_t)b * Sk + j) * a.ldv + hh * D : nullptr, lane);
-    const float* relcol = a.rel ? a.rel + (int64_t)hh * R + (j + Sq - 1) : nullptr;                  // read at [-i] for allowed (i, j) only
+    t5_row_operand<D>(kr, jv ? a.k + (row.k0 + j) * a.ldk + hh * D : nullptr, lane);
+    t5_row_operand<D>(vr, jv ? a.v + (row.k0 + j) * a.ldv + hh * D : nullptr, lane);
+    const float* relcol = a.rel ? a.rel + (int64_t)hh * R + (j + a.Sq - 1) : nullptr;                  // read at [-i] for allowed (i, j) only
     f32x4v acck[D / 16], accv[D / 16];
 #pragma unroll
     for (int n = 0; n < D / 16; ++n) acck[n] = accv[n] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -310,12 +322,12 @@ t5l_attn_bwd_kv_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, c
     for (int q0 = qb_first * T5L_QB; q0 < Sq; q0 += T5L_QB) {
         const int rows = min(T5L_QB, Sq - q0), nt = (rows + 15) / 16;
         __syncthreads();                                                    // (the block before is consumed)
-        t5_stage<D>(Qs, a.q + ((int64_t)b * Sq + q0) * a.ldq + hh * D, a.ldq, rows, nt * 16);
-        t5_stage<D>(Gs, d_o + ((int64_t)b * Sq + q0) * ldo + hh * D, ldo, rows, nt * 16);
+        t5_stage<D>(Qs, a.q + (row.q0 + q0) * a.ldq + hh * D, a.ldq, rows, nt * 16);
+        t5_stage<D>(Gs, d_o + (row.q0 + q0) * ldo + hh * D, ldo, rows, nt * 16);
         for (int il = threadIdx.x; il < T5L_QB; il += T5_THREADS) {
-            ls[il] = il < rows ? lse[((int64_t)b * a.H + hh) * Sq + q0 + il] : 0.f;
-            dls[il] = il < rows ? delta[((int64_t)b * a.H + hh) * Sq + q0 + il] : 0.f;
-            cs[il] = il < rows ? norm[((int64_t)b * a.H + hh) * Sq + q0 + il] : 0.f;
+            ls[il] = il < rows ? lse[row.l0 + q0 + il] : 0.f;
+            dls[il] = il < rows ? delta[row.l0 + q0 + il] : 0.f;
+            cs[il] = il < rows ? norm[row.l0 + q0 + il] : 0.f;
         }
         __syncthreads();
         if (active)
@@ -336,8 +348,8 @@ t5l_attn_bwd_kv_kernel(const T5Args a, const float* __restrict__ d_o, int ldo, c
             }
     }
     if (!active) return;
-    t5_store_rows<D>(dk + (int64_t)b * Sk * lddk + hh * D, lddk, j0, Sk, acck, lane);
-    t5_store_rows<D>(dv + (int64_t)b * Sk * lddv + hh * D, lddv, j0, Sk, accv, lane);
+    t5_store_rows<D>(dk + row.k0 * lddk + hh * D, lddk, j0, Sk, acck, lane);
+    t5_store_rows<D>(dv + row.k0 * lddv + hh * D, lddv, j0, Sk, accv, lane);
 }
 
 }  // namespace gamer
@@ -360,22 +372,22 @@ extern "C" int gamer_t5_attn_long_fwd(const float* q, int ldq, const float* k, i
     GAMER_CHECK_ARG(o && lse && ldo >= H * head_dim, "%s: bad output", name);
     const int nqb = (Sq + T5L_QB - 1) / T5L_QB;
     GAMER_TRY(t5l_grid(name, B, H, nqb));
-    if (head_dim == 64) return launch<t5l_attn_fwd_kernel<64>>(name, dim3(B * H * nqb), dim3(T5_THREADS), 0, ST(stream), a, o, ldo, lse);
-    return launch<t5l_attn_fwd_kernel<32>>(name, dim3(B * H * nqb), dim3(T5_THREADS), 0, ST(stream), a, o, ldo, lse);
+    if (head_dim == 64) return launch<t5l_attn_fwd_kernel<64, false>>(name, dim3(B * H * nqb), dim3(T5_THREADS), 0, ST(stream), a, o, ldo, lse);
+    return launch<t5l_attn_fwd_kernel<32, false>>(name, dim3(B * H * nqb), dim3(T5_THREADS), 0, ST(stream), a, o, ldo, lse);
 }
 
-template <int D>
+template <int D, bool PK>
 static int t5l_bwd(const char* name, const T5Args& a, const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk,
                    float* dv, int lddv, float* drel_partial, int n_slab, float* delta, hipStream_t st) {
     const int nqb = (a.Sq + T5L_QB - 1) / T5L_QB, nkb = (a.Sk + T5L_KB - 1) / T5L_KB, rows = a.B * a.H;
-    GAMER_TRY(launch<t5l_attn_bwd_q_kernel<D, false, false>>(name, dim3(rows * nqb), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, delta,
+    GAMER_TRY(launch<t5l_attn_bwd_q_kernel<D, false, false, PK>>(name, dim3(rows * nqb), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, delta,
                                                               (float*)nullptr, 0, (float*)nullptr, 0));
-    GAMER_TRY(launch<t5l_attn_bwd_kv_kernel<D>>(name, dim3(rows * nkb), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, (const float*)delta, dk, lddk,
+    GAMER_TRY(launch<t5l_attn_bwd_kv_kernel<D, PK>>(name, dim3(rows * nkb), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, (const float*)delta, dk, lddk,
                                                 dv, lddv));
     if (drel_partial)
-        return launch<t5l_attn_bwd_q_kernel<D, true, true>>(name, dim3(n_slab * a.H), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, delta, dq, lddq,
+        return launch<t5l_attn_bwd_q_kernel<D, true, true, PK>>(name, dim3(n_slab * a.H), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, delta, dq, lddq,
                                                             drel_partial, n_slab);
-    return launch<t5l_attn_bwd_q_kernel<D, true, false>>(name, dim3(rows * nqb), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, delta, dq, lddq,
+    return launch<t5l_attn_bwd_q_kernel<D, true, false, PK>>(name, dim3(rows * nqb), dim3(T5_THREADS), 0, st, a, d_o, ldo, lse, delta, dq, lddq,
                                                          (float*)nullptr, 0);
 }
 
@@ -391,6 +403,43 @@ extern "C" int gamer_t5_attn_long_bwd(const float* q, int ldq, const float* k, i
     GAMER_CHECK_ARG(n_slab > 0 && n_slab <= B, "%s: n_slab=%d (1 .. B: every slab is written by its workgroup)", name, n_slab);
     GAMER_CHECK_ARG(!rel == !drel_partial, "%s: drel_partial goes with the bias", name);
     GAMER_TRY(t5l_grid(name, B, H, ((Sq > Sk ? Sq : Sk) + T5L_QB - 1) / T5L_QB));
-    if (head_dim == 64) return t5l_bwd<64>(name, a, d_o, ldo, lse, dq, lddq, dk, lddk, dv, lddv, drel_partial, n_slab, row_ws, ST(stream));
-    return t5l_bwd<32>(name, a, d_o, ldo, lse, dq, lddq, dk, lddk, dv, lddv, drel_partial, n_slab, row_ws, ST(stream));
+    if (head_dim == 64) return t5l_bwd<64, false>(name, a, d_o, ldo, lse, dq, lddq, dk, lddk, dv, lddv, drel_partial, n_slab, row_ws, ST(stream));
+    return t5l_bwd<32, false>(name, a, d_o, ldo, lse, dq, lddq, dk, lddk, dv, lddv, drel_partial, n_slab, row_ws, ST(stream));
+}
+
+// ---- the packed forms: the grids keep the dense geometry (max_sq, max_sk); blocks past a row's end leave at once ---------------------------
+extern "C" int gamer_t5_attn_long_packed_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                                             const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                             const int32_t* k_start_host, const int32_t* kv_rows, int B, int kv_batch, int max_sq,
+                                             int max_sk, int H, int head_dim, int causal, float p_drop, uint64_t seed, float* o, int ldo,
+                                             float* lse, void* stream) {
+    const char* name = "gamer_t5_attn_long_packed_fwd";
+    T5Args a;
+    GAMER_TRY(t5_packed_args(name, a, q, ldq, k, ldk, v, ldv, rel, q_start, k_start, q_start_host, k_start_host, B, kv_rows ? kv_batch : B,
+                             max_sq, max_sk, H, head_dim, causal, p_drop, seed, T5L_MAX_S));
+    a.kv_rows = kv_rows;
+    GAMER_CHECK_ARG(o && lse && ldo >= H * head_dim, "%s: bad output", name);
+    const int nqb = (max_sq + T5L_QB - 1) / T5L_QB;
+    GAMER_TRY(t5l_grid(name, B, H, nqb));
+    if (head_dim == 64) return launch<t5l_attn_fwd_kernel<64, true>>(name, dim3(B * H * nqb), dim3(T5_THREADS), 0, ST(stream), a, o, ldo, lse);
+    return launch<t5l_attn_fwd_kernel<32, true>>(name, dim3(B * H * nqb), dim3(T5_THREADS), 0, ST(stream), a, o, ldo, lse);
+}
+
+extern "C" int gamer_t5_attn_long_packed_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                                             const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                             const int32_t* k_start_host, int B, int max_sq, int max_sk, int H, int head_dim, int causal,
+                                             float p_drop, uint64_t seed, const float* d_o, int ldo, const float* lse, float* dq, int lddq,
+                                             float* dk, int lddk, float* dv, int lddv, float* drel_partial, int n_slab, float* row_ws,
+                                             void* stream) {
+    const char* name = "gamer_t5_attn_long_packed_bwd";
+    T5Args a;
+    GAMER_TRY(t5_packed_args(name, a, q, ldq, k, ldk, v, ldv, rel, q_start, k_start, q_start_host, k_start_host, B, B, max_sq, max_sk, H,
+                             head_dim, causal, p_drop, seed, T5L_MAX_S));
+    GAMER_CHECK_ARG(d_o && lse && dq && dk && dv && row_ws, "%s: null pointer", name);
+    GAMER_CHECK_ARG(ldo >= H * head_dim && lddq >= H * head_dim && lddk >= H * head_dim && lddv >= H * head_dim, "%s: bad leading dims", name);
+    GAMER_CHECK_ARG(n_slab > 0 && n_slab <= B, "%s: n_slab=%d (1 .. B: every slab is written by its workgroup)", name, n_slab);
+    GAMER_CHECK_ARG(!rel == !drel_partial, "%s: drel_partial goes with the bias", name);
+    GAMER_TRY(t5l_grid(name, B, H, ((max_sq > max_sk ? max_sq : max_sk) + T5L_QB - 1) / T5L_QB));
+    if (head_dim == 64) return t5l_bwd<64, true>(name, a, d_o, ldo, lse, dq, lddq, dk, lddk, dv, lddv, drel_partial, n_slab, row_ws, ST(stream));
+    return t5l_bwd<32, true>(name, a, d_o, ldo, lse, dq, lddq, dk, lddk, dv, lddv, drel_partial, n_slab, row_ws, ST(stream));
 }

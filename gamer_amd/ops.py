@@ -931,12 +931,20 @@ def _tune_kchunk(dy, lddy, x, ldx, dW, lddw, rows, N_out, K_in, groups, group_of
     return best
 
 
-def linear_wgrad(dy, lddy, x, ldx, dW, lddw, rows, N_out, K_in, groups=1, group_offsets=None, strideC=0, kchunk=None):
+def wgrad_rows_bucket(rows: int) -> int:
+    """``tune_rows`` for callers whose row count changes from batch to batch (packed rows): rows rounded up to a step of about an
+    eighth of their size, at least 4096, so that a handful of measured chunks serve every batch"""
+    g = 1 << max(12, int(rows).bit_length() - 3)
+    return -(-int(rows) // g) * g
+
+
+def linear_wgrad(dy, lddy, x, ldx, dW, lddw, rows, N_out, K_in, groups=1, group_offsets=None, strideC=0, kchunk=None, tune_rows=None):
     """dW[N_out,K_in] += dy[rows,N_out]^T @ x[rows,K_in]   (dW must be initialised).  The token chunks of the split-K form are
     combined in chunk order through a workspace (two passes, the default in fp32; opt-in for bf16: ``deterministic``) or with fp32
-    atomics (GAMER_WGRAD_TWO_PASS=0)."""
+    atomics (GAMER_WGRAD_TWO_PASS=0).  ``tune_rows``: the row count under which the measured chunk is kept (default: rows itself;
+    a caller whose row count differs in every batch passes wgrad_rows_bucket(rows), or every step would measure again)."""
     if kchunk is None:
-        key = (rows, N_out, K_in, groups, dy.dtype, F32_MATMUL_TERMS)
+        key = (tune_rows or rows, N_out, K_in, groups, dy.dtype, F32_MATMUL_TERMS)
         kchunk = _WGRAD_TUNED.get(key)
         if kchunk is None and _tune_key_str(key) in _WGRAD_FILE_CACHE:
             kchunk = _WGRAD_TUNED[key] = _WGRAD_FILE_CACHE[_tune_key_str(key)]
@@ -2129,3 +2137,114 @@ def t5_bias_fold(drel_partial, bucket, dtable):
         raise RuntimeError("t5_bias_fold: drel_partial [layers, n, h, R], bucket [R], dtable [num_buckets, h]")
     nl, n, h, R = drel_partial.shape
     call("gamer_t5_bias_fold", ptr(drel_partial), nl, n, h, R, ptr(bucket), dtable.shape[0], ptr(dtable), stream_ptr())
+
+
+# ---- the packed (variable-length) forms of both families: rows one behind the other, no padding tokens ------------------------------
+class T5Offsets:
+    """The row offsets of a packed batch: ``host`` int32 [n + 1] on the CPU (what every argument check reads, so that no call copies
+    from the device) and ``dev``, its device copy, which the kernels read.  ``total`` = host[n] rows, ``max_len`` the longest row.
+    Refused here, before anything touches the library: offsets that do not start at 0 or decrease."""
+
+    def __init__(self, host, device=None, dev=None):
+        host = torch.as_tensor(host).detach()
+        if host.is_cuda or host.dim() != 1 or host.numel() < 2 or host.dtype not in (torch.int32, torch.int64):
+            raise ValueError("T5Offsets: a CPU int tensor of n + 1 >= 2 row offsets")
+        if int(host[0]) != 0:
+            raise ValueError(f"T5Offsets: offsets start at 0 (got {int(host[0])})")
+        lens = host[1:] - host[:-1]
+        if int(lens.min()) < 0:
+            raise ValueError(f"T5Offsets: offsets decrease at row {int((lens < 0).nonzero()[0, 0])}")
+        if int(host[-1]) >= 2 ** 31:
+            raise ValueError("T5Offsets: more than 2^31 - 1 rows")
+        self.host = host.to(torch.int32).contiguous()
+        self.n, self.total, self.max_len = host.numel() - 1, int(host[-1]), int(lens.max())
+        self.dev = dev if dev is not None else (self.host.to(device) if device is not None else None)
+
+    @classmethod
+    def from_lengths(cls, lengths, device=None):
+        """the offsets of rows of ``lengths`` tokens (CPU int tensor [n], every entry >= 0)"""
+        lengths = torch.as_tensor(lengths).detach().to("cpu", torch.int64).flatten()
+        if lengths.numel() < 1 or int(lengths.min()) < 0:
+            raise ValueError("T5Offsets.from_lengths: n >= 1 lengths, none negative")
+        return cls(torch.cat([lengths.new_zeros(1), lengths.cumsum(0)]), device)
+
+    @classmethod
+    def uniform(cls, n, S, device=None):
+        """dense rows of S tokens each (the decoder side of a cross attention)"""
+        return cls(torch.arange(n + 1, dtype=torch.int64) * S, device)
+
+
+def _t5_packed_common(name, q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, Bkv, _long):
+    (t5_long_check_limits if _long else t5_check_limits)(max_sq, max_sk, h, d)
+    for off, what, n, max_s in ((q_off, "q_start", B, max_sq), (k_off, "k_start", Bkv, max_sk)):
+        if not isinstance(off, T5Offsets) or off.n != n:
+            raise RuntimeError(f"{name}: {what} must be the T5Offsets of {n} rows")
+        if off.max_len > max_s:
+            lens = off.host[1:] - off.host[:-1]
+            raise ValueError(f"{name}: row {int(lens.argmax())} of {what} holds {off.max_len} tokens, more than max {max_s}")
+        if off.total < 1:
+            raise ValueError(f"{name}: {what} holds no token")
+        if off.dev is None or not off.dev.is_cuda or off.dev.dtype != torch.int32 or off.dev.numel() != n + 1 or not off.dev.is_contiguous():
+            raise RuntimeError(f"{name}: {what} needs its int32 [{n + 1}] device copy")
+    for t, n, T in ((q, "q", q_off.total), (k, "k", k_off.total), (v, "v", k_off.total)):
+        _chk(t, torch.float32, n)
+        if t.dim() != 2 or t.shape != (T, h * d) or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+            raise RuntimeError(f"{name}: {n} must be a [{T}, {h * d}] row-strided view (16-byte aligned, row stride % 4 == 0)")
+    if rel is not None and _dense(rel, torch.float32, "rel").shape != (h, max_sq + max_sk - 1):
+        raise RuntimeError(f"{name}: rel [{h}, {max_sq + max_sk - 1}]")
+
+
+def t5_attn_packed_fwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, o, lse, kv_rows=None, kv_batch=None,
+                       _long=False):
+    """gamer_t5_attn_packed_fwd: q / o [Tq, h d], k / v [Tk, h d] (row-strided views), q_off / k_off the rows' T5Offsets, rel
+    [h, max_sq + max_sk - 1] or None, lse [h, Tq].  (max_sq, max_sk) is the shape of the dense run that the call replaces: bias
+    offsets and dropout counters are those of that run.  kv_rows int32 [B] with kv_batch: k_off holds kv_batch rows."""
+    name = "t5_attn_long_packed_fwd" if _long else "t5_attn_packed_fwd"
+    if (kv_rows is None) != (kv_batch is None) or (kv_rows is not None and _dense(kv_rows, torch.int32, "kv_rows").shape != (B,)):
+        raise RuntimeError(f"{name}: kv_rows int32 [B] goes with kv_batch")
+    _t5_packed_common(name, q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, B if kv_batch is None else kv_batch, _long)
+    _chk(o, torch.float32, "o"), _dense(lse, torch.float32, "lse")
+    if o.shape != (q_off.total, h * d) or o.stride(1) != 1 or lse.numel() != h * q_off.total:
+        raise RuntimeError(f"{name}: o [Tq, h d] and lse [h, Tq]")
+    call("gamer_" + name, ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(q_off.dev), ptr(k_off.dev),
+         q_off.host.data_ptr(), k_off.host.data_ptr(), ptr(kv_rows), B, 0 if kv_batch is None else kv_batch, max_sq, max_sk, h, d,
+         int(bool(causal)), float(p_drop), int(seed), ptr(o), o.stride(0), ptr(lse), stream_ptr())
+
+
+def t5_attn_packed_bwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial,
+                       _long=False):
+    """gamer_t5_attn_packed_bwd: dq / dk / dv (the layouts of q / k / v) are written in full; drel_partial
+    [n, h, max_sq + max_sk - 1] as in t5_attn_bwd."""
+    name = "t5_attn_long_packed_bwd" if _long else "t5_attn_packed_bwd"
+    _t5_packed_common(name, q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, B, _long)
+    for t, n, T in ((d_o, "d_o", q_off.total), (dq, "dq", q_off.total), (dk, "dk", k_off.total), (dv, "dv", k_off.total)):
+        _chk(t, torch.float32, n)
+        if t.shape != (T, h * d) or t.stride(1) != 1:
+            raise RuntimeError(f"{name}: {n} must be a [{T}, {h * d}] row-strided view")
+    if _dense(lse, torch.float32, "lse").numel() != h * q_off.total:
+        raise RuntimeError(f"{name}: lse [h, Tq]")
+    if (rel is None) != (drel_partial is None):
+        raise RuntimeError(f"{name}: drel_partial goes with the bias")
+    n = t5_n_slab(B, h)
+    if drel_partial is not None:
+        n = drel_partial.shape[0]
+        if _dense(drel_partial, torch.float32, "drel_partial").shape != (n, h, max_sq + max_sk - 1) or not 0 < n <= B:
+            raise RuntimeError(f"{name}: drel_partial [n, {h}, {max_sq + max_sk - 1}], 0 < n <= B")
+    args = (ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(rel), ptr(q_off.dev), ptr(k_off.dev), q_off.host.data_ptr(),
+            k_off.host.data_ptr(), B, max_sq, max_sk, h, d, int(bool(causal)), float(p_drop), int(seed), ptr(d_o), d_o.stride(0), ptr(lse),
+            ptr(dq), dq.stride(0), ptr(dk), dk.stride(0), ptr(dv), dv.stride(0), ptr(drel_partial), n)
+    if _long:
+        row_ws = torch.empty(2, h, q_off.total, dtype=torch.float32, device=q.device)  # the softmax backward's row terms
+        call("gamer_" + name, *args, ptr(row_ws), stream_ptr())
+    else:
+        call("gamer_" + name, *args, stream_ptr())
+
+
+def t5_attn_long_packed_fwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, o, lse, kv_rows=None, kv_batch=None):
+    """gamer_t5_attn_long_packed_fwd: the arguments of t5_attn_packed_fwd, max_sq, max_sk <= 512."""
+    t5_attn_packed_fwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, o, lse, kv_rows, kv_batch, _long=True)
+
+
+def t5_attn_long_packed_bwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial):
+    """gamer_t5_attn_long_packed_bwd: the arguments of t5_attn_packed_bwd, max_sq, max_sk <= 512; allocates the row terms [2, h, Tq]."""
+    t5_attn_packed_bwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial, _long=True)

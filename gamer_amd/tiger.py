@@ -22,6 +22,12 @@ Every step runs as HIP kernels, with no PyTorch fallback (a CPU tensor raises):
                 the [B T, V] logits are not formed in training.  ``forward(..., labels=None)`` or ``want_logits=True``
                 materialises them (tests, decoding)
 
+  packed rows   ``forward(..., packed=True, lengths=None)`` (also ``encode`` and ``beam_search``; default off): the encoder side runs on
+                the T = sum of the rows' token counts of a right-padded batch instead of B x S_max - the kept ids gathered into
+                [T], the same autograd functions on [T, D] (they are token-wise), attention through gamer_t5_attn_packed_* /
+                gamer_t5_attn_long_packed_* with per-row offsets, the decoder dense with its cross attention reading the packed
+                encoder output.  Bias offsets and dropout counters of the attention keep the dense geometry
+
 Not the reference's: a query row with NO allowed key gives a zero context and zero gradients here; HF's additive finfo.min mask
 gives a softmax over the bias alone in that case.  Real inputs cannot produce it: every row holds at least ``</s>``.  Dropout
 masks come from the project's counter-based hash.
@@ -178,11 +184,12 @@ def _linear(x, W):
     return y
 
 
-def _linear_bwd(dy, x, W, dx=None, accumulate=False):
-    """(dx [M, K], dW) of y = x W^T from dy [M, N] (row-strided views allowed); ``dx``: written (or added to) in place"""
+def _linear_bwd(dy, x, W, dx=None, accumulate=False, packed=False):
+    """(dx [M, K], dW) of y = x W^T from dy [M, N] (row-strided views allowed); ``dx``: written (or added to) in place.  ``packed``:
+    M changes from batch to batch, so the weight gradient's measured chunk is kept per bucket of M"""
     M, (N, K) = x.shape[0], W.shape
     dW = torch.zeros_like(W)
-    ops.linear_wgrad(dy, dy.stride(0), x, x.stride(0), dW, K, M, N, K)
+    ops.linear_wgrad(dy, dy.stride(0), x, x.stride(0), dW, K, M, N, K, tune_rows=ops.wgrad_rows_bucket(M) if packed else None)
     if dx is None:
         dx = torch.empty(M, K, **_f32(x.device))
     ops.linear_dgrad(dy, dy.stride(0), W, K, dx, dx.stride(0), M, N, K, accumulate=accumulate)
@@ -202,13 +209,67 @@ def _rms_bwd(x, w, eps, dy, dx):
     return colsum(part)
 
 
-def _attn_fwd(q, k, v, rel, keep, B, Sq, Sk, *rest, **kw):
-    """t5_attn_fwd on the kernel family that the shape needs: resident up to ops.T5_MAX_S, key-streaming above"""
-    (ops.t5_attn_long_fwd if max(Sq, Sk) > ops.T5_MAX_S else ops.t5_attn_fwd)(q, k, v, rel, keep, B, Sq, Sk, *rest, **kw)
+def _attn_fwd(q, k, v, rel, keep, B, Sq, Sk, *rest, pack=None, **kw):
+    """t5_attn_fwd on the kernel family that the shape needs: resident up to ops.T5_MAX_S, key-streaming above.  ``pack``: the
+    (query, key) ops.T5Offsets of packed rows - (Sq, Sk) is then the shape of the dense run and ``keep`` is not read"""
+    long = max(Sq, Sk) > ops.T5_MAX_S
+    if pack is not None:
+        return (ops.t5_attn_long_packed_fwd if long else ops.t5_attn_packed_fwd)(q, k, v, rel, *pack, B, Sq, Sk, *rest, **kw)
+    (ops.t5_attn_long_fwd if long else ops.t5_attn_fwd)(q, k, v, rel, keep, B, Sq, Sk, *rest, **kw)
 
 
-def _attn_bwd(q, k, v, rel, keep, B, Sq, Sk, *rest):
-    (ops.t5_attn_long_bwd if max(Sq, Sk) > ops.T5_MAX_S else ops.t5_attn_bwd)(q, k, v, rel, keep, B, Sq, Sk, *rest)
+def _attn_bwd(q, k, v, rel, keep, B, Sq, Sk, *rest, pack=None):
+    long = max(Sq, Sk) > ops.T5_MAX_S
+    if pack is not None:
+        return (ops.t5_attn_long_packed_bwd if long else ops.t5_attn_packed_bwd)(q, k, v, rel, *pack, B, Sq, Sk, *rest)
+    (ops.t5_attn_long_bwd if long else ops.t5_attn_bwd)(q, k, v, rel, keep, B, Sq, Sk, *rest)
+
+
+def packed_lengths(attention_mask: torch.Tensor) -> torch.Tensor:
+    """int64 [B] on the CPU: the token counts of the rows of a right-padded mask (mask[b, j] != 0 exactly for j < len_b).  Any other
+    form raises ValueError naming the row: the relative positions are the original ones, so a hole cannot be packed away."""
+    m = attention_mask.detach() != 0
+    if m.dim() != 2:
+        raise ValueError(f"packed rows: attention_mask [B, S] (got {tuple(m.shape)})")
+    lengths = m.sum(1)
+    bad = (m != (torch.arange(m.shape[1], device=m.device)[None, :] < lengths[:, None])).any(1)
+    code = torch.where(bad, -1 - lengths, lengths).to("cpu")                      # (the one copy: B integers, a bad row negative)
+    if int(code.min()) < 0:
+        b = int((code < 0).nonzero()[0, 0])
+        raise ValueError(f"packed rows need right-padded masks: row {b} of attention_mask is not {-1 - int(code[b])} ones followed by zeros")
+    return code
+
+
+@dataclasses.dataclass
+class PackedRows:
+    """A packed encoder batch: ``off`` the rows' ops.T5Offsets, ``S`` the padded length of the dense run it replaces, ``rows`` int64
+    [T] on the device, the flat [B S] indices of the kept tokens."""
+    off: "ops.T5Offsets"
+    S: int
+    rows: torch.Tensor
+    _dense: dict = dataclasses.field(default_factory=dict)
+
+    def dense_offsets(self, B, S, device):
+        """the offsets of B dense rows of S tokens (the decoder's queries in cross attention), built once per batch"""
+        if (B, S) not in self._dense:
+            self._dense[B, S] = ops.T5Offsets.uniform(B, S, device)
+        return self._dense[B, S]
+
+    @classmethod
+    def build(cls, lengths, B, S, device):
+        lengths = torch.as_tensor(lengths).detach()
+        if lengths.is_cuda or lengths.dim() != 1 or lengths.numel() != B or lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"packed rows: lengths is a CPU int tensor [{B}]")
+        lengths = lengths.to(torch.int64)
+        if int(lengths.min()) < 0 or int(lengths.max()) > S:
+            b = int(((lengths < 0) | (lengths > S)).nonzero()[0, 0])
+            raise ValueError(f"packed rows: row {b} holds {int(lengths[b])} tokens of {S}")
+        if int(lengths.sum()) == 0:
+            raise ValueError("packed rows: the batch holds no token")
+        off = ops.T5Offsets.from_lengths(lengths, device)
+        pos = torch.arange(off.total, dtype=torch.int64) - torch.repeat_interleave(off.host[:-1].long(), lengths)
+        rows = torch.repeat_interleave(torch.arange(B, dtype=torch.int64) * S, lengths) + pos
+        return cls(off, S, rows.to(device))
 
 
 class _BiasStack:
@@ -236,18 +297,24 @@ class _BiasStack:
 
 
 class _BlockFn(torch.autograd.Function):
-    """One T5Block.  x [B, S, D]; enc [B, Se, D] or None (encoder block).  params: ln0, q, k, v, o, [ln1, cq, ck, cv, co,] lnf, wi,
+    """One T5Block.  x [B, S, D]; enc [B, Se, D] or None (encoder block).  Packed rows (meta["pack"], a PackedRows): an encoder
+    block takes x [T, D], a decoder block enc [T, D] next to its dense x; every other step is token-wise.  params: ln0, q, k, v, o, [ln1, cq, ck, cv, co,] lnf, wi,
     wo, then block 0's bias table (or None: a later block, whose offset gradient block 0 folds)."""
 
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def forward(ctx, x, enc, meta, *params):
-        B, S, D = x.shape
-        T = B * S
+        dec = enc is not None
+        pk = meta.get("pack")
+        if pk is not None and not dec:
+            (T, D), B, S = x.shape, pk.off.n, pk.S
+        else:
+            B, S, D = x.shape
+            T = B * S
+        spack = (pk.off, pk.off) if pk is not None and not dec else None
         h, d, eps, bias = meta["heads"], meta["d_kv"], meta["eps"], meta["bias"]
         I = h * d
         p = meta["dropout"] if meta["training"] else 0.0
-        dec = enc is not None
         ln0, wq, wk, wv, wo = params[:5]
         lnf, wi, wff = params[-4:-1]
         seeds = [modules._SeedCounter.next() for _ in range(6)]
@@ -256,21 +323,22 @@ class _BlockFn(torch.autograd.Function):
         n0 = _rms(xf, ln0, eps)
         wqkv = torch.cat([wq, wk, wv], 0).contiguous()
         qkv = _linear(n0, wqkv)
-        c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
+        c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(h * T, **_f32(x.device))
         keep = None if dec else meta["keep"]
-        _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0)
+        _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0, pack=spack)
         x1 = add_dropout(xf, _linear(c0, wo), p, seeds[1])
         saved = [xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0]
         if dec:
             ln1, cq, ck, cv, co = params[5:10]
-            Se = enc.shape[1]
-            ef = enc.reshape(B * Se, D).contiguous().float()
+            Se = pk.S if pk is not None else enc.shape[1]
+            xpack = (pk.dense_offsets(B, S, x.device), pk.off) if pk is not None else None
+            ef = enc.reshape(-1, D).contiguous().float()
             n1 = _rms(x1, ln1, eps)
             q1 = _linear(n1, cq)
             wkv = torch.cat([ck, cv], 0).contiguous()
             kv = _linear(ef, wkv)
-            c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(B, h, S, **_f32(x.device))
-            _attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1)
+            c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(h * T, **_f32(x.device))
+            _attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1, pack=xpack)
             x2 = add_dropout(x1, _linear(c1, co), p, seeds[3])
             saved += [ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1, x2]
         else:
@@ -284,8 +352,9 @@ class _BlockFn(torch.autograd.Function):
         x3 = add_dropout(x2, _linear(actd, wff), p, seeds[5])
         saved += [lnf, wi, wff, n2, pre, actd]
         ctx.save_for_backward(*saved, meta["keep"])
-        ctx.meta = dict(meta, p=p, seeds=seeds, shape=(B, S, D), dec=dec, table=params[-1])
-        return x3.view(B, S, D)
+        ctx.meta = dict(meta, p=p, seeds=seeds, shape=(B, S, D), dec=dec, table=params[-1], spack=spack, xpack=xpack if dec else None,
+                        Se=Se if dec else None, enc_shape=enc.shape if dec else None)
+        return x3.view(x.shape)
 
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
@@ -293,7 +362,8 @@ class _BlockFn(torch.autograd.Function):
         sv = list(ctx.saved_tensors)
         mt = ctx.meta
         B, S, D = mt["shape"]
-        T, h, d, eps, p, seeds, dec, bias = B * S, mt["heads"], mt["d_kv"], mt["eps"], mt["p"], mt["seeds"], mt["dec"], mt["bias"]
+        T, h, d, eps, p, seeds, dec, bias = sv[0].shape[0], mt["heads"], mt["d_kv"], mt["eps"], mt["p"], mt["seeds"], mt["dec"], mt["bias"]
+        pk = mt["spack"] is not None                                              # a packed encoder block: T differs in every batch
         I = h * d
         keep_mask = sv.pop()
         xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0 = sv[:9]
@@ -303,37 +373,37 @@ class _BlockFn(torch.autograd.Function):
         dx = dout.reshape(T, D).contiguous().float().clone()                      # the gradient of the residual stream, added to in place
         # feed forward
         df = _dropout_bwd(dx, D, p, seeds[5])
-        dactd, dwff = _linear_bwd(df, actd, wff)
+        dactd, dwff = _linear_bwd(df, actd, wff, packed=pk)
         dact = _dropout_bwd(dactd, dactd.shape[1], p, seeds[4])
         ops.bias_act_bwd(pre, dact, ops.ACTIVATIONS["relu"], dact, torch.empty(_N_PARTIAL, pre.shape[1], **_f32(dev)))
-        dn2, dwi = _linear_bwd(dact, n2, wi)
+        dn2, dwi = _linear_bwd(dact, n2, wi, packed=pk)
         dlnf = _rms_bwd(x2, lnf, eps, dn2, dx)
         cross = [None] * 5
         denc = None
         if dec:
             ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1 = sv[9:19]
-            Se = ef.shape[0] // B
+            Se = mt["Se"]
             da = _dropout_bwd(dx, D, p, seeds[3])
             dc1, dco = _linear_bwd(da, c1, co)
-            dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(B * Se, 2 * I, **_f32(dev))
+            dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(ef.shape[0], 2 * I, **_f32(dev))
             _attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
-                      dkv[:, :I], dkv[:, I:], None)
+                      dkv[:, :I], dkv[:, I:], None, pack=mt["xpack"])
             dn1, dcq = _linear_bwd(dq1, n1, cq)
-            denc, dwkv = _linear_bwd(dkv, ef, wkv)
+            denc, dwkv = _linear_bwd(dkv, ef, wkv, packed=mt["xpack"] is not None)
             dln1 = _rms_bwd(x1, ln1, eps, dn1, dx)
             cross = [dln1, dcq, dwkv[:I], dwkv[I:], dco]
-            denc = denc.view(B, Se, D)
+            denc = denc.view(mt["enc_shape"])
         # self attention
         da = _dropout_bwd(dx, D, p, seeds[1])
-        dc0, dwo = _linear_bwd(da, c0, wo)
+        dc0, dwo = _linear_bwd(da, c0, wo, packed=pk)
         dqkv = torch.empty(T, 3 * I, **_f32(dev))
         _attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
-                  seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B))
-        dn0, dwqkv = _linear_bwd(dqkv, n0, wqkv)
+                  seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B), pack=mt["spack"])
+        dn0, dwqkv = _linear_bwd(dqkv, n0, wqkv, packed=pk)
         dln0 = _rms_bwd(xf, ln0, eps, dn0, dx)
         dtable = bias.fold(mt["table"].shape[0]) if mt["table"] is not None else None
         grads = [dln0, dwqkv[:I], dwqkv[I:2 * I], dwqkv[2 * I:], dwo] + (cross if dec else []) + [dlnf, dwi, dwff, dtable]
-        return (dx.view(B, S, D), denc, None, *grads)
+        return (dx.view(dout.shape), denc, None, *grads)
 
 
 class _FinalNormFn(torch.autograd.Function):
@@ -341,12 +411,11 @@ class _FinalNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, eps, p, seed, scale):
-        B, S, D = x.shape
-        xf = x.reshape(B * S, D).contiguous().float()
+        xf = x.reshape(-1, x.shape[-1]).contiguous().float()
         y = dropout_fwd(_rms(xf, w, eps), p, seed)
         ctx.meta = (eps, p, seed, scale, x.shape)
         ctx.save_for_backward(xf, w)
-        return (y * scale if scale != 1.0 else y).view(B, S, D)
+        return (y * scale if scale != 1.0 else y).view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
@@ -447,18 +516,25 @@ class TIGER(nn.Module):
         if ids.dim() != 2 or ids.shape[1] < 1 or ids.shape[1] > limit:
             raise NotImplementedError(f"TIGER on the HIP path: {what} length in [1, {limit}] (got {tuple(ids.shape)})")
 
-    def _stack(self, stack: T5Stack, ids, keep, enc=None, shared=None):
-        """keep: uint8 [B, Se] over the ENCODER tokens (the encoder's own keys, the decoder's cross-attention keys)"""
+    def _stack(self, stack: T5Stack, ids, keep, enc=None, shared=None, pack=None):
+        """keep: uint8 [B, Se] over the ENCODER tokens (the encoder's own keys, the decoder's cross-attention keys).  ``pack``
+        (PackedRows, keep = None): the encoder runs on the [T] kept tokens of ids [B, S] and returns [T, D]; the decoder takes
+        enc [T, D]"""
         c = self.config
         p = c.dropout_rate if self.training else 0.0
         B, S = ids.shape
-        x = EmbedDropoutFn.apply(ids.long().contiguous(), stack.embed_tokens.weight, p, _next_seed(), shared, -1)
+        ids = ids.long().contiguous()
+        if pack is not None and not stack.is_decoder:
+            ids = ids.reshape(-1)[pack.rows][None, :].contiguous()
+        x = EmbedDropoutFn.apply(ids, stack.embed_tokens.weight, p, _next_seed(), shared, -1)
+        if pack is not None and not stack.is_decoder:
+            x = x[0]
         blk0 = stack.block[0].layer[0].SelfAttention
         table = blk0.relative_attention_bias.weight
         bias = _BiasStack(table, self._bucket(S, not stack.is_decoder, ids.device), S, len(stack.block))
         for l, blk in enumerate(stack.block):
             meta = dict(heads=c.num_heads, d_kv=c.d_kv, eps=c.layer_norm_epsilon, dropout=c.dropout_rate, training=self.training,
-                        bias=bias, keep=keep, layer=l, zero_bias=self._zero_bias)
+                        bias=bias, keep=keep, layer=l, zero_bias=self._zero_bias, pack=pack)
             a = blk.layer[0]
             params = [a.layer_norm.weight, a.SelfAttention.q.weight, a.SelfAttention.k.weight, a.SelfAttention.v.weight,
                       a.SelfAttention.o.weight]
@@ -472,18 +548,29 @@ class TIGER(nn.Module):
         scale = c.d_model ** -0.5 if stack.is_decoder else 1.0
         return _FinalNormFn.apply(x, stack.final_layer_norm.weight, c.layer_norm_epsilon, p, _next_seed(), scale)
 
-    def encode(self, input_ids, attention_mask=None):
-        """(encoder output [B, Se, D], keep uint8 [B, Se])"""
+    def _pack(self, input_ids, attention_mask, lengths) -> PackedRows:
+        """the packed form of a batch: from ``lengths`` (CPU int [B]) without any copy from the device, else from the mask"""
+        B, S = input_ids.shape
+        if lengths is None:
+            lengths = torch.full((B,), S, dtype=torch.int64) if attention_mask is None else packed_lengths(attention_mask)
+        return PackedRows.build(lengths, B, S, input_ids.device)
+
+    def encode(self, input_ids, attention_mask=None, packed=False, lengths=None):
+        """(encoder output [B, Se, D], keep uint8 [B, Se]); ``packed=True``: (encoder output [T, D] without the padding tokens, the
+        PackedRows of the batch, whose ``off`` holds k_start)"""
         self._check(input_ids, MAX_LONG_ENCODER_LEN, "encoder")
+        if packed:
+            pack = self._pack(input_ids, attention_mask, lengths)
+            return self._stack(self.encoder, input_ids, None, pack=pack), pack
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         keep = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous()
         return self._stack(self.encoder, input_ids, keep), keep
 
-    def decode(self, decoder_input_ids, enc, keep, shared=None):
+    def decode(self, decoder_input_ids, enc, keep, shared=None, pack=None):
         """the decoder's output rows, already scaled by d_model ** -0.5: [B, T, D]"""
         self._check(decoder_input_ids, MAX_DECODER_LEN, "decoder")
-        return self._stack(self.decoder, decoder_input_ids, keep, enc, shared)
+        return self._stack(self.decoder, decoder_input_ids, keep, enc, shared, pack)
 
     def logits(self, dec_out: torch.Tensor) -> torch.Tensor:
         """the materialised logits [B, T, V] of decoder rows (no gradient: tests and decoding)"""
@@ -494,9 +581,12 @@ class TIGER(nn.Module):
             ops.linear_fwd(dec_out.detach().reshape(B * T, D).contiguous(), D, self.shared.weight.detach(), D, out, V, B * T, V, D)
         return out.view(B, T, V)
 
-    def forward(self, input_ids, attention_mask=None, labels=None, decoder_input_ids=None, want_logits=None, **kwargs):
+    def forward(self, input_ids, attention_mask=None, labels=None, decoder_input_ids=None, want_logits=None, packed=False,
+                lengths=None, **kwargs):
         """(loss, logits).  With labels the loss is the mean over the positions with label != -100 of CE(logits / temperature); the
-        logits are formed only without labels or with ``want_logits=True`` (default: formed when no gradient is recorded)."""
+        logits are formed only without labels or with ``want_logits=True`` (default: formed when no gradient is recorded).
+        ``packed=True``: the encoder side runs on the sum of the rows' token counts, without the padding tokens (right-padded masks
+        only); ``lengths`` (CPU int [B]) spares the one copy of B integers that reading them from the mask costs."""
         for name in ("head_mask", "decoder_head_mask", "cross_attn_head_mask", "inputs_embeds", "decoder_inputs_embeds",
                      "output_attentions", "output_hidden_states", "past_key_values", "encoder_outputs", "decoder_attention_mask"):
             if kwargs.pop(name, None) not in (None, False):
@@ -514,9 +604,12 @@ class TIGER(nn.Module):
         self._check(input_ids, MAX_LONG_ENCODER_LEN, "encoder")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        keep = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous()
-        enc = self._stack(self.encoder, input_ids, keep, shared=shared)
-        out = self.decode(decoder_input_ids.to(input_ids.device), enc, keep, shared)
+        if packed:
+            keep, pack = None, self._pack(input_ids, attention_mask, lengths)
+        else:
+            keep, pack = (attention_mask.to(input_ids.device) != 0).to(torch.uint8).contiguous(), None
+        enc = self._stack(self.encoder, input_ids, keep, shared=shared, pack=pack)
+        out = self.decode(decoder_input_ids.to(input_ids.device), enc, keep, shared, pack)
         loss = None
         if labels is not None:
             flat = labels.to(input_ids.device).long().flatten()
@@ -535,9 +628,14 @@ class _DecoderEval:
     """The decoder without autograd for beam search: the concatenated weights once per search, the cross-attention keys / values
     once per USER and layer; a beam row reads its user's copy through the attention kernel's row map."""
 
-    def __init__(self, model: "TIGER", enc: torch.Tensor, keep: torch.Tensor):
+    def __init__(self, model: "TIGER", enc: torch.Tensor, keep):
+        """enc [B, Se, D] with keep uint8 [B, Se], or the packed encoder output [T, D] with its PackedRows"""
         c = model.config
-        self.model, self.keep, self.users, self.Se = model, keep, enc.shape[0], enc.shape[1]
+        self.pack = keep if isinstance(keep, PackedRows) else None
+        if self.pack is not None:
+            self.model, self.keep, self.users, self.Se = model, None, self.pack.off.n, self.pack.S
+        else:
+            self.model, self.keep, self.users, self.Se = model, keep, enc.shape[0], enc.shape[1]
         ef = enc.reshape(-1, c.d_model).contiguous()
         self.layers = []
         with ops.f32_matmul("f32"):
@@ -562,6 +660,7 @@ class _DecoderEval:
         table = m.decoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
         rel = _BiasStack(table, m._bucket(S, False, dev), S, len(self.layers)).rel
         lse = torch.empty(N, h, S, **_f32(dev))
+        xpack = (self.pack.dense_offsets(N, S, dev), self.pack.off) if self.pack is not None else None
         relu = ops.ACTIVATIONS["relu"]
         for L in self.layers:
             qkv = _linear(_rms(x, L["ln0"], eps), L["wqkv"])
@@ -571,7 +670,7 @@ class _DecoderEval:
             q1 = _linear(_rms(x, L["ln1"], eps), L["cq"])
             c1 = torch.empty(N * S, I, **_f32(dev))
             _attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
-                      kv_rows=kv_rows, kv_batch=self.users)
+                      kv_rows=kv_rows, kv_batch=self.users, pack=xpack)
             x = add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
             pre = _linear(_rms(x, L["lnf"], eps), L["wi"])
             act = torch.empty_like(pre)
@@ -582,7 +681,8 @@ class _DecoderEval:
 
 
 @torch.no_grad()
-def beam_search(model: TIGER, input_ids, attention_mask, trie, num_beams: int, max_new_tokens: int, decoder_prefix=None):
+def beam_search(model: TIGER, input_ids, attention_mask, trie, num_beams: int, max_new_tokens: int, decoder_prefix=None, packed=False,
+                lengths=None):
     """Trie-constrained beam search as ``generate(..., num_beams=k, num_return_sequences=k, prefix_allowed_tokens_fn=...,
     early_stopping=True)`` runs it for ref:SeqRec/tasks/test_decoder.py and test_SMB_decoder.py.  ``trie``: a decode.ItemTrie over
     the full decoder sequences ([decoder_start] + ...), every one of them ``len(prefix) + max_new_tokens`` tokens long (so all
@@ -609,7 +709,7 @@ def beam_search(model: TIGER, input_ids, attention_mask, trie, num_beams: int, m
     was_training = model.training
     model.eval()
     try:
-        enc, keep = model.encode(input_ids, attention_mask)
+        enc, keep = model.encode(input_ids, attention_mask, packed, lengths)     # (packed: keep is the batch's PackedRows)
         dec = _DecoderEval(model, enc, keep)
         seqs = prefix[:, None, :].expand(B, nb, P).contiguous()
         run_scores = torch.zeros(B, nb, device=dev)

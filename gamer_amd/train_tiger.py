@@ -11,7 +11,8 @@ Mirrors ``TrainDecoder.invoke`` (ref:SeqRec/tasks/train_decoder.py) for ``--back
   testing    a trie over all items ([decoder_start] + item tokens + </s>), tiger.beam_search with ``--num_beams``, then
              metrics.py (hit / ndcg / recall @ k) averaged over the test samples, written to ``--results_file``
 Single device.  ``--fp16``, ``--bf16``, ``--deepspeed`` and ``--resume_from_checkpoint`` are refused by name; gradient accumulation
-is not built (``--per_device_batch_size`` is the step's batch)."""
+is not built (``--per_device_batch_size`` is the step's batch).  ``--pack_rows`` (default off) runs the encoder side of training,
+of the evaluation loss and of the test on the rows' own tokens, without the padding tokens (tiger.TIGER.forward(packed=True))."""
 from __future__ import annotations
 
 import argparse
@@ -29,6 +30,18 @@ from .metrics import get_metrics_results, get_topk_results
 from .seqrec_data import EncoderDecoderCollator, SeqRecData, T5_EOS_ID
 
 DEFAULT_METRICS = "hit@1,hit@5,hit@10,ndcg@5,ndcg@10"
+
+
+def add_pack_rows(ap):
+    ap.add_argument("--pack_rows", action="store_true",
+                    help="run the encoder side on the rows' own tokens, without the padding tokens (tiger.TIGER.forward(packed=True))")
+
+
+def pack_kwargs(a, batch):
+    """the ``packed`` / ``lengths`` arguments of a collated batch: the lengths are read from the mask on the host, before the upload"""
+    if not getattr(a, "pack_rows", False):
+        return {}
+    return dict(packed=True, lengths=tiger.packed_lengths(batch["attention_mask"]))
 
 
 def parse_args(argv=None):
@@ -61,6 +74,7 @@ def parse_args(argv=None):
     ap.add_argument("--test_batch_size", type=int, default=32)
     ap.add_argument("--metrics", default=DEFAULT_METRICS)
     ap.add_argument("--results_file", default="./results/test-decoder.json")
+    add_pack_rows(ap)
     a = ap.parse_args(argv)
     for name in ("fp16", "bf16", "deepspeed", "resume_from_checkpoint"):
         if getattr(a, name):
@@ -120,13 +134,14 @@ def _batches(samples, collator, batch_size, order=None):
         yield collator(samples, order[i:i + batch_size])
 
 
-def eval_loss(model, samples, collator, batch_size, dev):
+def eval_loss(model, samples, collator, batch_size, dev, a=None):
     """the evaluation loss as HF's Trainer reports it: the mean over the batches of the batch's loss"""
     model.eval()
     losses = []
     with torch.no_grad():
         for b in _batches(samples, collator, batch_size):
-            loss, _ = model(b["input_ids"].to(dev), b["attention_mask"].to(dev), labels=b["labels"].to(dev), want_logits=False)
+            loss, _ = model(b["input_ids"].to(dev), b["attention_mask"].to(dev), labels=b["labels"].to(dev), want_logits=False,
+                            **pack_kwargs(a, b))
             losses.append(loss)
     return float(torch.stack(losses).mean())
 
@@ -145,7 +160,8 @@ def test(model, data, collator, a, dev):
     totals, n = {m: 0.0 for m in metrics}, 0
     model.eval()
     for b in _batches(samples, collator, a.test_batch_size):
-        seqs, scores = tiger.beam_search(model, b["input_ids"].to(dev), b["attention_mask"].to(dev), trie, a.num_beams, item_len + 1)
+        seqs, scores = tiger.beam_search(model, b["input_ids"].to(dev), b["attention_mask"].to(dev), trie, a.num_beams, item_len + 1,
+                                         **pack_kwargs(a, b))
         pred = seqs[:, 1:1 + item_len].cpu().tolist()
         labels = b["labels"][:, :item_len].tolist()
         targets = [[row] for row in labels]
@@ -192,13 +208,13 @@ def run(a, tag, data, collator, test_fn):
                 if n % accum == 0:
                     for p in model.parameters():
                         p.grad = None
-                loss, _ = model(b["input_ids"].to(dev), b["attention_mask"].to(dev), labels=b["labels"].to(dev))
+                loss, _ = model(b["input_ids"].to(dev), b["attention_mask"].to(dev), labels=b["labels"].to(dev), **pack_kwargs(a, b))
                 (loss if accum == 1 else loss / accum).backward()
                 losses.append(loss.detach())
                 if (n + 1) % accum == 0 or n + 1 == batches_per_epoch:
                     opt.step(schedule.cosine_with_warmup(step, a.learning_rate, warmup, total))
                     step += 1
-            ev = eval_loss(model, valid, collator, a.per_device_batch_size, dev)
+            ev = eval_loss(model, valid, collator, a.per_device_batch_size, dev, a)
             print(f"[{tag}] epoch {epoch + 1}/{a.epochs} loss {float(torch.stack(losses).mean()):.4f} eval_loss {ev:.4f}", flush=True)
             if ev < best:
                 best, patience = ev, 0

@@ -24,6 +24,7 @@ import torch
 from . import mb_data, t5_mb_data, tiger
 from .decode import ItemTrie
 from .metrics import get_metrics_results, get_topk_results
+from .train_tiger import pack_kwargs
 from .train_tiger_smb import add_train_flags, check_row_limit, check_train_flags
 
 DEFAULT_METRICS = "hit@1,hit@5,hit@10,ndcg@5,ndcg@10"
@@ -95,7 +96,7 @@ def test(model, data, collator, a, dev):
     for i in range(0, len(samples), a.test_batch_size):
         inputs, targets = collator.test(samples, range(i, min(i + a.test_batch_size, len(samples))))
         seqs, scores = tiger.beam_search(model, inputs["input_ids"].to(dev), inputs["attention_mask"].to(dev), trie, a.num_beams, steps,
-                                         decoder_prefix=prefix)
+                                         decoder_prefix=prefix, **pack_kwargs(a, inputs))
         pred = seqs[:, 1:1 + K].cpu().tolist()
         topk = get_topk_results(pred, scores.cpu().tolist(), targets, a.num_beams)
         for m, v in get_metrics_results(topk, metrics, targets).items():

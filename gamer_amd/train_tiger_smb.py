@@ -59,6 +59,8 @@ def add_train_flags(ap, model_max_length: int):
     ap.add_argument("--deepspeed", default=None)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--wandb_run_name", default="default")
+    from .train_tiger import add_pack_rows
+    add_pack_rows(ap)
 
 
 def check_train_flags(a, prog: str):
@@ -136,6 +138,7 @@ def merge_rows(rows: List[Dict[str, float]], counts: Sequence[int], metrics: Seq
 
 def test_behavior(model, data, samples, collator, a, dev, behavior: str) -> Dict[str, float]:
     """test_single_behavior (test_SMB_decoder.py:90-285) on ``samples`` = test_samples.filter_by_behavior(behavior)"""
+    from .train_tiger import pack_kwargs
     metrics = a.metrics.split(",")
     c = model.config
     K = data.sole_item_len
@@ -146,7 +149,7 @@ def test_behavior(model, data, samples, collator, a, dev, behavior: str) -> Dict
         inputs, targets = collator.test(samples, range(i, min(i + a.test_batch_size, len(samples))))
         # the trie's sequences end with </s>; the search stops after the item's tokens (max_new_tokens = sole_item_len)
         seqs, scores = tiger.beam_search(model, inputs["input_ids"].to(dev), inputs["attention_mask"].to(dev), trie, a.num_beams, K,
-                                         decoder_prefix=prefix)
+                                         decoder_prefix=prefix, **pack_kwargs(a, inputs))
         pred = seqs[:, 2:2 + K].cpu().tolist()
         topk = get_topk_results(pred, scores.cpu().tolist(), targets, a.num_beams)
         for m, v in get_metrics_results(topk, metrics, targets).items():

@@ -1123,6 +1123,38 @@ int gamer_t5_attn_long_bwd(const float* q, int ldq, const float* k, int ldk, con
                            const uint8_t* keep, int B, int Sq, int Sk, int H, int head_dim, int causal, float p_drop, uint64_t seed,
                            const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
                            float* drel_partial, int n_slab, float* row_ws, void* stream);
+/* The packed (variable-length) forms of both families: the batch's rows lie one behind the other without padding tokens.  Row b's
+ * queries are rows q_start[b] .. q_start[b + 1] of q [Tq, ldq], its keys and values rows k_start[b] .. k_start[b + 1] of k / v
+ * [Tk, ld*]; o, dq, dk, dv have the layouts of q / k / v, lse is [H][Tq], the long backward's row_ws 2 H Tq floats.  q_start / k_start
+ * are DEVICE arrays of B + 1 int32 (self attention passes one array twice; cross attention from dense rows passes q_start[b] = b Sd);
+ * q_start_host / k_start_host are their HOST copies, which the argument check reads, so a call makes no device-to-host copy.
+ * max_sq, max_sk: the shape of the dense [B, S_max] run that the call replaces.  rel stays [H][max_sq + max_sk - 1], read at
+ * j - i + max_sq - 1, drel_partial keeps its [n_slab][H][max_sq + max_sk - 1] slabs (gamer_t5_bias_expand / _fold unchanged) and the
+ * dropout counter of element (b, head, i, j) is ((b H + head) max_sq + i) max_sk + j: a packed call draws the mask of the padded
+ * call.  No keep argument (every key of a packed row is real); causal compares the indices inside the row.  kv_rows (forward only):
+ * row b reads the keys of packed row kv_rows[b], and k_start then has kv_batch + 1 entries (kv_batch is not read without kv_rows).
+ * A row without keys gives a zero context, lse = -inf and zero gradients; a row without queries contributes nothing.  No float
+ * atomics; the slab ownership of the dense backward holds.  Refused before any launch, outputs untouched: offsets that do not start
+ * at 0 or decrease, a row longer than max_s*, an array without any token, max_s* beyond the family's bound (128 / 512), H > 16, a
+ * head_dim other than 32 or 64, and the alignment rules of the dense entry points. */
+int gamer_t5_attn_packed_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                             const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host, const int32_t* k_start_host,
+                             const int32_t* kv_rows, int B, int kv_batch, int max_sq, int max_sk, int H, int head_dim, int causal,
+                             float p_drop, uint64_t seed, float* o, int ldo, float* lse, void* stream);
+int gamer_t5_attn_packed_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                             const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host, const int32_t* k_start_host,
+                             int B, int max_sq, int max_sk, int H, int head_dim, int causal, float p_drop, uint64_t seed,
+                             const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk, int lddk, float* dv, int lddv,
+                             float* drel_partial, int n_slab, void* stream);
+int gamer_t5_attn_long_packed_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                                  const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                  const int32_t* k_start_host, const int32_t* kv_rows, int B, int kv_batch, int max_sq, int max_sk, int H,
+                                  int head_dim, int causal, float p_drop, uint64_t seed, float* o, int ldo, float* lse, void* stream);
+int gamer_t5_attn_long_packed_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* rel,
+                                  const int32_t* q_start, const int32_t* k_start, const int32_t* q_start_host,
+                                  const int32_t* k_start_host, int B, int max_sq, int max_sk, int H, int head_dim, int causal,
+                                  float p_drop, uint64_t seed, const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk,
+                                  int lddk, float* dv, int lddv, float* drel_partial, int n_slab, float* row_ws, void* stream);
 /* rel [H][n_offsets] = table [num_buckets][H] at bucket[offset] (the bucket of every relative offset is computed on the host) */
 int gamer_t5_bias_expand(const float* table, const int32_t* bucket, int num_buckets, int H, int n_offsets, float* rel, void* stream);
 /* dtable [num_buckets][H] from drel_partial [n_layers][n_slab][H][n_offsets]: per layer the slabs in order and the offsets of a bucket
