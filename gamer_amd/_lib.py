@@ -146,6 +146,9 @@ _SIGNATURES = {
     "gamer_swiglu_fwd_ld": [P, L, I, I, F, U, P, P],
     "gamer_swiglu_bwd_ld": [P, L, I, I, P, F, U, P],
     "gamer_swiglu_fwd_ld_tbl": [P, L, I, I, F, U, P, P, P, P],
+    "gamer_pba_router": [P, I, I, I, I, I, I, I, P, I, I, I, I, I, P, P, P, P, P],
+    "gamer_relu_tbl_fwd": [P, L, I, I, F, U, P, P, P, I, P],
+    "gamer_relu_tbl_bwd": [P, L, I, I, P, F, U, P, P, I, P],
     "gamer_swiglu_bwd_ld_tbl": [P, L, I, I, P, F, U, P, P, P],
     "gamer_silu_fwd_ld": [P, L, I, I, F, U, P, P],
     "gamer_silu_bwd_ld": [P, L, I, I, P, F, U, P],

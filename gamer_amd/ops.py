@@ -1148,6 +1148,47 @@ def swiglu_bwd_ld_tbl(gu, ld, T, I, dhm, p, seed, tbl, row_group):
     call("gamer_swiglu_bwd_ld_tbl", ptr(gu), ld, T, I, ptr(dhm), p, seed, ptr(tbl), ptr(row_group), stream_ptr())
 
 
+def pba_router(ids, decoder, num_positions, n_items, moe_behavior_only, use_behavior_token, behavior_lut, nb1, num_experts, pad_id,
+               eos_id, expert, beh_idx, key, bad_token):
+    """PBATransformer's encoder (``decoder=False``) or decoder router in one launch (gamer_pba_router): ids int64 [B, S] -> expert,
+    beh_idx and (or None) key = expert * nb1 + beh_idx, int32 [B, S]; ``bad_token`` int32 [1] is added to, never cleared.
+    ``behavior_lut``: int32 [vocab] on the device (-1: no behaviour token), None without behaviour tokens."""
+    B, S = ids.shape
+    _chk(ids, torch.int64, "input_ids")
+    for name, t in (("expert", expert), ("beh_idx", beh_idx), ("key", key), ("bad_token", bad_token), ("behavior_lut", behavior_lut)):
+        if t is not None:
+            _chk(t, torch.int32, name)
+    if expert.numel() != B * S or beh_idx.numel() != B * S or (key is not None and key.numel() != B * S):
+        raise ValueError(f"pba_router: outputs of {B * S} entries")
+    call("gamer_pba_router", ptr(ids), B, S, 1 if decoder else 0, num_positions, n_items, 1 if moe_behavior_only else 0,
+         1 if use_behavior_token else 0, ptr(behavior_lut), behavior_lut.numel() if behavior_lut is not None else 0, nb1, num_experts,
+         pad_id, eos_id, ptr(expert), ptr(beh_idx), ptr(key), ptr(bad_token), stream_ptr())
+
+
+def _relu_tbl_args(name, pre, ld, T, I, other, tbl, row_group, n_groups):
+    _chk(pre, torch.float32, "pre"), _chk(other, torch.float32, name)
+    if pre.numel() < (T - 1) * ld + I or other.numel() < T * I:
+        raise ValueError(f"relu_tbl: pre holds {pre.numel()} and {name} {other.numel()} values (T={T}, I={I}, ld={ld})")
+    if (tbl is None) != (row_group is None):
+        raise ValueError("relu_tbl: tbl and row_group come together")
+    if tbl is not None:
+        _chk(tbl, torch.float32, "tbl"), _chk(row_group, torch.int32, "row_group")
+        if tbl.numel() < n_groups * I or row_group.numel() < T:
+            raise ValueError(f"relu_tbl: tbl [{n_groups}, {I}] and row_group [{T}] (got {tbl.numel()} and {row_group.numel()} entries)")
+
+
+def relu_tbl_fwd(pre, ld, T, I, p, seed, act, tbl=None, row_group=None, n_groups=0):
+    """act [T, I] = drop(relu(pre[:, :I] + tbl[row_group])) (gamer_relu_tbl_fwd; pre has row stride ld; tbl None: no table)."""
+    _relu_tbl_args("act", pre, ld, T, I, act, tbl, row_group, n_groups)
+    call("gamer_relu_tbl_fwd", ptr(pre), ld, T, I, p, seed, ptr(act), ptr(tbl), ptr(row_group), n_groups, stream_ptr())
+
+
+def relu_tbl_bwd(pre, ld, T, I, dact, p, seed, tbl=None, row_group=None, n_groups=0):
+    """In place: pre[:, :I] <- drop_mask * dact * (pre + tbl[row_group] > 0) (gamer_relu_tbl_bwd)."""
+    _relu_tbl_args("dact", pre, ld, T, I, dact, tbl, row_group, n_groups)
+    call("gamer_relu_tbl_bwd", ptr(pre), ld, T, I, ptr(dact), p, seed, ptr(tbl), ptr(row_group), n_groups, stream_ptr())
+
+
 def inject_table_fwd(Eb, W, ldw, col0, E, twoI, tbl):
     """tbl [E * NB1, 2I] <- the behaviour-embedding share of the gate|up projection per (expert, behaviour) (gamer_inject_table_fwd)."""
     NB1, EB = Eb.shape

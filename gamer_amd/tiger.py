@@ -296,6 +296,90 @@ class _BiasStack:
         return dtable
 
 
+def attn_half_fwd(x, enc, meta, params, seeds):
+    """The attention layers of one T5Block, shared by every model built on this stack: x + dropout(o(attn(norm(x)))) and, in a
+    decoder block, the same over the encoder output.  ``params``: ln0, q, k, v, o, [ln1, cq, ck, cv, co]; ``seeds``: the block's
+    six dropout seeds, of which this half takes the first four.  Returns (x2 [T, D], the tensors its backward needs, the entries
+    of the block's ctx.meta)."""
+    dec = enc is not None
+    pk = meta.get("pack")
+    if pk is not None and not dec:
+        (T, D), B, S = x.shape, pk.off.n, pk.S
+    else:
+        B, S, D = x.shape
+        T = B * S
+    spack = (pk.off, pk.off) if pk is not None and not dec else None
+    h, d, eps, bias = meta["heads"], meta["d_kv"], meta["eps"], meta["bias"]
+    I = h * d
+    p = meta["dropout"] if meta["training"] else 0.0
+    ln0, wq, wk, wv, wo = params[:5]
+    xf = x.reshape(T, D).contiguous().float()
+    # self attention: x + dropout(o(attn(norm(x))))
+    n0 = _rms(xf, ln0, eps)
+    wqkv = torch.cat([wq, wk, wv], 0).contiguous()
+    qkv = _linear(n0, wqkv)
+    c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(h * T, **_f32(x.device))
+    keep = None if dec else meta["keep"]
+    _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0, pack=spack)
+    x1 = add_dropout(xf, _linear(c0, wo), p, seeds[1])
+    saved = [xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0]
+    if dec:
+        ln1, cq, ck, cv, co = params[5:10]
+        Se = pk.S if pk is not None else enc.shape[1]
+        xpack = (pk.dense_offsets(B, S, x.device), pk.off) if pk is not None else None
+        ef = enc.reshape(-1, D).contiguous().float()
+        n1 = _rms(x1, ln1, eps)
+        q1 = _linear(n1, cq)
+        wkv = torch.cat([ck, cv], 0).contiguous()
+        kv = _linear(ef, wkv)
+        c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(h * T, **_f32(x.device))
+        _attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1, pack=xpack)
+        x2 = add_dropout(x1, _linear(c1, co), p, seeds[3])
+        saved += [ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1, x2]
+    else:
+        x2 = x1
+    info = dict(p=p, seeds=seeds, shape=(B, S, D), dec=dec, spack=spack, xpack=xpack if dec else None, Se=Se if dec else None,
+                enc_shape=enc.shape if dec else None)
+    return x2, saved, info
+
+
+def attn_half_bwd(sv, mt, dx, keep_mask):
+    """The backward of attn_half_fwd, after the feed-forward layer's: ``sv`` the tensors it saved, ``mt`` the block's ctx.meta,
+    ``dx`` [T, D] the gradient of the residual stream, added to in place.  Returns (denc or None, the gradients of ``params`` in
+    their order, the folded gradient of the stack's bias table after block 0 or None)."""
+    B, S, D = mt["shape"]
+    T, h, d, eps, p, seeds, dec, bias = sv[0].shape[0], mt["heads"], mt["d_kv"], mt["eps"], mt["p"], mt["seeds"], mt["dec"], mt["bias"]
+    pk = mt["spack"] is not None                                              # a packed encoder block: T differs in every batch
+    I = h * d
+    xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0 = sv[:9]
+    dev = xf.device
+    cross = [None] * 5
+    denc = None
+    if dec:
+        ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1 = sv[9:19]
+        Se = mt["Se"]
+        da = _dropout_bwd(dx, D, p, seeds[3])
+        dc1, dco = _linear_bwd(da, c1, co)
+        dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(ef.shape[0], 2 * I, **_f32(dev))
+        _attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
+                  dkv[:, :I], dkv[:, I:], None, pack=mt["xpack"])
+        dn1, dcq = _linear_bwd(dq1, n1, cq)
+        denc, dwkv = _linear_bwd(dkv, ef, wkv, packed=mt["xpack"] is not None)
+        dln1 = _rms_bwd(x1, ln1, eps, dn1, dx)
+        cross = [dln1, dcq, dwkv[:I], dwkv[I:], dco]
+        denc = denc.view(mt["enc_shape"])
+    # self attention
+    da = _dropout_bwd(dx, D, p, seeds[1])
+    dc0, dwo = _linear_bwd(da, c0, wo, packed=pk)
+    dqkv = torch.empty(T, 3 * I, **_f32(dev))
+    _attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
+              seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B), pack=mt["spack"])
+    dn0, dwqkv = _linear_bwd(dqkv, n0, wqkv, packed=pk)
+    dln0 = _rms_bwd(xf, ln0, eps, dn0, dx)
+    dtable = bias.fold(mt["table"].shape[0]) if mt["table"] is not None else None
+    return denc, [dln0, dwqkv[:I], dwqkv[I:2 * I], dwqkv[2 * I:], dwo] + (cross if dec else []), dtable
+
+
 class _BlockFn(torch.autograd.Function):
     """One T5Block.  x [B, S, D]; enc [B, Se, D] or None (encoder block).  Packed rows (meta["pack"], a PackedRows): an encoder
     block takes x [T, D], a decoder block enc [T, D] next to its dense x; every other step is token-wise.  params: ln0, q, k, v, o, [ln1, cq, ck, cv, co,] lnf, wi,
@@ -304,47 +388,12 @@ class _BlockFn(torch.autograd.Function):
     @staticmethod
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def forward(ctx, x, enc, meta, *params):
-        dec = enc is not None
-        pk = meta.get("pack")
-        if pk is not None and not dec:
-            (T, D), B, S = x.shape, pk.off.n, pk.S
-        else:
-            B, S, D = x.shape
-            T = B * S
-        spack = (pk.off, pk.off) if pk is not None and not dec else None
-        h, d, eps, bias = meta["heads"], meta["d_kv"], meta["eps"], meta["bias"]
-        I = h * d
-        p = meta["dropout"] if meta["training"] else 0.0
-        ln0, wq, wk, wv, wo = params[:5]
         lnf, wi, wff = params[-4:-1]
         seeds = [modules._SeedCounter.next() for _ in range(6)]
-        xf = x.reshape(T, D).contiguous().float()
-        # self attention: x + dropout(o(attn(norm(x))))
-        n0 = _rms(xf, ln0, eps)
-        wqkv = torch.cat([wq, wk, wv], 0).contiguous()
-        qkv = _linear(n0, wqkv)
-        c0, lse0 = torch.empty(T, I, **_f32(x.device)), torch.empty(h * T, **_f32(x.device))
-        keep = None if dec else meta["keep"]
-        _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, keep, B, S, S, h, d, dec, p, seeds[0], c0, lse0, pack=spack)
-        x1 = add_dropout(xf, _linear(c0, wo), p, seeds[1])
-        saved = [xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0]
-        if dec:
-            ln1, cq, ck, cv, co = params[5:10]
-            Se = pk.S if pk is not None else enc.shape[1]
-            xpack = (pk.dense_offsets(B, S, x.device), pk.off) if pk is not None else None
-            ef = enc.reshape(-1, D).contiguous().float()
-            n1 = _rms(x1, ln1, eps)
-            q1 = _linear(n1, cq)
-            wkv = torch.cat([ck, cv], 0).contiguous()
-            kv = _linear(ef, wkv)
-            c1, lse1 = torch.empty(T, I, **_f32(x.device)), torch.empty(h * T, **_f32(x.device))
-            _attn_fwd(q1, kv[:, :I], kv[:, I:], None, meta["keep"], B, S, Se, h, d, False, p, seeds[2], c1, lse1, pack=xpack)
-            x2 = add_dropout(x1, _linear(c1, co), p, seeds[3])
-            saved += [ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1, x2]
-        else:
-            x2 = x1
+        x2, saved, info = attn_half_fwd(x, enc, meta, params[:-4], seeds)
+        p = info["p"]
         # feed forward: x + dropout(wo(dropout(relu(wi(norm(x))))))
-        n2 = _rms(x2, lnf, eps)
+        n2 = _rms(x2, lnf, meta["eps"])
         pre = _linear(n2, wi)
         act = torch.empty_like(pre)
         ops.bias_act_fwd(pre, meta["zero_bias"], ops.ACTIVATIONS["relu"], act)
@@ -352,8 +401,7 @@ class _BlockFn(torch.autograd.Function):
         x3 = add_dropout(x2, _linear(actd, wff), p, seeds[5])
         saved += [lnf, wi, wff, n2, pre, actd]
         ctx.save_for_backward(*saved, meta["keep"])
-        ctx.meta = dict(meta, p=p, seeds=seeds, shape=(B, S, D), dec=dec, table=params[-1], spack=spack, xpack=xpack if dec else None,
-                        Se=Se if dec else None, enc_shape=enc.shape if dec else None)
+        ctx.meta = dict(meta, table=params[-1], **info)
         return x3.view(x.shape)
 
     @staticmethod
@@ -362,14 +410,12 @@ class _BlockFn(torch.autograd.Function):
         sv = list(ctx.saved_tensors)
         mt = ctx.meta
         B, S, D = mt["shape"]
-        T, h, d, eps, p, seeds, dec, bias = sv[0].shape[0], mt["heads"], mt["d_kv"], mt["eps"], mt["p"], mt["seeds"], mt["dec"], mt["bias"]
+        T, eps, p, seeds, dec = sv[0].shape[0], mt["eps"], mt["p"], mt["seeds"], mt["dec"]
         pk = mt["spack"] is not None                                              # a packed encoder block: T differs in every batch
-        I = h * d
         keep_mask = sv.pop()
-        xf, n0, wqkv, qkv, c0, lse0, wo, x1, ln0 = sv[:9]
         lnf, wi, wff, n2, pre, actd = sv[-6:]
-        x2 = sv[19] if dec else x1
-        dev = xf.device
+        x2 = sv[19] if dec else sv[7]
+        dev = sv[0].device
         dx = dout.reshape(T, D).contiguous().float().clone()                      # the gradient of the residual stream, added to in place
         # feed forward
         df = _dropout_bwd(dx, D, p, seeds[5])
@@ -378,32 +424,8 @@ class _BlockFn(torch.autograd.Function):
         ops.bias_act_bwd(pre, dact, ops.ACTIVATIONS["relu"], dact, torch.empty(_N_PARTIAL, pre.shape[1], **_f32(dev)))
         dn2, dwi = _linear_bwd(dact, n2, wi, packed=pk)
         dlnf = _rms_bwd(x2, lnf, eps, dn2, dx)
-        cross = [None] * 5
-        denc = None
-        if dec:
-            ln1, cq, wkv, co, ef, n1, q1, kv, c1, lse1 = sv[9:19]
-            Se = mt["Se"]
-            da = _dropout_bwd(dx, D, p, seeds[3])
-            dc1, dco = _linear_bwd(da, c1, co)
-            dq1, dkv = torch.empty(T, I, **_f32(dev)), torch.empty(ef.shape[0], 2 * I, **_f32(dev))
-            _attn_bwd(q1, kv[:, :I], kv[:, I:], None, keep_mask, B, S, Se, h, d, False, p, seeds[2], dc1, lse1, dq1,
-                      dkv[:, :I], dkv[:, I:], None, pack=mt["xpack"])
-            dn1, dcq = _linear_bwd(dq1, n1, cq)
-            denc, dwkv = _linear_bwd(dkv, ef, wkv, packed=mt["xpack"] is not None)
-            dln1 = _rms_bwd(x1, ln1, eps, dn1, dx)
-            cross = [dln1, dcq, dwkv[:I], dwkv[I:], dco]
-            denc = denc.view(mt["enc_shape"])
-        # self attention
-        da = _dropout_bwd(dx, D, p, seeds[1])
-        dc0, dwo = _linear_bwd(da, c0, wo, packed=pk)
-        dqkv = torch.empty(T, 3 * I, **_f32(dev))
-        _attn_bwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], bias.rel, None if dec else keep_mask, B, S, S, h, d, dec, p,
-                  seeds[0], dc0, lse0, dqkv[:, :I], dqkv[:, I:2 * I], dqkv[:, 2 * I:], bias.slab(mt["layer"], B), pack=mt["spack"])
-        dn0, dwqkv = _linear_bwd(dqkv, n0, wqkv, packed=pk)
-        dln0 = _rms_bwd(xf, ln0, eps, dn0, dx)
-        dtable = bias.fold(mt["table"].shape[0]) if mt["table"] is not None else None
-        grads = [dln0, dwqkv[:I], dwqkv[I:2 * I], dwqkv[2 * I:], dwo] + (cross if dec else []) + [dlnf, dwi, dwff, dtable]
-        return (dx.view(dout.shape), denc, None, *grads)
+        denc, agrads, dtable = attn_half_bwd(sv[:-6], mt, dx, keep_mask)
+        return (dx.view(dout.shape), denc, None, *agrads, dlnf, dwi, dwff, dtable)
 
 
 class _FinalNormFn(torch.autograd.Function):
@@ -516,6 +538,28 @@ class TIGER(nn.Module):
         if ids.dim() != 2 or ids.shape[1] < 1 or ids.shape[1] > limit:
             raise NotImplementedError(f"TIGER on the HIP path: {what} length in [1, {limit}] (got {tuple(ids.shape)})")
 
+    # the feed-forward layer of a block is the model's own: a model built on this stack (gamer_amd.pbatransformer) overrides these
+    def _route(self, stack, ids):
+        """what the feed-forward layers of a stack call need to know about its ids [B, S] (here: nothing)"""
+        return None
+
+    def _block(self, stack, l, x, enc, meta, attn_params, table, route):
+        ff = stack.block[l].layer[-1]
+        return _BlockFn.apply(x, enc, meta, *attn_params, ff.layer_norm.weight, ff.DenseReluDense.wi.weight, ff.DenseReluDense.wo.weight,
+                              table)
+
+    def _eval_ffn_weights(self, stack, l) -> dict:
+        """the feed-forward weights of decoder block l as _DecoderEval keeps them for a search"""
+        ff = stack.block[l].layer[-1]
+        return dict(lnf=ff.layer_norm.weight.detach(), wi=ff.DenseReluDense.wi.weight.detach(), wff=ff.DenseReluDense.wo.weight.detach())
+
+    def _eval_ffn(self, x, L, route):
+        """x + wo(relu(wi(norm(x)))) on the rows x [N S, D] of a search step; L: the layer's _DecoderEval entry"""
+        pre = _linear(_rms(x, L["lnf"], self.config.layer_norm_epsilon), L["wi"])
+        act = torch.empty_like(pre)
+        ops.bias_act_fwd(pre, self._zero_bias, ops.ACTIVATIONS["relu"], act)
+        return add_dropout(x, _linear(act, L["wff"]), 0.0, 0)
+
     def _stack(self, stack: T5Stack, ids, keep, enc=None, shared=None, pack=None):
         """keep: uint8 [B, Se] over the ENCODER tokens (the encoder's own keys, the decoder's cross-attention keys).  ``pack``
         (PackedRows, keep = None): the encoder runs on the [T] kept tokens of ids [B, S] and returns [T, D]; the decoder takes
@@ -532,6 +576,7 @@ class TIGER(nn.Module):
         blk0 = stack.block[0].layer[0].SelfAttention
         table = blk0.relative_attention_bias.weight
         bias = _BiasStack(table, self._bucket(S, not stack.is_decoder, ids.device), S, len(stack.block))
+        route = self._route(stack, ids)
         for l, blk in enumerate(stack.block):
             meta = dict(heads=c.num_heads, d_kv=c.d_kv, eps=c.layer_norm_epsilon, dropout=c.dropout_rate, training=self.training,
                         bias=bias, keep=keep, layer=l, zero_bias=self._zero_bias, pack=pack)
@@ -542,9 +587,7 @@ class TIGER(nn.Module):
                 x_ = blk.layer[1]
                 e = x_.EncDecAttention
                 params += [x_.layer_norm.weight, e.q.weight, e.k.weight, e.v.weight, e.o.weight]
-            ff = blk.layer[-1]
-            params += [ff.layer_norm.weight, ff.DenseReluDense.wi.weight, ff.DenseReluDense.wo.weight, table if l == 0 else None]
-            x = _BlockFn.apply(x, enc, meta, *params)
+            x = self._block(stack, l, x, enc, meta, params, table if l == 0 else None, route)
         scale = c.d_model ** -0.5 if stack.is_decoder else 1.0
         return _FinalNormFn.apply(x, stack.final_layer_norm.weight, c.layer_norm_epsilon, p, _next_seed(), scale)
 
@@ -639,14 +682,14 @@ class _DecoderEval:
         ef = enc.reshape(-1, c.d_model).contiguous()
         self.layers = []
         with ops.f32_matmul("f32"):
-            for blk in model.decoder.block:
-                a, e, ff = blk.layer[0], blk.layer[1], blk.layer[2]
+            for l, blk in enumerate(model.decoder.block):
+                a, e = blk.layer[0], blk.layer[1]
                 cat = lambda *ws: torch.cat([w.weight.detach() for w in ws], 0).contiguous()
                 self.layers.append(dict(
                     ln0=a.layer_norm.weight.detach(), wqkv=cat(a.SelfAttention.q, a.SelfAttention.k, a.SelfAttention.v),
                     wo=a.SelfAttention.o.weight.detach(), ln1=e.layer_norm.weight.detach(), cq=e.EncDecAttention.q.weight.detach(),
                     kv=_linear(ef, cat(e.EncDecAttention.k, e.EncDecAttention.v)), co=e.EncDecAttention.o.weight.detach(),
-                    lnf=ff.layer_norm.weight.detach(), wi=ff.DenseReluDense.wi.weight.detach(), wff=ff.DenseReluDense.wo.weight.detach()))
+                    **model._eval_ffn_weights(model.decoder, l)))
 
     @ops.scoped_f32_matmul(lambda *a: "f32")
     def last_rows(self, ids: torch.Tensor, kv_rows: torch.Tensor) -> torch.Tensor:
@@ -661,7 +704,7 @@ class _DecoderEval:
         rel = _BiasStack(table, m._bucket(S, False, dev), S, len(self.layers)).rel
         lse = torch.empty(N, h, S, **_f32(dev))
         xpack = (self.pack.dense_offsets(N, S, dev), self.pack.off) if self.pack is not None else None
-        relu = ops.ACTIVATIONS["relu"]
+        route = m._route(m.decoder, ids)
         for L in self.layers:
             qkv = _linear(_rms(x, L["ln0"], eps), L["wqkv"])
             c0 = torch.empty(N * S, I, **_f32(dev))
@@ -672,10 +715,7 @@ class _DecoderEval:
             _attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
                       kv_rows=kv_rows, kv_batch=self.users, pack=xpack)
             x = add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
-            pre = _linear(_rms(x, L["lnf"], eps), L["wi"])
-            act = torch.empty_like(pre)
-            ops.bias_act_fwd(pre, m._zero_bias, relu, act)
-            x = add_dropout(x, _linear(act, L["wff"]), 0.0, 0)
+            x = m._eval_ffn(x, L, route)
         last = x.view(N, S, -1)[:, -1, :].contiguous()
         return _rms(last, m.decoder.final_layer_norm.weight.detach(), eps) * (c.d_model ** -0.5)
 

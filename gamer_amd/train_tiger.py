@@ -172,21 +172,25 @@ def test(model, data, collator, a, dev):
     return {m: totals[m] / max(n, 1) for m in metrics}
 
 
-def run(a, tag, data, collator, test_fn):
+def run(a, tag, data, collator, test_fn, make_model=None):
     """The train-and-test loop of the TIGER commands (train_tiger, train_tiger_smb, train_tiger_mb).  ``data``: ``vocab_size`` and
     ``samples(mode, max_his_len)``; ``collator(samples, index)`` -> input_ids / attention_mask / labels; ``test_fn(model, data,
     collator, a, dev)`` -> (what goes to ``--results_file``, its one-line summary).  ``a.gradient_accumulation_steps`` (where the
     command has the flag) micro-batches share one update, each weighing 1 / steps as HF's Trainer scales them; the last group of an
-    epoch may be shorter."""
+    epoch may be shorter.  ``make_model(a, data)``: another backbone with TIGER's surface (train_pbatransformer), on the CPU with its
+    vocabulary sized; a model with ``check_inputs()`` has it called after every epoch."""
     random.seed(a.seed)
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
     dev = torch.device("cuda")
     os.makedirs(a.output_dir, exist_ok=True)
-    config = tiger.TigerConfig.from_pretrained(a.base_model)
-    model = tiger.TIGER(config)
-    model.set_hyper(a.temperature)
-    model.resize_token_embeddings(data.vocab_size)
+    if make_model is None:
+        config = tiger.TigerConfig.from_pretrained(a.base_model)
+        model = tiger.TIGER(config)
+        model.set_hyper(a.temperature)
+        model.resize_token_embeddings(data.vocab_size)
+    else:
+        model = make_model(a, data)
     model.to(dev)
     ckpt = os.path.join(a.output_dir, "best_model.pth")
     accum = getattr(a, "gradient_accumulation_steps", 1)
@@ -214,6 +218,8 @@ def run(a, tag, data, collator, test_fn):
                 if (n + 1) % accum == 0 or n + 1 == batches_per_epoch:
                     opt.step(schedule.cosine_with_warmup(step, a.learning_rate, warmup, total))
                     step += 1
+            if hasattr(model, "check_inputs"):
+                model.check_inputs()
             ev = eval_loss(model, valid, collator, a.per_device_batch_size, dev, a)
             print(f"[{tag}] epoch {epoch + 1}/{a.epochs} loss {float(torch.stack(losses).mean()):.4f} eval_loss {ev:.4f}", flush=True)
             if ev < best:

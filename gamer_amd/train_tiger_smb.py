@@ -63,12 +63,12 @@ def add_train_flags(ap, model_max_length: int):
     add_pack_rows(ap)
 
 
-def check_train_flags(a, prog: str):
+def check_train_flags(a, prog: str, backbone: str = "TIGER"):
     for name in ("fp16", "bf16", "deepspeed", "resume_from_checkpoint"):
         if getattr(a, name):
             raise NotImplementedError(f"--{name} is not supported by {prog} (fp32, single device, training from the start)")
-    if a.backbone != "TIGER":
-        raise NotImplementedError(f"--backbone {a.backbone}: {prog} trains TIGER")
+    if a.backbone != backbone:
+        raise NotImplementedError(f"--backbone {a.backbone}: {prog} trains {backbone}")
     if a.lr_scheduler_type != "cosine":
         raise NotImplementedError(f"--lr_scheduler_type {a.lr_scheduler_type}: only cosine (gamer_amd/schedule.py)")
     if a.optim not in ("adamw_torch", "adamw"):

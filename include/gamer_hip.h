@@ -726,6 +726,27 @@ int gamer_segment_colsum(const float* x, int64_t ld, int rows, int cols, const i
                          int64_t ws_floats, float* out, void* stream);
 int gamer_inject_table_bwd(const float* seg, const float* Eb, const float* W, int64_t ldw, int col0, int E, int twoI, int NB1, int EB,
                            float* dW, float* dEb, float* scratch, void* stream);
+/* (additive in ABI 9) PBATransformer, the position- and behaviour-aware T5 (ref:SeqRec/models/generative/PBATransformer; csrc/pbat5.hip).
+ *   gamer_pba_router   both routers of router.py as one launch per stack call.  ids int64 [B][S]; expert / beh_idx int32 [B][S];
+ *                      key int32 [B][S] or NULL: expert * nb1 + beh_idx, -1 where expert >= num_experts (no expert owns the position:
+ *                      Moe_behavior_only with behaviour tokens).  decoder = 0: token s has position (s mod P) + 1 (Moe_behavior_only:
+ *                      1 at s mod P = 0 and 2 elsewhere with behaviour tokens, 1 everywhere without) and 0 from n_items * P on;
+ *                      behaviour lut[token at s - s mod P] + 1 for s mod P != 0 and s < (S / P) * P, else 0.  decoder = 1: position
+ *                      [0, 1 .. P, 0][s], behaviour lut[token at 1] + 1 for 2 <= s <= P.  Both 0 at pad / eos.  behavior_lut int32
+ *                      [vocab] on the device (-1: not a behaviour token), NULL allowed without behaviour tokens.  bad_token: the
+ *                      count of positions whose behaviour is used and whose slot token is not mapped (to an index below nb1 - 1) is
+ *                      ADDED to it (never cleared).
+ *   gamer_relu_tbl_fwd act[t][j] = drop(relu(pre[t][j] + tbl[row_group[t]][j])): pre [T][ld] (ld >= I, multiples of 4), act [T][I],
+ *                      tbl [n_groups][I] fp32 with row_group int32 [T], or both NULL (no injection); a row whose group lies outside
+ *                      [0, n_groups) adds nothing.  Dropout mask of element (t, j) <-> flat index t I + j, as gamer_swiglu_fwd_ld.
+ *   gamer_relu_tbl_bwd in place: pre[t][j] <- mask * scale * dact[t][j] * (pre + tbl > 0) (the derivative at 0 is 0).              */
+int gamer_pba_router(const int64_t* ids, int B, int S, int decoder, int num_positions, int n_items, int moe_behavior_only,
+                     int use_behavior_token, const int32_t* behavior_lut, int vocab, int nb1, int num_experts, int pad_id, int eos_id,
+                     int32_t* expert, int32_t* beh_idx, int32_t* key, int32_t* bad_token, void* stream);
+int gamer_relu_tbl_fwd(const float* pre, int64_t ld, int T, int I, float p_drop, uint64_t seed, float* act, const float* tbl,
+                       const int32_t* row_group, int n_groups, void* stream);
+int gamer_relu_tbl_bwd(float* pre, int64_t ld, int T, int I, const float* dact, float p_drop, uint64_t seed, const float* tbl,
+                       const int32_t* row_group, int n_groups, void* stream);
 int gamer_swiglu_fwd_ld_bf16(const gamer_bf16* gu, int64_t ld, int T, int I, float p_drop, uint64_t seed, gamer_bf16* hm,
                              void* stream);
 int gamer_swiglu_bwd_ld_bf16(gamer_bf16* gu, int64_t ld, int T, int I, const gamer_bf16* dhm, float p_drop, uint64_t seed,
