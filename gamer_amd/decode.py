@@ -19,6 +19,11 @@ test_SMB_decoder.py:470-500): the same sequences in the same order and the same 
   Engine.forward).  One reference defect is NOT reproduced: its cross-attention cache lives on the module and is not re-ordered with the beams
   (model.py:569,785,844-860), which perturbs samples whose target row is "empty" (oracle/decode_oracle.py,
   tests/test_decode.py quantify it).
+* ``Engine(dtype="bf16")`` (Qwen3Multi): the search runs in the arithmetic of the ``--bf16`` run - bf16 prompt and generated (self)
+  caches, ``gamer_attn_decode_bf16`` (csrc/decode_bf16.hip), the bf16 twins on the shadow weights, fp32 residual stream and
+  logits.  A row without an allowed key gives 0 in bf16, so none of the three things the fp32 path does for the uniform-average
+  quirk exists there (``uniform_len``, ``uniform``, the generated cross rows and their slot order): cached and re-run path are
+  one computation, ``reorder_cross_cache`` changes nothing (tests/test_decode_bf16_gpu.py).
 """
 from __future__ import annotations
 
@@ -166,6 +171,13 @@ def _graphs_enabled() -> bool:
     return os.environ.get("GAMER_DECODE_GRAPH", "0") == "1"
 
 
+def _check_generation_dtype(engine):
+    """Generation on a bf16 engine is built for the default variant (Qwen3Multi) only."""
+    if engine.dtype != "f32" and engine.variant != "multi":
+        raise NotImplementedError(f"generation on a dtype={engine.dtype!r} engine is built for the default variant (Qwen3Multi), "
+                                  f"not for variant {engine.variant!r}: generate from an fp32 engine of it")
+
+
 def _session_kw(engine, session_ids, extended_session_ids) -> dict:
     """The session ids of a session engine ("session", "qwen3_session") on the device - required there - and {} for the others."""
     if engine.variant not in ("session", "qwen3_session"):
@@ -188,7 +200,7 @@ class DecodeSession:
     hooks ``_eval_forward`` (its prompt pass), ``_row_inputs`` (the step's per-row inputs) and ``_layer_tail`` (a layer after
     its self-attention block) - ``Qwen3DecodeSession`` overrides them for the plain Qwen3 baselines.
     ONE LIVE SESSION PER SHAPE: the sessions of an engine with the same (batch, prompt length, beams, new tokens, model, cross
-    cache order, matmul form) share their buffers (``_DecodeStatic``).  Creating a session takes them over; ``step`` and
+    cache order, matmul form, dtype) share their buffers (``_DecodeStatic``).  Creating a session takes them over; ``step`` and
     ``reorder`` of an older session of that shape then raise RuntimeError instead of attending over the newer one's caches
     (``beam_search`` runs one session at a time)."""
 
@@ -205,15 +217,20 @@ class DecodeSession:
         the self attention and the prompt's last cross-mask row in the cross attention, exactly as for Qwen3Multi
         (Qwen3SessionMulti/model.py:598-613, 716-728), with RoPE positions last extended id + 1, + 2, ...
         (:969-982)."""
+        _check_generation_dtype(engine)
         cfg, dev = engine.cfg, engine.device
         self.eng, self.nb, self.tmax = engine, num_beams, max_new_tokens
-        self.reorder_cross_cache = bool(reorder_cross_cache)
+        # bf16 engine (Qwen3Multi): bf16 caches and step activations on the shadow weights, fp32 residual stream and logits.  A row
+        # without an allowed key gives 0 there (csrc/attention_bf16.hip), so the generated positions' cross K / V - masked for every
+        # other row - are never read: no cross rows are cached and ``reorder_cross_cache`` changes nothing
+        self.bf16 = engine.dtype == "bf16"
+        self.reorder_cross_cache = bool(reorder_cross_cache) and not self.bf16
         self.B, self.L0 = input_ids.shape
         B, L0 = self.B, self.L0
         self.N = N = B * num_beams
         sess = _session_kw(engine, session_ids, extended_session_ids)
         statics = engine.__dict__.setdefault("_decode_static", {})
-        key = (B, L0, num_beams, max_new_tokens, engine.variant, self.reorder_cross_cache, engine.matmul)
+        key = (B, L0, num_beams, max_new_tokens, engine.variant, self.reorder_cross_cache, engine.matmul, engine.dtype)
         st = statics.get(key)
         if st is None:
             if len(statics) >= 4:                     # (a few shapes at most: the buffers of a shape are ~2.5 GB at 256 users)
@@ -286,20 +303,25 @@ class DecodeSession:
             self.pos_last = keep("pos_last", sess["extended_session_ids"].max(dim=1).values.to(torch.int32).repeat_interleave(num_beams))
         self._row_inputs(keep, ids0, am0, act0, sess)
         if st.gen is None:
-            st.gen = {kk: (torch.zeros(N, max_new_tokens, self.NKV, **f32), torch.zeros(N, max_new_tokens, self.NKV, **f32))
-                      for kk in self.kp}
+            # the activations between the fp32 residual stream x and the fp32 logits have the engine's activation dtype; a bf16
+            # session keeps generated rows for the self blocks only
+            act = dict(dtype=engine.act_dtype, device=dev)
+            st.gen = {kk: (torch.zeros(N, max_new_tokens, self.NKV, **act), torch.zeros(N, max_new_tokens, self.NKV, **act))
+                      for kk in self.kp if not (self.bf16 and kk[1] == "cross")}
             H, I = cfg.hidden_size, cfg.intermediate_size
-            st.buf = dict(x=[torch.empty(N, H, **f32) for _ in range(2)], h=torch.empty(N, H, **f32),
-                          qkv=torch.empty(N, QKV, **f32), q=torch.empty(N, self.NQ, **f32), k=torch.empty(N, self.NKV, **f32),
-                          ao=torch.empty(N, self.NQ, **f32), gu=torch.empty(N, 2 * I, **f32), hm=torch.empty(N, I, **f32),
-                          xn=torch.empty(N, H, **f32), logits=torch.empty(N, engine.ws.ldl, **f32),
-                          gen_tmp=torch.empty(N, max(1, max_new_tokens - 1), self.NKV, **f32))
+            st.buf = dict(x=[torch.empty(N, H, **f32) for _ in range(2)], h=torch.empty(N, H, **act),
+                          qkv=torch.empty(N, QKV, **act), q=torch.empty(N, self.NQ, **act), k=torch.empty(N, self.NKV, **act),
+                          ao=torch.empty(N, self.NQ, **act), gu=torch.empty(N, 2 * I, **act), hm=torch.empty(N, I, **act),
+                          xn=torch.empty(N, H, **act), logits=torch.empty(N, engine.ws.ldl, **f32),
+                          gen_tmp=torch.empty(N, max(1, max_new_tokens - 1), self.NKV, **act))
+            if self.bf16:         # the head's bf16 logits (padding columns stay zero), widened into ``logits`` for the beam scores
+                st.buf["logits16"] = torch.zeros(N, engine.ws.ldl, **act)
             if cfg.cross_attention_decoder or cfg.behavior_injection_decoder:
                 # Qwen3Multi's layers: the state after the cross block, its o_proj and gate outputs, and the FFN input widened
                 # by the injected behaviour embedding (without these layers the FFN reads h)
                 st.buf["x"].append(torch.empty(N, H, **f32))
-                st.buf.update(op=torch.empty(N, H, **f32), gate=torch.empty(N, H, **f32),
-                              hin=torch.empty(N, H + cfg.behavior_embedding_dim, **f32))
+                st.buf.update(op=torch.empty(N, H, **act), gate=torch.empty(N, H, **act),
+                              hin=torch.empty(N, H + cfg.behavior_embedding_dim, **act))
             st.small["tok"] = torch.zeros(N, dtype=torch.int64, device=dev)
             st.small["parent"] = torch.arange(N, dtype=torch.int64, device=dev)
         # (stale generated rows of an earlier session are never read: gamer_attn_decode takes the number of valid positions)
@@ -380,7 +402,7 @@ class DecodeSession:
         if g is not None:
             g.replay()
             return self.buf["logits"]
-        if _graphs_enabled() and st.sessions >= 3 and tokens.is_cuda:
+        if _graphs_enabled() and not self.bf16 and st.sessions >= 3 and tokens.is_cuda:      # (a bf16 session always steps eagerly)
             self.eng.rope(self.L0 + self.tmax)          # (cached tables: nothing may be built on the host during the capture)
             if self.eng._amax is not None:
                 self.eng._amax.reserve(512)             # (a fresh slot pool is zero-filled at allocation: not inside the graph)
@@ -424,13 +446,20 @@ class DecodeSession:
         x, x1 = b["x"][:2]
         ops.embedding_fwd(self.st.small["tok"], eng.params["model.embed_tokens.weight"], x)
         # x holds the layer input and receives the layer output; x1 is the state after the self-attention block
+        # (W: norm weights and tables, always the fp32 masters; eng.Wm: what the GEMMs read - the masters, or a bf16 engine's shadow copies)
         for l in range(cfg.num_hidden_layers):
             W = eng.W[l]
             ops.rmsnorm_fwd(x, W.ln1, eps, b["h"])
             self._attend(t, "self", l, W.self_attn)
-            ops.gemm(b["ao"], NQ, 1, W.self_attn["o"], NQ, 1, x1, H, N, H, NQ, resid=x)
+            ops.gemm(b["ao"], NQ, 1, eng.Wm[l].self_attn["o"], NQ, 1, x1, H, N, H, NQ, resid=x)
             self._layer_tail(t, l, W, x, x1)
         ops.rmsnorm_fwd(x, eng.params["model.norm.weight"], eps, b["xn"])
+        if self.bf16:
+            # bf16 logits against the bf16 copy of the tied table, as the scoring forward's head gives them; fp32 for gamer_trie_logprobs
+            lg16 = b["logits16"]
+            ops.linear_fwd(b["xn"], H, eng.shadow.params16["model.embed_tokens.weight"], H, lg16, lg16.stride(0), N, cfg.vocab_size, H)
+            b["logits"].copy_(lg16)
+            return
         ops.linear_fwd(b["xn"], H, eng.params["model.embed_tokens.weight"], H, b["logits"], b["logits"].stride(0), N,
                        cfg.vocab_size, H)
 
@@ -445,6 +474,18 @@ class DecodeSession:
         cos, sin, pos_ids = self._rope
         is_self = kind == "self"
         bias = {} if is_self else dict(bias_q=Wa["bq"], bias_k=Wa["bk"], bias_v=Wa["bv"], act_idx=act_idx)
+        if self.bf16:
+            # the bf16 twins on the shadow weights; only a self block appends its new position, and a cross block - whose generated keys
+            # no row can read - attends the prompt cache alone (gamer_attn_decode_bf16 with gen_ok = 0 never touches kg / vg)
+            Wm = self.eng.Wm[layer]
+            ops.linear_fwd(b["h"], H, (Wm.self_attn if is_self else Wm.cross_attn)["qkv"], H, b["qkv"], QKV, N, QKV, H)
+            ops.qknorm_rope_fwd(b["qkv"], 1, nq, nkv, Wa["qn"], Wa["kn"], eps, cos, sin, b["q"], b["k"], pos_ids=pos_ids, **bias)
+            kg, vg = self.gen[(layer, "self")]
+            if is_self:
+                ops.kv_append_bf16(b["k"], b["qkv"][:, NQ + NKV:], kg, vg, t - 1)
+            ops.attn_decode_bf16(b["q"], self.kp[(layer, kind)], self.vp[(layer, kind)], self.ok_self if is_self else self.ok_cross,
+                                 kg, vg, t, is_self, self.B, self.nb, self.L0, nq, nkv, scale, b["ao"])
+            return
         if self._fuse_qk:
             ops.gemm(b["h"], H, 1, Wa["qkv"], H, 1, b["qkv"], QKV, N, QKV, H,
                      qknorm=dict(wq=Wa["qn"], wk=Wa["kn"], eps=eps, cos=cos, sin=sin, q_rot=b["q"], k_rot=b["k"], pos_ids=pos_ids,
@@ -463,19 +504,20 @@ class DecodeSession:
         the behaviour biases and the output gate, the behaviour injection and the position-routed expert FFN."""
         eng, cfg, b, N = self.eng, self.eng.cfg, self.buf, self.N
         H, I, E, NQ, eps = cfg.hidden_size, cfg.intermediate_size, cfg.num_experts, self.NQ, float(cfg.rms_norm_eps)
+        Wm = eng.Wm[l]                                   # the GEMMs' operands (W itself in fp32)
         xc = x1
         if W.cross:
             xc = b["x"][2]
             ops.rmsnorm_fwd(x1, W.ln2, eps, b["h"])
             self._attend(t, "cross", l, W.cross_attn, self.beh)
-            ops.linear_fwd(b["ao"], NQ, W.cross_attn["o"], NQ, b["op"], H, N, H, NQ)
-            ops.linear_fwd(b["h"], H, W.cross_attn["gate"], H, b["gate"], H, N, H, H)
+            ops.linear_fwd(b["ao"], NQ, Wm.cross_attn["o"], NQ, b["op"], H, N, H, NQ)
+            ops.linear_fwd(b["h"], H, Wm.cross_attn["gate"], H, b["gate"], H, N, H, H)
             ops.silu_gate_fwd(b["op"], b["gate"], xc, resid=x1)
         # the expert of the new tokens' common position (router.py:28-54 table, the same for every row); a dense layer's one MLP
         pos = (self.L0 + t - 1) % cfg.num_positions
         if not (W.sparse and W.gated and not cfg.Moe_behavior_only):
             # the FFN ablation forms (dense layer, PBATransformer experts, behaviour-only routing: semantic tokens have no expert)
-            eng.ffn_rows(W, pos, xc, self.beh if W.inject else None, x)
+            eng.ffn_rows(W, pos, xc, self.beh if W.inject else None, x, Wm)
             return
         hin, din = b.get("hin", b["h"]), W.din
         ops.rmsnorm_fwd(xc, W.ln3, eps, hin, din)
@@ -494,9 +536,9 @@ class DecodeSession:
             ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
             ops.gemm(b["hm"], I, 1, W.down, I, 1, x, H, N, H, I, strideB=H * I, resid=xc, **grp)
             return
-        ops.linear_fwd(hin, din, W.gu[e * 2 * I:(e + 1) * 2 * I], din, b["gu"], 2 * I, N, 2 * I, din)      # gate | up of expert e
+        ops.linear_fwd(hin, din, Wm.gu[e * 2 * I:(e + 1) * 2 * I], din, b["gu"], 2 * I, N, 2 * I, din)      # gate | up of expert e
         ops.swiglu_fwd_ld(b["gu"], 2 * I, N, I, 0.0, 0, b["hm"])
-        ops.gemm(b["hm"], I, 1, W.down[e * H:(e + 1) * H], I, 1, x, H, N, H, I, resid=xc)
+        ops.gemm(b["hm"], I, 1, Wm.down[e * H:(e + 1) * H], I, 1, x, H, N, H, I, resid=xc)
 
 
 class Qwen3DecodeSession(DecodeSession):
@@ -510,8 +552,7 @@ class Qwen3DecodeSession(DecodeSession):
 
     def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int, session_ids=None,
                  extended_session_ids=None):
-        if engine.dtype != "f32":
-            raise NotImplementedError("generation (cached decode) is built for dtype='f32' only")
+        _check_generation_dtype(engine)
         super().__init__(engine, input_ids, attention_mask, None, num_beams, max_new_tokens, session_ids, extended_session_ids)
 
     @staticmethod
@@ -554,8 +595,7 @@ class Qwen3MoeDecodeSession(DecodeSession):
     item's behaviour token)."""
 
     def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int):
-        if engine.dtype != "f32":
-            raise NotImplementedError("generation (cached decode) is built for dtype='f32' only")
+        _check_generation_dtype(engine)
         _check_moe_generation(engine, input_ids.shape[1], max_new_tokens)
         super().__init__(engine, input_ids, attention_mask, None, num_beams, max_new_tokens)
 
@@ -576,14 +616,22 @@ class Qwen3MoeDecodeSession(DecodeSession):
 @torch.no_grad()
 def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, actions: torch.Tensor, trie: ItemTrie,
                 num_beams: int, max_new_tokens: int = 4, use_cache: bool = True, session_ids=None,
-                extended_session_ids=None, reorder_cross_cache: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                extended_session_ids=None, reorder_cross_cache: bool = False, return_trace: bool = False):
     """input_ids / attention_mask / actions: [B, L0] left-padded prompts ending with the target behaviour token
     (``actions`` None for the "qwen3" baseline, which has no behaviour levels).
     Returns (sequences [B*num_beams, L0+max_new_tokens] int64, sequences_scores [B*num_beams] fp32), the beams of
     sample b at rows b*num_beams .., best first - the layout of HF's GenerateBeamOutput.
     ``use_cache=False`` re-runs the whole sequence every step (the cross-check of the cache path; it has no slots, so
     it needs ``reorder_cross_cache=True``).  ``reorder_cross_cache``: see ``DecodeSession`` (False = the reference).
-    ``session_ids`` / ``extended_session_ids`` [B, L0]: required by a "session" engine (see DecodeSession)."""
+    ``session_ids`` / ``extended_session_ids`` [B, L0]: required by a "session" engine (see DecodeSession).
+    ``return_trace=True``: a third value, the list over the steps of (parent [B, nb] int64 - the beam slot each kept candidate
+    continues -, token [B, nb] int64, running_score [B, nb] fp32 - the sum of its log-probs), best first.
+    A ``dtype="bf16"`` engine (Qwen3Multi only) searches in the arithmetic it was trained in: a row without an allowed key gives
+    0 there, so ``reorder_cross_cache`` is accepted and changes nothing, and the cached and the re-run path compute the same."""
+    _check_generation_dtype(engine)
+    bf16 = engine.dtype == "bf16"
+    reorder_cross_cache = reorder_cross_cache or bf16          # (one and the same search in bf16: the re-run path may always run)
+    trace = []
     qwen3 = engine.variant in ("qwen3", "qwen3_session")
     moe = engine.variant == "qwen3moe"          # (no behaviour levels either: no actions, no cross cache)
     if not use_cache and not reorder_cross_cache and not (qwen3 or moe):
@@ -650,11 +698,16 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
                 engine.check_inputs()
             logits2d = engine.ws.logits
             rows = (torch.arange(N, device=dev, dtype=torch.int32) // (nb if step == 0 else 1)) * cur + (cur - 1)
+            if bf16:            # the last rows of the head's bf16 logits, widened for gamer_trie_logprobs
+                logits2d = logits2d.index_select(0, rows.to(torch.int64)).to(torch.float32)
+                rows = torch.arange(N, device=dev, dtype=torch.int32)
         ops.trie_logprobs(logits2d, rows, run_scores.reshape(N).contiguous(), node, trie.child_start, trie.child_tok,
                           V, scores)
         top_s, top_i = torch.topk(scores.view(B, nb * V), K)
         beam_i, tok = top_i // V, top_i % V
         cand = torch.cat([torch.gather(seqs, 1, beam_i[:, :, None].expand(B, K, cur)), tok[:, :, None]], 2)
+        if return_trace:
+            trace.append((beam_i[:, :nb].clone(), tok[:, :nb].clone(), top_s[:, :nb].clone()))
         if step == max_new_tokens - 1:
             final = (cand[:, :nb].reshape(N, cur + 1), (top_s[:, :nb] / max_new_tokens).reshape(N))
             break
@@ -667,4 +720,4 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
         ops.trie_advance(node[parent].contiguous(), tok[:, :nb].reshape(N).contiguous(), trie.child_start,
                          trie.child_tok, trie.child_node, nxt)
         node, nxt = nxt.clone(), nxt
-    return final
+    return final + (trace,) if return_trace else final

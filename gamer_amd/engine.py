@@ -671,7 +671,9 @@ class Engine:
         receives the keys (after k-norm + RoPE) and values of every attention ("self" / "cross") - the K/V cache of
         gamer_amd.decode.DecodeSession; ``last_row_logits``: the prompt pass of a generation needs the logits of the
         last position only (HF's ``logits_to_keep``): final norm and head run on B rows instead of B*S and the
-        returned logits are [B, 1, V].
+        returned logits are [B, 1, V].  A ``dtype="bf16"`` engine of this variant takes ``kv_sink`` (bf16 keys / values),
+        ``last_row_logits`` (bf16 logits of the B rows against the bf16 copy of the tied table, widened to fp32) and
+        ``uniform_len`` (ignored: an empty row gives 0 in bf16 whatever the length) too; ``kv_dest`` stays fp32-only.
 
         ``hidden_sink``: a list that receives copies [B, S, H] of the residual stream at the entry of every decoder layer and of
         the final norm's output - HF's ``output_hidden_states`` tuple (model.py:822-873).  fp32 in both dtypes (the residual
@@ -689,8 +691,7 @@ class Engine:
         c = self._prologue(input_ids, attention_mask, labels, train, dropout, cfg.dropout_rate, kv_dest, hidden_sink,
                            last_row_logits, uniform_len,
                            eval_only="last_row_logits is an evaluation-only option" if last_row_logits else None,
-                           f32_only=("generation (cached decode / re-run scoring) is built for dtype='f32' only"
-                                     if last_row_logits or uniform_len not in (0, S) else None))
+                           f32_only=self._bf16_refusal(kv_dest, last_row_logits or uniform_len not in (0, S)))
         ws, ids, am, bf16 = c.ws, c.ids, c.am, c.bf16
         T, H, nq, nkv, I, E = c.T, c.H, c.nq, c.nkv, c.I, cfg.num_experts
         NQ, NKV, QKV, eps, scale, cos, sin, p_res = c.NQ, c.NKV, c.QKV, c.eps, c.scale, c.cos, c.sin, c.p_res
@@ -830,7 +831,7 @@ class Engine:
                 f32 = dict(dtype=torch.float32, device=self.device)
                 beh = r["beh_idx"].view(-1).index_select(0, rows).contiguous() if W.inject else None
                 x_last = torch.empty(B, H, **f32)
-                self.ffn_rows(W, (S - 1) % cfg.num_positions, xl, beh, x_last)
+                self.ffn_rows(W, (S - 1) % cfg.num_positions, xl, beh, x_last, Wm)
                 break
             xnext = ws.x[l + 1][0] if l + 1 < cfg.num_hidden_layers else ws.x_final
             if not self._shipped_ffn_layer(W):
@@ -894,6 +895,17 @@ class Engine:
             act_zero_col = S - 1
         if act_zero_col is not None:
             r["act_idx"][:, act_zero_col] = 0
+        return None
+
+    def _bf16_refusal(self, kv_dest, generation: bool) -> Optional[str]:
+        """What a bf16 engine of this class refuses (the message; None: nothing): ``kv_dest`` - its session copies the caches
+        through ``kv_sink`` - and, outside the default variant, the generation options (``last_row_logits``, a ``uniform_len``
+        that is not the sequence length).  Qwen3Multi in bf16 accepts them; ``uniform_len`` changes nothing there, since a row
+        without an allowed key gives 0 in bf16 (csrc/attention_bf16.hip)."""
+        if kv_dest is not None:
+            return "kv_dest is built for dtype='f32' only (a bf16 generation copies its caches through kv_sink)"
+        if generation and self.variant != "multi":
+            return f"generation on a dtype='bf16' engine is built for the default variant (Qwen3Multi), not for variant {self.variant!r}"
         return None
 
     def _shipped_ffn_layer(self, W) -> bool:
@@ -963,29 +975,31 @@ class Engine:
         self._norm_bwd(c, xlast, W.ln3, ws.dhin, din, G.ln3, True, slot,
                        branch=None if W.cross else (self._seed(l, 1), None))
 
-    def ffn_rows(self, W, pos: int, x, beh, out):
-        """The FFN of layer W on rows that all sit at item position ``pos`` (fp32, no dropout): out = x + FFN(x) - a
+    def ffn_rows(self, W, pos: int, x, beh, out, Wm=None):
+        """The FFN of layer W on rows that all sit at item position ``pos`` (no dropout): out = x + FFN(x) - a
         generation's prompt pass (its last position) and decode step.  ``beh``: the rows' behaviour indices (injecting
         layers).  A sparse layer runs the position's expert (config.position_experts); behaviour-only routing gives the
-        semantic positions no expert, so out = x there."""
+        semantic positions no expert, so out = x there.  ``Wm``: the layer's GEMM operands when they are not the fp32
+        masters (the bf16 engine's shadow copies: bf16 activations between the fp32 rows x and out, as in its forward)."""
         cfg = self.cfg
+        Wm = W if Wm is None else Wm
         B, H, I, din, nI = x.shape[0], cfg.hidden_size, cfg.intermediate_size, W.din, W.nI
         e = cfg.position_experts()[pos] if W.sparse else 0
         if e >= W.ne:
             out.copy_(x)
             return
-        f32 = dict(dtype=torch.float32, device=self.device)
-        hin = torch.empty(B, din, **f32)
+        act = dict(dtype=Wm.gu.dtype, device=self.device)
+        hin = torch.empty(B, din, **act)
         ops.rmsnorm_fwd(x, W.ln3, float(cfg.rms_norm_eps), hin, din)
         if W.inject:
             ops.rowtable_fwd(W.beh, beh, hin, din, H)
-        gu, hm = torch.empty(B, nI, **f32), torch.empty(B, I, **f32)
-        ops.linear_fwd(hin, din, W.gu[e * nI:(e + 1) * nI], din, gu, nI, B, nI, din)
+        gu, hm = torch.empty(B, nI, **act), torch.empty(B, I, **act)
+        ops.linear_fwd(hin, din, Wm.gu[e * nI:(e + 1) * nI], din, gu, nI, B, nI, din)
         if W.gated:
             ops.swiglu_fwd_ld(gu, nI, B, I, 0.0, 0, hm)
         else:
             ops.silu_fwd_ld(gu, nI, B, I, 0.0, 0, hm)
-        ops.gemm(hm, I, 1, W.down[e * H:(e + 1) * H], I, 1, out, H, B, H, I, resid=x)
+        ops.gemm(hm, I, 1, Wm.down[e * H:(e + 1) * H], I, 1, out, H, B, H, I, resid=x)
 
     def _pass(self, B: int, S: int, p_res: float, p_att: float) -> SimpleNamespace:
         """Shapes, dropout and kernel forms of one forward or backward pass (the context of the shared blocks below)."""
@@ -1110,10 +1124,16 @@ class Engine:
         ws, B, S, H, eps = c.ws, c.B, c.S, c.H, c.eps
         V = self.cfg.vocab_size
         if x_last is not None:
-            xn = torch.empty_like(x_last)
+            xn = torch.empty_like(x_last, dtype=self.act_dtype)
             ops.rmsnorm_fwd(x_last, self.params["model.norm.weight"], eps, xn)
             small = torch.empty(B, ws.ldl, dtype=torch.float32, device=self.device)
-            ops.linear_fwd(xn, H, self.params["model.embed_tokens.weight"], H, small, ws.ldl, B, V, H)
+            if c.bf16:
+                # the head against the bf16 copy of the tied table: bf16 logits as in the scoring forward, widened for the beam scores
+                small16 = torch.zeros(B, ws.ldl, dtype=torch.bfloat16, device=self.device)
+                ops.linear_fwd(xn, H, self.shadow.params16["model.embed_tokens.weight"], H, small16, ws.ldl, B, V, H)
+                small.copy_(small16)
+            else:
+                ops.linear_fwd(xn, H, self.params["model.embed_tokens.weight"], H, small, ws.ldl, B, V, H)
             self._saved = None
             self.last_logits_buf = small               # [B, ldl] (columns >= V are padding), what DecodeSession scores
             return None, small.view(B, 1, ws.ldl)[:, :, :V]

@@ -138,7 +138,8 @@ class Qwen3Engine(Engine):
         c = self._prologue(input_ids, attention_mask, labels, train, dropout, 0.0, kv_dest, hidden_sink, last_row_logits, 0,
                            eval_only=("last_row_logits / rope_from_mask are evaluation-only options"
                                       if last_row_logits or rope_from_mask else None),
-                           f32_only="generation (cached decode) is built for dtype='f32' only" if last_row_logits else None)
+                           f32_only=(f"generation (cached decode) of variant {self.variant!r} is built for dtype='f32' only"
+                                     if last_row_logits else None))
         cfg, ws, m = self.cfg, c.ws, c.ws.mask
         B, S, T, H, I, L, eps = c.B, c.S, c.T, c.H, c.I, cfg.num_hidden_layers, c.eps
         span, pos_ids = ws.self_span = self._self_mask(c, rope_from_mask, session_ids, extended_session_ids)

@@ -1286,8 +1286,26 @@ def attn_decode(q, kp, vp, key_ok, kg, vg, t, gen_ok, uniform, B, nb, L0, nq, nk
          stream_ptr())
 
 
+def kv_append_bf16(k, v, kg, vg, g):
+    """kv_append on bf16 rows (the bf16 engine's generated self cache)."""
+    for name, x in (("k", k), ("v", v), ("kg", kg), ("vg", vg)):
+        _chk(x, torch.bfloat16, name)
+    N, tmax, C = kg.shape
+    call("gamer_kv_append_bf16", ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(kg), ptr(vg), kg.stride(1), tmax, g, N, C, stream_ptr())
+
+
+def attn_decode_bf16(q, kp, vp, key_ok, kg, vg, t, gen_ok, B, nb, L0, nq, nkv, scale, o):
+    """attn_decode on a bf16 cache with the bf16 attention's semantics (gamer_attn_decode_bf16): a row with no allowed key gives
+    zeros - no ``uniform`` -, and with ``gen_ok`` False (a cross block) kg / vg are not read.  q [N, >= nq*64] and o [N, nq*64] bf16."""
+    for name, x in (("q", q), ("kp", kp), ("vp", vp), ("kg", kg), ("vg", vg), ("o", o)):
+        _chk(x, torch.bfloat16, name)
+    _chk(key_ok, torch.int32, "key_ok")
+    call("gamer_attn_decode_bf16", ptr(q), q.stride(0), ptr(kp), kp.stride(0), ptr(vp), vp.stride(0), ptr(key_ok), ptr(kg), ptr(vg),
+         kg.stride(1), kg.shape[1], t, 1 if gen_ok else 0, B, nb, L0, nq, nkv, scale, ptr(o), stream_ptr())
+
+
 # ---- post-LN encoder of the discriminative baselines (SeqRec/modules/layers/transformer.py) --------------------
-ACTIVATIONS = {"none": 0, "relu": 1, "gelu": 2, "swish": 3, "tanh": 4, "sigmoid": 5, "elu": 6}
+ACTIVATIONS ={"none": 0, "relu": 1, "gelu": 2, "swish": 3, "tanh": 4, "sigmoid": 5, "elu": 6}
 
 
 def bias_act_fwd(x, bias, act: int, y=None):

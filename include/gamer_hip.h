@@ -882,6 +882,19 @@ int gamer_attn_decode_split(const float* q, int ldq, const float* kp, int ldkp, 
                             const int32_t* key_ok, const float* kg, const float* vg, int ldg, int tmax, int t, int gen_ok,
                             const int32_t* uniform, int B, int nb, int L0, int nq, int nkv, float scale, float* o,
                             const uint32_t* amax_k, const uint32_t* amax_v, void* stream);
+/* (ABI 9, additive) The cached decode attention of the bf16 engine (csrc/decode_bf16.hip): gamer_attn_decode on a bf16 cache with the
+ * semantics of gamer_attn_fwd_bf16 - a row with no allowed key gives exact zeros, so there is no `uniform` argument, and with
+ * gen_ok = 0 (a cross block) kg / vg are never read.  bf16 q / k / v, fp32 scores and softmax statistics, un-normalised
+ * probabilities rounded to bf16 for the P V product, fp32 accumulation, bf16 o [N, nq*64].  nq / nkv in {1, 2}, nb * nq / nkv <= 64,
+ * 0 <= t <= tmax, any L0 >= 1 with L0 + t <= 11,904 (one softmax reference per 32 keys and row in LDS: probabilities are rounded relative
+ * to what gamer_attn_fwd_bf16 would use for the same keys); every base 16-byte aligned, every leading dim % 8 == 0: checked before anything is launched.  No
+ * atomics: two calls give the same bits.  Reads B * nkv * L0 * 64 * 2 * 2 bytes of prompt cache per call. */
+int gamer_attn_decode_bf16(const gamer_bf16* q, int ldq, const gamer_bf16* kp, int ldkp, const gamer_bf16* vp, int ldvp,
+                           const int32_t* key_ok, const gamer_bf16* kg, const gamer_bf16* vg, int ldg, int tmax, int t, int gen_ok,
+                           int B, int nb, int L0, int nq, int nkv, float scale, gamer_bf16* o, void* stream);
+/* gamer_kv_append on bf16 rows: C and the leading dims % 8 == 0, 16-byte aligned. */
+int gamer_kv_append_bf16(const gamer_bf16* k, int ldk, const gamer_bf16* v, int ldv, gamer_bf16* kg, gamer_bf16* vg, int ldg, int tmax,
+                         int g, int N, int C, void* stream);
 
 /* (ABI 9) Catalogue-wide head of the discriminative baselines (csrc/catalog.hip; SASRec's CE loss and full-sort ranking,
  * ref:SeqRec/modules/model_base/seq_model.py:67-122).  h rows r = 0..R-1 are h + row_idx[r] * ldh (row_idx int32 when idx64 == 0,
