@@ -124,6 +124,16 @@ static inline int grid_for_waves(int64_t n_waves, int max_blocks = EW_MAX_BLOCKS
     if (blocks > max_blocks) blocks = max_blocks;
     return (int)blocks;
 }
+// ... and of a kernel whose threads stride over theirs
+#ifndef EW_MAX_BLOCKS_T
+#define EW_MAX_BLOCKS_T 16384
+#endif
+static inline int grid_for_threads(int64_t n, int max_blocks = EW_MAX_BLOCKS_T) {
+    int64_t blocks = (n + EW_THREADS - 1) / EW_THREADS;
+    if (blocks < 1) blocks = 1;
+    if (blocks > max_blocks) blocks = max_blocks;
+    return (int)blocks;
+}
 
 // rows of a behaviour table (the table-row kernels of elementwise.hip, the bias rows of qknorm_rope.hip): num_behavior + 1 <= 8
 constexpr int TBL_MAXROWS = 8;
@@ -400,6 +410,38 @@ __device__ __forceinline__ float silu_f(float x) { return x * sigmoid_f(x); }
 __device__ __forceinline__ float dsilu_f(float x) {
     const float s = sigmoid_f(x);
     return s * (1.f + x * (1.f - s));
+}
+
+// The feed-forward activation rules, each stated once per element: ffn_act.hip's walks and the SwiGLU epilogues of the GEMMs apply
+// the same functions, which is what keeps a fused epilogue and the stand-alone kernels bit-identical.  NIN = inputs read per element
+// (a rule of one input ignores b and has no bwd_b), m = the element's dropout multiplier, d = m * (gradient of the output);
+// bwd_a / bwd_b = the gradient of the first / second input.
+struct SwigluRule {
+    static constexpr int NIN = 2;
+    static __device__ __forceinline__ float fwd(float a, float b, float m) { return m * (silu_f(a) * b); }
+    static __device__ __forceinline__ float bwd_a(float a, float b, float d) { return d * b * dsilu_f(a); }
+    static __device__ __forceinline__ float bwd_b(float a, float, float d) { return d * silu_f(a); }
+};
+struct SiluRule {
+    static constexpr int NIN = 1;
+    static __device__ __forceinline__ float fwd(float a, float, float m) { return m * silu_f(a); }
+    static __device__ __forceinline__ float bwd_a(float a, float, float d) { return d * dsilu_f(a); }
+};
+struct ReluRule {
+    static constexpr int NIN = 1;
+    static __device__ __forceinline__ float fwd(float a, float, float m) { return a > 0.f ? m * a : 0.f; }
+    static __device__ __forceinline__ float bwd_a(float a, float, float d) { return a > 0.f ? d : 0.f; }
+};
+// a rule on the four elements of a quad (db is written by a rule of two inputs only)
+template <class R>
+__device__ __forceinline__ float4 act_fwd4(const float4 a, const float4 b, const float (&m)[4]) {
+    return make_float4(R::fwd(a.x, b.x, m[0]), R::fwd(a.y, b.y, m[1]), R::fwd(a.z, b.z, m[2]), R::fwd(a.w, b.w, m[3]));
+}
+template <class R>
+__device__ __forceinline__ void act_bwd4(const float4 a, const float4 b, const float4 dout, const float (&m)[4], float4& da, float4& db) {
+    const float d0 = m[0] * dout.x, d1 = m[1] * dout.y, d2 = m[2] * dout.z, d3 = m[3] * dout.w;
+    da = make_float4(R::bwd_a(a.x, b.x, d0), R::bwd_a(a.y, b.y, d1), R::bwd_a(a.z, b.z, d2), R::bwd_a(a.w, b.w, d3));
+    if constexpr (R::NIN == 2) db = make_float4(R::bwd_b(a.x, b.x, d0), R::bwd_b(a.y, b.y, d1), R::bwd_b(a.z, b.z, d2), R::bwd_b(a.w, b.w, d3));
 }
 
 // (gemm_as.hip) the activation-stationary Linear forward of gamer_gemm_f32_split(terms = 3): eligibility of a descriptor, launch

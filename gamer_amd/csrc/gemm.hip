@@ -1120,12 +1120,13 @@ gemm_f32_tile(const GemmParams& p, float* __restrict__ smem_all, const int vbloc
                 b.x += tb_u.x; b.y += tb_u.y; b.z += tb_u.z; b.w += tb_u.w;
                 float m[4];
                 rng.mult4((uint32_t)(((int64_t)row * p.N + col) >> 2), m);
+                // (the rule element by element, dg and du in turn: act_bwd4's order, all of dg first, schedules this kernel differently)
                 const float d0 = m[0] * v.x, d1 = m[1] * v.y, d2 = m[2] * v.z, d3 = m[3] * v.w;
                 float4 dg, du;
-                dg.x = d0 * b.x * dsilu_f(a.x); du.x = d0 * silu_f(a.x);
-                dg.y = d1 * b.y * dsilu_f(a.y); du.y = d1 * silu_f(a.y);
-                dg.z = d2 * b.z * dsilu_f(a.z); du.z = d2 * silu_f(a.z);
-                dg.w = d3 * b.w * dsilu_f(a.w); du.w = d3 * silu_f(a.w);
+                dg.x = SwigluRule::bwd_a(a.x, b.x, d0); du.x = SwigluRule::bwd_b(a.x, b.x, d0);
+                dg.y = SwigluRule::bwd_a(a.y, b.y, d1); du.y = SwigluRule::bwd_b(a.y, b.y, d1);
+                dg.z = SwigluRule::bwd_a(a.z, b.z, d2); du.z = SwigluRule::bwd_b(a.z, b.z, d2);
+                dg.w = SwigluRule::bwd_a(a.w, b.w, d3); du.w = SwigluRule::bwd_b(a.w, b.w, d3);
                 *reinterpret_cast<float4*>(ga) = dg;
                 *reinterpret_cast<float4*>(ua) = du;
                 if (amax_on) {
@@ -1210,7 +1211,7 @@ gemm_f32_tile(const GemmParams& p, float* __restrict__ smem_all, const int vbloc
                 float m[4];
                 rng.mult4((uint32_t)(e >> 2), m);
                 const float d = m[e & 3] * v;
-                const float dg = d * b * dsilu_f(a), du = d * silu_f(a);
+                const float dg = SwigluRule::bwd_a(a, b, d), du = SwigluRule::bwd_b(a, b, d);
                 ga[0] = dg; ga[p.N] = du;
                 if (GAMER_GEMM_CAMAX_BUILD && p.amax_c != nullptr) emax = fmaxf(emax, fmaxf(fabsf(dg), fabsf(du)));
                 return;

@@ -336,10 +336,8 @@ gemm_as_kernel(const AsParams p) {
                                 const DropoutRng rng(p.p_drop, p.seed);
                                 float mu[4];
                                 rng.mult4((uint32_t)(((int64_t)m * p.N + col) >> 2), mu);
-                                const float d0 = mu[0] * t4.x, d1 = mu[1] * t4.y, d2 = mu[2] * t4.z, d3 = mu[3] * t4.w;
-                                const float4 dg = make_float4(d0 * b4.x * dsilu_f(a4.x), d1 * b4.y * dsilu_f(a4.y), d2 * b4.z * dsilu_f(a4.z),
-                                                              d3 * b4.w * dsilu_f(a4.w));
-                                const float4 du = make_float4(d0 * silu_f(a4.x), d1 * silu_f(a4.y), d2 * silu_f(a4.z), d3 * silu_f(a4.w));
+                                float4 dg, du;
+                                act_bwd4<SwigluRule>(a4, b4, t4, mu, dg, du);
                                 *reinterpret_cast<float4*>(ga) = dg;
                                 *reinterpret_cast<float4*>(ga + p.N) = du;
                                 emax = fmaxf(fmaxf(fmaxf(emax, fmaxf(fabsf(dg.x), fabsf(du.x))), fmaxf(fabsf(dg.y), fabsf(du.y))),
@@ -375,8 +373,7 @@ gemm_as_kernel(const AsParams p) {
                                     const DropoutRng rng(p.p_drop, p.seed);
                                     float mu[4];
                                     rng.mult4((uint32_t)(((int64_t)m * half + hc) >> 2), mu);
-                                    const float4 o = make_float4(mu[0] * (silu_f(g.x) * x4.x), mu[1] * (silu_f(g.y) * x4.y),
-                                                                 mu[2] * (silu_f(g.z) * x4.z), mu[3] * (silu_f(g.w) * x4.w));
+                                    const float4 o = act_fwd4<SwigluRule>(g, x4, mu);
                                     *reinterpret_cast<float4*>(p.hm + (int64_t)m * half + hc) = o;
                                     emax = fmaxf(fmaxf(fmaxf(emax, fabsf(o.x)), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)));
                                 }

@@ -331,8 +331,8 @@ __device__ __forceinline__ void hb_epilogue(const GemmBf16Params& p, f32x16 (&ac
                             for (int e = 0; e < 8; ++e) {
                                 const float d = m[e] * round_as<bf16_t>(v[e]);       // (d(hm) is a bf16 tensor in the unfused path)
                                 const float a = (float)a8[e], b = (float)b8[e];
-                                dg[e] = d * b * dsilu_f(a);
-                                du[e] = d * silu_f(a);
+                                dg[e] = SwigluRule::bwd_a(a, b, d);
+                                du[e] = SwigluRule::bwd_b(a, b, d);
                             }
                             *reinterpret_cast<bf16x8*>(ga) = __builtin_convertvector(dg, bf16x8);
                             *reinterpret_cast<bf16x8*>(ga + p.N) = __builtin_convertvector(du, bf16x8);
@@ -355,8 +355,8 @@ __device__ __forceinline__ void hb_epilogue(const GemmBf16Params& p, f32x16 (&ac
                                 float m[4];
                                 rng.mult4((uint32_t)(e >> 2), m);
                                 const float d = m[e & 3] * round_as<bf16_t>(acc[i][j][r]);
-                                ga[0] = (bf16_t)(d * b * dsilu_f(a));
-                                ga[p.N] = (bf16_t)(d * silu_f(a));
+                                ga[0] = (bf16_t)SwigluRule::bwd_a(a, b, d);
+                                ga[p.N] = (bf16_t)SwigluRule::bwd_b(a, b, d);
                             }
                         }
                 }

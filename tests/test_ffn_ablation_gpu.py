@@ -118,7 +118,13 @@ def test_ablation_bf16_against_reference_autocast_fixture():
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_silu_kernels_against_fp64_and_the_swiglu_dropout_mask(dtype):
-    T, I, ld, p, seed = 300, 192, 200, 0.25, 1234
+    # (5, 260, 520): 65 quads per row, a second trip of the lane loop with one lane
+    for T, I, ld in ((300, 192, 200), (5, 260, 520)):
+        _silu_kernels_case(T, I, ld, dtype)
+
+
+def _silu_kernels_case(T, I, ld, dtype):
+    p, seed = 0.25, 1234
     g = torch.Generator().manual_seed(5)
     h = (torch.randn(T, ld, generator=g) * 3).to(dtype)
     dhm = torch.randn(T, I, generator=g).to(dtype)
@@ -141,7 +147,7 @@ def test_silu_kernels_against_fp64_and_the_swiglu_dropout_mask(dtype):
     ops.silu_fwd_ld(hg, ld, T, I, p, seed, hm)
     assert torch.equal(hm.cpu(), hm_sw.cpu())
     kept = hm.cpu().double() != 0
-    assert abs(float(kept.double().mean()) - (1 - p)) < 0.02
+    assert abs(float(kept.double().mean()) - (1 - p)) < max(0.02, 4 * (p * (1 - p) / (T * I)) ** 0.5)    # (four sigma of T * I draws)
     ops.silu_bwd_ld(hg, ld, T, I, dhm.to(DEV), p, seed)
     ref = torch.where(kept, ref / (1 - p), torch.zeros_like(ref))
     assert float((hg[:, :I].cpu().double() - ref).abs().max()) < tol * float(ref.abs().max())

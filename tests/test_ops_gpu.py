@@ -898,12 +898,44 @@ def test_elementwise_dropout_family():
     assert float((z2.cpu() != mask).float().mean()) > 0.2
 
 
+def _swiglu_flat_against_fp64(n, dtype):
+    """The contiguous pair alone on n elements, against fp64 under the kernel's own mask (an all-positive input, same seed).
+    Tolerances: fp32 1e-5 of the largest value (__expf, a 1-ulp reciprocal and three products: under ten ulps of an element,
+    an element at most the largest); bf16 1e-2 (one rounding of the output, 2^-9, on top of that)."""
+    p, seed = 0.2, 11
+    gen = torch.Generator(device=DEV).manual_seed(n)
+    g, u, dhm = (torch.randn(n, generator=gen, device=DEV).to(dtype) for _ in range(3))
+    two, raw = torch.full((n,), 2.0, dtype=dtype, device=DEV), torch.full((n,), float("nan"), dtype=dtype, device=DEV)
+    ops.swiglu_fwd(two, two, n, p, seed, raw)
+    kept = raw > 0
+    assert bool(((raw == 0) | kept).all()) and float(raw[kept].max()) == float(raw[kept].min())     # (no NaN left: all written)
+    assert abs(float(kept.double().mean()) - (1 - p)) < 0.01
+    mult = kept.double() * float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+    gd, ud, dd = g.double(), u.double(), dhm.double()
+    s = torch.sigmoid(gd)
+    tol = 1e-5 if dtype == torch.float32 else 1e-2
+    hm = torch.full((n,), float("nan"), dtype=dtype, device=DEV)
+    ops.swiglu_fwd(g, u, n, p, seed, hm)
+    want = mult * gd * s * ud
+    assert float((hm.double() - want).abs().max()) < tol * float(want.abs().max())
+    ops.swiglu_bwd(g, u, dhm, n, p, seed)
+    want_g, want_u = mult * dd * ud * (s * (1 + gd * (1 - s))), mult * dd * gd * s
+    assert float((g.double() - want_g).abs().max()) < tol * float(want_g.abs().max())
+    assert float((u.double() - want_u).abs().max()) < tol * float(want_u.abs().max())
+    for t in (hm, g, u):                                     # the last quads (the second trip) among them
+        assert bool((t[-12:] != 0).any())
+
+
+# (32773 rows: more than the 4 * 8192 waves of the row kernels' largest grid, a second trip of the row loop; ld None: the contiguous
+# pair alone on 16384 * 256 + 3 quads, more than the 16384 blocks of the flat kernels' largest grid hold - a second trip of theirs)
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("rows,I,ld", [(300, 512, 1024), (37, 96, 200), (1, 4, 8)])
+@pytest.mark.parametrize("rows,I,ld", [(300, 512, 1024), (37, 96, 200), (1, 4, 8), (32773, 4, 8), (16384 * 256 + 3, 4, None)])
 def test_swiglu_on_the_fused_gate_up_buffer_equals_the_contiguous_kernels(rows, I, ld, dtype):
     """gamer_swiglu_fwd_ld / _bwd_ld read gate and up from the column halves of one [T, ld] buffer (the output of the fused
     gate|up projection): bit-identical values and dropout masks to gamer_swiglu_fwd / _bwd on two contiguous arrays, padding
     columns (ld > 2 I) untouched; with the maxima sink armed, the whole-gradient maximum of the backward lands in one slot."""
+    if ld is None:
+        return _swiglu_flat_against_fp64(rows * I, dtype)
     p, seed = 0.2, 11
     gen = torch.Generator().manual_seed(rows)
     g = torch.randn(rows, I, generator=gen).to(dtype)

@@ -167,12 +167,36 @@ def bench_elem(args):
     print(f"rmsnorm_bwd {t:.3f} ms  {4 * T * H * 4 / t / 1e6:.0f} GB/s")
     t = timeit(lambda: ops.residual_dropout_fwd(x, y, 0.2, 3, None, dx), args.iters)
     print(f"residual_dropout_fwd {t:.3f} ms  {3 * T * H * 4 / t / 1e6:.0f} GB/s")
-    g, u, hm = torch.randn(T, I, device=dev), torch.randn(T, I, device=dev), torch.empty(T, I, device=dev)
-    t = timeit(lambda: ops.swiglu_fwd(g, u, T * I, 0.2, 3, hm), args.iters)
-    print(f"swiglu_fwd {t:.3f} ms  {3 * T * I * 4 / t / 1e6:.0f} GB/s")
-    t = timeit(lambda: ops.swiglu_bwd(g, u, hm, T * I, 0.2, 3), args.iters)
-    print(f"swiglu_bwd {t:.3f} ms  {5 * T * I * 4 / t / 1e6:.0f} GB/s")
+    bench_ffn_act(args, T, I)
     bench_qknorm(args, T, S)
+
+
+def bench_ffn_act(args, T, I, groups=8):
+    """the FFN activation kernels (csrc/ffn_act.hip), forward and in-place backward: the contiguous SwiGLU pair, the row forms on the
+    fused gate|up buffer (ld = 2 I) and on a non-gated wi output (ld = I), with and without a table row per row group"""
+    dev = "cuda"
+    group = torch.randint(0, groups, (T,), device=dev, dtype=torch.int32)
+
+    def line(name, t, passes, es):
+        print(f"{name} {t:.3f} ms  {passes * T * I * es / t / 1e6:.0f} GB/s")
+
+    for dt, sfx in ((torch.float32, ""), (torch.bfloat16, "_bf16")):
+        es = 4 if dt == torch.float32 else 2
+        g, u, hm = (torch.randn(T, I, device=dev).to(dt) for _ in range(3))
+        gu = torch.randn(T, 2 * I, device=dev).to(dt)
+        line(f"swiglu_fwd{sfx}", timeit(lambda: ops.swiglu_fwd(g, u, T * I, args.p, 3, hm), args.iters), 3, es)
+        line(f"swiglu_bwd{sfx}", timeit(lambda: ops.swiglu_bwd(g, u, hm, T * I, args.p, 3), args.iters), 5, es)
+        line(f"swiglu_fwd_ld{sfx}", timeit(lambda: ops.swiglu_fwd_ld(gu, 2 * I, T, I, args.p, 3, hm), args.iters), 3, es)
+        line(f"swiglu_bwd_ld{sfx}", timeit(lambda: ops.swiglu_bwd_ld(gu, 2 * I, T, I, hm, args.p, 3), args.iters), 5, es)
+        line(f"silu_fwd_ld{sfx}", timeit(lambda: ops.silu_fwd_ld(g, I, T, I, args.p, 3, hm), args.iters), 2, es)
+        line(f"silu_bwd_ld{sfx}", timeit(lambda: ops.silu_bwd_ld(g, I, T, I, hm, args.p, 3), args.iters), 3, es)
+    g, hm, gu = torch.randn(T, I, device=dev), torch.randn(T, I, device=dev), torch.randn(T, 2 * I, device=dev)
+    tbl2, tbl1 = torch.randn(groups, 2 * I, device=dev), torch.randn(groups, I, device=dev)
+    line("swiglu_fwd_ld_tbl", timeit(lambda: ops.swiglu_fwd_ld_tbl(gu, 2 * I, T, I, args.p, 3, hm, tbl2, group), args.iters), 3, 4)
+    line("swiglu_bwd_ld_tbl", timeit(lambda: ops.swiglu_bwd_ld_tbl(gu, 2 * I, T, I, hm, args.p, 3, tbl2, group), args.iters), 5, 4)
+    for name, kw in (("relu_tbl", dict(tbl=tbl1, row_group=group, n_groups=groups)), ("relu", {})):
+        line(f"{name}_fwd", timeit(lambda: ops.relu_tbl_fwd(g, I, T, I, args.p, 3, hm, **kw), args.iters), 2, 4)
+        line(f"{name}_bwd", timeit(lambda: ops.relu_tbl_bwd(g, I, T, I, hm, args.p, 3, **kw), args.iters), 3, 4)
 
 
 def bench_qknorm(args, T, S, nq=6, nkv=3, nb1=4):
