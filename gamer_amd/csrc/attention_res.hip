@@ -58,9 +58,12 @@ constexpr int RES_THREADS = 512;
 constexpr int RIMG = RB_KEYS * 64;           // 16-bit elements of one piece image of a block ([256][64], swizzled like a tile image)
 constexpr int RES_MAX_TILES = 64;            // 32-query row tiles per head the kernels are built for (S <= 2048)
 
+constexpr int QIMG = 4 * SIMG;               // 16-bit elements of one piece image of four key tiles (16 KB)
+enum { RES_K = 0, RES_V = 2 };               // first image of K / of V within a half; its second piece is the next image
 struct ResSmem {
-    bf16_t K[2][RIMG];
-    bf16_t V[2][RIMG];
+    // [half: key tiles 0-3 / 4-7][K piece 0, K piece 1, V piece 0, V piece 1][tile of the half][32 x 64, swizzled like a tile image].
+    // A half is 64 KB: from a pointer into one image of a tile, the tile's other three images are within reach of a ds immediate.
+    bf16_t img[2][4][QIMG];
     int32_t kl[RB_KEYS];                     // key levels (INT_MAX past the end of the sequence)
     uint32_t kw[RB_KEYS];                    // dropout key words
     int32_t klmax[RB_TILES];                 // largest key level per 32-key tile
@@ -68,6 +71,43 @@ struct ResSmem {
     int32_t ctr;                             // the block's row-tile queue: next item (waves take items with an LDS atomic)
     int32_t pad_[6];
     int32_t ntot[2 * RES_MAX_TILES];         // key tiles every (head of the pair, row tile) needs, written by the block-0 pass
+};
+static_assert(sizeof(ResSmem) <= 160 * 1024, "one workgroup per CU: the resident block and its metadata fit the CU's LDS");
+static_assert(offsetof(ResSmem, img) % 16 == 0 && (QIMG * sizeof(bf16_t)) % 16 == 0 && offsetof(ResSmem, kl) % 16 == 0 &&
+              offsetof(ResSmem, kw) % 16 == 0, "16-byte reads of the images and the key words");
+static_assert(4 * QIMG * sizeof(bf16_t) <= 65536, "every image of a tile is reached by an immediate from a pointer into its half");
+// The per-lane LDS pointers of a row tile's key loop (attention_split_common.h: lds_next), at tile 0 of the resident block; next(tl)
+// moves them from tile tl to the next one.  One pointer per distinct lane offset: a tile's other images and its second half of rows
+// are immediates (row(s, image), tr(s2, db, image)).
+struct ResKeyPtrs {
+    lds_img_p pr[4];           // image 0 + lo.row[s]
+    lds_img_p pt[2][2];        // image 0 + lo.tr[c][db]
+    lds_i32_p kq;              // kl + 4 h; the dropout key words lie KW further on
+    static constexpr int KW = (offsetof(ResSmem, kw) - offsetof(ResSmem, kl)) / 4;
+    __device__ __forceinline__ ResKeyPtrs(const ResSmem& sm, const SlOffsets& lo, int h) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) pr[s] = (lds_img_p)sm.img[0][0] + lo.row[s];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int db = 0; db < 2; ++db) pt[c][db] = (lds_img_p)sm.img[0][0] + lo.tr[c][db];
+        kq = (lds_i32_p)sm.kl + 4 * h;
+    }
+    __device__ __forceinline__ void next(int tl) {
+        const int step = tl == 3 ? 4 * QIMG - 3 * SIMG : SIMG;          // (tile 3 -> 4: on to the second half)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) lds_next(pr[s], step);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int db = 0; db < 2; ++db) lds_next(pt[c][db], step);
+        lds_next(kq, 32);
+    }
+    // row read of k-step s (read_row8) / transposing read of rows 16 s2 .. + 15, columns 32 db .. + 31 (read_tr8) of the tile's image
+    __device__ __forceinline__ bf16x8 row(int s, int image) const { return lds_row8(pr[s] + image * QIMG); }
+    __device__ __forceinline__ bf16x8 tr(int s2, int db, int image) const {
+        return lds_tr8(pt[0][db] + 16 * s2 * 64 + image * QIMG, pt[1][db] + 16 * s2 * 64 + image * QIMG);
+    }
 };
 // the row tile a wave will process after the current one: its q rows (and row data) are requested into the L2 while the current
 // tile is multiplied - a row tile's prologue is otherwise two dependent HBM round trips with nothing to overlap them
@@ -101,14 +141,14 @@ __device__ __forceinline__ void res_stage_block(ResSmem& sm, const float* __rest
         const int f = tid + RES_THREADS * p;
         const int row = f >> 4;
         const bool ok = j0 + row < S;
-        const int off = sl_off(row, (f & 15) << 2);
+        bf16_t* dst = sm.img[row >> 7][0] + sl_off(row & 127, (f & 15) << 2);
         uint32_t a0, a1, b0, b1;
         cut2h_quad(ok ? rk[p].x : 0.f, ok ? rk[p].y : 0.f, ok ? rk[p].z : 0.f, ok ? rk[p].w : 0.f, sc.k, a0, a1, b0, b1);
-        *reinterpret_cast<uint2*>(sm.K[0] + off) = make_uint2(a0, b0);
-        *reinterpret_cast<uint2*>(sm.K[1] + off) = make_uint2(a1, b1);
+        *reinterpret_cast<uint2*>(dst + RES_K * QIMG) = make_uint2(a0, b0);
+        *reinterpret_cast<uint2*>(dst + (RES_K + 1) * QIMG) = make_uint2(a1, b1);
         cut2h_quad(ok ? rv[p].x : 0.f, ok ? rv[p].y : 0.f, ok ? rv[p].z : 0.f, ok ? rv[p].w : 0.f, sc.v, a0, a1, b0, b1);
-        *reinterpret_cast<uint2*>(sm.V[0] + off) = make_uint2(a0, b0);
-        *reinterpret_cast<uint2*>(sm.V[1] + off) = make_uint2(a1, b1);
+        *reinterpret_cast<uint2*>(dst + RES_V * QIMG) = make_uint2(a0, b0);
+        *reinterpret_cast<uint2*>(dst + (RES_V + 1) * QIMG) = make_uint2(a1, b1);
     }
     if (tid < RB_KEYS) {
         const int v = klv;
@@ -123,17 +163,15 @@ __device__ __forceinline__ void res_stage_block(ResSmem& sm, const float* __rest
 }
 
 // st += K(tile) q^T: 4 k-steps x 3 piece products; the fragments of k-step s + 1 are requested before the products of k-step s
-__device__ __forceinline__ f32x16 res_qk_tile(const ResSmem& sm, int tl, const SlOffsets& lo, const bf16x8 (&qf)[2][4], f32x16 st) {
-    const bf16_t* k0 = sm.K[0] + tl * SIMG;
-    const bf16_t* k1 = sm.K[1] + tl * SIMG;
+__device__ __forceinline__ f32x16 res_qk_tile(const ResKeyPtrs& kp, const bf16x8 (&qf)[2][4], f32x16 st) {
     bf16x8 kf[2][2];
-    kf[0][0] = *reinterpret_cast<const bf16x8*>(k0 + lo.row[0]);
-    kf[0][1] = *reinterpret_cast<const bf16x8*>(k1 + lo.row[0]);
+    kf[0][0] = kp.row(0, RES_K);
+    kf[0][1] = kp.row(0, RES_K + 1);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         if (s + 1 < 4) {
-            kf[(s + 1) & 1][0] = *reinterpret_cast<const bf16x8*>(k0 + lo.row[s + 1]);
-            kf[(s + 1) & 1][1] = *reinterpret_cast<const bf16x8*>(k1 + lo.row[s + 1]);
+            kf[(s + 1) & 1][0] = kp.row(s + 1, RES_K);
+            kf[(s + 1) & 1][1] = kp.row(s + 1, RES_K + 1);
         }
         __builtin_amdgcn_sched_barrier(0);
         // smallest piece products first: (k1 q0), (k0 q1), (k0 q0)
@@ -263,53 +301,56 @@ res_fwd_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const int32_t
     RES_MARK(1);                                           // 1: row-tile prologue (row data, q load + cut, carried state)
 
     uint32_t tq = 0, tm = 0;                               // (destinations of the next tile's L2 warm-up loads: never read)
+    // The key loop, once for a row tile of "empty" rows only and once for every other: which of the two a wave runs does not change
+    // inside the loop, and with both kinds of tile in one loop the accumulators of the second product had to stay apart from their own
+    // inputs across the other kind's code (32 register copies per trip).
+    auto key_loop = [&]<bool ALL_EMPTY>() {
+        ResKeyPtrs kp(sm, lo, h);
 #pragma unroll 1
-    for (int jt = jt_lo; jt < jt_hi; ++jt) {
-        const int j0 = jt * 32, tl = jt - jt_lo;
-        if (RES_TOUCH_Q && jt == jt_lo && nx.valid) {
-            // one 128-byte line per lane: lane (r, h) takes half h of row r of the next tile's q rows; its row data by lane half
-            const int64_t ntok = (int64_t)b * S + (ORD ? nx.perm : min(nx.t * 32 + r, S - 1));
-            tq = *reinterpret_cast<const uint32_t*>(q + ntok * ldq + nx.head * 64 + 32 * h);
-            tm = *reinterpret_cast<const uint32_t*>(((h == 1 && ql) ? ql : row_empty) + ntok);
-        }
-        const bool beyond = j0 > wave_q_hi;                // every key of the tile is in every normal row's future
-        if (beyond && !wave_has_empty) continue;
-        f32x16 st;
-        if (!wave_all_empty && !beyond) {
-            const float init = -m_ref * (sc.q * sc.k);     // (the products carry the operands' scales)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) st[i] = init;
-            st = res_qk_tile(sm, tl, lo, qf, st);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) st[i] *= sc.inv_qk;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) st[i] = 0.f;      // (beyond: the mask below blocks every normal row)
-        }
-        const bf16_t* v0 = sm.V[0] + tl * SIMG;
-        const bf16_t* v1 = sm.V[1] + tl * SIMG;
-        const int32_t* klt = sm.kl + tl * 32;
-        const int32_t* kwt = reinterpret_cast<const int32_t*>(sm.kw) + tl * 32;
-        // O^T[d][query] += sum_key V[key][d] * P[query][key]   (rows of V past the sequence end are zero)
-        auto pv_tile = [&]<bool ONE_PIECE>() {
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                bf16x8 pf[3];
-                cut8_regs_t<true>(st, 8 * s2, H2Scales::P, pf);
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    bf16x8 vf[3];
-                    vf[0] = read_tr8(v0, lo, 16 * s2, db);
-                    vf[1] = read_tr8(v1, lo, 16 * s2, db);
-                    vf[2] = vf[1];
-                    oacc[db] = mfma_pieces<true, ONE_PIECE>(vf, pf, oacc[db]);
-                }
+        for (int jt = jt_lo; jt < jt_hi; kp.next(jt - jt_lo), ++jt) {
+            const int j0 = jt * 32, tl = jt - jt_lo;
+            if (RES_TOUCH_Q && jt == jt_lo && nx.valid) {
+                // one 128-byte line per lane: lane (r, h) takes half h of row r of the next tile's q rows; its row data by lane half
+                const int64_t ntok = (int64_t)b * S + (ORD ? nx.perm : min(nx.t * 32 + r, S - 1));
+                tq = *reinterpret_cast<const uint32_t*>(q + ntok * ldq + nx.head * 64 + 32 * h);
+                tm = *reinterpret_cast<const uint32_t*>(((h == 1 && ql) ? ql : row_empty) + ntok);
             }
-        };
-        auto softmax_tile = [&]<bool MASK, bool EMPTYSEL>() {
-            if (MASK) {
+            const bool beyond = j0 > wave_q_hi;                // every key of the tile is in every normal row's future
+            if (beyond && !wave_has_empty) continue;
+            f32x16 st;
+            if (!ALL_EMPTY && !beyond) {
+                const float init = -m_ref * (sc.q * sc.k);     // (the products carry the operands' scales)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) st[i] = init;
+                st = res_qk_tile(kp, qf, st);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) st[i] *= sc.inv_qk;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) st[i] = 0.f;      // (beyond: the mask below blocks every normal row)
+            }
+            // O^T[d][query] += sum_key V[key][d] * P[query][key]   (rows of V past the sequence end are zero)
+            auto pv_tile = [&]<bool ONE_PIECE>() {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    bf16x8 pf[3];
+                    cut8_regs_t<true>(st, 8 * s2, H2Scales::P, pf);
+#pragma unroll
+                    for (int db = 0; db < 2; ++db) {
+                        bf16x8 vf[3];
+                        vf[0] = kp.tr(s2, db, RES_V);
+                        vf[1] = kp.tr(s2, db, RES_V + 1);
+                        vf[2] = vf[1];
+                        oacc[db] = mfma_pieces<true, ONE_PIECE>(vf, pf, oacc[db]);
+                    }
+                }
+            };
+            // The softmax of the tile in stages, each one piece of code for every kind of tile: only the first and the third differ between
+            // kinds, and neither touches the output accumulators - so these stay in one place across the whole trip (written per kind, with
+            // the rescale and the second product inside each, the compiler moved all 32 of them between the variants' register sets).
+            auto mask_tile = [&]() {
                 int klv[16];
-                read_key_quads(klt, h, klv);
+                lds_quads(kp.kq, klv);
                 const int t_pos = sp.hi - j0 - 4 * h;        // key (reg&3)+8*(reg>>2) of the tile is <= hi (= iq without spans)
                 const int t_lo = sp.hole_lo - j0 - 4 * h, t_hi = sp.hole_hi - j0 - 4 * h;
 #pragma unroll
@@ -319,63 +360,67 @@ res_fwd_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const int32_t
                     if (SPAN) allowed = allowed & !((ko >= t_lo) & (ko < t_hi));
                     st[reg] = allowed ? st[reg] : -INFINITY;
                 }
-            }
-            float mloc = st[0];
+            };
+            auto exp_tile = [&]<bool EMPTYSEL>() {
+                float rowsum = 0.f;
 #pragma unroll
-            for (int reg = 1; reg < 16; ++reg) mloc = fmaxf(mloc, st[reg]);
-            mloc = xor32_max(mloc);
-            // (P is cut into fp16 pieces of P * 2^13 - it must stay below 2^3, so the reference follows the maximum closely)
-            bool need = (l_run == 0.f) ? (mloc > -INFINITY) : (mloc > 2.f);
-            if (EMPTYSEL) need = need && !my_empty;
-            if (__any(need ? 1 : 0)) {
-                const float d = need ? mloc : 0.f;
-                const float alpha = (l_run == 0.f) ? 1.f : __builtin_amdgcn_exp2f(-d);
-                m_ref += d;
-                l_run *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { oacc[0][i] *= alpha; oacc[1][i] *= alpha; st[i] -= d; }
-            }
-            float rowsum = 0.f;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                float pe = __builtin_amdgcn_exp2f(st[reg]);            // masked -> exp2(-inf) = 0
-                if (EMPTYSEL) pe = my_empty ? 1.f : pe;
-                rowsum += pe;
-                st[reg] = pe;
-            }
-            rowsum = xor32_sum(rowsum);
-            l_run += rowsum;
-            if (DROP) {
+                for (int reg = 0; reg < 16; ++reg) {
+                    float pe = __builtin_amdgcn_exp2f(st[reg]);            // masked -> exp2(-inf) = 0
+                    if (EMPTYSEL) pe = my_empty ? 1.f : pe;
+                    rowsum += pe;
+                    st[reg] = pe;
+                }
+                rowsum = xor32_sum(rowsum);
+                l_run += rowsum;
+            };
+            if constexpr (ALL_EMPTY) {
+                // every row of the wave is an empty row: P = keep, no scores, no softmax state
                 int kwv[16];
-                read_key_quads(kwt, h, kwv);
+                if (DROP) lds_quads(kp.kq + kp.KW, kwv);
 #pragma unroll
-                for (int reg = 0; reg < 16; ++reg) st[reg] = rng.keep(aw, (uint32_t)kwv[reg]) ? st[reg] : 0.f;
-            }
-            pv_tile.template operator()<false>();
-        };
-        if (wave_all_empty) {
-            // every row of the wave is an empty row: P = keep, no scores, no softmax state
-            int kwv[16];
-            if (DROP) read_key_quads(kwt, h, kwv);
+                for (int reg = 0; reg < 16; ++reg) {
+                    const bool on = DROP ? rng.keep(aw, (uint32_t)kwv[reg]) : true;
+                    st[reg] = on ? 1.f : 0.f;
+                }
+            } else {
+                bool free_tile = false;
+                if (!wave_has_empty) {
+                    const int klmax = __builtin_amdgcn_readfirstlane(sm.klmax[tl]);
+                    free_tile = (j0 + 31 <= wave_q_lo) && (klmax < wave_ql_min) && (!SPAN || j0 + 31 < wave_hole_lo || j0 >= wave_hole_hi);
+                }
+                if (!free_tile) mask_tile();
+                float mloc = st[0];
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const bool on = DROP ? rng.keep(aw, (uint32_t)kwv[reg]) : true;
-                st[reg] = on ? 1.f : 0.f;
+                for (int reg = 1; reg < 16; ++reg) mloc = fmaxf(mloc, st[reg]);
+                mloc = xor32_max(mloc);
+                // (P is cut into fp16 pieces of P * 2^13 - it must stay below 2^3, so the reference follows the maximum closely)
+                bool need = (l_run == 0.f) ? (mloc > -INFINITY) : (mloc > 2.f);
+                need = need && !my_empty;                      // (only a tile with "empty" rows has a lane where this matters)
+                if (__any(need ? 1 : 0)) {
+                    const float d = need ? mloc : 0.f;
+                    const float alpha = (l_run == 0.f) ? 1.f : __builtin_amdgcn_exp2f(-d);
+                    m_ref += d;
+                    l_run *= alpha;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) { oacc[0][i] *= alpha; oacc[1][i] *= alpha; st[i] -= d; }
+                }
+                if (wave_has_empty) exp_tile.template operator()<true>();
+                else exp_tile.template operator()<false>();
+                if (DROP) {
+                    int kwv[16];
+                    lds_quads(kp.kq + kp.KW, kwv);
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) st[reg] = rng.keep(aw, (uint32_t)kwv[reg]) ? st[reg] : 0.f;
+                }
             }
-            pv_tile.template operator()<true>();
-        } else if (wave_has_empty) {
-            softmax_tile.template operator()<true, true>();
-        } else {
-            const int klmax = __builtin_amdgcn_readfirstlane(sm.klmax[tl]);
-            const bool free_tile = (j0 + 31 <= wave_q_lo) && (klmax < wave_ql_min) &&
-                                   (!SPAN || j0 + 31 < wave_hole_lo || j0 >= wave_hole_hi);
-            if (free_tile) softmax_tile.template operator()<false, false>();
-            else softmax_tile.template operator()<true, false>();
-        }
+            pv_tile.template operator()<ALL_EMPTY>();
 #if RES_STAMP
-        ph_[6] += 1;                                       // 6: key tiles
+            ph_[6] += 1;                                       // 6: key tiles
 #endif
-    }
+        }
+    };
+    if (wave_all_empty) key_loop.template operator()<true>();
+    else key_loop.template operator()<false>();
     RES_MARK(2);                                           // 2: key loop
 
     if (last) {
@@ -658,17 +703,12 @@ res_dq_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const float* _
             }
     }
 
+    ResKeyPtrs kp(sm, lo, h);
 #pragma unroll 1
-    for (int jt = jt_lo; jt < jt_hi; ++jt) {
+    for (int jt = jt_lo; jt < jt_hi; kp.next(jt - jt_lo), ++jt) {
         const int j0 = jt * 32, tl = jt - jt_lo;
         const bool beyond = j0 > wave_q_hi;
         if (beyond && !wave_has_empty) continue;
-        const bf16_t* k0 = sm.K[0] + tl * SIMG;
-        const bf16_t* k1 = sm.K[1] + tl * SIMG;
-        const bf16_t* v0 = sm.V[0] + tl * SIMG;
-        const bf16_t* v1 = sm.V[1] + tl * SIMG;
-        const int32_t* klt = sm.kl + tl * 32;
-        const int32_t* kwt = reinterpret_cast<const int32_t*>(sm.kw) + tl * 32;
         f32x16 st, dp;
         const float st0 = !beyond ? neg_lse2 * (sc.q * sc.k) : neg_lse2;   // (the products carry the operands' scales)
 #pragma unroll
@@ -676,13 +716,13 @@ res_dq_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const float* _
         // dP^T[key][query] = sum_d V[key][d] dO[query][d]
         {
             bf16x8 vf[2][2];
-            vf[0][0] = *reinterpret_cast<const bf16x8*>(v0 + lo.row[0]);
-            vf[0][1] = *reinterpret_cast<const bf16x8*>(v1 + lo.row[0]);
+            vf[0][0] = kp.row(0, RES_V);
+            vf[0][1] = kp.row(0, RES_V + 1);
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 if (s + 1 < 4) {
-                    vf[(s + 1) & 1][0] = *reinterpret_cast<const bf16x8*>(v0 + lo.row[s + 1]);
-                    vf[(s + 1) & 1][1] = *reinterpret_cast<const bf16x8*>(v1 + lo.row[s + 1]);
+                    vf[(s + 1) & 1][0] = kp.row(s + 1, RES_V);
+                    vf[(s + 1) & 1][1] = kp.row(s + 1, RES_V + 1);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 dp = mfma_piece<true>(vf[s & 1][1], dof[0][s], dp);
@@ -691,7 +731,7 @@ res_dq_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const float* _
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (!beyond && !wave_all_empty) st = res_qk_tile(sm, tl, lo, qf, st);
+        if (!beyond && !wave_all_empty) st = res_qk_tile(kp, qf, st);
         {
             const float cdp = sc.inv_v * my_inv_do;
 #pragma unroll
@@ -705,7 +745,7 @@ res_dq_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const float* _
         // u = mult * dP - delta  (mult = keep / (1 - p))
         if (DROP) {
             int kwv[16];
-            read_key_quads(kwt, h, kwv);
+            lds_quads(kp.kq + kp.KW, kwv);
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const float tt = rng.keep(aw, (uint32_t)kwv[reg]) ? dp[reg] : 0.f;
@@ -719,7 +759,7 @@ res_dq_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const float* _
         auto ds_tile = [&]<bool MASK, bool EMPTYSEL>() {
             if (MASK) {
                 int klv[16];
-                read_key_quads(klt, h, klv);
+                lds_quads(kp.kq, klv);
                 const int t_pos = sp.hi - j0 - 4 * h;
                 const int t_lo = sp.hole_lo - j0 - 4 * h, t_hi = sp.hole_hi - j0 - 4 * h;
 #pragma unroll
@@ -757,8 +797,8 @@ res_dq_rowtile(ResSmem& sm, const float* __restrict__ q, int ldq, const float* _
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 bf16x8 kf[3];
-                kf[0] = read_tr8(k0, lo, 16 * s2, db);
-                kf[1] = read_tr8(k1, lo, 16 * s2, db);
+                kf[0] = kp.tr(s2, db, RES_K);
+                kf[1] = kp.tr(s2, db, RES_K + 1);
                 kf[2] = kf[1];
                 dqacc[db] = mfma_pieces<true>(kf, df, dqacc[db]);
             }
@@ -1203,10 +1243,13 @@ attn_bwd_dkv_r_kernel(const float* __restrict__ q, int ldq, const float* __restr
 // =============================================================================================
 constexpr int QB2 = 128;                      // query slots of one resident block
 constexpr int QB2_TILES = QB2 / 32;
-constexpr int QIMG2 = QB2 * 64;               // 16-bit elements of one piece image of one head
+constexpr int PIMG2 = 2 * SIMG;               // 16-bit elements of one piece image of a pair of query tiles (8 KB)
+enum { R2_DO = 0, R2_Q = 2 };                 // first image of dO / of Q within a head; its second piece is the next image
 struct DkvR2Smem {
-    bf16_t Q[2][2][QIMG2];                    // head x piece
-    bf16_t dO[2][2][QIMG2];
+    // [pair of query tiles: 0-1 / 2-3][head][dO piece 0, dO piece 1, Q piece 0, Q piece 1][tile of the pair][32 x 64, swizzled like a tile
+    // image].  A pair is 64 KB: from a pointer into one image of a tile, the tile's other seven images (both heads) are within reach of a
+    // ds immediate (Dkv2Ptrs).
+    bf16_t img[2][2][4][PIMG2];
     float nlse2[2][QB2];
     float ndelta[2][QB2];
     uint32_t aw[2][QB2];
@@ -1288,17 +1331,60 @@ res2_stage_queries(DkvR2Smem& sm, const float* __restrict__ q, int ldq, const fl
             const int f = tid + DKV_R_THREADS * p;
             const int row = f >> 4;
             const bool ok = s0 + row < S;
-            const int off = sl_off(row, (f & 15) << 2);
+            bf16_t* dst = sm.img[row >> 6][g][0] + sl_off(row & 63, (f & 15) << 2);
             uint32_t a0, a1, b0, b1;
             cut2h_quad(ok ? rq[g][p].x : 0.f, ok ? rq[g][p].y : 0.f, ok ? rq[g][p].z : 0.f, ok ? rq[g][p].w : 0.f, sc.q, a0, a1, b0, b1);
-            *reinterpret_cast<uint2*>(sm.Q[g][0] + off) = make_uint2(a0, b0);
-            *reinterpret_cast<uint2*>(sm.Q[g][1] + off) = make_uint2(a1, b1);
+            *reinterpret_cast<uint2*>(dst + R2_Q * PIMG2) = make_uint2(a0, b0);
+            *reinterpret_cast<uint2*>(dst + (R2_Q + 1) * PIMG2) = make_uint2(a1, b1);
             cut2h_quad(ok ? rd[g][p].x : 0.f, ok ? rd[g][p].y : 0.f, ok ? rd[g][p].z : 0.f, ok ? rd[g][p].w : 0.f, sc.d_o, a0, a1, b0, b1);
-            *reinterpret_cast<uint2*>(sm.dO[g][0] + off) = make_uint2(a0, b0);
-            *reinterpret_cast<uint2*>(sm.dO[g][1] + off) = make_uint2(a1, b1);
+            *reinterpret_cast<uint2*>(dst + R2_DO * PIMG2) = make_uint2(a0, b0);
+            *reinterpret_cast<uint2*>(dst + (R2_DO + 1) * PIMG2) = make_uint2(a1, b1);
         }
     }
 }
+
+static_assert(sizeof(DkvR2Smem) <= 160 * 1024, "one workgroup per CU: the resident query block and its metadata fit the CU's LDS");
+static_assert(offsetof(DkvR2Smem, img) % 16 == 0 && (PIMG2 * sizeof(bf16_t)) % 16 == 0 && offsetof(DkvR2Smem, nlse2) % 16 == 0 &&
+              offsetof(DkvR2Smem, ndelta) % 16 == 0 && offsetof(DkvR2Smem, aw) % 16 == 0 && offsetof(DkvR2Smem, ql) % 16 == 0 &&
+              offsetof(DkvR2Smem, empty) % 16 == 0 && offsetof(DkvR2Smem, pos) % 16 == 0 && offsetof(DkvR2Smem, hole_lo) % 16 == 0 &&
+              offsetof(DkvR2Smem, hole_hi) % 16 == 0, "16-byte reads of the images and the per-row words");
+static_assert(8 * PIMG2 * sizeof(bf16_t) <= 65536, "every image of a tile is reached by an immediate from a pointer into its pair");
+// The per-lane LDS pointers of a key tile's query-tile loop (attention_split_common.h: lds_next), at query tile qt; next(qt) moves them
+// from tile qt to the next one.  One pointer per distinct lane offset: head, image and row group of a read are immediates, and so is
+// the array of a per-row word (word<FIELD>(g, g4): the four words of rows 8 g4 + 4 h .. + 3 of the tile).
+struct Dkv2Ptrs {
+    lds_img_p pr[4];           // image 0 of head 0 + lo.row[s]
+    lds_img_p pt[2][2];        // image 0 of head 0 + lo.tr[c][db]
+    lds_i32_p pw;              // nlse2[0] + 4 h
+    __device__ __forceinline__ Dkv2Ptrs(const DkvR2Smem& sm, const SlOffsets& lo, int h, int qt) {
+        const int t0 = (qt >> 1) * 8 * PIMG2 + (qt & 1) * SIMG;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) pr[s] = (lds_img_p)sm.img[0][0][0] + (lo.row[s] + t0);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int db = 0; db < 2; ++db) pt[c][db] = (lds_img_p)sm.img[0][0][0] + (lo.tr[c][db] + t0);
+        pw = (lds_i32_p)sm.nlse2[0] + (4 * h + 32 * qt);
+    }
+    __device__ __forceinline__ void next(int qt) {
+        const int step = qt == 1 ? 8 * PIMG2 - SIMG : SIMG;             // (tile 1 -> 2: on to the second pair)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) lds_next(pr[s], step);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int db = 0; db < 2; ++db) lds_next(pt[c][db], step);
+        lds_next(pw, 32);
+    }
+    __device__ __forceinline__ bf16x8 row(int s, int g, int image) const { return lds_row8(pr[s] + (4 * g + image) * PIMG2); }
+    __device__ __forceinline__ bf16x8 tr(int s2, int db, int g, int image) const {
+        return lds_tr8(pt[0][db] + 16 * s2 * 64 + (4 * g + image) * PIMG2, pt[1][db] + 16 * s2 * 64 + (4 * g + image) * PIMG2);
+    }
+    template <size_t FIELD>
+    __device__ __forceinline__ i32x4v word(int g, int g4) const {
+        return *reinterpret_cast<const i32x4v GAMER_LDS*>(pw + ((int)(FIELD - offsetof(DkvR2Smem, nlse2)) / 4 + g * QB2 + 8 * g4));
+    }
+};
 
 // classes of a query tile (the same for both heads: they share the rows)
 enum { QT_FREE = 0, QT_MASK = 1, QT_EMPTYSEL = 2, QT_ALL_EMPTY = 3 };
@@ -1424,18 +1510,18 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
 
     // ---- the pieces of a tile's work ------------------------------------------------------------------------------------------
     // F, k-step s of head g / tile qt: the row fragments of dO and Q (A operands)
-    auto f_reads = [&](int g, int qt, int s, bf16x8 (&a)[4]) {
-        a[0] = *reinterpret_cast<const bf16x8*>(sm.dO[g][0] + qt * SIMG + lo.row[s]);
-        a[1] = *reinterpret_cast<const bf16x8*>(sm.dO[g][1] + qt * SIMG + lo.row[s]);
-        a[2] = *reinterpret_cast<const bf16x8*>(sm.Q[g][0] + qt * SIMG + lo.row[s]);
-        a[3] = *reinterpret_cast<const bf16x8*>(sm.Q[g][1] + qt * SIMG + lo.row[s]);
+    auto f_reads = [&](const Dkv2Ptrs& qp, int g, int s, bf16x8 (&a)[4]) {
+        a[0] = qp.row(s, g, R2_DO);
+        a[1] = qp.row(s, g, R2_DO + 1);
+        a[2] = qp.row(s, g, R2_Q);
+        a[3] = qp.row(s, g, R2_Q + 1);
     };
     // S, group (s2, db) of head g / tile qt: dV^T += dO^T P, dK^T += Q^T dS (transposing reads of the resident images)
-    auto s_reads = [&](int g, int qt, int s2, int db, bf16x8 (&a)[4]) {
-        a[0] = read_tr8(sm.dO[g][0] + qt * SIMG, lo, 16 * s2, db);
-        a[1] = read_tr8(sm.dO[g][1] + qt * SIMG, lo, 16 * s2, db);
-        a[2] = read_tr8(sm.Q[g][0] + qt * SIMG, lo, 16 * s2, db);
-        a[3] = read_tr8(sm.Q[g][1] + qt * SIMG, lo, 16 * s2, db);
+    auto s_reads = [&](const Dkv2Ptrs& qp, int g, int s2, int db, bf16x8 (&a)[4]) {
+        a[0] = qp.tr(s2, db, g, R2_DO);
+        a[1] = qp.tr(s2, db, g, R2_DO + 1);
+        a[2] = qp.tr(s2, db, g, R2_Q);
+        a[3] = qp.tr(s2, db, g, R2_Q + 1);
     };
     auto e_cut = [&](int s2, const f32x16& st, const f32x16& dp, bf16x8 (&pf)[2][2], bf16x8 (&df)[2][2]) {
         bf16x8 t3[3];
@@ -1465,38 +1551,37 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
     };
     // E, registers 4 g4 .. 4 g4 + 3 of head g / tile qt (query = register, key = lane):  P -> st (1 / (1 - p) applied at the end), dS -> dp
     // Rows past the end of the sequence have Q = dO = 0, lse = delta = 0: p = 1 but dS = 0 and dO = 0.
-    auto e_chunk = [&]<int CLS>(int g, int qt, int g4, f32x16& st, f32x16& dp) {
+    auto e_chunk = [&]<int CLS>(const Dkv2Ptrs& qp, int g, int g4, f32x16& st, f32x16& dp) {
         constexpr bool MASK = CLS == QT_MASK || CLS == QT_EMPTYSEL, EMPTYSEL = CLS == QT_EMPTYSEL, ALL_EMPTY = CLS == QT_ALL_EMPTY;
-        const int qb = qt * 32 + 8 * g4 + 4 * h;
-        const float4 d4 = *reinterpret_cast<const float4*>(&sm.ndelta[g][qb]);
-        const float ndl[4] = {d4.x, d4.y, d4.z, d4.w};
+        const i32x4v d4 = qp.word<offsetof(DkvR2Smem, ndelta)>(g, g4);
+        const float ndl[4] = {__int_as_float(d4[0]), __int_as_float(d4[1]), __int_as_float(d4[2]), __int_as_float(d4[3])};
         float nl[4] = {0.f, 0.f, 0.f, 0.f};
         int qlv[4] = {0, 0, 0, 0}, posv[4] = {0, 0, 0, 0}, emv[4] = {0, 0, 0, 0};
         uint32_t awv[4] = {0, 0, 0, 0};
         if (!ALL_EMPTY) {
-            const float4 l4 = *reinterpret_cast<const float4*>(&sm.nlse2[g][qb]);
-            nl[0] = l4.x; nl[1] = l4.y; nl[2] = l4.z; nl[3] = l4.w;
+            const i32x4v l4 = qp.word<offsetof(DkvR2Smem, nlse2)>(g, g4);
+            nl[0] = __int_as_float(l4[0]); nl[1] = __int_as_float(l4[1]); nl[2] = __int_as_float(l4[2]); nl[3] = __int_as_float(l4[3]);
         }
         int hlo[4] = {0, 0, 0, 0}, hhi[4] = {0, 0, 0, 0};
         if (MASK) {
-            const int4 q4 = *reinterpret_cast<const int4*>(&sm.ql[qb]);
-            const int4 p4 = *reinterpret_cast<const int4*>(&sm.pos[qb]);
-            qlv[0] = q4.x; qlv[1] = q4.y; qlv[2] = q4.z; qlv[3] = q4.w;
-            posv[0] = p4.x; posv[1] = p4.y; posv[2] = p4.z; posv[3] = p4.w;
+            const i32x4v q4 = qp.word<offsetof(DkvR2Smem, ql)>(0, g4);
+            const i32x4v p4 = qp.word<offsetof(DkvR2Smem, pos)>(0, g4);
+            qlv[0] = q4[0]; qlv[1] = q4[1]; qlv[2] = q4[2]; qlv[3] = q4[3];
+            posv[0] = p4[0]; posv[1] = p4[1]; posv[2] = p4[2]; posv[3] = p4[3];
             if (SPAN) {
-                const int4 a4 = *reinterpret_cast<const int4*>(&sm.hole_lo[qb]);
-                const int4 b4 = *reinterpret_cast<const int4*>(&sm.hole_hi[qb]);
-                hlo[0] = a4.x; hlo[1] = a4.y; hlo[2] = a4.z; hlo[3] = a4.w;
-                hhi[0] = b4.x; hhi[1] = b4.y; hhi[2] = b4.z; hhi[3] = b4.w;
+                const i32x4v a4 = qp.word<offsetof(DkvR2Smem, hole_lo)>(0, g4);
+                const i32x4v b4 = qp.word<offsetof(DkvR2Smem, hole_hi)>(0, g4);
+                hlo[0] = a4[0]; hlo[1] = a4[1]; hlo[2] = a4[2]; hlo[3] = a4[3];
+                hhi[0] = b4[0]; hhi[1] = b4[1]; hhi[2] = b4[2]; hhi[3] = b4[3];
             }
         }
         if (EMPTYSEL) {
-            const int4 e4 = *reinterpret_cast<const int4*>(&sm.empty[qb]);
-            emv[0] = e4.x; emv[1] = e4.y; emv[2] = e4.z; emv[3] = e4.w;
+            const i32x4v e4 = qp.word<offsetof(DkvR2Smem, empty)>(0, g4);
+            emv[0] = e4[0]; emv[1] = e4[1]; emv[2] = e4[2]; emv[3] = e4[3];
         }
         if (DROP) {
-            const uint4 a4 = *reinterpret_cast<const uint4*>(&sm.aw[g][qb]);
-            awv[0] = a4.x; awv[1] = a4.y; awv[2] = a4.z; awv[3] = a4.w;
+            const i32x4v a4 = qp.word<offsetof(DkvR2Smem, aw)>(g, g4);
+            awv[0] = (uint32_t)a4[0]; awv[1] = (uint32_t)a4[1]; awv[2] = (uint32_t)a4[2]; awv[3] = (uint32_t)a4[3];
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -1529,8 +1614,9 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
     while (q_first < n_qt && sm.t_maxpos[q_first] < wave_k_lo && sm.t_empty[q_first] == 0) ++q_first;
     q_first = __builtin_amdgcn_readfirstlane(q_first);
 
+    Dkv2Ptrs qp(sm, lo, h, q_first);
 #pragma unroll 1
-    for (int qt = q_first; qt < n_qt; ++qt) {
+    for (int qt = q_first; qt < n_qt; qp.next(qt), ++qt) {
         const bool tile_has_empty = __builtin_amdgcn_readfirstlane(sm.t_empty[qt]) != 0;
         const int posmin = __builtin_amdgcn_readfirstlane(sm.t_posmin[qt]);
         const int qlmin = __builtin_amdgcn_readfirstlane(sm.t_qlmin[qt]);
@@ -1554,7 +1640,7 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
         {
             bf16x8 a[4][4];
 #pragma unroll
-            for (int s = 0; s < 4; ++s) f_reads(0, qt, s, a[s]);
+            for (int s = 0; s < 4; ++s) f_reads(qp, 0, s, a[s]);
             if (need_s) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) f_step.template operator()<true>(a[s], s, stA, dpA);
@@ -1567,11 +1653,11 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
         auto slot2 = [&]<int CLS, bool NEED_S>() {
             bf16x8 a[4][4];
 #pragma unroll
-            for (int s = 0; s < 4; ++s) f_reads(1, qt, s, a[s]);
+            for (int s = 0; s < 4; ++s) f_reads(qp, 1, s, a[s]);
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 f_step.template operator()<NEED_S>(a[s], s, stB, dpB);
-                e_chunk.template operator()<CLS>(0, qt, s, stA, dpA);
+                e_chunk.template operator()<CLS>(qp, 0, s, stA, dpA);
                 if (s & 1) e_cut(s >> 1, stA, dpA, pfA, dfA);
             }
         };
@@ -1579,11 +1665,11 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
         auto slot3 = [&]<int CLS>() {
             bf16x8 a[4][4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) s_reads(0, qt, i >> 1, i & 1, a[i]);
+            for (int i = 0; i < 4; ++i) s_reads(qp, 0, i >> 1, i & 1, a[i]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 s_step(a[i], pfA, dfA, i >> 1, i & 1);
-                e_chunk.template operator()<CLS>(1, qt, i, stB, dpB);
+                e_chunk.template operator()<CLS>(qp, 1, i, stB, dpB);
                 if (i & 1) e_cut(i >> 1, stB, dpB, pfB, dfB);
             }
         };
@@ -1597,7 +1683,7 @@ res2_dkv_step(DkvR2Smem& sm, const float* __restrict__ k, int ldk, const float* 
         {
             bf16x8 a[4][4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) s_reads(1, qt, i >> 1, i & 1, a[i]);
+            for (int i = 0; i < 4; ++i) s_reads(qp, 1, i >> 1, i & 1, a[i]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) s_step(a[i], pfB, dfB, i >> 1, i & 1);
         }

@@ -45,6 +45,34 @@ __device__ __forceinline__ bf16x8 read_tr8(const bf16_t* __restrict__ img, const
     return out;
 }
 
+// ---- per-lane LDS pointers of the resident kernels' tile loops (attention_res.hip) ---------------------------------
+// A ds instruction takes one address register and a 16-bit immediate.  The resident images span 128 KB, so a fragment read written
+// as `image + tile * SIMG + lane offset` costs an integer add per read once its constant passes 64 KB.  The tile loops carry
+// these pointers instead: one per distinct lane offset and 64 KB window, set up once per row (key) tile, advanced by one tile per loop
+// trip (lds_next) and otherwise only used with compile-time offsets, which become the immediates.  lds_next hides the pointer from the
+// compiler behind an empty asm statement: it cannot re-derive one pointer from another plus a (large) constant.
+#define GAMER_LDS __attribute__((address_space(3)))
+typedef const bf16_t GAMER_LDS* lds_img_p;           // into a 16-bit piece image
+typedef const int32_t GAMER_LDS* lds_i32_p;          // into an array of per-row / per-key words
+typedef int32_t i32x4v __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ __forceinline__ void lds_next(T GAMER_LDS*& p, int elems) { p += elems; asm volatile("" : "+v"(p)); }
+// row read / transposing read through such pointers (read_row8 / read_tr8: p = image + lo.row[s], pc = image + lo.tr[c][db])
+__device__ __forceinline__ bf16x8 lds_row8(lds_img_p p) { return *reinterpret_cast<const bf16x8 GAMER_LDS*>(p); }
+__device__ __forceinline__ bf16x8 lds_tr8(lds_img_p p0, lds_img_p p1) {
+    const bf16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 GAMER_LDS*)p0);
+    const bf16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf16x4 GAMER_LDS*)p1);
+    return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+// read_key_quads (attention_common.h) through a pointer that already holds the lane's 4 * h
+__device__ __forceinline__ void lds_quads(lds_i32_p p, int (&out)[16]) {
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        const i32x4v t = *reinterpret_cast<const i32x4v GAMER_LDS*>(p + 8 * g4);
+        out[4 * g4] = t[0]; out[4 * g4 + 1] = t[1]; out[4 * g4 + 2] = t[2]; out[4 * g4 + 3] = t[3];
+    }
+}
+
 // ---- the exact three-way cut (csrc/gemm.hip: split3) ---------------------------------------------------------------
 // upper halves of (w1, w0) -> one register {bf16(w0), bf16(w1)}
 __device__ __forceinline__ uint32_t hi16_pair(uint32_t w0, uint32_t w1) { return __builtin_amdgcn_perm(w1, w0, 0x07060302u); }

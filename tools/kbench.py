@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of single kernels at the bench shapes (for A/B work and rocprofv3 --pmc runs).
 
-  python tools/kbench.py attn --B 256          attention fwd + bwd, self and cross, dropout 0.2
+  python tools/kbench.py attn --B 256          attention fwd + bwd, self and cross, dropout 0.2 (--matmul split3: the fp16 three-product form)
   python tools/kbench.py gemm --B 256          the GEMM shapes of one decoder layer (fwd/dgrad/wgrad)
   python tools/kbench.py elem --B 256          the HBM-bound kernels (--only qknorm: the q/k norm + RoPE calls alone)
 """
@@ -78,6 +78,17 @@ def bench_attn(args):
                                  order=od)
         b = lambda: ops.attn_bwd(q, nq * 64, k, nkv * 64, v, qkv.shape[1], o, do, lse, kl, ql, re_, te, B, S, nq, nkv,
                                  0.125, p, 7, delta, dq, nq * 64, dk, nkv * 64, dv, qkv.shape[1], order=od)
+        if args.matmul == "split3":
+            # the three-product fp16 form of Engine(matmul="split3") - the resident kernels of csrc/attention_res.hip at these shapes;
+            # operand maxima measured once, lse from a forward of the same form
+            with ops.amax_reuse(everything=True):
+                fs = lambda: ops.attn_fwd_split(q, nq * 64, k, nkv * 64, v, qkv.shape[1], kl, ql, re_, B, S, nq, nkv, 0.125, p, 7, o, lse,
+                                                order=od, h2=True)
+                bs = lambda: ops.attn_bwd_split(q, nq * 64, k, nkv * 64, v, qkv.shape[1], o, do, lse, kl, ql, re_, te, B, S, nq, nkv, 0.125,
+                                                p, 7, delta, dq, nq * 64, dk, nkv * 64, dv, qkv.shape[1], order=od, h2=True)
+                tf, tb = timeit(fs, args.iters), timeit(bs, args.iters)
+            print(f"attn_{name} split3: fwd {tf:.3f} ms  bwd {tb:.3f} ms")
+            continue
         dsw = torch.empty(ops.attn_ds_work_numel(B, S, nq), device=dev)
         b2 = lambda: ops.attn_bwd(q, nq * 64, k, nkv * 64, v, qkv.shape[1], o, do, lse, kl, ql, re_, te, B, S, nq, nkv,
                                   0.125, p, 7, delta, dq, nq * 64, dk, nkv * 64, dv, qkv.shape[1], order=od, ds_work=dsw)
