@@ -500,3 +500,62 @@ def base_model_config_moe(path: str, vocab_size: int, num_behavior: int, behavio
     if pad_token_id is not None:
         cfg.pad_token_id = int(pad_token_id)
     return apply_mb_runtime_fields(cfg, num_behavior, behavior_maps, use_behavior_token, num_positions, max_his_len)
+
+
+class Qwen3SessionMoeConfig(Qwen3MoeConfig):
+    """Configuration of the Qwen3SessionMoe model (ref:SeqRec/models/generative/Qwen3SessionMoe/model.py: Qwen3Moe's layers
+    and router under Qwen3Session's session-wise self mask): ``Qwen3MoeConfig`` plus the two integer fields its model asserts
+    (model.py:404-405) - ``num_positions`` (tokens per item) and ``model_max_length`` (the in-item mask covers
+    ``(model_max_length // num_positions) * num_positions`` tokens).  The reference constructs this class in no task; the
+    harness sets the run-time fields of the Qwen3SessionMulti branch (train_SMB_decoder.py:321-367)."""
+
+    REQUIRED = Qwen3SessionConfig.REQUIRED
+
+    def __init__(self, **kwargs):
+        for key, msg in self.REQUIRED:
+            if not isinstance(kwargs.get(key), int) or isinstance(kwargs.get(key), bool):
+                raise ValueError(msg)
+        super().__init__(**kwargs)
+
+    @classmethod
+    def coerce(cls, config) -> "Qwen3SessionMoeConfig":
+        """As ``Qwen3MoeConfig.coerce``; an HF config object must carry both run-time fields as attributes."""
+        if isinstance(config, cls):
+            return config
+        if isinstance(config, dict):
+            return cls(**config)
+        for key, msg in cls.REQUIRED:
+            if not hasattr(config, key):
+                raise ValueError(msg)
+        base = Qwen3MoeConfig.coerce(config).to_dict()
+        for key, _ in cls.REQUIRED:
+            base[key] = getattr(config, key)
+        return cls(**base)
+
+    @property
+    def max_item_tokens(self) -> int:
+        """Length of the reference's in-item mask: the longest sequence its forward accepts."""
+        return (self.model_max_length // self.num_positions) * self.num_positions
+
+    def validate(self):
+        super().validate()
+        if self.num_positions <= 0:
+            raise ValueError("num_positions must be positive")
+
+
+def base_model_config_session_moe(path: str, vocab_size: int, num_behavior: int, behavior_maps: dict, num_positions: int,
+                                  n_positions: int, pad_token_id: int = None,
+                                  model_max_length: int = 1024) -> Qwen3SessionMoeConfig:
+    """``--base_model DIR`` for ``--backbone Qwen3SessionMoe``: DIR/config.json is a Qwen3Moe base config (mlp_type absent ->
+    the reference's "PBATransformer"), the vocabulary resized to the tokenizer's, then the run-time fields the reference's
+    Qwen3SessionMulti branch sets (train_SMB_decoder.py:321-367, ``apply_runtime_fields``) with ``model_max_length``.  The
+    reference has no branch of its own for this backbone."""
+    f = os.path.join(path, "config.json") if os.path.isdir(path) else path
+    with open(f) as fh:
+        d = json.load(fh)
+    d.setdefault("mlp_type", "PBATransformer")
+    d.update(vocab_size=int(vocab_size), num_positions=int(num_positions), model_max_length=int(model_max_length))
+    if pad_token_id is not None:
+        d["pad_token_id"] = int(pad_token_id)
+    cfg = Qwen3SessionMoeConfig(**d)
+    return apply_runtime_fields(cfg, num_behavior, behavior_maps, num_positions, n_positions, model_max_length)

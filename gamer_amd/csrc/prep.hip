@@ -131,16 +131,21 @@ router_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ attn_
 // CROSS = true: Qwen3SessionMulti, after the router (kl_cross / ql_cross in, the cross span and empty flags out).
 // CROSS = false: Qwen3Session (HF Qwen3ForCausalLM with the same self mask, no router): kl_self is written here, 0 for a
 // kept key and INT_BIG for a padded one, as causal_prep_kernel does; no cross input or output is touched.
+// The work of one workgroup (= one sequence b) is session_spans_row; ``sraw`` is its LDS, S (8 + 4 (CROSS ? 4 : 2)) bytes
+// (session_span_lds).  The kernels of gamer_session_spans / gamer_session_prep are this function alone;
+// session_moe_prep_kernel runs it behind Qwen3Moe's routing.
 template <bool CROSS>
-__global__ void __launch_bounds__(ROUTER_THREADS)
-session_span_kernel(const int64_t* __restrict__ sess, const int64_t* __restrict__ ext_ids,
-                    const int64_t* __restrict__ attn_mask, const int32_t* __restrict__ kl_cross,
-                    const int32_t* __restrict__ ql_cross, int S, int P, int n_pos, int32_t* __restrict__ kl_self,
-                    int32_t* __restrict__ span_self, int32_t* __restrict__ span_cross, int32_t* __restrict__ pos_ids,
-                    int32_t* __restrict__ empty_self, int32_t* __restrict__ empty_cross,
-                    int32_t* __restrict__ tile_empty_self, int32_t* __restrict__ tile_empty_cross,
-                    int32_t* __restrict__ violations) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sraw[];
+constexpr size_t session_span_lds(int S) { return (size_t)S * (sizeof(int64_t) + (CROSS ? 4 : 2) * sizeof(int32_t)); }
+
+template <bool CROSS>
+__device__ __forceinline__ void
+session_spans_row(unsigned char* sraw, const int64_t* __restrict__ sess, const int64_t* __restrict__ ext_ids,
+                  const int64_t* __restrict__ attn_mask, const int32_t* __restrict__ kl_cross,
+                  const int32_t* __restrict__ ql_cross, int S, int P, int n_pos, int32_t* __restrict__ kl_self,
+                  int32_t* __restrict__ span_self, int32_t* __restrict__ span_cross, int32_t* __restrict__ pos_ids,
+                  int32_t* __restrict__ empty_self, int32_t* __restrict__ empty_cross,
+                  int32_t* __restrict__ tile_empty_self, int32_t* __restrict__ tile_empty_cross,
+                  int32_t* __restrict__ violations) {
     int64_t* sess_s = reinterpret_cast<int64_t*>(sraw);                 // [S]
     int32_t* keep_s = reinterpret_cast<int32_t*>(sess_s + S);           // [S]
     int32_t* klc_s = keep_s + S;                                        // [S] cross key level (INT_MAX if padded; CROSS only)
@@ -204,6 +209,20 @@ session_span_kernel(const int64_t* __restrict__ sess, const int64_t* __restrict_
         tile_empty_self[(int64_t)b * n_tiles + qt] = es;
         if constexpr (CROSS) tile_empty_cross[(int64_t)b * n_tiles + qt] = ec;
     }
+}
+
+template <bool CROSS>
+__global__ void __launch_bounds__(ROUTER_THREADS)
+session_span_kernel(const int64_t* __restrict__ sess, const int64_t* __restrict__ ext_ids,
+                    const int64_t* __restrict__ attn_mask, const int32_t* __restrict__ kl_cross,
+                    const int32_t* __restrict__ ql_cross, int S, int P, int n_pos, int32_t* __restrict__ kl_self,
+                    int32_t* __restrict__ span_self, int32_t* __restrict__ span_cross, int32_t* __restrict__ pos_ids,
+                    int32_t* __restrict__ empty_self, int32_t* __restrict__ empty_cross,
+                    int32_t* __restrict__ tile_empty_self, int32_t* __restrict__ tile_empty_cross,
+                    int32_t* __restrict__ violations) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sraw[];
+    session_spans_row<CROSS>(sraw, sess, ext_ids, attn_mask, kl_cross, ql_cross, S, P, n_pos, kl_self, span_self, span_cross,
+                             pos_ids, empty_self, empty_cross, tile_empty_self, tile_empty_cross, violations);
 }
 
 // ---- expert lists ---------------------------------------------------------------------------
@@ -372,7 +391,7 @@ extern "C" int gamer_session_spans(const int64_t* session_ids, const int64_t* ex
     GAMER_CHECK_ARG(B > 0 && S > 0 && num_positions > 0 && n_rope_positions > 0,
                     "gamer_session_spans: bad shape B=%d S=%d P=%d n_pos=%d", B, S, num_positions, n_rope_positions);
     GAMER_CHECK_ARG(S <= 2048, "gamer_session_spans: S=%d > 2048 unsupported", S);
-    const size_t shmem = (size_t)S * (sizeof(int64_t) + 4 * sizeof(int32_t));
+    const size_t shmem = session_span_lds<true>(S);
     hipLaunchKernelGGL(session_span_kernel<true>, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
                        session_ids, extended_session_ids, attn_mask, kl_cross, ql_cross, S, num_positions,
                        n_rope_positions, nullptr, span_self, span_cross, pos_ids, empty_self, empty_cross,
@@ -390,7 +409,7 @@ extern "C" int gamer_session_prep(const int64_t* session_ids, const int64_t* ext
     GAMER_CHECK_ARG(B > 0 && S > 0 && num_positions > 0 && n_rope_positions > 0,
                     "gamer_session_prep: bad shape B=%d S=%d P=%d n_pos=%d", B, S, num_positions, n_rope_positions);
     GAMER_CHECK_ARG(S <= 2048, "gamer_session_prep: S=%d > 2048 unsupported", S);
-    const size_t shmem = (size_t)S * (sizeof(int64_t) + 2 * sizeof(int32_t));
+    const size_t shmem = session_span_lds<false>(S);
     hipLaunchKernelGGL(session_span_kernel<false>, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
                        session_ids, extended_session_ids, attn_mask, nullptr, nullptr, S, num_positions,
                        n_rope_positions, kl_self, span_self, nullptr, pos_ids, empty_self, nullptr,
@@ -502,6 +521,28 @@ extern "C" int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t
 //                (the reference fails in its embedding there) and gets 0.  use_beh == 0: 0 everywhere.
 //   kl_self / empty_self / tile_empty_self / pos_ids / next_pos: as causal_prep_kernel.
 // One workgroup per sequence; LDS holds the kept-flag prefix sum (2 S int32).
+// expert[t] and beh_idx[t] of token t of one row (``ids`` / ``expert`` / ``beh_idx``: the row's); returns 1 for a non-special
+// item start outside behavior_maps (the row's share of bad_token), else 0.
+__device__ __forceinline__ int
+moe_route_token(const int64_t* __restrict__ ids, int t, const int32_t* __restrict__ lut, int vocab,
+                const int32_t* __restrict__ table, int P, int slots, int use_beh, int pad_id, int eos_id,
+                int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx) {
+    const int64_t id = ids[t];
+    const bool special = (id == pad_id) || (id == eos_id);
+    const int p = t % P;
+    int e = 0, bi = 0;
+    if (!special && t < slots) {
+        e = table ? table[p] : p + 1;
+        if (use_beh && p != 0) {
+            const int64_t btok = ids[t - p];
+            if (btok >= 0 && btok < vocab && lut[btok] >= 0) bi = lut[btok] + 1;
+        }
+    }
+    expert[t] = e;
+    beh_idx[t] = bi;
+    return (use_beh && p == 0 && !special && t < slots && !(id >= 0 && id < vocab && lut[id] >= 0)) ? 1 : 0;
+}
+
 __global__ void __launch_bounds__(ROUTER_THREADS)
 moe_router_prep_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ attn_mask,
                        const int32_t* __restrict__ lut, int vocab, const int32_t* __restrict__ table, int S, int P,
@@ -518,20 +559,7 @@ moe_router_prep_kernel(const int64_t* __restrict__ ids, const int64_t* __restric
     const int slots = n_items * P;
     int bad = 0;
     for (int t = threadIdx.x; t < S; t += blockDim.x) {
-        const int64_t id = ids[base + t];
-        const bool special = (id == pad_id) || (id == eos_id);
-        const int p = t % P;
-        int e = 0, bi = 0;
-        if (!special && t < slots) {
-            e = table ? table[p] : p + 1;
-            if (use_beh && p != 0) {
-                const int64_t btok = ids[base + t - p];
-                if (btok >= 0 && btok < vocab && lut[btok] >= 0) bi = lut[btok] + 1;
-            }
-        }
-        if (use_beh && p == 0 && !special && t < slots && !(id >= 0 && id < vocab && lut[id] >= 0)) ++bad;
-        expert[base + t] = e;
-        beh_idx[base + t] = bi;
+        bad += moe_route_token(ids + base, t, lut, vocab, table, P, slots, use_beh, pad_id, eos_id, expert + base, beh_idx + base);
         const int keep = attn_mask ? (attn_mask[base + t] != 0 ? 1 : 0) : 1;
         kl_self[base + t] = keep ? 0 : INT_BIG;
         a[t] = keep;
@@ -577,5 +605,56 @@ extern "C" int gamer_moe_router_prep(const int64_t* ids, const int64_t* attn_mas
                        use_behavior_token ? 1 : 0, pad_id, eos_id, expert, beh_idx, kl_self, empty_self, tile_empty_self,
                        pos_ids, next_pos, bad_token);
     GAMER_CHECK_LAUNCH("gamer_moe_router_prep");
+    return 0;
+}
+
+// ---- Qwen3SessionMoe: Qwen3Moe's router + Qwen3Session's mask (one launch) ---------------------------------------------
+// ref:SeqRec/models/generative/Qwen3SessionMoe/model.py: the layers and router of Qwen3Moe (:23-93) under the self mask and
+// RoPE positions of Qwen3Session (:402-468, :680-703).  One workgroup per sequence: moe_route_token per token (expert, beh_idx,
+// bad_token as moe_router_prep_kernel), then session_spans_row<false> (kl_self, span_self, pos_ids, empty flags, violations as
+// gamer_session_prep's kernel).  The two halves share no output, so no barrier stands between them.
+__global__ void __launch_bounds__(ROUTER_THREADS)
+session_moe_prep_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ attn_mask,
+                        const int64_t* __restrict__ sess, const int64_t* __restrict__ ext_ids,
+                        const int32_t* __restrict__ lut, int vocab, const int32_t* __restrict__ table, int S, int P,
+                        int n_items, int use_beh, int pad_id, int eos_id, int n_pos,
+                        int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx, int32_t* __restrict__ bad_token,
+                        int32_t* __restrict__ kl_self, int32_t* __restrict__ span_self, int32_t* __restrict__ pos_ids,
+                        int32_t* __restrict__ empty_self, int32_t* __restrict__ tile_empty_self,
+                        int32_t* __restrict__ violations) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sraw[];
+    const int64_t base = (int64_t)blockIdx.x * S;
+    const int slots = n_items * P;
+    int bad = 0;
+    for (int t = threadIdx.x; t < S; t += blockDim.x)
+        bad += moe_route_token(ids + base, t, lut, vocab, table, P, slots, use_beh, pad_id, eos_id, expert + base, beh_idx + base);
+    if (bad) atomicAdd(bad_token, bad);
+    session_spans_row<false>(sraw, sess, ext_ids, attn_mask, nullptr, nullptr, S, P, n_pos, kl_self, span_self, nullptr, pos_ids,
+                             empty_self, nullptr, tile_empty_self, nullptr, violations);
+}
+
+extern "C" int gamer_session_moe_prep(const int64_t* ids, const int64_t* attn_mask, const int64_t* session_ids,
+                                      const int64_t* extended_session_ids, const int32_t* behavior_lut, int vocab,
+                                      const int32_t* position_table, int B, int S, int num_positions, int n_items,
+                                      int use_behavior_token, int pad_id, int eos_id, int n_rope_positions,
+                                      int32_t* expert, int32_t* beh_idx, int32_t* bad_token, int32_t* kl_self,
+                                      int32_t* span_self, int32_t* pos_ids, int32_t* empty_self, int32_t* tile_empty_self,
+                                      int32_t* violations, void* stream) {
+    GAMER_CHECK_ARG(ids && session_ids && expert && beh_idx && bad_token && kl_self && span_self && pos_ids && empty_self &&
+                    tile_empty_self && violations, "gamer_session_moe_prep: null pointer");
+    GAMER_CHECK_ARG(!use_behavior_token || (behavior_lut && vocab > 0),
+                    "gamer_session_moe_prep: use_behavior_token needs the behaviour table");
+    GAMER_CHECK_ARG(B > 0 && S > 0 && num_positions > 0 && n_items > 0 && n_rope_positions > 0,
+                    "gamer_session_moe_prep: bad shape B=%d S=%d P=%d n_items=%d n_pos=%d", B, S, num_positions, n_items,
+                    n_rope_positions);
+    GAMER_CHECK_ARG(S <= 2048, "gamer_session_moe_prep: S=%d > 2048 unsupported", S);
+    GAMER_CHECK_ARG((int64_t)n_items * num_positions + 1 >= S,
+                    "gamer_session_moe_prep: S=%d is longer than the router's table (n_items * P + 1 = %lld)", S,
+                    (long long)n_items * num_positions + 1);
+    hipLaunchKernelGGL(session_moe_prep_kernel, dim3(B), dim3(ROUTER_THREADS), session_span_lds<false>(S), (hipStream_t)stream,
+                       ids, attn_mask, session_ids, extended_session_ids, behavior_lut, vocab, position_table, S,
+                       num_positions, n_items, use_behavior_token ? 1 : 0, pad_id, eos_id, n_rope_positions, expert, beh_idx,
+                       bad_token, kl_self, span_self, pos_ids, empty_self, tile_empty_self, violations);
+    GAMER_CHECK_LAUNCH("gamer_session_moe_prep");
     return 0;
 }

@@ -179,8 +179,9 @@ def _check_generation_dtype(engine):
 
 
 def _session_kw(engine, session_ids, extended_session_ids) -> dict:
-    """The session ids of a session engine ("session", "qwen3_session") on the device - required there - and {} for the others."""
-    if engine.variant not in ("session", "qwen3_session"):
+    """The session ids of a session engine ("session", "qwen3_session", "qwen3_session_moe") on the device - required there -
+    and {} for the others."""
+    if engine.variant not in ("session", "qwen3_session", "qwen3_session_moe"):
         return {}
     if session_ids is None or extended_session_ids is None:
         raise ValueError("a session engine needs session_ids and extended_session_ids")
@@ -613,6 +614,30 @@ class Qwen3MoeDecodeSession(DecodeSession):
         self.beh = keep("beh", beh.repeat_interleave(self.nb))
 
 
+class Qwen3SessionMoeDecodeSession(Qwen3MoeDecodeSession):
+    """K/V cache + single-token step of Qwen3SessionMoe (``Engine(variant="qwen3_session_moe")``): ``Qwen3MoeDecodeSession``
+    with a session model's prompt pass and positions.  The prompt pass runs with the session mask as key spans, the extended
+    ids as positions and the router by column (gamer_session_moe_prep, ``session_ids`` / ``extended_session_ids`` [B, L0]
+    required); the generated tokens see every kept key (model.py:444-455), are rotated by max(extended_session_ids[row]) + t
+    (``DecodeSession``'s ``pos_last`` of a session model; model.py:688-703) and routed to the expert of their column."""
+
+    def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int, session_ids=None,
+                 extended_session_ids=None):
+        _check_generation_dtype(engine)
+        _check_moe_generation(engine, input_ids.shape[1], max_new_tokens)
+        DecodeSession.__init__(self, engine, input_ids, attention_mask, None, num_beams, max_new_tokens, session_ids,
+                               extended_session_ids)
+
+    @staticmethod
+    def _eval_forward(engine, ids, am, act, sess: dict, L0: int, **kw):
+        engine.forward(ids, am, train=False, **sess, **kw)
+
+    def _row_inputs(self, keep, ids0, am0, act0, sess: dict):
+        """The behaviour of the prompt's last token for the injection layers (``pos_last`` is the session model's)."""
+        beh = (self.eng.lut[ids0[:, -1]].to(torch.int32) + 1).clamp_(min=0)
+        self.beh = keep("beh", beh.repeat_interleave(self.nb))
+
+
 @torch.no_grad()
 def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, actions: torch.Tensor, trie: ItemTrie,
                 num_beams: int, max_new_tokens: int = 4, use_cache: bool = True, session_ids=None,
@@ -633,11 +658,13 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     reorder_cross_cache = reorder_cross_cache or bf16          # (one and the same search in bf16: the re-run path may always run)
     trace = []
     qwen3 = engine.variant in ("qwen3", "qwen3_session")
-    moe = engine.variant == "qwen3moe"          # (no behaviour levels either: no actions, no cross cache)
+    session_moe = engine.variant == "qwen3_session_moe"
+    moe = engine.variant == "qwen3moe" or session_moe       # (no behaviour levels either: no actions, no cross cache)
     if not use_cache and not reorder_cross_cache and not (qwen3 or moe):
         raise ValueError("use_cache=False re-computes every position for its own beam: it can only reproduce "
                          "reorder_cross_cache=True (the shipped reference's un-reordered cross cache needs the cache)")
-    cls = Qwen3DecodeSession if qwen3 else (Qwen3MoeDecodeSession if moe else DecodeSession)
+    cls = (Qwen3DecodeSession if qwen3 else Qwen3SessionMoeDecodeSession if session_moe else
+           Qwen3MoeDecodeSession if moe else DecodeSession)
     if moe:
         _check_moe_generation(engine, input_ids.shape[1], max_new_tokens)
     dev = engine.device
@@ -664,6 +691,8 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
         session = None
     elif qwen3:
         session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens, **sess0)
+    elif session_moe:
+        session = Qwen3SessionMoeDecodeSession(engine, ids0, am0, nb, max_new_tokens, **sess0)
     elif moe:
         session = Qwen3MoeDecodeSession(engine, ids0, am0, nb, max_new_tokens)
     else:

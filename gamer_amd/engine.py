@@ -405,6 +405,9 @@ class Engine:
         elif cls is Engine and variant == "qwen3moe":       # Qwen3Moe (gamer_amd/engine_qwen3moe.py)
             from .engine_qwen3moe import Qwen3MoeEngine
             cls = Qwen3MoeEngine
+        elif cls is Engine and variant == "qwen3_session_moe":      # Qwen3SessionMoe (the same module)
+            from .engine_qwen3moe import Qwen3SessionMoeEngine
+            cls = Qwen3SessionMoeEngine
         return super().__new__(cls)
 
     def __init__(self, cfg: Qwen3MultiConfig, device="cuda", temperature: float = 1.0, variant: str = "multi",
@@ -439,9 +442,11 @@ class Engine:
         matmul = _matmul_arg(dtype, matmul)
         _check_split_dtype(dtype, matmul)
         if variant not in self._VARIANTS:
-            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3, qwen3_session or qwen3moe)")
+            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3, qwen3_session, qwen3moe or "
+                             "qwen3_session_moe)")
         _check_dtype(dtype)
-        self.key_spans = variant == "session"
+        if variant == "session":
+            self.key_spans = True
         self._init_core(cfg, device, temperature, variant, dtype, matmul, share_buffers_of, deterministic)
         if self._amax is not None and self._amax.planes is not None and cfg.hidden_size == 256 and \
                 os.environ.get("GAMER_GEMM_OSF", "0") == "1":
@@ -737,6 +742,9 @@ class Engine:
             ops.session_spans(sid, ext, am, cfg.num_positions, S, r, ws.session)     # overwrites r["empty_*"]
             span_self, span_cross, pos_ids = (ws.session["span_self"], ws.session["span_cross"],
                                               ws.session["pos_ids"])
+        elif self.key_spans:
+            # (a model whose own prep launch built the key spans next to its router outputs: ``_route`` left them in ws.session)
+            span_self = ws.session["span_self"]
         if cfg.cross_attention_decoder:
             # (bf16: the rows without an allowed key - 70 % of them in the cross attention - output 0; sorted behind the
             # others they cost nothing)
@@ -1207,7 +1215,7 @@ class Engine:
         nq, nkv, NQ, NKV, QKV, eps, cos, sin, p_res = c.nq, c.nkv, c.NQ, c.NKV, c.QKV, c.eps, c.cos, c.sin, c.p_res
         NB1 = cfg.num_behavior + 1
         span_self = span_cross = pos_ids = None
-        if self.variant == "session":
+        if self.key_spans:
             span_self, span_cross, pos_ids = ws.session["span_self"], ws.session["span_cross"], ws.session["pos_ids"]
         r = ws.router
         NP = ws.norm_partial[-1]                    # scratch table (rowtable_bwd); the norm backward takes the others in turn

@@ -14,6 +14,11 @@ window, data parallelism).  What this engine changes:
     behaviour tokens (task ``mb``: behaviour index 0, no injection) and ``Moe_behavior_only`` without a behaviour token
     (every semantic token in expert 1);
   - training sequences need not be a whole number of items (the router covers ``n_positions * num_positions + 1`` tokens).
+
+``Engine(cfg, variant="qwen3_session_moe")`` constructs ``Qwen3SessionMoeEngine``, the Qwen3SessionMoe model
+(ref:SeqRec/models/generative/Qwen3SessionMoe/model.py): the same layers, router and loops under Qwen3Session's session-wise
+self mask and RoPE positions.  ``gamer_session_moe_prep`` builds the router outputs and the mask in one launch; that launch,
+its buffers and the argument checks are all the class adds.
 """
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .config import Qwen3MoeConfig
+from .config import Qwen3MoeConfig, Qwen3SessionMoeConfig
 from .engine import Engine, ParamLayout
 
 
@@ -38,11 +43,12 @@ class Qwen3MoeEngine(Engine):
     _VARIANTS = ("qwen3moe",)
     _item_aligned = False
     _layout_cls = Qwen3MoeLayout
+    _config_cls = Qwen3MoeConfig
 
     def __init__(self, cfg: Qwen3MoeConfig, device="cuda", temperature: float = 1.0, variant: str = "qwen3moe",
                  dtype: str = "f32", matmul: Optional[str] = None, share_buffers_of: Optional["Qwen3MoeEngine"] = None,
                  deterministic: Optional[bool] = None):
-        cfg = Qwen3MoeConfig.coerce(cfg)
+        cfg = self._config_cls.coerce(cfg)
         super().__init__(cfg, device, temperature, variant, dtype, matmul, share_buffers_of, deterministic)
         # the router's table per position inside an item (router.py:29-54); None = the kernel's own p + 1
         P = int(cfg.num_positions)
@@ -82,3 +88,78 @@ class Qwen3MoeEngine(Engine):
         return super().forward(input_ids, attention_mask, None, labels, num_items_in_batch, train=train, dropout=dropout,
                                kv_sink=kv_sink, kv_dest=kv_dest, last_row_logits=last_row_logits, hidden_sink=hidden_sink,
                                rope_from_mask=rope_from_mask)
+
+
+class Qwen3SessionMoeEngine(Qwen3MoeEngine):
+    """The Qwen3SessionMoe model (``--backbone Qwen3SessionMoe``): Qwen3Moe's parameters, router tables, FFN switches and
+    loops with Qwen3Session's self mask (a token sees its own item up to itself and every kept token of a strictly earlier
+    session, model.py:402-468) and RoPE positions ``extended_session_ids`` (model.py:680-703).  ``gamer_session_moe_prep``
+    writes the router outputs and the mask - as per-query key spans, which the attention kernels take in every form (split3,
+    split6, f32, bf16) - in the pass's one prep launch."""
+
+    _VARIANTS = ("qwen3_session_moe",)
+    _config_cls = Qwen3SessionMoeConfig
+    key_spans = True
+    _session_in = None          # (session ids, extended ids) of the forward in progress, on the device: ``_route`` reads them
+
+    @staticmethod
+    def _bind_masks(ws, B: int, S: int):
+        """The router buffers of ``Engine._bind_masks`` plus the session buffers of ``Qwen3SessionEngine._bind_masks``: key
+        spans, RoPE positions and the violation count (key levels and empty rows / tiles are the router's ``*_self``)."""
+        Qwen3MoeEngine._bind_masks(ws, B, S)
+        i32 = torch.int32
+        if "s_violations" not in ws._store:
+            ws._store["s_violations"] = torch.zeros(1, dtype=i32, device=ws.device)
+        ws.session = dict(span_self=ws._buf("s_span_self", (B, S, 4), i32), span_cross=None,
+                          pos_ids=ws._buf("s_pos_ids", (B, S), i32), violations=ws._store["s_violations"])
+
+    def forward(self, input_ids, attention_mask=None, actions=None, labels=None, num_items_in_batch=None,
+                train: bool = False, dropout: Optional[bool] = None, kv_sink=None, kv_dest=None, session_ids=None,
+                extended_session_ids=None, last_row_logits: bool = False, hidden_sink: Optional[list] = None):
+        """``Qwen3MoeEngine.forward`` with the session-wise mask: ``session_ids`` [B,S] are required (the reference asserts
+        the same), ``extended_session_ids`` [B,S] are the RoPE positions (None: 0..S-1).  ``actions`` are ignored."""
+        if session_ids is None:
+            raise ValueError("Session IDs must be provided to generate session-wise causal mask.")
+        S = input_ids.shape[1]
+        # the reference's in-item mask has (model_max_length // num_positions) * num_positions rows: a longer sequence fails
+        # there; the mask kernel keeps a row's session ids in LDS up to 2048 tokens; the router's table ends at max_len()
+        if S > self.cfg.max_item_tokens:
+            raise ValueError(f"sequence length {S} exceeds the reference's in-item mask, (model_max_length // "
+                             f"num_positions) * num_positions = {self.cfg.max_item_tokens}")
+        if S > 2048:
+            raise ValueError(f"sequence length {S} > 2048: the session mask kernel (gamer_session_moe_prep) is built for "
+                             "S <= 2048")
+        if S > self.max_len():
+            raise ValueError(f"sequence length {S} exceeds the router's table, n_positions * num_positions + 1 = "
+                             f"{self.max_len()} (router.py:46-60)")
+        # (ops.session_moe_prep checks both shapes against input_ids)
+        self._session_in = (session_ids.to(self.device, torch.int64).contiguous(),
+                            None if extended_session_ids is None else
+                            extended_session_ids.to(self.device, torch.int64).contiguous())
+        try:
+            return super().forward(input_ids, attention_mask, None, labels, num_items_in_batch, train=train, dropout=dropout,
+                                   kv_sink=kv_sink, kv_dest=kv_dest, last_row_logits=last_row_logits, hidden_sink=hidden_sink)
+        finally:
+            self._session_in = None
+
+    def _route(self, c, actions, act_zero_col, rope_from_mask: bool):
+        """gamer_session_moe_prep: the expert and behaviour indices into ``ws.router``, the session mask's key levels and
+        empty rows there too, its key spans, positions and violation count into ``ws.session``.  Returns the positions."""
+        if rope_from_mask:
+            raise ValueError("rope_from_mask is not an option of a session model (its positions are extended_session_ids)")
+        cfg, ws = self.cfg, c.ws
+        sid, ext = self._session_in
+        ws.session["violations"].zero_()
+        ops.session_moe_prep(c.ids, c.am, sid, ext, self.lut, self.moe_table, cfg.num_positions, cfg.n_positions,
+                             cfg.use_behavior_token, cfg.pad_token_id, cfg.eos_token_id, c.S, {**ws.router, **ws.session})
+        return ws.session["pos_ids"]
+
+    def check_inputs(self):
+        """``Engine.check_inputs`` (behaviour tokens, labels) and rows whose session ids cannot be expressed as key spans
+        (``forward`` has already refused sequences past the in-item mask, 2048 tokens or the router's table)."""
+        super().check_inputs()
+        n = int(self.ws.session["violations"].item())
+        if n:
+            raise ValueError(f"{n} row(s) with session ids that decrease along the sequence or RoPE positions "
+                             "outside [0, S): the session masks are built as causal key spans "
+                             "(gamer_session_moe_prep), which needs the dataset's layout (SMB_dataset.py:194-222)")

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .config import Qwen3MoeConfig, Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig
+from .config import Qwen3MoeConfig, Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig, Qwen3SessionMoeConfig
 from .engine import Engine
 
 
@@ -476,3 +476,18 @@ class Qwen3MoeWithTemperature(Qwen3WithTemperature):
             out["aux_loss"] = 0
             out["router_logits"] = tuple((torch.zeros(1, dtype=torch.int64),) for _ in range(self._cfg.num_hidden_layers))
         return out
+
+
+class Qwen3SessionMoeWithTemperature(Qwen3WithTemperature):
+    """ref:SeqRec/models/generative/Qwen3SessionMoe/model.py:590-735 - Qwen3Moe's position-routed experts under Qwen3Session's
+    session-wise self-attention mask, with the temperature loss (``--backbone Qwen3SessionMoe``; the reference constructs this
+    class in no task) - on ``Engine(variant="qwen3_session_moe")`` (gamer_amd/engine_qwen3moe.py).  The surface of the other
+    ``*WithTemperature`` classes and Qwen3Moe's state-dict names.  The config must carry integer ``num_positions`` and
+    ``model_max_length`` (model.py:404-405 asserts both).  ``forward`` needs ``session_ids`` and takes the RoPE positions from
+    ``extended_session_ids``; ``generate`` takes both and no ``actions``.  As the reference's forward, which is
+    ``Qwen3ForCausalLM``'s, the output carries no ``aux_loss`` and no ``router_logits``."""
+    VARIANT = "qwen3_session_moe"
+    CONFIG_CLASS = Qwen3SessionMoeConfig
+    USES_SESSIONS = True
+
+    _check_config = staticmethod(Qwen3MultiWithTemperature._check_config)

@@ -146,6 +146,33 @@ def session_prep(session_ids, extended_session_ids, attn_mask, num_positions, n_
          ptr(out["tile_empty_self"]), ptr(out["violations"]), stream_ptr())
 
 
+def session_moe_prep(ids, attn_mask, session_ids, extended_session_ids, behavior_lut, position_table, num_positions,
+                     n_items, use_behavior_token, pad_id, eos_id, n_rope_positions, out: dict):
+    """Qwen3SessionMoe's one prep launch (gamer_session_moe_prep): the router outputs of ``moe_router_prep`` (``out``:
+    expert, beh_idx, bad_token) and the mask outputs of ``session_prep`` (``out``: kl_self, span_self, pos_ids, empty_self,
+    tile_empty_self, violations); bad_token and violations are incremented, not cleared."""
+    B, S = ids.shape
+    _chk(ids, torch.int64, "input_ids")
+    _chk(session_ids, torch.int64, "session_ids")
+    if tuple(session_ids.shape) != (B, S):
+        raise ValueError(f"session_ids has shape {tuple(session_ids.shape)}, input_ids {(B, S)}")
+    if extended_session_ids is not None:
+        _chk(extended_session_ids, torch.int64, "extended_session_ids")
+        if tuple(extended_session_ids.shape) != (B, S):
+            raise ValueError(f"extended_session_ids has shape {tuple(extended_session_ids.shape)}, input_ids {(B, S)}")
+    if attn_mask is not None:
+        _chk(attn_mask, torch.int64, "attention_mask")
+    if position_table is not None:
+        _chk(position_table, torch.int32, "position_table")
+        if position_table.numel() != num_positions:
+            raise ValueError(f"position_table has {position_table.numel()} entries, num_positions is {num_positions}")
+    call("gamer_session_moe_prep", ptr(ids), ptr(attn_mask), ptr(session_ids), ptr(extended_session_ids), ptr(behavior_lut),
+         behavior_lut.numel() if behavior_lut is not None else 0, ptr(position_table), B, S, num_positions, n_items,
+         1 if use_behavior_token else 0, pad_id, eos_id, n_rope_positions, ptr(out["expert"]), ptr(out["beh_idx"]),
+         ptr(out["bad_token"]), ptr(out["kl_self"]), ptr(out["span_self"]), ptr(out["pos_ids"]), ptr(out["empty_self"]),
+         ptr(out["tile_empty_self"]), ptr(out["violations"]), stream_ptr())
+
+
 def router_position_table(expert, table):
     """expert[i] <- table[expert[i]] in place (gamer_router_position_table; int32 tensors on the device)."""
     _chk(expert, torch.int32, "expert")

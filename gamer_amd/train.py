@@ -28,6 +28,10 @@ reads ``<dataset>.MB.*.json`` (gamer_amd/mb_data.py) for ``--backbone Qwen3Moe``
 of Qwen3Moe or ``--base_model DIR`` plus train_MB_decoder.py:319-362's run-time fields; mb_explicit_back is refused, its
 behaviour token ends the item) or ``--backbone Qwen3``; checkpoints load into ``Qwen3MoeWithTemperature`` /
 ``Qwen3WithTemperature``.
+``--backbone Qwen3SessionMoe`` trains Qwen3Moe's experts under Qwen3Session's session mask (``Engine(variant=
+"qwen3_session_moe")``) on the SMB tasks.  The reference constructs this class in no task: the harness takes Qwen3Moe's
+config.json (or ``--base_model DIR``) and sets the run-time fields of the Qwen3SessionMulti branch (train_SMB_decoder.py:
+321-367) plus ``model_max_length``; checkpoints load into ``Qwen3SessionMoeWithTemperature``.  The MB tasks refuse it.
 """
 from __future__ import annotations
 
@@ -39,8 +43,8 @@ import time
 import torch
 
 from . import synthetic
-from .config import (Qwen3Config, Qwen3MoeConfig, Qwen3SessionConfig, apply_mb_runtime_fields, base_model_config,
-                     synthetic_config)
+from .config import (Qwen3Config, Qwen3MoeConfig, Qwen3SessionConfig, Qwen3SessionMoeConfig, apply_mb_runtime_fields,
+                     apply_runtime_fields, base_model_config, base_model_config_session_moe, synthetic_config)
 from .dp import GradAllReducer, all_reduce_scalar_
 from .engine import Engine
 from .schedule import cosine_with_warmup, warmup_steps_for
@@ -66,7 +70,7 @@ def parse_args(argv=None):
     ap.add_argument("--index_file", type=str, default=".index.json")
     ap.add_argument("--tasks", type=str, default="smb_explicit_decoder_4")
     ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti", "Qwen3",
-                                                                                 "Qwen3Session", "Qwen3Moe"])
+                                                                                 "Qwen3Session", "Qwen3Moe", "Qwen3SessionMoe"])
     ap.add_argument("--patience", type=int, default=10, help="early stopping: evaluations without a better eval_loss")
     ap.add_argument("--save_total_limit", type=int, default=2)
     ap.add_argument("--bf16", action="store_true",
@@ -171,11 +175,14 @@ class Prefetcher:
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti", "Qwen3Moe"):
-        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti / Qwen3Moe backbones")
+    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti", "Qwen3Moe", "Qwen3SessionMoe"):
+        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti / Qwen3Moe / Qwen3SessionMoe backbones")
     if args.fp16:
         raise SystemExit("--fp16 is not built (the MI355X path has fp32 and bf16; the reference's recipe uses neither "
                          "loss scaling nor fp16 kernels of its own)")
+    mb = args.tasks.lower().startswith("mb")
+    if args.data_path and mb and args.backbone not in ("Qwen3Moe", "Qwen3"):
+        raise SystemExit("MB tasks train --backbone Qwen3Moe or Qwen3 (the decoder-only backbones of train_MB_decoder)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -184,16 +191,13 @@ def main(argv=None):
         import torch.distributed as dist
         dist.init_process_group("nccl", init_method="env://", device_id=torch.device("cuda", local_rank))
     variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3", "Qwen3Session": "qwen3_session",
-               "Qwen3Moe": "qwen3moe"}.get(args.backbone, "multi")
-    mb = args.tasks.lower().startswith("mb")
+               "Qwen3Moe": "qwen3moe", "Qwen3SessionMoe": "qwen3_session_moe"}.get(args.backbone, "multi")
     accum = args.gradient_accumulation_steps
     real = None
     if args.data_path and mb:
         # load_MB_datasets(..., tasks) of the MB decoder harness (loading_MB.py:9-135, train_MB_decoder.py:240-364): the
         # Qwen3Moe model or the plain Qwen3 baseline
         from . import mb_data
-        if variant not in ("qwen3moe", "qwen3"):
-            raise SystemExit("MB tasks train --backbone Qwen3Moe or Qwen3 (the decoder-only backbones of train_MB_decoder)")
         ds = mb_data.MBData(args.data_path, args.dataset, args.tasks, args.index_file)
         samples = ds.train_samples(args.max_his_len)
         coll = mb_data.MBCollator(ds)
@@ -235,6 +239,17 @@ def main(argv=None):
             # Qwen3-Light plus the item length and the tokenizer's model_max_length (train_SMB_decoder.py:369-378)
             cfg = Qwen3SessionConfig(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id,
                                      num_positions=cfg.num_positions, model_max_length=cfg.model_max_length)
+        elif variant == "qwen3_session_moe":
+            # Qwen3Moe's config.json (or --base_model) with the run-time fields of the Qwen3SessionMulti branch
+            # (train_SMB_decoder.py:321-367) and model_max_length; the reference has no branch of its own for this backbone
+            rt = (cfg.vocab_size, cfg.num_behavior, cfg.behavior_maps, cfg.num_positions, cfg.n_positions)
+            if args.base_model:
+                cfg = base_model_config_session_moe(args.base_model, *rt, pad_token_id=cfg.pad_token_id,
+                                                    model_max_length=cfg.model_max_length)
+            else:
+                cfg = apply_runtime_fields(Qwen3SessionMoeConfig(vocab_size=rt[0], pad_token_id=cfg.pad_token_id,
+                                                                 num_positions=rt[3], model_max_length=cfg.model_max_length),
+                                           rt[1], rt[2], rt[3], rt[4], cfg.model_max_length)
         per_step = args.per_device_batch_size * accum * world
         args.steps_per_epoch = max(1, len(samples) // per_step)            # drop_last, as the window needs equal shards
         real = dict(samples=samples, coll=coll, valid=ds.valid_samples(args.max_his_len), only_response=only_response)
@@ -251,6 +266,14 @@ def main(argv=None):
     elif variant == "qwen3_session":
         cfg = Qwen3SessionConfig(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID,
                                  num_positions=synthetic.TOKENS_PER_ITEM, model_max_length=1024)
+    elif variant == "qwen3_session_moe":
+        # synthetic batches with sessions of mean 4 items on Qwen3Moe's config.json (or --base_model)
+        rt = (synthetic.vocab_size(256, 3), 3, synthetic.behavior_maps(256, 3), synthetic.TOKENS_PER_ITEM, args.max_his_len + 1)
+        if args.base_model:
+            cfg = base_model_config_session_moe(args.base_model, *rt, pad_token_id=synthetic.PAD_ID)
+        else:
+            cfg = apply_runtime_fields(Qwen3SessionMoeConfig(vocab_size=rt[0], pad_token_id=synthetic.PAD_ID, num_positions=rt[3],
+                                                             model_max_length=1024), *rt[1:])
     elif args.base_model:
         cfg = synthetic_base_model_config(args.base_model, args.max_his_len)
     else:
@@ -293,7 +316,7 @@ def main(argv=None):
             return real_micro(step)
         return [synthetic.make_batch(args.per_device_batch_size, items, 256, 3, ragged=args.ragged,
                                      seed=args.seed + 7919 * (step * accum + a) + 104729 * rank,
-                                     session_mean=4.0 if variant in ("session", "qwen3_session") else None)
+                                     session_mean=4.0 if variant in ("session", "qwen3_session", "qwen3_session_moe") else None)
                 for a in range(accum)]
 
     feed = Prefetcher(make_step, state["global_step"], total_steps, args.prefetch)

@@ -143,6 +143,24 @@ int gamer_moe_router_prep(const int64_t* ids, const int64_t* attn_mask, const in
                           int32_t* kl_self, int32_t* empty_self, int32_t* tile_empty_self, int32_t* pos_ids,
                           int32_t* next_pos, int32_t* bad_token, void* stream);
 
+/* Router + session mask of the Qwen3SessionMoe model (ref:SeqRec/models/generative/Qwen3SessionMoe/model.py: Qwen3Moe's layers
+ * and router, :23-93, under Qwen3Session's self mask and RoPE positions, :402-468 and :680-703) in one launch.  Built from the
+ * device functions of the two kernels it combines:
+ *   ids, attn_mask, behavior_lut / vocab, position_table, num_positions, n_items, use_behavior_token, pad_id, eos_id and the
+ *   outputs expert [B,S], beh_idx [B,S], bad_token [1]: exactly as gamer_moe_router_prep's
+ *   session_ids int64 [B,S], extended_session_ids int64 [B,S] (may be NULL: positions 0..S-1), n_rope_positions and the outputs
+ *   kl_self [B,S], span_self [B,S,4], pos_ids [B,S], empty_self [B,S], tile_empty_self [B, ceil(S/32)], violations [1]: exactly
+ *   as gamer_session_prep's
+ * bad_token and violations are incremented, not cleared.  S <= 2048 (the session mask's LDS) and S <= n_items * num_positions + 1
+ * (the router's table); both are refused on the host.  No host synchronisation (graph-capture safe).  Additive in ABI 9.    */
+int gamer_session_moe_prep(const int64_t* ids, const int64_t* attn_mask, const int64_t* session_ids,
+                           const int64_t* extended_session_ids, const int32_t* behavior_lut, int vocab,
+                           const int32_t* position_table, int B, int S, int num_positions, int n_items,
+                           int use_behavior_token, int pad_id, int eos_id, int n_rope_positions,
+                           int32_t* expert, int32_t* beh_idx, int32_t* bad_token, int32_t* kl_self,
+                           int32_t* span_self, int32_t* pos_ids, int32_t* empty_self, int32_t* tile_empty_self,
+                           int32_t* violations, void* stream);
+
 /* Expert token lists for the position-routed FFN (replaces the boolean-mask gather/scatter loop of
  * MyQwen3SparseMLP.forward, ref:SeqRec/models/generative/Qwen3Moe/FFN.py:63-68, and its 6 host
  * syncs per layer).  Deterministic order: expert-major, then token order.
