@@ -107,6 +107,7 @@ _SIGNATURES = {
     "gamer_causal_prep": [P, I, I, P, P, P, P, P, P],
     "gamer_session_prep": [P, P, P, I, I, I, I, P, P, P, P, P, P, P],
     "gamer_moe_router_prep": [P, P, P, I, P, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P],
+    "gamer_moe_action_router_prep": [P, P, P, I, P, I, I, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "gamer_session_moe_prep": [P, P, P, P, P, I, P, I, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P],
     "gamer_embedding_fwd": [P, P, I, I, I, P, P],
     "gamer_embedding_bwd": [P, P, I, I, I, I, P, P],

@@ -198,6 +198,11 @@ class Qwen3MultiConfig:
         return (self.gated_mlp and not self.Moe_behavior_only and
                 sorted(self.sparse_layers_decoder) == list(range(self.num_hidden_layers)))
 
+    @property
+    def num_ffn_experts(self) -> int:
+        """Experts of a sparse layer's FFN.  Here the router's count ``num_experts``; Qwen3MoeAction has more."""
+        return int(self.num_experts)
+
     def position_experts(self):
         """Expert index of each position inside an item (router.py:28-54): 1..num_positions, or with
         Moe_behavior_only 1 for the behaviour token and 2 for every semantic token.  Pad and eos go to expert 0.
@@ -559,3 +564,60 @@ def base_model_config_session_moe(path: str, vocab_size: int, num_behavior: int,
         d["pad_token_id"] = int(pad_token_id)
     cfg = Qwen3SessionMoeConfig(**d)
     return apply_runtime_fields(cfg, num_behavior, behavior_maps, num_positions, n_positions, model_max_length)
+
+
+class Qwen3MoeActionConfig(Qwen3MoeConfig):
+    """Configuration of the Qwen3MoeAction model (ref:SeqRec/models/generative/Qwen3MoeAction/{model,FFN}.py: Qwen3Moe whose FFN
+    expert is chosen by the pair (behaviour of the token's item, position inside the item)).  ``num_experts`` stays the
+    router's count (num_positions + 1, or 2 under Moe_behavior_only); a sparse layer has ``num_ffn_experts`` =
+    (num_experts - 1) * num_behavior + 1 experts (FFN.py:21).  Only ``mlp_type == "Qwen3"`` can run: with "PBATransformer" -
+    the value an absent field falls back to (model.py:49-52) - the reference's decoder layer calls
+    ``PBATransformerSparseMLP.forward`` with four arguments and raises TypeError, so construction refuses it.  The reference
+    constructs this class in no task; the harness sets Qwen3Moe's run-time fields (``apply_mb_runtime_fields``)."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self._check_mlp_type()
+
+    def _check_mlp_type(self):
+        if self.mlp_type != "Qwen3":
+            raise ValueError(f"Qwen3MoeAction runs mlp_type 'Qwen3' only, not {self.mlp_type!r}: the reference's decoder layer "
+                             "calls PBATransformerSparseMLP.forward with four arguments (hidden states, position, behaviour "
+                             "and action index) and raises TypeError; 'PBATransformer' is also what a config.json without "
+                             "mlp_type falls back to (Qwen3MoeAction/model.py:49-52)")
+
+    @classmethod
+    def coerce(cls, config) -> "Qwen3MoeActionConfig":
+        """As ``Qwen3MoeConfig.coerce`` (an HF config object without ``mlp_type`` is refused, as its "PBATransformer")."""
+        if isinstance(config, cls):
+            return config
+        if isinstance(config, dict):
+            return cls(**config)
+        return cls(**Qwen3MoeConfig.coerce(config).to_dict())
+
+    @property
+    def num_ffn_experts(self) -> int:
+        """(num_experts - 1) * num_behavior + 1 (FFN.py:21): expert 0 for pad / eos and tokens without an action, then
+        num_experts - 1 position experts per behaviour."""
+        return (int(self.num_experts) - 1) * int(self.num_behavior) + 1
+
+    def validate(self):
+        self._check_mlp_type()
+        if not self.use_behavior_token:
+            raise ValueError("Qwen3MoeAction needs behaviour tokens (use_behavior_token=True): without them every action "
+                             "index is 0 and the model collapses to one expert")
+        super().validate()
+        if self.num_ffn_experts > 64:
+            raise ValueError(f"num_ffn_experts = (num_experts - 1) * num_behavior + 1 = {self.num_ffn_experts}: the expert "
+                             "lists (gamer_expert_lists) hold at most 64 groups")
+
+
+def base_model_config_moe_action(path: str, vocab_size: int, num_behavior: int, behavior_maps: dict, num_positions: int,
+                                 max_his_len: int = 20, pad_token_id: int = None) -> Qwen3MoeActionConfig:
+    """``--base_model DIR`` for ``--backbone Qwen3MoeAction``: DIR/config.json (a file without mlp_type is refused, see the
+    class), the vocabulary resized to the tokenizer's, then ``apply_mb_runtime_fields`` with behaviour tokens."""
+    cfg = Qwen3MoeActionConfig.from_pretrained(path)
+    cfg.vocab_size = int(vocab_size)
+    if pad_token_id is not None:
+        cfg.pad_token_id = int(pad_token_id)
+    return apply_mb_runtime_fields(cfg, num_behavior, behavior_maps, True, num_positions, max_his_len)

@@ -521,16 +521,16 @@ extern "C" int gamer_causal_prep(const int64_t* attn_mask, int B, int S, int32_t
 //                (the reference fails in its embedding there) and gets 0.  use_beh == 0: 0 everywhere.
 //   kl_self / empty_self / tile_empty_self / pos_ids / next_pos: as causal_prep_kernel.
 // One workgroup per sequence; LDS holds the kept-flag prefix sum (2 S int32).
-// expert[t] and beh_idx[t] of token t of one row (``ids`` / ``expert`` / ``beh_idx``: the row's); returns 1 for a non-special
-// item start outside behavior_maps (the row's share of bad_token), else 0.
+// Position expert ``e`` and behaviour index ``bi`` of token t of one row (``ids``: the row's); returns 1 for a non-special item
+// start outside behavior_maps (the row's share of bad_token), else 0.
 __device__ __forceinline__ int
-moe_route_token(const int64_t* __restrict__ ids, int t, const int32_t* __restrict__ lut, int vocab,
-                const int32_t* __restrict__ table, int P, int slots, int use_beh, int pad_id, int eos_id,
-                int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx) {
+moe_route_indices(const int64_t* __restrict__ ids, int t, const int32_t* __restrict__ lut, int vocab,
+                  const int32_t* __restrict__ table, int P, int slots, int use_beh, int pad_id, int eos_id, int& e, int& bi) {
     const int64_t id = ids[t];
     const bool special = (id == pad_id) || (id == eos_id);
     const int p = t % P;
-    int e = 0, bi = 0;
+    e = 0;
+    bi = 0;
     if (!special && t < slots) {
         e = table ? table[p] : p + 1;
         if (use_beh && p != 0) {
@@ -538,16 +538,56 @@ moe_route_token(const int64_t* __restrict__ ids, int t, const int32_t* __restric
             if (btok >= 0 && btok < vocab && lut[btok] >= 0) bi = lut[btok] + 1;
         }
     }
-    expert[t] = e;
-    beh_idx[t] = bi;
     return (use_beh && p == 0 && !special && t < slots && !(id >= 0 && id < vocab && lut[id] >= 0)) ? 1 : 0;
 }
 
+// expert[t] and beh_idx[t] of token t of one row (``expert`` / ``beh_idx``: the row's): Qwen3Moe's routing.
+__device__ __forceinline__ int
+moe_route_token(const int64_t* __restrict__ ids, int t, const int32_t* __restrict__ lut, int vocab,
+                const int32_t* __restrict__ table, int P, int slots, int use_beh, int pad_id, int eos_id,
+                int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx) {
+    int e, bi;
+    const int bad = moe_route_indices(ids, t, lut, vocab, table, P, slots, use_beh, pad_id, eos_id, e, bi);
+    expert[t] = e;
+    beh_idx[t] = bi;
+    return bad;
+}
+
+// Qwen3MoeAction's routing of token t (ref:SeqRec/models/generative/Qwen3Multi/router.py:154-199 with cache_position = arange(S),
+// Qwen3MoeAction/FFN.py:43-44): the action index is lut[ids[item start]] + 1 on every token of the item, the behaviour token
+// included; 0 at pad / eos, in the action table's own eos slot - column ((S + P - 2) / P) P, inside the sequence only as the
+// last column of S = n P + 1 tokens -, in column ``act_zero_col`` (a generation's re-run: what the cache holds for the
+// prompt's last column; -1: none), and for an item start outside behavior_maps.  expert[t] is the FFN's index
+// max(0, pos_experts (action - 1) + position expert).
+__device__ __forceinline__ int
+moe_action_route_token(const int64_t* __restrict__ ids, int t, const int32_t* __restrict__ lut, int vocab,
+                       const int32_t* __restrict__ table, int S, int P, int slots, int use_beh, int pad_id, int eos_id,
+                       int pos_experts, int act_zero_col, int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx,
+                       int32_t* __restrict__ act_idx) {
+    int e, bi;
+    const int bad = moe_route_indices(ids, t, lut, vocab, table, P, slots, use_beh, pad_id, eos_id, e, bi);
+    const int64_t id = ids[t];
+    int act = 0;
+    if (use_beh && id != pad_id && id != eos_id && t < slots && t != ((S + P - 2) / P) * P && t != act_zero_col) {
+        const int64_t btok = ids[t - t % P];
+        if (btok >= 0 && btok < vocab && lut[btok] >= 0) act = lut[btok] + 1;
+    }
+    const int idx = pos_experts * (act - 1) + e;
+    expert[t] = idx < 0 ? 0 : idx;
+    beh_idx[t] = bi;
+    act_idx[t] = act;
+    return bad;
+}
+
+// ACTION = true: Qwen3MoeAction (moe_action_route_token: ``expert`` is the FFN's index, ``act_idx`` is written); the mask half
+// is the same code.
+template <bool ACTION>
 __global__ void __launch_bounds__(ROUTER_THREADS)
 moe_router_prep_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ attn_mask,
                        const int32_t* __restrict__ lut, int vocab, const int32_t* __restrict__ table, int S, int P,
-                       int n_items, int use_beh, int pad_id, int eos_id,
-                       int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx, int32_t* __restrict__ kl_self,
+                       int n_items, int use_beh, int pad_id, int eos_id, int pos_experts, int act_zero_col,
+                       int32_t* __restrict__ expert, int32_t* __restrict__ beh_idx, int32_t* __restrict__ act_idx,
+                       int32_t* __restrict__ kl_self,
                        int32_t* __restrict__ empty_self, int32_t* __restrict__ tile_empty_self,
                        int32_t* __restrict__ pos_ids, int32_t* __restrict__ next_pos, int32_t* __restrict__ bad_token) {
     extern __shared__ __attribute__((aligned(16))) int32_t ms[];
@@ -559,7 +599,11 @@ moe_router_prep_kernel(const int64_t* __restrict__ ids, const int64_t* __restric
     const int slots = n_items * P;
     int bad = 0;
     for (int t = threadIdx.x; t < S; t += blockDim.x) {
-        bad += moe_route_token(ids + base, t, lut, vocab, table, P, slots, use_beh, pad_id, eos_id, expert + base, beh_idx + base);
+        if (ACTION)
+            bad += moe_action_route_token(ids + base, t, lut, vocab, table, S, P, slots, use_beh, pad_id, eos_id, pos_experts,
+                                          act_zero_col, expert + base, beh_idx + base, act_idx + base);
+        else
+            bad += moe_route_token(ids + base, t, lut, vocab, table, P, slots, use_beh, pad_id, eos_id, expert + base, beh_idx + base);
         const int keep = attn_mask ? (attn_mask[base + t] != 0 ? 1 : 0) : 1;
         kl_self[base + t] = keep ? 0 : INT_BIG;
         a[t] = keep;
@@ -600,11 +644,41 @@ extern "C" int gamer_moe_router_prep(const int64_t* ids, const int64_t* attn_mas
                     "gamer_moe_router_prep: S=%d is longer than the router's table (n_items * P + 1 = %lld)", S,
                     (long long)n_items * num_positions + 1);
     const size_t shmem = (size_t)2 * S * sizeof(int32_t);
-    hipLaunchKernelGGL(moe_router_prep_kernel, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
+    hipLaunchKernelGGL(moe_router_prep_kernel<false>, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
                        ids, attn_mask, behavior_lut, vocab, position_table, S, num_positions, n_items,
-                       use_behavior_token ? 1 : 0, pad_id, eos_id, expert, beh_idx, kl_self, empty_self, tile_empty_self,
-                       pos_ids, next_pos, bad_token);
+                       use_behavior_token ? 1 : 0, pad_id, eos_id, 0, -1, expert, beh_idx, nullptr, kl_self, empty_self,
+                       tile_empty_self, pos_ids, next_pos, bad_token);
     GAMER_CHECK_LAUNCH("gamer_moe_router_prep");
+    return 0;
+}
+
+// ---- Qwen3MoeAction router + causal mask (one launch) -----------------------------------------------------------------
+// gamer_moe_router_prep with the action index and the (action, position) FFN index of moe_action_route_token.
+extern "C" int gamer_moe_action_router_prep(const int64_t* ids, const int64_t* attn_mask, const int32_t* behavior_lut, int vocab,
+                                            const int32_t* position_table, int B, int S, int num_positions, int n_items,
+                                            int use_behavior_token, int pad_id, int eos_id, int num_position_experts,
+                                            int act_zero_col, int32_t* expert, int32_t* beh_idx, int32_t* act_idx,
+                                            int32_t* kl_self, int32_t* empty_self, int32_t* tile_empty_self, int32_t* pos_ids,
+                                            int32_t* next_pos, int32_t* bad_token, void* stream) {
+    GAMER_CHECK_ARG(ids && expert && beh_idx && act_idx && kl_self && empty_self && tile_empty_self && bad_token,
+                    "gamer_moe_action_router_prep: null pointer");
+    GAMER_CHECK_ARG(!use_behavior_token || (behavior_lut && vocab > 0),
+                    "gamer_moe_action_router_prep: use_behavior_token needs the behaviour table");
+    GAMER_CHECK_ARG(B > 0 && S > 0 && num_positions > 0 && n_items > 0 && num_position_experts > 0,
+                    "gamer_moe_action_router_prep: bad shape B=%d S=%d P=%d n_items=%d position experts=%d", B, S,
+                    num_positions, n_items, num_position_experts);
+    GAMER_CHECK_ARG(act_zero_col >= -1 && act_zero_col < S, "gamer_moe_action_router_prep: act_zero_col=%d outside [-1, S=%d)",
+                    act_zero_col, S);
+    GAMER_CHECK_ARG(S <= 8192, "gamer_moe_action_router_prep: S=%d > 8192 unsupported", S);
+    GAMER_CHECK_ARG((int64_t)n_items * num_positions + 1 >= S,
+                    "gamer_moe_action_router_prep: S=%d is longer than the router's table (n_items * P + 1 = %lld)", S,
+                    (long long)n_items * num_positions + 1);
+    const size_t shmem = (size_t)2 * S * sizeof(int32_t);
+    hipLaunchKernelGGL(moe_router_prep_kernel<true>, dim3(B), dim3(ROUTER_THREADS), shmem, (hipStream_t)stream,
+                       ids, attn_mask, behavior_lut, vocab, position_table, S, num_positions, n_items,
+                       use_behavior_token ? 1 : 0, pad_id, eos_id, num_position_experts, act_zero_col, expert, beh_idx, act_idx,
+                       kl_self, empty_self, tile_empty_self, pos_ids, next_pos, bad_token);
+    GAMER_CHECK_LAUNCH("gamer_moe_action_router_prep");
     return 0;
 }
 

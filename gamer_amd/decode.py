@@ -504,7 +504,7 @@ class DecodeSession:
         """Layer ``l`` after its self-attention block (output x1): the layer output into x.  Qwen3Multi: the cross block with
         the behaviour biases and the output gate, the behaviour injection and the position-routed expert FFN."""
         eng, cfg, b, N = self.eng, self.eng.cfg, self.buf, self.N
-        H, I, E, NQ, eps = cfg.hidden_size, cfg.intermediate_size, cfg.num_experts, self.NQ, float(cfg.rms_norm_eps)
+        H, I, E, NQ, eps = cfg.hidden_size, cfg.intermediate_size, cfg.num_ffn_experts, self.NQ, float(cfg.rms_norm_eps)
         Wm = eng.Wm[l]                                   # the GEMMs' operands (W itself in fp32)
         xc = x1
         if W.cross:
@@ -638,6 +638,59 @@ class Qwen3SessionMoeDecodeSession(Qwen3MoeDecodeSession):
         self.beh = keep("beh", beh.repeat_interleave(self.nb))
 
 
+def _check_moe_action_generation(engine, L0: int, max_new_tokens: int):
+    """What a Qwen3MoeAction generation is built for besides ``_check_moe_generation``: a prompt of n P + 1 tokens (whole items
+    and the target behaviour token) and new tokens inside the target item, so that every generated token has the target
+    behaviour's action and the only column the reference's cache freezes at action 0 is the prompt's last."""
+    _check_moe_generation(engine, L0, max_new_tokens)
+    P = int(engine.cfg.num_positions)
+    if L0 % P != 1 % P or max_new_tokens > P:
+        raise ValueError(f"a Qwen3MoeAction generation takes prompts of n * num_positions + 1 tokens and at most num_positions "
+                         f"new ones (got {L0} and {max_new_tokens}, num_positions = {P})")
+
+
+class Qwen3MoeActionDecodeSession(Qwen3MoeDecodeSession):
+    """K/V cache + single-token step of Qwen3MoeAction (``Engine(variant="qwen3moe_action")``): ``Qwen3MoeDecodeSession`` whose
+    rows sit in up to ``num_behavior`` experts per step.  The prompt pass is gamer_moe_action_router_prep's: the last column of
+    the n P + 1 prompt tokens keeps the reference's action 0 (the action table's eos slot) in the cache.  The token generated
+    at step t runs in expert (num_experts - 1) * (a_row - 1) + table[(L0 + t - 1) % P], a_row = the behaviour of the row's
+    last prompt token, which is also its injected behaviour.  A row's behaviour never changes and beams stay inside their
+    user, so the rows' expert lists (gamer_expert_lists over the [B, beams] index) are built once per session, one set per
+    position of an item, at fixed addresses; a step sorts its rows through them for the grouped GEMMs as the forward pass
+    does - no host loop over experts, no synchronisation."""
+
+    def __init__(self, engine, input_ids, attention_mask, num_beams: int, max_new_tokens: int):
+        _check_generation_dtype(engine)
+        _check_moe_action_generation(engine, input_ids.shape[1], max_new_tokens)
+        super().__init__(engine, input_ids, attention_mask, num_beams, max_new_tokens)
+
+    @staticmethod
+    def _eval_forward(engine, ids, am, act, sess: dict, L0: int, **kw):
+        """The prompt pass, and the cache-free re-run with what the cache freezes: action 0 in column L0 - 1."""
+        engine.forward(ids, am, train=False, rope_from_mask=True, act_zero_col=L0 - 1, **kw)
+
+    def _row_inputs(self, keep, ids0, am0, act0, sess: dict):
+        super()._row_inputs(keep, ids0, am0, act0, sess)
+        eng, cfg = self.eng, self.eng.cfg
+        P = int(cfg.num_positions)
+        table = torch.tensor(cfg.position_experts(), dtype=torch.int32, device=eng.device)
+        self.lists = {}
+        for t in range(1, self.tmax):
+            p = (self.L0 + t - 1) % P
+            e = ((cfg.num_experts - 1) * (self.beh - 1) + table[p]).clamp_(min=0).to(torch.int32).view(self.B, self.nb)
+            self.lists[p] = tuple(keep(f"action_{name}_{p}", v) for name, v in zip(("perm", "slot", "offsets"), eng.row_lists(e)))
+
+    def _layer_tail(self, t: int, l: int, W, x, x1):
+        """The FFN: a dense layer's one MLP, or the experts of the rows' (behaviour, position) pairs."""
+        eng, b = self.eng, self.buf
+        pos = (self.L0 + t - 1) % eng.cfg.num_positions
+        beh = self.beh if W.inject else None
+        if not W.sparse:
+            eng.ffn_rows(W, pos, x1, beh, x, eng.Wm[l])
+            return
+        eng.ffn_rows_grouped(W, self.lists[pos], x1, beh, x, bufs=dict(hin=b.get("hin", b["h"]), gu=b["gu"], hm=b["hm"]))
+
+
 @torch.no_grad()
 def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, actions: torch.Tensor, trie: ItemTrie,
                 num_beams: int, max_new_tokens: int = 4, use_cache: bool = True, session_ids=None,
@@ -659,13 +712,16 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
     trace = []
     qwen3 = engine.variant in ("qwen3", "qwen3_session")
     session_moe = engine.variant == "qwen3_session_moe"
-    moe = engine.variant == "qwen3moe" or session_moe       # (no behaviour levels either: no actions, no cross cache)
+    action_moe = engine.variant == "qwen3moe_action"
+    moe = engine.variant == "qwen3moe" or session_moe or action_moe     # (no behaviour levels either: no actions, no cross cache)
     if not use_cache and not reorder_cross_cache and not (qwen3 or moe):
         raise ValueError("use_cache=False re-computes every position for its own beam: it can only reproduce "
                          "reorder_cross_cache=True (the shipped reference's un-reordered cross cache needs the cache)")
     cls = (Qwen3DecodeSession if qwen3 else Qwen3SessionMoeDecodeSession if session_moe else
-           Qwen3MoeDecodeSession if moe else DecodeSession)
-    if moe:
+           Qwen3MoeActionDecodeSession if action_moe else Qwen3MoeDecodeSession if moe else DecodeSession)
+    if action_moe:
+        _check_moe_action_generation(engine, input_ids.shape[1], max_new_tokens)
+    elif moe:
         _check_moe_generation(engine, input_ids.shape[1], max_new_tokens)
     dev = engine.device
     B, L0 = input_ids.shape
@@ -693,6 +749,8 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
         session = Qwen3DecodeSession(engine, ids0, am0, nb, max_new_tokens, **sess0)
     elif session_moe:
         session = Qwen3SessionMoeDecodeSession(engine, ids0, am0, nb, max_new_tokens, **sess0)
+    elif action_moe:
+        session = Qwen3MoeActionDecodeSession(engine, ids0, am0, nb, max_new_tokens)
     elif moe:
         session = Qwen3MoeDecodeSession(engine, ids0, am0, nb, max_new_tokens)
     else:

@@ -84,7 +84,7 @@ class ParamLayout(_FlatLayout):
     def __init__(self, cfg: Qwen3MultiConfig, version: int = 2):
         H, dh = cfg.hidden_size, cfg.head_dim
         nq, nkv, I = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.intermediate_size
-        Eb, NB1, E = cfg.behavior_embedding_dim, cfg.num_behavior + 1, cfg.num_experts
+        Eb, NB1, E = cfg.behavior_embedding_dim, cfg.num_behavior + 1, cfg.num_ffn_experts
         self.version = version
         decay: List[Tuple[str, tuple]] = [("model.embed_tokens.weight", (cfg.vocab_size, H))]
         nodecay: List[Tuple[str, tuple]] = []
@@ -150,7 +150,7 @@ class _LayerW:
 
     def __init__(self, cfg, layout: ParamLayout, flat: torch.Tensor, l: int):
         H, dh = cfg.hidden_size, cfg.head_dim
-        nq, nkv, I, E = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.intermediate_size, cfg.num_experts
+        nq, nkv, I, E = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.intermediate_size, cfg.num_ffn_experts
         QKV = (nq + 2 * nkv) * dh
         v = layout.views(flat)
         lp = f"model.layers.{l}."
@@ -405,6 +405,9 @@ class Engine:
         elif cls is Engine and variant == "qwen3moe":       # Qwen3Moe (gamer_amd/engine_qwen3moe.py)
             from .engine_qwen3moe import Qwen3MoeEngine
             cls = Qwen3MoeEngine
+        elif cls is Engine and variant == "qwen3moe_action":        # Qwen3MoeAction (the same module)
+            from .engine_qwen3moe import Qwen3MoeActionEngine
+            cls = Qwen3MoeActionEngine
         elif cls is Engine and variant == "qwen3_session_moe":      # Qwen3SessionMoe (the same module)
             from .engine_qwen3moe import Qwen3SessionMoeEngine
             cls = Qwen3SessionMoeEngine
@@ -442,8 +445,8 @@ class Engine:
         matmul = _matmul_arg(dtype, matmul)
         _check_split_dtype(dtype, matmul)
         if variant not in self._VARIANTS:
-            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3, qwen3_session, qwen3moe or "
-                             "qwen3_session_moe)")
+            raise ValueError(f"unknown variant {variant!r} (multi, session, qwen3, qwen3_session, qwen3moe, "
+                             "qwen3_session_moe or qwen3moe_action)")
         _check_dtype(dtype)
         if variant == "session":
             self.key_spans = True
@@ -461,7 +464,7 @@ class Engine:
         # sorted by (expert, behaviour).  GAMER_SPLIT_INJECT=0: the reference's concatenated [T, 320] input (A/B runs).
         nb1 = cfg.num_behavior + 1
         self.split_inject = bool(self.dtype != "bf16" and os.environ.get("GAMER_SPLIT_INJECT", "1") != "0" and
-                                 cfg.behavior_injection_decoder and cfg.num_experts * nb1 <= 64 and nb1 <= 16 and
+                                 cfg.behavior_injection_decoder and cfg.num_ffn_experts * nb1 <= 64 and nb1 <= 16 and
                                  cfg.behavior_embedding_dim % 4 == 0 and cfg.behavior_embedding_dim <= 256 and cfg.shipped_ffn)
         # Moe_behavior_only: the router's position table [1, 2, 2, ...] (pad / eos 0) over gamer_router_fwd's [1, 2, 3, ...]
         self.position_table = (torch.tensor([0] + cfg.position_experts(), dtype=torch.int32, device=self.device)
@@ -624,7 +627,7 @@ class Engine:
         """The router's outputs (attention masks, expert / behaviour / action indices), the expert lists and the query-row
         order of the cross attention, at the workspace's new shape."""
         i32 = torch.int32
-        T, E, n_t32 = B * S, ws.cfg.num_experts, (S + 31) // 32
+        T, E, n_t32 = B * S, ws.cfg.num_ffn_experts, (S + 31) // 32
         buf = ws._buf
         ws.router = {k: buf("r_" + k, (B, S), i32) for k in
                      ("expert", "beh_idx", "act_idx", "kl_self", "kl_cross", "ql_cross", "empty_self", "empty_cross")}
@@ -698,7 +701,7 @@ class Engine:
                            eval_only="last_row_logits is an evaluation-only option" if last_row_logits else None,
                            f32_only=self._bf16_refusal(kv_dest, last_row_logits or uniform_len not in (0, S)))
         ws, ids, am, bf16 = c.ws, c.ids, c.am, c.bf16
-        T, H, nq, nkv, I, E = c.T, c.H, c.nq, c.nkv, c.I, cfg.num_experts
+        T, H, nq, nkv, I, E = c.T, c.H, c.nq, c.nkv, c.I, cfg.num_ffn_experts
         NQ, NKV, QKV, eps, scale, cos, sin, p_res = c.NQ, c.NKV, c.QKV, c.eps, c.scale, c.cos, c.sin, c.p_res
         r = ws.router
         r["bad_token"].zero_()
@@ -839,7 +842,7 @@ class Engine:
                 f32 = dict(dtype=torch.float32, device=self.device)
                 beh = r["beh_idx"].view(-1).index_select(0, rows).contiguous() if W.inject else None
                 x_last = torch.empty(B, H, **f32)
-                self.ffn_rows(W, (S - 1) % cfg.num_positions, xl, beh, x_last, Wm)
+                self._ffn_last_rows(W, S, rows, xl, beh, x_last, Wm)
                 break
             xnext = ws.x[l + 1][0] if l + 1 < cfg.num_hidden_layers else ws.x_final
             if not self._shipped_ffn_layer(W):
@@ -1008,6 +1011,11 @@ class Engine:
         else:
             ops.silu_fwd_ld(gu, nI, B, I, 0.0, 0, hm)
         ops.gemm(hm, I, 1, Wm.down[e * H:(e + 1) * H], I, 1, out, H, B, H, I, resid=x)
+
+    def _ffn_last_rows(self, W, S: int, rows, x, beh, out, Wm):
+        """The FFN of a prompt pass's last layer on the last position of every sample (token rows ``rows`` of the pass): here
+        one position, hence one expert, for every row."""
+        self.ffn_rows(W, (S - 1) % self.cfg.num_positions, x, beh, out, Wm)
 
     def _pass(self, B: int, S: int, p_res: float, p_att: float) -> SimpleNamespace:
         """Shapes, dropout and kernel forms of one forward or backward pass (the context of the shared blocks below)."""
@@ -1211,7 +1219,7 @@ class Engine:
         all-reduce overlap, gamer_amd.dp)."""
         cfg = self.cfg
         c = self._backward_head(dloss, dloss_dev, rows=self._ffn_rows(cfg.num_hidden_layers - 1))
-        ws, B, S, T, H, I, E = c.ws, c.B, c.S, c.T, c.H, c.I, cfg.num_experts
+        ws, B, S, T, H, I, E = c.ws, c.B, c.S, c.T, c.H, c.I, cfg.num_ffn_experts
         nq, nkv, NQ, NKV, QKV, eps, cos, sin, p_res = c.nq, c.nkv, c.NQ, c.NKV, c.QKV, c.eps, c.cos, c.sin, c.p_res
         NB1 = cfg.num_behavior + 1
         span_self = span_cross = pos_ids = None

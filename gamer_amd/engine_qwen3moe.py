@@ -19,6 +19,13 @@ window, data parallelism).  What this engine changes:
 (ref:SeqRec/models/generative/Qwen3SessionMoe/model.py): the same layers, router and loops under Qwen3Session's session-wise
 self mask and RoPE positions.  ``gamer_session_moe_prep`` builds the router outputs and the mask in one launch; that launch,
 its buffers and the argument checks are all the class adds.
+
+``Engine(cfg, variant="qwen3moe_action")`` constructs ``Qwen3MoeActionEngine``, the Qwen3MoeAction model
+(ref:SeqRec/models/generative/Qwen3MoeAction/{model,FFN}.py): Qwen3Moe whose FFN expert is chosen by the pair (behaviour of
+the token's item, position inside the item) among ``cfg.num_ffn_experts`` = (num_experts - 1) * num_behavior + 1 experts.
+``gamer_moe_action_router_prep`` writes that index where Qwen3Moe's launch writes the position's; the layout, the expert
+lists and the grouped GEMMs take their count from ``cfg.num_ffn_experts``, so the class adds only the launch - and the FFN
+of rows that sit at one position but in several experts (a generation's last prompt row and decode step).
 """
 from __future__ import annotations
 
@@ -27,7 +34,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .config import Qwen3MoeConfig, Qwen3SessionMoeConfig
+from .config import Qwen3MoeActionConfig, Qwen3MoeConfig, Qwen3SessionMoeConfig
 from .engine import Engine, ParamLayout
 
 
@@ -163,3 +170,82 @@ class Qwen3SessionMoeEngine(Qwen3MoeEngine):
             raise ValueError(f"{n} row(s) with session ids that decrease along the sequence or RoPE positions "
                              "outside [0, S): the session masks are built as causal key spans "
                              "(gamer_session_moe_prep), which needs the dataset's layout (SMB_dataset.py:194-222)")
+
+
+class Qwen3MoeActionEngine(Qwen3MoeEngine):
+    """The Qwen3MoeAction model (``--backbone Qwen3MoeAction``): Qwen3Moe's layers, mask, positions and loops; the router's
+    one launch also writes the action index and routes every token to expert max(0, (num_experts - 1) * (action - 1) +
+    position expert) of ``cfg.num_ffn_experts`` (FFN.py:43-44).  With the shipped five positions and four behaviours the 21
+    experts times 5 behaviour indices exceed the 64 groups of the (expert, behaviour) inject table, so ``split_inject`` is
+    off and the fp32 forms take the concatenated [T, H + Eb] input, as the bf16 form always does."""
+
+    _VARIANTS = ("qwen3moe_action",)
+    _config_cls = Qwen3MoeActionConfig
+
+    def _route(self, c, actions, act_zero_col, rope_from_mask: bool):
+        """gamer_moe_action_router_prep: ``Qwen3MoeEngine._route`` with the action index and the FFN's expert index.
+        ``act_zero_col`` (a generation's re-run): the column whose action stays 0, as in the reference's cache."""
+        cfg, ws = self.cfg, c.ws
+        pos = None
+        if rope_from_mask:
+            pos = ws._buf("moe_pos_ids", (c.B, c.S), torch.int32)
+            self.next_pos = ws._buf("moe_next_pos", (c.B,), torch.int32)
+        if c.S > self.max_len():
+            raise ValueError(f"sequence length {c.S} exceeds the router's table, n_positions * num_positions + 1 = "
+                             f"{self.max_len()} (router.py:46-60)")
+        ops.moe_action_router_prep(c.ids, c.am, self.lut, self.moe_table, cfg.num_positions, cfg.n_positions,
+                                   cfg.use_behavior_token, cfg.pad_token_id, cfg.eos_token_id, cfg.num_experts - 1,
+                                   cfg.num_ffn_experts, ws.router, pos_ids=pos, next_pos=self.next_pos if rope_from_mask else None,
+                                   act_zero_col=act_zero_col)
+        return pos
+
+    def forward(self, input_ids, attention_mask=None, actions=None, labels=None, num_items_in_batch=None,
+                train: bool = False, dropout: Optional[bool] = None, kv_sink=None, kv_dest=None, session_ids=None,
+                extended_session_ids=None, last_row_logits: bool = False, hidden_sink: Optional[list] = None,
+                rope_from_mask: bool = False, act_zero_col: Optional[int] = None):
+        """``Qwen3MoeEngine.forward``; ``act_zero_col`` (evaluation only) as in ``Engine.forward``."""
+        return Engine.forward(self, input_ids, attention_mask, None, labels, num_items_in_batch, train=train, dropout=dropout,
+                              act_zero_col=act_zero_col, kv_sink=kv_sink, kv_dest=kv_dest, last_row_logits=last_row_logits,
+                              hidden_sink=hidden_sink, rope_from_mask=rope_from_mask)
+
+    def row_lists(self, expert: torch.Tensor) -> tuple:
+        """(perm, slot, offsets) of gamer_expert_lists over ``expert`` [B, n] int32 on the device: the FFN index of B * n
+        rows, which ``ffn_rows_grouped`` takes."""
+        B, n = expert.shape
+        E = self.cfg.num_ffn_experts
+        i32 = dict(dtype=torch.int32, device=self.device)
+        perm, slot = torch.empty(B * n, **i32), torch.empty(B * n, **i32)
+        offsets = torch.empty(E + 1, **i32)
+        ops.expert_lists(expert.contiguous(), E, perm, slot, offsets, torch.empty((B + 1) * E, **i32))
+        return perm, slot, offsets
+
+    def ffn_rows_grouped(self, W, lists: tuple, x, beh, out, bufs: Optional[dict] = None):
+        """The FFN of a sparse layer W on rows in several experts (no dropout): out = x + FFN(x), with the rows sorted by
+        expert (``lists`` of ``row_lists``) for the grouped GEMMs exactly as in the forward pass - the norm writes sorted rows,
+        the down projection's epilogue adds the residual and scatters back.  A row in no group (behaviour-only routing) keeps
+        out = x.  ``bufs``: hin / gu / hm buffers at fixed addresses (a decode step); fp32 operands only."""
+        cfg = self.cfg
+        perm, slot, offsets = lists
+        N, H, I, din, nI = x.shape[0], cfg.hidden_size, cfg.intermediate_size, W.din, W.nI
+        f32 = dict(dtype=torch.float32, device=self.device)
+        hin = (bufs["hin"] if bufs else torch.empty(N, din, **f32)).view(-1)[:N * din].view(N, din)
+        gu = bufs["gu"] if bufs else torch.empty(N, nI, **f32)
+        hm = bufs["hm"] if bufs else torch.empty(N, I, **f32)
+        grp = dict(groups=W.ne, group_offsets=offsets)
+        ops.rmsnorm_fwd(x, W.ln3, float(cfg.rms_norm_eps), hin, din, slot)
+        if W.inject:
+            ops.rowtable_fwd(W.beh, beh, hin, din, H, slot)
+        if cfg.Moe_behavior_only:
+            gu.zero_()          # (rows in no group are never written by the GEMM)
+            out.copy_(x)
+        ops.linear_fwd(hin, din, W.gu, din, gu, nI, N, nI, din, strideB=nI * din, **grp)
+        ops.swiglu_fwd_ld(gu, nI, N, I, 0.0, 0, hm)
+        ops.gemm(hm, I, 1, W.down, I, 1, out, H, N, H, I, strideB=H * I, resid=x, row_map=perm, **grp)
+
+    def _ffn_last_rows(self, W, S: int, rows, x, beh, out, Wm):
+        """The last prompt position of every sample in its own row's expert (a prompt of n P + 1 tokens: expert 0, the action
+        table's eos slot)."""
+        if not W.sparse:
+            return super()._ffn_last_rows(W, S, rows, x, beh, out, Wm)
+        e = self.ws.router["expert"].view(-1).index_select(0, rows).view(-1, 1)
+        self.ffn_rows_grouped(W, self.row_lists(e), x, beh, out)

@@ -1,7 +1,8 @@
 """Evaluation loop of one target behaviour: beam search + ranking metrics.
 
 Mirror of ``TestSMBDecoder.test_single_behavior`` (ref:SeqRec/tasks/test_SMB_decoder.py:90-285) for the
-Qwen3Multi backbones and the plain Qwen3 baseline (which ignores ``actions``): every batch is a dict with left-padded
+Qwen3Multi backbones, the plain Qwen3 baseline and the Qwen3Moe family (which ignore ``actions``; ``beam_search`` picks the decode
+session of the engine's variant - Qwen3MoeAction's users may have different target behaviours in one batch): every batch is a dict with left-padded
 ``input_ids`` / ``attention_mask`` / ``actions`` that already end with the target behaviour token (test_SMB_decoder.py:112-118) and ``targets``: per sample the
 list of held-out items (token tuples of the 4 semantic IDs).  Under ``torch.distributed`` every rank evaluates its
 own batches and the metric sums are all-reduced (the reference gathers Python objects; the sums are the same).

@@ -236,17 +236,18 @@ class MBCollator:
         return res
 
 
-def qwen3moe_config(data: MBData, max_his_len: int, base_model: Optional[str] = None, **overrides):
+def qwen3moe_config(data: MBData, max_his_len: int, base_model: Optional[str] = None, config_cls=None, **overrides):
     """The config of ``--backbone Qwen3Moe`` (train_MB_decoder.py:251-252, 326-362): config.json (``base_model`` DIR, or this
     project's copy of the reference's defaults) with the tokenizer's vocabulary, behaviour token id -> index in
     ``behaviors`` order, behaviour tokens or not, tokens per item, the routing mode's expert count, n_positions =
     max_his_len + 1.  ``mb_explicit_back`` is refused: its behaviour token ends the item, and the router reads behaviour
-    tokens at item starts (router.py:97-120)."""
+    tokens at item starts (router.py:97-120).  ``config_cls``: a subclass of ``Qwen3MoeConfig`` (``--backbone Qwen3MoeAction``)."""
     from .config import Qwen3MoeConfig, apply_mb_runtime_fields
+    config_cls = config_cls or Qwen3MoeConfig
     if data.kind == "explicit" and not data.behavior_first:
         raise ValueError("task mb_explicit_back puts the behaviour token last; the Qwen3Moe router reads behaviour tokens "
                          "at item starts - use --backbone Qwen3 for this task")
-    cfg = Qwen3MoeConfig.from_pretrained(base_model) if base_model else Qwen3MoeConfig()
+    cfg = config_cls.from_pretrained(base_model) if base_model else config_cls()
     cfg.vocab_size, cfg.pad_token_id = len(data.tokens), data.tokens.pad_id
     for k, v in overrides.items():
         setattr(cfg, k, v)

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .config import Qwen3MoeConfig, Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig, Qwen3SessionMoeConfig
+from .config import Qwen3MoeActionConfig, Qwen3MoeConfig, Qwen3Config, Qwen3MultiConfig, Qwen3SessionConfig, Qwen3SessionMoeConfig
 from .engine import Engine
 
 
@@ -491,3 +491,14 @@ class Qwen3SessionMoeWithTemperature(Qwen3WithTemperature):
     USES_SESSIONS = True
 
     _check_config = staticmethod(Qwen3MultiWithTemperature._check_config)
+
+
+class Qwen3ActionMoeWithTemperature(Qwen3MoeWithTemperature):
+    """ref:SeqRec/models/generative/Qwen3MoeAction/model.py:608-660 - Qwen3Moe whose FFN expert is chosen by the pair
+    (behaviour of the token's item, position inside the item), with the temperature loss (``--backbone Qwen3MoeAction``; the
+    reference constructs this class in no task) - on ``Engine(variant="qwen3moe_action")`` (gamer_amd/engine_qwen3moe.py).
+    The surface of ``Qwen3MoeWithTemperature``, ``aux_loss = 0`` and ``router_logits`` included (model.py:585-604); a sparse
+    layer's state dict has ``mlp.experts.expert_{0 .. (num_experts - 1) * num_behavior}``.  The config must have
+    ``mlp_type == "Qwen3"`` and behaviour tokens (``Qwen3MoeActionConfig``)."""
+    VARIANT = "qwen3moe_action"
+    CONFIG_CLASS = Qwen3MoeActionConfig

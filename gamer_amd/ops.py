@@ -132,6 +132,34 @@ def moe_router_prep(ids, attn_mask, behavior_lut, position_table, num_positions,
          stream_ptr())
 
 
+MAX_EXPERT_GROUPS = 64          # gamer_expert_lists: row groups at most
+
+
+def moe_action_router_prep(ids, attn_mask, behavior_lut, position_table, num_positions, n_items, use_behavior_token, pad_id,
+                           eos_id, num_position_experts, num_ffn_experts, out: dict, pos_ids=None, next_pos=None,
+                           act_zero_col=None):
+    """Qwen3MoeAction's router outputs and causal + key-padding mask in one launch (gamer_moe_action_router_prep): the
+    arguments and outputs of ``moe_router_prep``, plus ``out["act_idx"]`` and ``out["expert"]`` = the FFN's index
+    max(0, num_position_experts * (act_idx - 1) + position expert) among ``num_ffn_experts`` experts.  ``act_zero_col``: a
+    column whose action index is forced to 0 (a generation's re-run), or None."""
+    B, S = ids.shape
+    _chk(ids, torch.int64, "input_ids")
+    if attn_mask is not None:
+        _chk(attn_mask, torch.int64, "attention_mask")
+    if position_table is not None:
+        _chk(position_table, torch.int32, "position_table")
+        if position_table.numel() != num_positions:
+            raise ValueError(f"position_table has {position_table.numel()} entries, num_positions is {num_positions}")
+    if not 0 < num_ffn_experts <= MAX_EXPERT_GROUPS:
+        raise ValueError(f"num_ffn_experts = {num_ffn_experts}: the expert lists (gamer_expert_lists) hold at most "
+                         f"{MAX_EXPERT_GROUPS} groups")
+    call("gamer_moe_action_router_prep", ptr(ids), ptr(attn_mask), ptr(behavior_lut),
+         behavior_lut.numel() if behavior_lut is not None else 0, ptr(position_table), B, S, num_positions, n_items,
+         1 if use_behavior_token else 0, pad_id, eos_id, num_position_experts, -1 if act_zero_col is None else int(act_zero_col),
+         ptr(out["expert"]), ptr(out["beh_idx"]), ptr(out["act_idx"]), ptr(out["kl_self"]), ptr(out["empty_self"]),
+         ptr(out["tile_empty_self"]), ptr(pos_ids), ptr(next_pos), ptr(out["bad_token"]), stream_ptr())
+
+
 def session_prep(session_ids, extended_session_ids, attn_mask, num_positions, n_rope_positions, out: dict):
     """Qwen3Session's self mask as per-query key spans plus its RoPE positions, without a router (gamer_session_prep).
     ``out``: kl_self, span_self, pos_ids, empty_self, tile_empty_self, violations (incremented, not cleared)."""

@@ -32,6 +32,10 @@ behaviour token ends the item) or ``--backbone Qwen3``; checkpoints load into ``
 "qwen3_session_moe")``) on the SMB tasks.  The reference constructs this class in no task: the harness takes Qwen3Moe's
 config.json (or ``--base_model DIR``) and sets the run-time fields of the Qwen3SessionMulti branch (train_SMB_decoder.py:
 321-367) plus ``model_max_length``; checkpoints load into ``Qwen3SessionMoeWithTemperature``.  The MB tasks refuse it.
+``--backbone Qwen3MoeAction`` trains Qwen3Moe with one FFN expert per (behaviour, position) pair (``Engine(variant=
+"qwen3moe_action")``) where Qwen3Moe trains with behaviour tokens: the MB tasks except ``mb``, and synthetic batches.  The
+reference constructs this class in no task either: the harness sets Qwen3Moe's run-time fields on Qwen3Moe's config.json (or
+``--base_model DIR``, which must carry ``mlp_type: "Qwen3"``); checkpoints load into ``Qwen3ActionMoeWithTemperature``.
 """
 from __future__ import annotations
 
@@ -43,7 +47,7 @@ import time
 import torch
 
 from . import synthetic
-from .config import (Qwen3Config, Qwen3MoeConfig, Qwen3SessionConfig, Qwen3SessionMoeConfig, apply_mb_runtime_fields,
+from .config import (Qwen3Config, Qwen3MoeActionConfig, Qwen3MoeConfig, Qwen3SessionConfig, Qwen3SessionMoeConfig, apply_mb_runtime_fields,
                      apply_runtime_fields, base_model_config, base_model_config_session_moe, synthetic_config)
 from .dp import GradAllReducer, all_reduce_scalar_
 from .engine import Engine
@@ -70,7 +74,8 @@ def parse_args(argv=None):
     ap.add_argument("--index_file", type=str, default=".index.json")
     ap.add_argument("--tasks", type=str, default="smb_explicit_decoder_4")
     ap.add_argument("--backbone", type=str, default="Qwen3Multi", choices=["Qwen3Multi", "Qwen3SessionMulti", "Qwen3",
-                                                                                 "Qwen3Session", "Qwen3Moe", "Qwen3SessionMoe"])
+                                                                                 "Qwen3Session", "Qwen3Moe", "Qwen3SessionMoe",
+                                                                                 "Qwen3MoeAction"])
     ap.add_argument("--patience", type=int, default=10, help="early stopping: evaluations without a better eval_loss")
     ap.add_argument("--save_total_limit", type=int, default=2)
     ap.add_argument("--bf16", action="store_true",
@@ -175,14 +180,26 @@ class Prefetcher:
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti", "Qwen3Moe", "Qwen3SessionMoe"):
-        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti / Qwen3Moe / Qwen3SessionMoe backbones")
+    if args.base_model and args.backbone not in ("Qwen3Multi", "Qwen3SessionMulti", "Qwen3Moe", "Qwen3SessionMoe",
+                                                 "Qwen3MoeAction"):
+        raise SystemExit("--base_model is read for the Qwen3Multi / Qwen3SessionMulti / Qwen3Moe / Qwen3SessionMoe / "
+                         "Qwen3MoeAction backbones")
     if args.fp16:
         raise SystemExit("--fp16 is not built (the MI355X path has fp32 and bf16; the reference's recipe uses neither "
                          "loss scaling nor fp16 kernels of its own)")
     mb = args.tasks.lower().startswith("mb")
-    if args.data_path and mb and args.backbone not in ("Qwen3Moe", "Qwen3"):
-        raise SystemExit("MB tasks train --backbone Qwen3Moe or Qwen3 (the decoder-only backbones of train_MB_decoder)")
+    if args.data_path and mb and args.backbone not in ("Qwen3Moe", "Qwen3", "Qwen3MoeAction"):
+        raise SystemExit("MB tasks train --backbone Qwen3Moe or Qwen3 (the decoder-only backbones of train_MB_decoder), or "
+                         "Qwen3MoeAction")
+    if args.backbone == "Qwen3MoeAction" and args.data_path:
+        # the action index is the item's behaviour token: a task without behaviour tokens leaves one expert
+        if not mb:
+            raise SystemExit("--backbone Qwen3MoeAction trains on the MB tasks with behaviour tokens (mb_explicit*), or on "
+                             "synthetic batches")
+        from . import mb_data
+        if mb_data._task_kind(args.tasks)[0] != "explicit":
+            raise SystemExit(f"--backbone Qwen3MoeAction needs behaviour tokens: task {args.tasks} has none (every action "
+                             "index would be 0 and the model one expert); use an mb_explicit* task")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -191,7 +208,8 @@ def main(argv=None):
         import torch.distributed as dist
         dist.init_process_group("nccl", init_method="env://", device_id=torch.device("cuda", local_rank))
     variant = {"Qwen3SessionMulti": "session", "Qwen3": "qwen3", "Qwen3Session": "qwen3_session",
-               "Qwen3Moe": "qwen3moe", "Qwen3SessionMoe": "qwen3_session_moe"}.get(args.backbone, "multi")
+               "Qwen3Moe": "qwen3moe", "Qwen3SessionMoe": "qwen3_session_moe",
+               "Qwen3MoeAction": "qwen3moe_action"}.get(args.backbone, "multi")
     accum = args.gradient_accumulation_steps
     real = None
     if args.data_path and mb:
@@ -203,6 +221,9 @@ def main(argv=None):
         coll = mb_data.MBCollator(ds)
         if variant == "qwen3moe":
             cfg = mb_data.qwen3moe_config(ds, args.max_his_len, base_model=args.base_model or None)
+        elif variant == "qwen3moe_action":
+            cfg = mb_data.qwen3moe_config(ds, args.max_his_len, base_model=args.base_model or None,
+                                          config_cls=Qwen3MoeActionConfig)
         else:
             cfg = Qwen3Config(vocab_size=len(ds.tokens), pad_token_id=ds.tokens.pad_id)
         per_step = args.per_device_batch_size * accum * world
@@ -258,9 +279,10 @@ def main(argv=None):
                               "steps_per_epoch": args.steps_per_epoch}), flush=True)
     elif variant == "qwen3":
         cfg = Qwen3Config(vocab_size=synthetic.vocab_size(256, 3), pad_token_id=synthetic.PAD_ID)
-    elif variant == "qwen3moe":
+    elif variant in ("qwen3moe", "qwen3moe_action"):
         # synthetic batches (behaviour token + 4 semantic tokens per item) on config.json's architecture
-        cfg = Qwen3MoeConfig.from_pretrained(args.base_model) if args.base_model else Qwen3MoeConfig()
+        cls = Qwen3MoeActionConfig if variant == "qwen3moe_action" else Qwen3MoeConfig
+        cfg = cls.from_pretrained(args.base_model) if args.base_model else cls()
         cfg.vocab_size, cfg.pad_token_id = synthetic.vocab_size(256, 3), synthetic.PAD_ID
         apply_mb_runtime_fields(cfg, 3, synthetic.behavior_maps(256, 3), True, synthetic.TOKENS_PER_ITEM, args.max_his_len)
     elif variant == "qwen3_session":

@@ -143,6 +143,29 @@ int gamer_moe_router_prep(const int64_t* ids, const int64_t* attn_mask, const in
                           int32_t* kl_self, int32_t* empty_self, int32_t* tile_empty_self, int32_t* pos_ids,
                           int32_t* next_pos, int32_t* bad_token, void* stream);
 
+/* Router + causal mask of the Qwen3MoeAction model (ref:SeqRec/models/generative/Qwen3MoeAction/{model,FFN}.py: Qwen3Moe whose FFN
+ * expert is chosen by the pair (behaviour of the token's item, position inside the item)) in one launch: gamer_moe_router_prep
+ * plus the router's action index (Qwen3Multi/router.py:154-199 with cache_position = arange(S)).  Every argument of
+ * gamer_moe_router_prep means the same here, and beh_idx, kl_self, empty_self, tile_empty_self, pos_ids, next_pos and bad_token
+ * are written exactly as there.  Besides:
+ *   num_position_experts: config.num_experts - 1
+ *   act_zero_col: a column whose action index is forced to 0, or -1 - a generation's re-run of prompt + generated tokens, where
+ *           the reference's cache keeps the action 0 the prompt's last column got in the prompt pass
+ *   act_idx int32 [B,S]: use_behavior_token: behaviour index + 1 of the token's item on every token of it, the behaviour token
+ *           included; 0 at pad / eos, in the router's eos slot, in column ((S + P - 2) / P) * P - the action table's own eos slot,
+ *           inside the sequence only as the last column of S = n P + 1 tokens -, in act_zero_col and for an item start outside
+ *           behavior_maps; 0 everywhere without behaviour tokens
+ *   expert int32 [B,S]: the FFN's expert index max(0, num_position_experts * (act_idx - 1) + position expert) (FFN.py:43-44);
+ *           an index past the FFN's (num_experts - 1) * num_behavior + 1 experts names none (gamer_expert_lists leaves the row
+ *           in no group)
+ * No host synchronisation (graph-capture safe).  S <= 8192.  Additive in ABI 9.                                           */
+int gamer_moe_action_router_prep(const int64_t* ids, const int64_t* attn_mask, const int32_t* behavior_lut, int vocab,
+                                 const int32_t* position_table, int B, int S, int num_positions, int n_items,
+                                 int use_behavior_token, int pad_id, int eos_id, int num_position_experts, int act_zero_col,
+                                 int32_t* expert, int32_t* beh_idx, int32_t* act_idx, int32_t* kl_self, int32_t* empty_self,
+                                 int32_t* tile_empty_self, int32_t* pos_ids, int32_t* next_pos, int32_t* bad_token,
+                                 void* stream);
+
 /* Router + session mask of the Qwen3SessionMoe model (ref:SeqRec/models/generative/Qwen3SessionMoe/model.py: Qwen3Moe's layers
  * and router, :23-93, under Qwen3Session's self mask and RoPE positions, :402-468 and :680-703) in one launch.  Built from the
  * device functions of the two kernels it combines:
