@@ -182,6 +182,8 @@ _SIGNATURES = {
     "gamer_attn_decode_split": [P, I, P, I, P, I, P, P, P, I, I, I, I, P, I, I, I, I, I, F, P, P, P, P],
     "gamer_attn_decode_bf16": [P, I, P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, F, P, P],
     "gamer_kv_append_bf16": [P, I, P, I, P, P, I, I, I, I, I, P],
+    "gamer_attn_candidates": [P, I, P, I, P, I, P, P, P, I, I, I, I, P, I, I, I, I, I, F, P, P],
+    "gamer_token_logprob": [P, L, P, P, I, I, I, P, P],
     "gamer_catalog_ws_bytes": [I, I, I, I],
     "gamer_catalog_ce_fwd": [P, L, P, I, I, P, I, I, P, P, P, P, P, L, P],
     "gamer_catalog_ce_bwd": [P, L, P, I, I, P, I, I, P, P, P, F, P, P, L, P, L, P],

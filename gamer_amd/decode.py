@@ -24,6 +24,8 @@ test_SMB_decoder.py:470-500): the same sequences in the same order and the same 
   logits.  A row without an allowed key gives 0 in bf16, so none of the three things the fp32 path does for the uniform-average
   quirk exists there (``uniform_len``, ``uniform``, the generated cross rows and their slot order): cached and re-run path are
   one computation, ``reorder_cross_cache`` changes nothing (tests/test_decode_bf16_gpu.py).
+* ``score_items`` (end of the file): the exact log-likelihood of GIVEN items on the same cached path - rows are (user, candidate)
+  pairs, any number per user, through ``gamer_attn_candidates`` (csrc/candidates.hip); fp32 engines.
 """
 from __future__ import annotations
 
@@ -205,6 +207,9 @@ class DecodeSession:
     ``reorder`` of an older session of that shape then raise RuntimeError instead of attending over the newer one's caches
     (``beam_search`` runs one session at a time)."""
 
+    _STATIC_SLOT = "_decode_static"      # the engine attribute that holds this kind of session's buffers, by shape
+    _REORDERS = True                     # rows are beams: the generated caches follow ``reorder`` at the start of a step
+
     def __init__(self, engine, input_ids, attention_mask, actions, num_beams: int, max_new_tokens: int,
                  session_ids=None, extended_session_ids=None, reorder_cross_cache: bool = False):
         """``reorder_cross_cache=False`` (default) is the reference as shipped: its cross-attention K/V cache lives on
@@ -230,7 +235,7 @@ class DecodeSession:
         B, L0 = self.B, self.L0
         self.N = N = B * num_beams
         sess = _session_kw(engine, session_ids, extended_session_ids)
-        statics = engine.__dict__.setdefault("_decode_static", {})
+        statics = engine.__dict__.setdefault(self._STATIC_SLOT, {})
         key = (B, L0, num_beams, max_new_tokens, engine.variant, self.reorder_cross_cache, engine.matmul, engine.dtype)
         st = statics.get(key)
         if st is None:
@@ -422,7 +427,7 @@ class DecodeSession:
         eng, cfg, b = self.eng, self.eng.cfg, self.buf
         N, L0, NQ, NKV = self.N, self.L0, self.NQ, self.NKV
         H, eps = cfg.hidden_size, float(cfg.rms_norm_eps)
-        if t >= 2:
+        if t >= 2 and self._REORDERS:
             # the beams were re-ordered after the last step: the t - 1 generated positions follow them
             parent = self.st.small["parent"]
             for key, (kg, vg) in self.gen.items():
@@ -496,9 +501,15 @@ class DecodeSession:
             ops.qknorm_rope_fwd(b["qkv"], 1, nq, nkv, Wa["qn"], Wa["kn"], eps, cos, sin, b["q"], b["k"], pos_ids=pos_ids, **bias)
         kg, vg = self.gen[(layer, kind)]
         ops.kv_append(b["k"], b["qkv"][:, NQ + NKV:], kg, vg, t - 1)
+        self._attn_rows(layer, kind, kg, vg, t, scale)
+
+    def _attn_rows(self, layer: int, kind: str, kg, vg, t: int, scale: float):
+        """The fp32 step attention of the new rows b["q"] over the layer's prompt cache and their own generated positions, into
+        b["ao"]: ``gamer_attn_decode`` (num_beams * G <= 64 rows per sample; the three-piece form with the prompt caches' maxima)."""
+        cfg, b, is_self = self.eng.cfg, self.buf, kind == "self"
         ops.attn_decode(b["q"], self.kp[(layer, kind)], self.vp[(layer, kind)], self.ok_self if is_self else self.ok_cross,
-                        kg, vg, t, is_self, None if is_self else self.uniform_cross, self.B, self.nb, self.L0, nq, nkv,
-                        scale, b["ao"], amax=self.kv_amax.get((layer, kind)))
+                        kg, vg, t, is_self, None if is_self else self.uniform_cross, self.B, self.nb, self.L0,
+                        cfg.num_attention_heads, cfg.num_key_value_heads, scale, b["ao"], amax=self.kv_amax.get((layer, kind)))
 
     def _layer_tail(self, t: int, l: int, W, x, x1):
         """Layer ``l`` after its self-attention block (output x1): the layer output into x.  Qwen3Multi: the cross block with
@@ -808,3 +819,119 @@ def beam_search(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, a
                          trie.child_tok, trie.child_node, nxt)
         node, nxt = nxt.clone(), nxt
     return final + (trace,) if return_trace else final
+
+
+# ---- exact scoring of given items on the cached decode path ---------------------------------------------------------------
+class _ScoreRows:
+    """Mixed in front of a decode session class: its rows are (user, candidate) pairs instead of beams.  Any number of rows per
+    user - the step attention is ``gamer_attn_candidates`` (csrc/candidates.hip; fp32 MFMA in every fp32 matmul form, the GEMMs
+    follow the engine's form) -, no beam re-ordering, and buffers of its own on the engine (``_score_static``), so that the
+    beam-search sessions' buffers (``_decode_static``) are neither taken over nor evicted."""
+
+    _STATIC_SLOT = "_score_static"
+    _REORDERS = False
+
+    def _attn_rows(self, layer: int, kind: str, kg, vg, t: int, scale: float):
+        cfg, b, is_self = self.eng.cfg, self.buf, kind == "self"
+        ops.attn_candidates(b["q"], self.kp[(layer, kind)], self.vp[(layer, kind)], self.ok_self if is_self else self.ok_cross,
+                            kg, vg, t, is_self, None if is_self else self.uniform_cross, self.B, self.nb, self.L0,
+                            cfg.num_attention_heads, cfg.num_key_value_heads, scale, b["ao"])
+
+    @ops.scoped_f32_matmul(lambda self, *a: self.eng.matmul)
+    @ops.scoped_amax(lambda self, *a: self.eng._amax)
+    def score_step(self, tokens: torch.Tensor, t: int) -> torch.Tensor:
+        """tokens [N] int64: token t - 1 of every row's item.  Returns the logits [N, ld] of the rows' token t.  ``t`` starts again
+        at 1 for every chunk of candidates: the generated caches are overwritten from position 0 (positions >= t are never read)."""
+        self._own()
+        self.st.small["tok"].copy_(tokens)
+        self.t = t
+        self._step_body(t)
+        return self.buf["logits"]
+
+
+_SCORE_CLASSES: Dict[type, type] = {}
+
+
+def _session_class(engine):
+    """The decode session class of the engine's variant, whether its constructor takes ``actions`` and whether it takes the
+    session ids."""
+    v = engine.variant
+    if v in ("qwen3", "qwen3_session"):
+        return Qwen3DecodeSession, False, True
+    if v == "qwen3_session_moe":
+        return Qwen3SessionMoeDecodeSession, False, True
+    if v == "qwen3moe_action":
+        return Qwen3MoeActionDecodeSession, False, False
+    if v == "qwen3moe":
+        return Qwen3MoeDecodeSession, False, False
+    if v in ("multi", "session"):
+        return DecodeSession, True, True
+    raise NotImplementedError(f"score_items: variant {v!r} has no decode session")
+
+
+@torch.no_grad()
+def score_items(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, actions: torch.Tensor, items: torch.Tensor,
+                session_ids=None, extended_session_ids=None, max_rows: int = 65536) -> torch.Tensor:
+    """Log-likelihood of GIVEN items after every user's prompt, on the cached decode path.
+
+    input_ids / attention_mask / actions: [B, L0] left-padded prompts ending with the target behaviour token, as for ``beam_search``
+    (``actions`` None for the models without behaviour levels; session engines need ``session_ids`` / ``extended_session_ids``).
+    ``items``: [C, T] int64 - one list for every user - or [B, C, T], a list per user.
+    Returns scores [B, C] fp32: scores[b, c] = (1 / T) * sum_t log_softmax(logits_t)[items[.., c, t]] over the whole vocabulary -
+    what ``beam_search`` returns as ``sequences_scores`` for the same tokens in the cache-consistent semantics
+    (``reorder_cross_cache=True``: every generated position's cross K/V belongs to its own row), i.e. what the cache-free re-run
+    ``_eval_forward(prompt + item)`` computes.
+    The prompt pass runs ONCE for the batch; token 0 is scored from the prefill logits (shared by a user's candidates); the
+    candidates then go through T - 1 single-token steps in chunks of at most ``max_rows // B`` per user (rows = (user, candidate),
+    ``gamer_attn_candidates`` as the step attention, ``gamer_token_logprob`` for a row's log-prob: no [N, V] log-softmax, no
+    top-k, no re-ordering).  Generated caches and step buffers are sized by the chunk.  fp32 engines only.  Candidates that share
+    a prefix are not merged: with 256-way codes nearly every depth-2 prefix of a catalogue belongs to one item."""
+    if engine.dtype != "f32":
+        raise NotImplementedError(f"score_items is built for fp32 engines, not for dtype={engine.dtype!r}: score from an fp32 "
+                                  "engine of the model")
+    cls, takes_actions, takes_sessions = _session_class(engine)
+    if items.dim() not in (2, 3) or items.dtype != torch.int64:
+        raise ValueError(f"score_items: items must be int64 [C, T] or [B, C, T], got {items.dtype} {tuple(items.shape)}")
+    B, L0 = input_ids.shape
+    if items.dim() == 3 and items.shape[0] != B:
+        raise ValueError(f"score_items: items [B, C, T] has {items.shape[0]} lists for {B} users")
+    C, T = items.shape[-2:]
+    if C < 1 or T < 1:
+        raise ValueError(f"score_items: empty item list {tuple(items.shape)}")
+    if max_rows < B:
+        raise ValueError(f"score_items: max_rows = {max_rows} < {B} users (one candidate per user is the smallest chunk)")
+    if cls is Qwen3MoeActionDecodeSession:
+        _check_moe_action_generation(engine, L0, T)
+    elif issubclass(cls, Qwen3MoeDecodeSession):
+        _check_moe_generation(engine, L0, T)
+    dev, V = engine.device, engine.cfg.vocab_size
+    n_chunks = -(-C // max(1, max_rows // B))
+    chunk = -(-C // n_chunks)                                  # (balanced: the last chunk is padded by < n_chunks candidates)
+    scls = _SCORE_CLASSES.get(cls)
+    if scls is None:
+        scls = _SCORE_CLASSES[cls] = type("Score" + cls.__name__, (_ScoreRows, cls), {})
+    sess = dict(session_ids=session_ids, extended_session_ids=extended_session_ids) if takes_sessions else {}
+    if takes_actions:
+        session = scls(engine, input_ids, attention_mask, actions, chunk, T, reorder_cross_cache=True, **sess)
+    else:
+        session = scls(engine, input_ids, attention_mask, chunk, T, **sess)
+    statics = engine.__dict__[scls._STATIC_SLOT]               # one shape of scoring buffers at a time (they are sized by the chunk)
+    for k in [k for k, st in statics.items() if st is not session.st]:
+        del statics[k]
+    it = items.to(dev)
+    if it.dim() == 2:
+        it = it[None].expand(B, C, T)
+    N = B * chunk
+    user = (torch.arange(N, device=dev, dtype=torch.int32) // chunk).contiguous()
+    out = torch.empty(B, n_chunks * chunk, dtype=torch.float32, device=dev)
+    acc = torch.empty(N, dtype=torch.float32, device=dev)
+    for ci in range(n_chunks):
+        c0 = ci * chunk
+        cols = torch.arange(c0, c0 + chunk, device=dev).clamp_(max=C - 1)      # (the last chunk repeats the last candidate)
+        tok = it.index_select(1, cols).reshape(N, T).t().contiguous()           # [T, N]
+        ops.token_logprob(session.prefill_logits, user, tok[0], V, acc)
+        for t in range(1, T):
+            logits = session.score_step(tok[t - 1], t)
+            ops.token_logprob(logits, None, tok[t], V, acc, accumulate=True)
+        out[:, c0:c0 + chunk] = acc.view(B, chunk)
+    return out[:, :C] / T

@@ -313,6 +313,17 @@ class Qwen3MultiWithTemperature(nn.Module, _GenerationMixin):
                                           reorder_cross_cache=bool(kwargs.get("reorder_cross_cache", False)))
         return CausalLMOutput(sequences=seqs, sequences_scores=scores)
 
+    @torch.no_grad()
+    def score_items(self, input_ids=None, attention_mask=None, actions=None, items=None, max_rows: int = 65536, **kwargs):
+        """Exact scores [B, C] of the given ``items`` ([C, T] for every user or [B, C, T]) after the prompts ``generate`` takes:
+        the mean log-probability of an item's tokens, what ``generate`` returns as ``sequences_scores`` for the same tokens with
+        ``reorder_cross_cache=True`` (``decode.score_items``: one prompt pass, the candidates on the cached decode path)."""
+        from . import decode
+        if attention_mask is None or actions is None or items is None:
+            raise ValueError("score_items() needs attention_mask, actions and items")
+        return decode.score_items(self.engine, input_ids, attention_mask, actions, items, session_ids=kwargs.get("session_ids"),
+                                  extended_session_ids=kwargs.get("extended_session_ids"), max_rows=max_rows)
+
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                 inputs_embeds=None, labels=None, use_cache=None, output_attentions=None, output_hidden_states=None,
                 cache_position=None, logits_to_keep=0, session_ids=None, extended_session_ids=None, actions=None,
@@ -445,6 +456,19 @@ class Qwen3WithTemperature(Qwen3MultiWithTemperature):
                                           use_cache=bool(kwargs.get("use_cache", True)), session_ids=kwargs.get("session_ids"),
                                           extended_session_ids=kwargs.get("extended_session_ids"))
         return CausalLMOutput(sequences=seqs, sequences_scores=scores)
+
+    @torch.no_grad()
+    def score_items(self, input_ids=None, attention_mask=None, items=None, max_rows: int = 65536, **kwargs):
+        """Exact scores [B, C] of the given ``items`` ([C, T] for every user or [B, C, T]) after the prompts ``generate`` takes:
+        the mean log-probability of an item's tokens = ``generate``'s ``sequences_scores`` for the same tokens
+        (``decode.score_items``: one prompt pass, the candidates on the cached decode path)."""
+        from . import decode
+        if items is None:
+            raise ValueError("score_items() needs items")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        return decode.score_items(self.engine, input_ids, attention_mask, None, items, session_ids=kwargs.get("session_ids"),
+                                  extended_session_ids=kwargs.get("extended_session_ids"), max_rows=max_rows)
 
 
 class Qwen3SessionWithTemperature(Qwen3WithTemperature):

@@ -1341,6 +1341,24 @@ def attn_decode(q, kp, vp, key_ok, kg, vg, t, gen_ok, uniform, B, nb, L0, nq, nk
          stream_ptr())
 
 
+def attn_candidates(q, kp, vp, key_ok, kg, vg, t, gen_ok, uniform, B, nb, L0, nq, nkv, scale, o):
+    """attn_decode for any number ``nb`` of rows per sample (gamer_attn_candidates: the waves of a workgroup share the staged
+    prompt tiles; fp32 MFMA in every fp32 matmul form): the step attention of ``decode.score_items``."""
+    for name, x in (("q", q), ("kp", kp), ("vp", vp), ("kg", kg), ("vg", vg), ("o", o)):
+        _chk(x, torch.float32, name)
+    _chk(key_ok, torch.int32, "key_ok")
+    call("gamer_attn_candidates", ptr(q), q.stride(0), ptr(kp), kp.stride(0), ptr(vp), vp.stride(0), ptr(key_ok), ptr(kg),
+         ptr(vg), kg.stride(1), kg.shape[1], t, 1 if gen_ok else 0, ptr(uniform), B, nb, L0, nq, nkv, scale, ptr(o),
+         stream_ptr())
+
+
+def token_logprob(logits2d, row_index, token, V, out, accumulate=False):
+    """out[n] (+)= log_softmax(logits2d[row_index[n], :V])[token[n]] (row_index None: row n), gamer_token_logprob."""
+    _chk(token, torch.int64, "token")
+    call("gamer_token_logprob", ptr(logits2d), logits2d.stride(0), ptr(row_index), ptr(token), token.numel(), V,
+         1 if accumulate else 0, ptr(out), stream_ptr())
+
+
 def kv_append_bf16(k, v, kg, vg, g):
     """kv_append on bf16 rows (the bf16 engine's generated self cache)."""
     for name, x in (("k", k), ("v", v), ("kg", kg), ("vg", vg)):

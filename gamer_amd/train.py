@@ -90,6 +90,12 @@ def parse_args(argv=None):
                     help="directory with the model's config.json (Qwen3Multi / Qwen3SessionMulti: its FFN ablation switches "
                          "mlp_type, sparse_layers_decoder and Moe_behavior_only are honoured; the run-time fields of "
                          "train_SMB_decoder.py:321-360 are set on top)")
+    ap.add_argument("--eval_mode", choices=["beam", "exact", "sampled"], default=None,
+                    help="SMB data: after training, rank the test users' held-out items per behaviour (gamer_amd.evaluate) - beam: among "
+                         "the 20 beams of the trie-constrained search; exact: among every item of the behaviour's catalogue by its exact "
+                         "log-likelihood (decode.score_items); sampled: among the targets + --eval_num_neg sampled negatives.  Default: "
+                         "no ranking evaluation")
+    ap.add_argument("--eval_num_neg", type=int, default=1000, help="--eval_mode sampled: negatives per user (seeded by --seed)")
     ap.add_argument("--output_dir", type=str, default="")
     ap.add_argument("--resume_from_checkpoint", type=str, default="")
     return ap.parse_args(argv)
@@ -188,6 +194,11 @@ def main(argv=None):
         raise SystemExit("--fp16 is not built (the MI355X path has fp32 and bf16; the reference's recipe uses neither "
                          "loss scaling nor fp16 kernels of its own)")
     mb = args.tasks.lower().startswith("mb")
+    if args.eval_mode and (not args.data_path or mb):
+        raise SystemExit("--eval_mode ranks the test users of an SMB dataset: give --data_path / --dataset and an smb_* task")
+    if args.eval_mode in ("exact", "sampled") and args.bf16:
+        raise SystemExit(f"--eval_mode {args.eval_mode} scores items on an fp32 engine (decode.score_items): drop --bf16 or use "
+                         "--eval_mode beam")
     if args.data_path and mb and args.backbone not in ("Qwen3Moe", "Qwen3", "Qwen3MoeAction"):
         raise SystemExit("MB tasks train --backbone Qwen3Moe or Qwen3 (the decoder-only backbones of train_MB_decoder), or "
                          "Qwen3MoeAction")
@@ -409,6 +420,13 @@ def main(argv=None):
             from safetensors.torch import save_file
             save_file({k: v.detach().cpu().contiguous() for k, v in eng.params.items()},
                       os.path.join(args.output_dir, "model.safetensors"))
+    if args.eval_mode:
+        from .evaluate import evaluate_dataset
+        res = evaluate_dataset(eng, ds, args.max_his_len, batch_size=min(args.per_device_batch_size, 64), rank=rank, world=world,
+                               mode=args.eval_mode, num_neg=args.eval_num_neg, seed=args.seed)
+        state["test_metrics"] = {"eval_mode": args.eval_mode, **res}
+        if rank == 0:
+            print(json.dumps({"test_metrics": state["test_metrics"]}), flush=True)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -937,6 +937,24 @@ int gamer_attn_decode_bf16(const gamer_bf16* q, int ldq, const gamer_bf16* kp, i
 int gamer_kv_append_bf16(const gamer_bf16* k, int ldk, const gamer_bf16* v, int ldv, gamer_bf16* kg, gamer_bf16* vg, int ldg, int tmax,
                          int g, int N, int C, void* stream);
 
+/* (ABI 9, additive) Scoring GIVEN items on the cached decode path (csrc/candidates.hip; decode.score_items).
+ * gamer_attn_candidates: gamer_attn_decode - the same arguments, the same semantics (key_ok, gen_ok, uniform, a row without an allowed
+ * key gives zeros) - for ANY number nb > 0 of rows per sample: one workgroup = (sample, kv head, block of 128 query rows = G heads x
+ * consecutive rows); its four waves own 32 query columns each and share every 32-key prompt tile, staged into LDS once per workgroup
+ * (double-buffered, one barrier per tile); the <= tmax generated keys of a row are added on the vector unit.  fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32), head size 64, nq / nkv in {1, 2}, 0 <= t <= tmax, L0 <= 7,680 (key_ok of a sample is held in LDS), q / kp / vp
+ * 16-byte aligned with leading dims % 4 == 0: checked before anything is launched.  No atomics: two calls give the same bits.  There is
+ * no three-piece fp16 form: in every fp32 matmul form the candidate attention is this kernel.  Reads the prompt cache of a (sample, kv
+ * head) once per block of 128 query rows (the re-reads of a sample's other blocks come out of L2). */
+int gamer_attn_candidates(const float* q, int ldq, const float* kp, int ldkp, const float* vp, int ldvp,
+                          const int32_t* key_ok, const float* kg, const float* vg, int ldg, int tmax, int t, int gen_ok,
+                          const int32_t* uniform, int B, int nb, int L0, int nq, int nkv, float scale, float* o,
+                          void* stream);
+/* out[n] = (accumulate ? out[n] : 0) + log_softmax(logits[row_n][0..V))[token[n]], row_n = row_index[n] (NULL: n), ld >= V floats
+ * between rows; one wave per row, the [N, V] log-softmax is not written.  A token outside [0, V) gives -inf. */
+int gamer_token_logprob(const float* logits, int64_t ld, const int32_t* row_index, const int64_t* token, int N, int V,
+                        int accumulate, float* out, void* stream);
+
 /* (ABI 9) Catalogue-wide head of the discriminative baselines (csrc/catalog.hip; SASRec's CE loss and full-sort ranking,
  * ref:SeqRec/modules/model_base/seq_model.py:67-122).  h rows r = 0..R-1 are h + row_idx[r] * ldh (row_idx int32 when idx64 == 0,
  * int64 otherwise, NULL = r); E [V][H] row-major, H % 4 == 0, H <= 256, any R and V.  fp32 MFMA (v_mfma_f32_16x16x4_f32) score
