@@ -237,6 +237,7 @@ _SIGNATURES = {
     "gamer_t5_attn_packed_bwd": [P, I, P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, F, U, P, I, P, P, I, P, I, P, I, P, I, P],
     "gamer_t5_attn_long_packed_fwd": [P, I, P, I, P, I, P, P, P, P, P, P, I, I, I, I, I, I, I, F, U, P, I, P, P],
     "gamer_t5_attn_long_packed_bwd": [P, I, P, I, P, I, P, P, P, P, P, I, I, I, I, I, I, F, U, P, I, P, P, I, P, I, P, I, P, I, P, P],
+    "gamer_t5_attn_candidates": [P, I, P, I, P, I, P, P, P, I, I, I, I, I, P, I, P],
     "gamer_t5_bias_expand": [P, P, I, I, I, P, P],
     "gamer_t5_bias_fold": [P, I, I, I, I, P, I, P, P],
 }

@@ -13,7 +13,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgamer_hip.so")
 TORCH_LIB = os.path.join(LIBDIR, "libgamer_torch.so")          # TORCH_LIBRARY(gamer, ...) wrappers over the C ABI
 SOURCES = ["prep.hip", "inject.hip", "elementwise.hip", "qknorm_rope.hip", "ffn_act.hip", "gemm.hip", "gemm_as.hip", "gemm_wg.hip", "gemm_os.hip", "gemm_bf16.hip", "attention.hip", "attention_split.hip", "attention_res.hip", "attention_bf16.hip", "optim.hip", "decode.hip", "decode_bf16.hip", "candidates.hip",
-           "modules.hip", "catalog.hip", "gru.hip", "mbs_attention.hip", "rqvae.hip", "mbht.hip", "pbat.hip", "pbat5.hip", "t5_attention.hip", "t5_attention_long.hip"]
+           "modules.hip", "catalog.hip", "gru.hip", "mbs_attention.hip", "rqvae.hip", "mbht.hip", "pbat.hip", "pbat5.hip", "t5_attention.hip", "t5_attention_long.hip", "t5_candidates.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++20", "-Wall", "-Wno-unused-function"]
 
 

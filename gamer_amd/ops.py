@@ -2380,3 +2380,37 @@ def t5_attn_long_packed_fwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d,
 def t5_attn_long_packed_bwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial):
     """gamer_t5_attn_long_packed_bwd: the arguments of t5_attn_packed_bwd, max_sq, max_sk <= 512; allocates the row terms [2, h, Tq]."""
     t5_attn_packed_bwd(q, k, v, rel, q_off, k_off, B, max_sq, max_sk, h, d, causal, p_drop, seed, d_o, lse, dq, dk, dv, drel_partial, _long=True)
+
+
+def t5_attn_candidates(q, k, v, keep, B, R, Sk, h, d, o, k_off=None):
+    """gamer_t5_attn_candidates: the decoder's cross attention for any number R of query rows per user.  q / o [B R, h d]
+    (row-strided views; user b's rows are b R .. b R + R - 1), k / v [B Sk, h d] with keep uint8 [B, Sk] or None - or, with ``k_off``
+    (the keys' T5Offsets of B rows), the packed [Tk, h d] rows, Sk their bound and no keep.  No bias, no causality, no dropout, no
+    1 / sqrt(d), no lse.  The kernel's limits (Sk <= 128, h <= 16, d in (32, 64), alignment) are refused by the library, which names
+    the entry point in gamer_last_error."""
+    name = "t5_attn_candidates"
+    if min(B, R, Sk, h, d) < 1:
+        raise RuntimeError(f"{name}: B, R, Sk, h, d >= 1 (got {B}, {R}, {Sk}, {h}, {d})")
+    if k_off is not None:
+        if keep is not None:
+            raise RuntimeError(f"{name}: packed keys take no keep")
+        if not isinstance(k_off, T5Offsets) or k_off.n != B:
+            raise RuntimeError(f"{name}: k_off must be the T5Offsets of {B} rows")
+        if k_off.max_len > Sk:
+            lens = k_off.host[1:] - k_off.host[:-1]
+            raise ValueError(f"{name}: row {int(lens.argmax())} of k_start holds {k_off.max_len} tokens, more than max {Sk}")
+        if k_off.total < 1:
+            raise ValueError(f"{name}: k_start holds no token")
+        if k_off.dev is None or not k_off.dev.is_cuda or k_off.dev.dtype != torch.int32 or k_off.dev.numel() != B + 1 or \
+                not k_off.dev.is_contiguous():
+            raise RuntimeError(f"{name}: k_start needs its int32 [{B + 1}] device copy")
+    Tk = B * Sk if k_off is None else k_off.total
+    for t, n, rows in ((q, "q", B * R), (k, "k", Tk), (v, "v", Tk), (o, "o", B * R)):
+        _chk(t, torch.float32, n)
+        if t.dim() != 2 or t.shape != (rows, h * d) or t.stride(1) != 1:
+            raise RuntimeError(f"{name}: {n} must be a [{rows}, {h * d}] row-strided view")
+    if keep is not None and _dense(keep, torch.uint8, "keep").shape != (B, Sk):
+        raise RuntimeError(f"{name}: keep uint8 [{B}, {Sk}]")
+    call("gamer_t5_attn_candidates", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(v), v.stride(0), ptr(keep),
+         ptr(k_off.dev) if k_off is not None else None, k_off.host.data_ptr() if k_off is not None else None, B, R, Sk, h, d, ptr(o),
+         o.stride(0), stream_ptr())

@@ -465,3 +465,16 @@ def beam_search(model: PBATransformerForConditionalGeneration, input_ids, attent
     out = tiger.beam_search(model, input_ids, attention_mask, trie, num_beams, max_new_tokens, decoder_prefix=decoder_prefix)
     model.check_inputs()
     return out
+
+
+@torch.no_grad()
+def score_items(model: PBATransformerForConditionalGeneration, input_ids, attention_mask, items, decoder_prefix=None, packed=False,
+                lengths=None, max_rows: int = 65536):
+    """``tiger.score_items`` with this model's feed-forward step: every candidate is routed by its OWN tokens (its behaviour is the
+    token at position 1 of its row, from ``decoder_prefix`` [B, 2]).  Arguments and result as tiger.score_items; ``packed=True`` is
+    refused (the routers read the padded rows); raises ValueError afterwards when a router met an unmapped behaviour token at a
+    used slot."""
+    out = tiger.score_items(model, input_ids, attention_mask, items, decoder_prefix=decoder_prefix, packed=packed, lengths=lengths,
+                            max_rows=max_rows)
+    model.check_inputs()
+    return out

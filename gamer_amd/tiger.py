@@ -719,6 +719,45 @@ class _DecoderEval:
         last = x.view(N, S, -1)[:, -1, :].contiguous()
         return _rms(last, m.decoder.final_layer_norm.weight.detach(), eps) * (c.d_model ** -0.5)
 
+    @ops.scoped_f32_matmul(lambda *a: "f32")
+    def all_rows(self, ids: torch.Tensor, per_user: int) -> torch.Tensor:
+        """the decoder output at EVERY position of ids [N, S], scaled for the tied head: [N, S, D].  The rows are user-major, N =
+        users x per_user: user b owns rows b per_user .. (score_items' candidates).  The cross attention of a user's per_user x S
+        query rows shares one staged copy of its K / V (gamer_t5_attn_candidates); encoders beyond ops.T5_MAX_S run on the
+        key-streaming kernels through the row map, as last_rows does."""
+        m, c = self.model, self.model.config
+        N, S = ids.shape
+        if N != self.users * per_user:
+            raise ValueError(f"all_rows: {N} rows are not {self.users} users x {per_user}")
+        h, d, eps, dev = c.num_heads, c.d_kv, c.layer_norm_epsilon, ids.device
+        I = h * d
+        x = torch.empty(N * S, c.d_model, **_f32(dev))
+        ops.embedding_fwd(ids.contiguous(), m.shared.weight.detach(), x)
+        table = m.decoder.block[0].layer[0].SelfAttention.relative_attention_bias.weight
+        rel = _BiasStack(table, m._bucket(S, False, dev), S, len(self.layers)).rel
+        lse = torch.empty(N, h, S, **_f32(dev))
+        long = self.Se > ops.T5_MAX_S
+        if long:
+            kv_rows = (torch.arange(N, device=dev, dtype=torch.int32) // per_user).contiguous()
+            xpack = (self.pack.dense_offsets(N, S, dev), self.pack.off) if self.pack is not None else None
+        route = m._route(m.decoder, ids)
+        for L in self.layers:
+            qkv = _linear(_rms(x, L["ln0"], eps), L["wqkv"])
+            c0 = torch.empty(N * S, I, **_f32(dev))
+            _attn_fwd(qkv[:, :I], qkv[:, I:2 * I], qkv[:, 2 * I:], rel, None, N, S, S, h, d, True, 0.0, 0, c0, lse)
+            x = add_dropout(x, _linear(c0, L["wo"]), 0.0, 0)
+            q1 = _linear(_rms(x, L["ln1"], eps), L["cq"])
+            c1 = torch.empty(N * S, I, **_f32(dev))
+            if long:
+                _attn_fwd(q1, L["kv"][:, :I], L["kv"][:, I:], None, self.keep, N, S, self.Se, h, d, False, 0.0, 0, c1, lse,
+                          kv_rows=kv_rows, kv_batch=self.users, pack=xpack)
+            else:
+                ops.t5_attn_candidates(q1, L["kv"][:, :I], L["kv"][:, I:], self.keep, self.users, per_user * S, self.Se, h, d, c1,
+                                       k_off=self.pack.off if self.pack is not None else None)
+            x = add_dropout(x, _linear(c1, L["co"]), 0.0, 0)
+            x = m._eval_ffn(x, L, route)
+        return (_rms(x, m.decoder.final_layer_norm.weight.detach(), eps) * (c.d_model ** -0.5)).view(N, S, -1)
+
 
 @torch.no_grad()
 def beam_search(model: TIGER, input_ids, attention_mask, trie, num_beams: int, max_new_tokens: int, decoder_prefix=None, packed=False,
@@ -787,5 +826,96 @@ def beam_search(model: TIGER, input_ids, attention_mask, trie, num_beams: int, m
                              trie.child_node, nxt)
             node, nxt = nxt.clone(), nxt
         return final
+    finally:
+        model.train(was_training)
+
+
+_LOGIT_FLOATS = 1 << 28            # score_items forms at most this many logits at a time (1 GiB of fp32)
+
+
+@torch.no_grad()
+def score_items(model: TIGER, input_ids, attention_mask, items, decoder_prefix=None, packed=False, lengths=None,
+                max_rows: int = 65536) -> torch.Tensor:
+    """Log-likelihood of GIVEN items after every user's history: scores [B, C] fp32,
+    scores[b, c] = (1 / T) * sum_t log_softmax(logits_t)[items[.., c, t]] over the whole vocabulary, on the logits ``beam_search``
+    forms (the decoder output scaled by d_model ** -0.5 against the tied table, no temperature) - what ``beam_search`` returns as
+    ``sequences_scores`` for the same tokens.  ``items``: int64 [C, T] - one list for every user - or [B, C, T], a list per user;
+    the T tokens are those ``beam_search`` generates (``max_new_tokens`` of them, </s> included where the trie carries it).
+    ``decoder_prefix``, ``packed`` and ``lengths`` as in ``beam_search``.
+    The encoder and the cross-attention K | V of every decoder layer run ONCE per user; the candidates go through the decoder
+    teacher-forced ([prefix | item tokens but the last], P + T - 1 <= MAX_DECODER_LEN positions) in balanced chunks of at most
+    ``max_rows // B`` per user, the last one padded by repeating the last candidate.  One decoder pass per chunk gives every scored
+    position (_DecoderEval.all_rows: cross attention on gamer_t5_attn_candidates, the key-streaming kernels beyond 128 encoder
+    tokens).  Token 0 depends on the prefix alone and is scored from one row per user; the log-probabilities come from
+    gamer_token_logprob (per-row LSE + pick, no [N, V] log-softmax)."""
+    items = torch.as_tensor(items)
+    if items.dim() not in (2, 3) or items.dtype != torch.int64:
+        raise ValueError(f"score_items: items must be int64 [C, T] or [B, C, T], got {items.dtype} {tuple(items.shape)}")
+    if input_ids.dim() != 2:
+        raise ValueError(f"score_items: input_ids [B, S] (got {tuple(input_ids.shape)})")
+    B = input_ids.shape[0]
+    if items.dim() == 3 and items.shape[0] != B:
+        raise ValueError(f"score_items: items [B, C, T] has {items.shape[0]} lists for {B} users")
+    C, T = items.shape[-2:]
+    if C < 1 or T < 1:
+        raise ValueError(f"score_items: empty item list {tuple(items.shape)}")
+    if max_rows < B:
+        raise ValueError(f"score_items: max_rows = {max_rows} < {B} users (one candidate per user is the smallest chunk)")
+    dev = input_ids.device
+    c = model.config
+    if decoder_prefix is None:
+        decoder_prefix = torch.full((B, 1), c.decoder_start_token_id, dtype=torch.int64)
+    prefix = torch.as_tensor(decoder_prefix, dtype=torch.int64)
+    if prefix.dim() == 1:
+        prefix = prefix[None, :].expand(B, -1)
+    if prefix.dim() != 2 or prefix.shape[0] != B:
+        raise ValueError(f"score_items: decoder_prefix [P] or [{B}, P] (got {tuple(prefix.shape)})")
+    P = prefix.shape[1]
+    S = P + T - 1
+    if P < 1 or S > MAX_DECODER_LEN:
+        raise NotImplementedError(f"tiger.score_items: 1 <= prefix and prefix + item tokens <= {MAX_DECODER_LEN + 1}")
+    was_training = model.training
+    model.eval()
+    try:
+        enc, keep = model.encode(input_ids, attention_mask, packed, lengths)     # (packed: keep is the batch's PackedRows)
+        dec = _DecoderEval(model, enc, keep)
+        prefix = prefix.to(dev).contiguous()
+        it = items.to(dev)
+        if it.dim() == 2:
+            it = it[None].expand(B, C, T)
+        E = model.shared.weight.detach()
+        V, D = E.shape
+        n_chunks = -(-C // max(1, max_rows // B))
+        chunk = -(-C // n_chunks)                                  # (balanced: the last chunk is padded by < n_chunks candidates)
+        N = B * chunk
+        user = (torch.arange(N, device=dev, dtype=torch.int32) // chunk).contiguous()
+        first = torch.arange(B, device=dev) * chunk
+        out = torch.empty(B, n_chunks * chunk, **_f32(dev))
+        acc = torch.empty(N, **_f32(dev))
+        step = max(B, min(N, _LOGIT_FLOATS // V))
+        logits = torch.empty(step, V, **_f32(dev))
+
+        def head(rows):
+            with ops.f32_matmul("f32"):
+                ops.linear_fwd(rows, D, E, D, logits, V, rows.shape[0], V, D)
+
+        for ci in range(n_chunks):
+            c0 = ci * chunk
+            cols = torch.arange(c0, c0 + chunk, device=dev).clamp_(max=C - 1)      # (the last chunk repeats the last candidate)
+            tok = it.index_select(1, cols).reshape(N, T)
+            ids = torch.cat([prefix[:, None, :].expand(B, chunk, P).reshape(N, P), tok[:, :T - 1]], 1).contiguous()
+            x = dec.all_rows(ids, chunk)                                            # [N, S, D]
+            tok = tok.t().contiguous()                                              # [T, N]
+            # token 0: position P - 1 sees the prefix alone, the same row for every candidate of a user
+            head(x[first, P - 1, :].contiguous())
+            ops.token_logprob(logits, user, tok[0], V, acc)
+            for t in range(1, T):
+                xt = x[:, P - 1 + t, :]
+                for n0 in range(0, N, step):
+                    n1 = min(N, n0 + step)
+                    head(xt[n0:n1].contiguous())
+                    ops.token_logprob(logits, None, tok[t, n0:n1], V, acc[n0:n1], accumulate=True)
+            out[:, c0:c0 + chunk] = acc.view(B, chunk)
+        return out[:, :C] / T
     finally:
         model.train(was_training)

@@ -9,7 +9,9 @@ Mirrors ``TrainDecoder.invoke`` (ref:SeqRec/tasks/train_decoder.py) for ``--back
              (gamer_amd/schedule.py); the evaluation loss on the validation split after every epoch; the best model by evaluation
              loss goes to ``best_model.pth`` (a state dict the reference class loads); ``--patience`` as EarlyStoppingCallback
   testing    a trie over all items ([decoder_start] + item tokens + </s>), tiger.beam_search with ``--num_beams``, then
-             metrics.py (hit / ndcg / recall @ k) averaged over the test samples, written to ``--results_file``
+             metrics.py (hit / ndcg / recall @ k) averaged over the test samples, written to ``--results_file``;
+             ``--eval_mode exact | sampled`` (tiger_eval.py; also on train_tiger_smb, train_tiger_mb and train_pbatransformer) ranks
+             the target by tiger.score_items among all items, or among itself + ``--eval_num_neg`` sampled negatives, at any k
 Single device.  ``--fp16``, ``--bf16``, ``--deepspeed`` and ``--resume_from_checkpoint`` are refused by name; gradient accumulation
 is not built (``--per_device_batch_size`` is the step's batch).  ``--pack_rows`` (default off) runs the encoder side of training,
 of the evaluation loss and of the test on the rows' own tokens, without the padding tokens (tiger.TIGER.forward(packed=True))."""
@@ -24,7 +26,7 @@ import sys
 import numpy as np
 import torch
 
-from . import ops, schedule, tiger
+from . import ops, schedule, tiger, tiger_eval
 from .decode import ItemTrie
 from .metrics import get_metrics_results, get_topk_results
 from .seqrec_data import EncoderDecoderCollator, SeqRecData, T5_EOS_ID
@@ -75,6 +77,7 @@ def parse_args(argv=None):
     ap.add_argument("--metrics", default=DEFAULT_METRICS)
     ap.add_argument("--results_file", default="./results/test-decoder.json")
     add_pack_rows(ap)
+    tiger_eval.add_eval_flags(ap)
     a = ap.parse_args(argv)
     for name in ("fp16", "bf16", "deepspeed", "resume_from_checkpoint"):
         if getattr(a, name):
@@ -159,6 +162,8 @@ def test(model, data, collator, a, dev):
     samples = data.samples("test", a.max_his_len)
     totals, n = {m: 0.0 for m in metrics}, 0
     model.eval()
+    if tiger_eval.ranked(a):
+        return test_ranked(model, samples, collator, a, dev, item_toks, metrics)
     for b in _batches(samples, collator, a.test_batch_size):
         seqs, scores = tiger.beam_search(model, b["input_ids"].to(dev), b["attention_mask"].to(dev), trie, a.num_beams, item_len + 1,
                                          **pack_kwargs(a, b))
@@ -169,6 +174,31 @@ def test(model, data, collator, a, dev):
         for m, v in get_metrics_results(topk, metrics, targets).items():
             totals[m] += v
         n += len(targets)
+    return {m: totals[m] / max(n, 1) for m in metrics}
+
+
+def test_ranked(model, samples, collator, a, dev, item_toks, metrics):
+    """--eval_mode exact / sampled: the held-out item ranked by tiger.score_items among all distinct items of the index file, or
+    among itself + --eval_num_neg negatives drawn outside the sample's history; the scored tokens are the beam search's (item +
+    </s>)"""
+    catalogue = tiger_eval.distinct_rows(item_toks)
+    index = {tuple(r): i for i, r in enumerate(catalogue.tolist())}
+    row_of = [index[tuple(t)] for t in item_toks]                                 # item row of the data layer -> catalogue row
+    items = torch.cat([catalogue, torch.full((len(catalogue), 1), T5_EOS_ID, dtype=torch.int64)], 1)
+    generator = torch.Generator().manual_seed(a.seed)
+    totals, n = {m: 0.0 for m in metrics}, 0
+    for i in range(0, len(samples), a.test_batch_size):
+        sel = list(range(i, min(i + a.test_batch_size, len(samples))))
+        b = collator(samples, sel)
+        ids, am, kw = b["input_ids"].to(dev), b["attention_mask"].to(dev), pack_kwargs(a, b)
+        tg = [[row_of[int(samples.target[s])]] for s in sel]
+        hist = [{row_of[int(j)] for j in samples.hist[samples.ptr[s]:samples.ptr[s + 1]]} for s in sel]
+        targets = [[catalogue[t[0]].tolist()] for t in tg]
+        sums, _, _ = tiger_eval.rank_batch(lambda it: tiger.score_items(model, ids, am, it, **kw), items, a.eval_mode, tg, hist, targets,
+                                           metrics, a.eval_num_neg, generator)
+        for m in metrics:
+            totals[m] += sums[m]
+        n += len(sel)
     return {m: totals[m] / max(n, 1) for m in metrics}
 
 
@@ -232,6 +262,7 @@ def run(a, tag, data, collator, test_fn, make_model=None):
                     break
     model.load_state_dict(torch.load(ckpt, map_location="cpu"))
     results, line = test_fn(model, data, collator, a, dev)
+    results = tiger_eval.tag_results(results, a)
     os.makedirs(os.path.dirname(os.path.abspath(a.results_file)), exist_ok=True)
     with open(a.results_file, "w") as f:
         json.dump(results, f, indent=4)

@@ -21,7 +21,7 @@ import sys
 
 import torch
 
-from . import mb_data, t5_mb_data, tiger
+from . import mb_data, t5_mb_data, tiger, tiger_eval
 from .decode import ItemTrie
 from .metrics import get_metrics_results, get_topk_results
 from .train_tiger import pack_kwargs
@@ -93,8 +93,28 @@ def test(model, data, collator, a, dev):
     steps = 1 + K + 1 - P                                                     # the rest of the item + </s>
     totals, n = {m: 0.0 for m in metrics}, 0
     model.eval()
+    if tiger_eval.ranked(a):
+        # --eval_mode exact / sampled: the target behaviour's catalogue (rows as the targets hold them, behaviour token included;
+        # the history is matched on the item tokens alone: its items carry their own behaviours) scored by tiger.score_items on
+        # the tokens the search generates, the rest of the row after the prefix + </s>
+        catalogue = tiger_eval.distinct_rows(r[1:-1] for r in td.trie_sequences(td.target_behavior, c.decoder_start_token_id))
+        index = {tuple(r): j for j, r in enumerate(catalogue.tolist())}
+        by_item = {r[P - 1:]: j for r, j in index.items()}
+        items = torch.cat([catalogue[:, P - 1:], torch.full((len(catalogue), 1), t5_mb_data.T5_EOS_ID, dtype=torch.int64)], 1)
+        generator = torch.Generator().manual_seed(a.seed)
     for i in range(0, len(samples), a.test_batch_size):
         inputs, targets = collator.test(samples, range(i, min(i + a.test_batch_size, len(samples))))
+        if tiger_eval.ranked(a):
+            ids, am, kw = inputs["input_ids"].to(dev), inputs["attention_mask"].to(dev), pack_kwargs(a, inputs)
+            hist = [set(tiger_eval.rows_to_items(by_item, tiger_eval.history_rows(samples, s, K, P - 1)))
+                    for s in range(i, min(i + a.test_batch_size, len(samples)))]
+            sums, _, _ = tiger_eval.rank_batch(lambda it: tiger.score_items(model, ids, am, it, decoder_prefix=prefix, **kw), items,
+                                               a.eval_mode, [tiger_eval.rows_to_items(index, t, strict=True) for t in targets], hist, targets,
+                                               metrics, a.eval_num_neg, generator)
+            for m in metrics:
+                totals[m] += sums[m]
+            n += len(targets)
+            continue
         seqs, scores = tiger.beam_search(model, inputs["input_ids"].to(dev), inputs["attention_mask"].to(dev), trie, a.num_beams, steps,
                                          decoder_prefix=prefix, **pack_kwargs(a, inputs))
         pred = seqs[:, 1:1 + K].cpu().tolist()

@@ -22,7 +22,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import t5_mb_data, tiger
+from . import t5_mb_data, tiger, tiger_eval
 from .decode import ItemTrie
 from .metrics import get_metrics_results, get_topk_results
 
@@ -61,6 +61,7 @@ def add_train_flags(ap, model_max_length: int):
     ap.add_argument("--wandb_run_name", default="default")
     from .train_tiger import add_pack_rows
     add_pack_rows(ap)
+    tiger_eval.add_eval_flags(ap)
 
 
 def check_train_flags(a, prog: str, backbone: str = "TIGER"):
@@ -145,8 +146,25 @@ def test_behavior(model, data, samples, collator, a, dev, behavior: str) -> Dict
     trie = ItemTrie(data.trie_sequences(behavior, c.decoder_start_token_id), device=dev, pad_token_id=c.pad_token_id)
     prefix = torch.tensor([c.decoder_start_token_id, data.behavior_token_ids[behavior]], dtype=torch.int64)
     totals, ratios, n = {m: 0.0 for m in metrics}, [], 0
+    if tiger_eval.ranked(a):
+        # --eval_mode exact / sampled: the behaviour's catalogue (or the targets + negatives outside the history) scored by
+        # tiger.score_items on the tokens the search generates; the duplicate ratio is that of the num_beams best candidates
+        catalogue = tiger_eval.distinct_rows(data.smb.candidate_tokens(behavior)[:, 1:])
+        index = {tuple(r): j for j, r in enumerate(catalogue.tolist())}
+        generator = torch.Generator().manual_seed(a.seed)
     for i in range(0, len(samples), a.test_batch_size):
         inputs, targets = collator.test(samples, range(i, min(i + a.test_batch_size, len(samples))))
+        if tiger_eval.ranked(a):
+            ids, am, kw = inputs["input_ids"].to(dev), inputs["attention_mask"].to(dev), pack_kwargs(a, inputs)
+            hist = [set(tiger_eval.rows_to_items(index, h)) for h in inputs["inters_item_list"]]
+            sums, _, best = tiger_eval.rank_batch(lambda it: tiger.score_items(model, ids, am, it, decoder_prefix=prefix, **kw), catalogue,
+                                                  a.eval_mode, [tiger_eval.rows_to_items(index, t, strict=True) for t in targets], hist, targets,
+                                                  metrics, a.eval_num_neg, generator, top=a.num_beams)
+            for m in metrics:
+                totals[m] += sums[m]
+            ratios += [len(set(r) & h) / len(set(r)) if r else 0 for r, h in zip(best, hist)]
+            n += len(targets)
+            continue
         # the trie's sequences end with </s>; the search stops after the item's tokens (max_new_tokens = sole_item_len)
         seqs, scores = tiger.beam_search(model, inputs["input_ids"].to(dev), inputs["attention_mask"].to(dev), trie, a.num_beams, K,
                                          decoder_prefix=prefix, **pack_kwargs(a, inputs))

@@ -1248,6 +1248,20 @@ int gamer_t5_attn_long_packed_bwd(const float* q, int ldq, const float* k, int l
                                   const int32_t* k_start_host, int B, int max_sq, int max_sk, int H, int head_dim, int causal,
                                   float p_drop, uint64_t seed, const float* d_o, int ldo, const float* lse, float* dq, int lddq, float* dk,
                                   int lddk, float* dv, int lddv, float* drel_partial, int n_slab, float* row_ws, void* stream);
+/* (ABI 9, additive) The decoder's cross attention for ANY number R of query rows per user (csrc/t5_candidates.hip;
+ * tiger.score_items, which ranks given items as the reference's discriminative baselines do: ref:SeqRec/trainers/SMBRec.py:102-107,
+ * SMBDisNegSampleEvalDataset; the attention itself is HF T5Attention's of ref:SeqRec/models/generative/TIGER/model.py).  q / o
+ * [B R, ld*]: the R rows of user b are rows b R .. b R + R - 1.  k / v of B users: dense [B Sk, ld*] with keep uint8 [B][Sk] or NULL
+ * (k_start = k_start_host = NULL), or packed with k_start / k_start_host, the device / host arrays of B + 1 offsets that
+ * gamer_t5_attn_packed_fwd takes on the key side (Sk is then the longest row's bound and keep must be NULL).  Semantics of
+ * gamer_t5_attn_fwd without bias, causality or dropout: score = q . k, no 1 / sqrt(d), softmax over the allowed keys, a row with no
+ * allowed key gives a zero context; no lse.  One workgroup = (user, head, block of 64 query rows), K and V of the (user, head) staged
+ * into LDS once per workgroup, one 16-query tile per wave, v_mfma_f32_16x16x4_f32.  A row's result depends on that row and its
+ * user's K / V only.  No atomics: two calls give the same bits.  Refused before any launch: Sk outside 1 .. 128, H > 16, a head_dim
+ * other than 32 or 64, R or B < 1, and the alignment rules of gamer_t5_attn_fwd. */
+int gamer_t5_attn_candidates(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const uint8_t* keep,
+                             const int32_t* k_start, const int32_t* k_start_host, int B, int R, int Sk, int H, int head_dim, float* o,
+                             int ldo, void* stream);
 /* rel [H][n_offsets] = table [num_buckets][H] at bucket[offset] (the bucket of every relative offset is computed on the host) */
 int gamer_t5_bias_expand(const float* table, const int32_t* bucket, int num_buckets, int H, int n_offsets, float* rel, void* stream);
 /* dtable [num_buckets][H] from drel_partial [n_layers][n_slab][H][n_offsets]: per layer the slabs in order and the offsets of a bucket
